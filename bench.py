@@ -36,8 +36,14 @@ exchange included -- every rank looks every k-mer up in its shard, so the shard-
 
 THE LINE.  Rank 0 prints one JSON line of at most 7.5 KB (the driver keeps 8 KB of stdout): flat, short keys, prose cut to
 < 120 characters; `--details FILE` also writes the verbose record (everything this script measured, with units and
-explanations) -- profiles/ holds those of the builder's own runs.  After the headline the same command measures the other
-BASELINE configurations as legs of >= 1 s each, every one a fresh process verified against the oracle, under config.also:
+explanations) -- profiles/ holds those of the builder's own runs.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (`value`, `ms_per_step` and the workload's shape);
+`--dump-outputs DIR` also writes what the last timed step computed -- always the first staged batch, the one with the planted hits
+(up to distinct-batches - 1 untimed warmup steps are added for that).  `--full` adds everything else this script measures or checks:
+the verification against the oracle, roofline and same-box calibration, the resident / host-visible / one-call figures, clocks,
+the CPU baseline and, for the default command, the other BASELINE configurations as legs of >= 1 s each, every one a fresh process
+verified against the oracle, under config.also (N > 1: the legs run before the headline, while no rank holds its GPU):
     --gpus 1   c3 at 0.4, c2, c2 at 0.4, one GPU's shard (1 of 8) of c4 / c5 (scored) / north-star
     --gpus 2   c3 at 0.4 (the thresholded exchange: mask all-gather + count all-reduce)
     --gpus 4   north-star 10M x 500k as a WHOLE index over the 4 GPUs, c3 at 0.4
@@ -56,6 +62,7 @@ import os
 # multi-process GPU work on these hosts needs dmabuf IPC (RCCL across ranks fails with hipIpcGetMemHandle otherwise); the driver's
 # environment exports it -- keep it if it does not.  Must be in place before any HIP runtime loads (torch, libbigsi_hip.so below)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+import shutil
 import socket
 import subprocess
 import sys
@@ -105,7 +112,13 @@ def parse():
     p.add_argument("--score", type=int, choices=[0, 1])
     p.add_argument("--k", type=int, default=31)
     p.add_argument("--and-draws", type=int, default=2, help="bit density of the synthetic index = 2^-draws")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="measure and check everything beside the headline (see the module docstring); a plain run sets up, warms up, times "
+                        "the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the last of them computed (the arrays its caller receives) as DIR/<name>.npy "
+                        "in float64, at most 64 MB in all")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the CPU baseline sample (0 = skip)")
     p.add_argument("--cpu-rows", type=int, default=200_000)
     p.add_argument("--dense", type=int, default=0, choices=[0, 1],
                    help="the hit-dense variant of the workload (what real thresholded searches produce; the plain workloads carry ~1 hit per query): "
@@ -130,8 +143,8 @@ def parse():
                    help="0: skip the host-visible measurements after the timed region (profiled runs: rocprofv3's per-kernel averages then "
                         "cover launches of the timed shape only)")
     p.add_argument("--also", default="auto", choices=["auto", "all", "none"],
-                   help="after the headline, run short legs of the other BASELINE configurations and report them under config.also "
-                        "(auto: only for the default single-GPU c3 run)")
+                   help="--full: run short legs of the other BASELINE configurations and report them under config.also "
+                        "(auto: only for the default c3 command)")
     p.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for several ranks on one GPU)")
     p.add_argument("--one-device", action="store_true", help="every rank uses device 0 (dry runs of the N>1 path on a 1-GPU box; needs --backend gloo)")
     p.add_argument("--one-stream", action="store_true", help="read workloads: every step on the index stream (no overlap of consecutive launches): the A/B "
@@ -143,6 +156,8 @@ def parse():
     p.add_argument("--force-dist", action="store_true",
                    help="initialise the process group and take the exchange path even with one rank (exercises the N>1 code)")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     w = dict(WORKLOADS[a.workload])
     a.custom = []
     for key, arg in (("rows", a.rows), ("cols", a.cols), ("hashes", a.hashes), ("batch", a.batch), ("qlen", a.qlen),
@@ -348,12 +363,44 @@ def leg_summary(d, what, extra, wall_s):
     return {k_: v_ for k_, v_ in out.items() if v_ is not None}
 
 
-def run_also_legs(args, world, rank, ports):
-    """The other BASELINE configurations: one fresh process per leg and rank (the headline's index has been freed, its process
-    group closed).  Under a launcher every rank runs its rank of each leg; rank 0 returns the summaries."""
+def want_legs(args):
+    return args.full and (args.also == "all" or (args.also == "auto" and args.workload == "c3" and not [c for c in args.custom if not c.startswith("rows<=")]
+                                                 and not args.shard_of and args.scaling == "strong" and not args.force_dist and not args.one_stream))
+
+
+def _sync_dir():
+    # (keyed like _err_file; the legs rendezvous on 127.0.0.1, so all ranks of a run that has legs share this machine's temp dir)
+    return os.path.join(tempfile.gettempdir(), "bigsi_bench_legs_%s_%d" % (os.environ.get("MASTER_PORT", "0"), os.getppid()))
+
+
+def file_barrier(world, rank, tag, payload=None, timeout=LEG_TIMEOUT_S + 120):
+    """Wait until every rank has reached `tag`; returns what rank 0 passed as `payload`.  Files, not a process group: the ranks that
+    run the legs of a multi-GPU command hold no GPU context while they do."""
+    d = _sync_dir()
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, "%s.%d.tmp" % (tag, rank)), "w") as f:
+        json.dump(payload, f)
+    os.replace(os.path.join(d, "%s.%d.tmp" % (tag, rank)), os.path.join(d, "%s.%d" % (tag, rank)))
+    t_end = time.time() + timeout
+    while not all(os.path.exists(os.path.join(d, "%s.%d" % (tag, r_))) for r_ in range(world)):
+        if time.time() > t_end:
+            raise RuntimeError("rank %d: not every rank reached %s within %d s" % (rank, tag, timeout))
+        time.sleep(0.1)
+    with open(os.path.join(d, "%s.0" % tag)) as f:
+        return json.load(f)
+
+
+def run_also_legs(args, world, rank):
+    """The other BASELINE configurations: one fresh process per leg and rank.  One GPU: after the headline (its index freed).  N > 1:
+    before it, every rank running its rank of each leg, and no rank starts a leg before every rank's process of the previous one has
+    exited -- N processes on the GPUs at a time.  Rank 0 returns the summaries."""
     out = {}
     timed_out = False
-    for (key, what, extra, steps), port in zip(also_legs_for(world), ports):
+    legs = also_legs_for(world)
+    ports = file_barrier(world, rank, "ports", free_ports(len(legs)) if rank == 0 else None) if world > 1 else [None] * len(legs)
+    for i_leg, ((key, what, extra, steps), port) in enumerate(zip(legs, ports)):
+        if world > 1:
+            file_barrier(world, rank, "leg%d" % i_leg)
         if timed_out:
             out[key] = {"error": "skipped: an earlier leg timed out"}
             continue
@@ -373,7 +420,7 @@ def run_also_legs(args, world, rank, ports):
             except Exception as e:  # noqa: BLE001
                 out[key] = {"error": ("%s: %s" % (type(e).__name__, e))[:160]}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--cpu-seconds", "0", "--also", "none", "--backend", args.backend,
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--full", "--cpu-seconds", "0", "--also", "none", "--backend", args.backend,
                "--steps", str(n_steps)] + (["--warmup", "3"] if "--warmup" not in extra else []) + extra
         if args.one_device:
             cmd.append("--one-device")
@@ -449,7 +496,7 @@ def condense(full):
         "k5_traffic_ratio": sig(cf.get("k5_traffic_ratio"), 4), "k5_line_ratio": sig(cf.get("k5_line_ratio"), 4), "early_exit": 1 if cf.get("early_exit") else None,
         "k56_ms": sig(pres.get("kernels_ms"), 4) if cf.get("dense") else None, "k56_GBps": sig(pres.get("GBps"), 4) if cf.get("dense") else None,
     }
-    roof = {"bound": "hbm", "achieved": sig(rf["achieved"]), "peak": rf["peak"], "unit": "GB/s", "frac": sig(rf["frac"], 4),
+    roof = None if not rf else {"bound": "hbm", "achieved": sig(rf["achieved"]), "peak": rf["peak"], "unit": "GB/s", "frac": sig(rf["frac"], 4),
             "traffic": sig(rf.get("traffic"), 6), "traffic_ratio": sig(rf["traffic"] / rf["alg_bytes_per_launch"], 4) if rf.get("traffic") else None,
             "traffic_source": cut(rf.get("traffic_source"), 60), "kernel": cut(rf["kernel"], 40), "kernel_ms": sig(rf["kernel_ms"]),
             "alg_bytes_per_launch": sig(rf["alg_bytes_per_launch"], 7), "launches_per_step": sig(rf["launches_per_step"], 4), "launches_timed": rf["launches_timed"],
@@ -464,9 +511,11 @@ def condense(full):
         # the library's own communicator reports it (ncclCommCount through bigsi_hip_comm_info; None: the exchange was not RCCL) and the
         # row-AND kernel's achieved GB/s on every rank (their sum over N x 8000 is the aggregate roofline fraction)
         line["rccl_ranks"] = cf.get("rccl_ranks")
-        line["per_rank_GBps"] = [sig(x, 4) for x in cf.get("per_rank_GBps") or []]
+        if cf.get("per_rank_GBps"):                 # (--full)
+            line["per_rank_GBps"] = [sig(x, 4) for x in cf["per_rank_GBps"]]
     line["config"] = {k_: v_ for k_, v_ in config.items() if v_ is not None}
-    line["roofline"] = {k_: v_ for k_, v_ in roof.items() if v_ is not None or k_ == "traffic"}
+    if roof:
+        line["roofline"] = {k_: v_ for k_, v_ in roof.items() if v_ is not None or k_ == "traffic"}
     cb = full.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = {"value": sig(cb["value"]), "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"], "sample": cut(cb["sample_short"]),
@@ -490,6 +539,23 @@ def condense(full):
             leg.pop(victim, None)
     assert len(json.dumps(line)) <= LINE_LIMIT + 500, "bench line too long (%d bytes)" % len(json.dumps(line))
     return line
+
+
+DUMP_BYTES = 63 << 20        # --dump-outputs: at most 64 MB of files, their .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (exact for the library's uint32 / uint64 outputs).  If together
+    they would exceed DUMP_BYTES, each array longer than its share is cut to a seeded sample of its positions (the same positions
+    from run to run while the array's length is)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k_: np.asarray(v_).ravel() for k_, v_ in arrays.items()}
+    share = DUMP_BYTES // 8 // max(len(arrays), 1)
+    cut_ = sum(a_.size for a_ in arrays.values()) * 8 > DUMP_BYTES
+    for name, a_ in arrays.items():
+        if cut_ and a_.size > share:
+            a_ = a_[np.sort(np.random.default_rng(SEED).choice(a_.size, share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a_.astype(np.float64))
 
 
 def smi_snapshot(device):
@@ -595,7 +661,10 @@ def main():
                         os._exit(1)
             threading.Thread(target=watch, daemon=True).start()
     try:
-        return run(args)
+        # N > 1: the legs first, while this process has not touched its GPU (a rank that ran the headline would hold its context
+        # beside its leg processes until it exits)
+        legs = run_also_legs(args, world, rank) if world > 1 and want_legs(args) else None
+        return run(args, legs)
     except (Exception, SystemExit) as e:  # noqa: BLE001
         if isinstance(e, SystemExit) and e.code in (0, None):
             raise
@@ -613,7 +682,7 @@ def main():
         raise
 
 
-def run(args):
+def run(args, legs=None):
     w = args.w
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -836,6 +905,7 @@ def run(args):
         t_a = time.perf_counter()
         rec, pbits, boff = b_.score_hits_end()
         scored["end_s"] += time.perf_counter() - t_a
+        scored["last"] = (rec, pbits, boff, off_own, nk_)
         o64 = off_own.astype(np.int64)
         from bigsi_amd.graph import bigsi as _front
         if _front._results is not None:
@@ -908,8 +978,12 @@ def run(args):
             fetched[0] = batch
             score_finish(job)                   # (with two staged batches this is the object just run again: its results are staged on the host)
 
+    # the last timed step runs the first staged batch (the one that holds the planted hits and whose unique k-mers `value` counts), so
+    # that the outputs of a run (--dump-outputs) are those of the same batch whatever --steps and --warmup are: up to nb - 1 untimed
+    # warmup steps more than asked for
+    warmup = args.warmup + (1 - args.warmup - args.steps) % len(batches)
     warm = _lib.Stats()
-    for i in range(args.warmup):
+    for i in range(warmup):
         step()
         if i == 0:            # the first step pays one-off costs (code object load, allocations): keep it out of the K1 / K4 figures
             sync_all()
@@ -924,7 +998,7 @@ def run(args):
     stats = _lib.Stats()
 
     sync_all()
-    clocks_before = smi_snapshot(local_rank) if rank == 0 else None
+    clocks_before = smi_snapshot(local_rank) if rank == 0 and args.full else None
     sync_all()
     # score=True steps build thousands of result dicts: as in BIGSI.search_stream (pause_gc), automatic passes of the cyclic collector
     # wait while the stream runs and the young generations are collected at batch boundaries (a full pass is ~40 ms with torch loaded)
@@ -942,12 +1016,34 @@ def run(args):
     elapsed = time.perf_counter() - t0
     if gc_paused:
         gc.enable()
-    clocks_after = smi_snapshot(local_rank) if rank == 0 else None
+    clocks_after = smi_snapshot(local_rank) if rank == 0 and args.full else None
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     check(_lib.lib().bigsi_hip_stats(st.handle, _lib.C.byref(stats), 1))
+
+    if args.dump_outputs:
+        # what the caller of the timed path holds after its last step (before anything below runs a batch again)
+        if stream_steps:
+            n_hits = int(s_off[-1])
+            outputs = {"num_kmers": s_nk, "num_unique": s_nu, "hit_offsets": s_off, "colours": s_col[0][:n_hits], "counts": s_cnt[0][:n_hits]}
+        else:
+            last = batches[(step_no[0] - 1) % len(batches)]
+            o_, c_, n_ = sh.fetch(last)              # (every rank: a fetch may have to redo the batch's exchange)
+            k_, u_, _ = last.unique()
+            outputs = {"num_kmers": k_, "num_unique": u_, "hit_offsets": o_, "colours": c_, "counts": n_}
+            if w["score"]:
+                # this rank's scored hits: the score records and the presence strings as bits (num_kmers of them per hit, no padding)
+                rec, pbits, boff, off_own, nk_ = scored["last"]
+                outputs.update({"score_" + f_: rec[f_] for f_ in rec.dtype.names if f_ != "reserved"})
+                nbits = np.repeat(nk_[: w["batch"]].astype(np.int64), np.diff(off_own.astype(np.int64)))
+                first = 8 * boff[: nbits.size].astype(np.int64) - np.concatenate([[0], np.cumsum(nbits)[:-1]])
+                outputs["presence"] = np.unpackbits(pbits)[np.repeat(first, nbits) + np.arange(int(nbits.sum()))]
+        if exact:
+            del outputs["counts"]                    # (an exact search's hits hold every unique k-mer: no count to report)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
 
     # --timed host: the same steps once more with the batches RESIDENT (sequences staged in HBM beforehand, hit lists left on the
     # device: the round 1-5 headline), untimed by the contract, reported beside `value` as config.resident_lookups_per_s; it also
@@ -955,7 +1051,7 @@ def run(args):
     resident_rate = None
     if host_steps:
         check(_lib.lib().bigsi_hip_set_profiling(st.handle, 0))
-        if stream_steps:
+        if stream_steps and args.full:
             stream_step(0)
             first_stream = (s_nu.copy(), s_off.copy(), s_col[0][: int(s_off[-1])].copy(), s_cnt[0][: int(s_off[-1])].copy())
         if use_dist:
@@ -965,7 +1061,7 @@ def run(args):
         for _ in range(len(batches)):
             sh.step(batches, thr, early_exit=bool(args.early_exit))
         sync_all()
-        if args.host_visible:          # (--host-visible 0, profiled runs: no further launches of another shape in rocprofv3's averages)
+        if args.host_visible and args.full:          # (--host-visible 0, profiled runs: no further launches of another shape in rocprofv3's averages)
             t1 = time.perf_counter()
             for _ in range(r_steps):
                 sh.step(batches, thr, early_exit=bool(args.early_exit))
@@ -981,7 +1077,7 @@ def run(args):
     # one-launch read kernels bound their waits and mark a launch in which a workgroup gave up (repeated when its hit lists are
     # fetched): fetch every staged batch's last run, so that such a launch -- none has ever been seen -- would be counted
     repeated = 0
-    if batches[0].info().one_launch:
+    if args.full and batches[0].info().one_launch:
         for b_ in batches[:step_no[0]]:        # (a short run may not have reached every staged batch)
             b_.hits()
         rs = _lib.Stats()
@@ -993,7 +1089,7 @@ def run(args):
     # (BIGSI_RUN_ONE_STREAM), events around every launch: that is roofline.kernel_ms / achieved / frac of such a workload; the
     # overlapped figures stay beside it (frac_overlapped) and the pipeline's own rate is step_frac.
     alone_ms = None
-    if batches[0].info().one_launch and args.alone_steps > 0 and not use_dist and not args.one_stream:
+    if args.full and batches[0].info().one_launch and args.alone_steps > 0 and not use_dist and not args.one_stream:
         check(_lib.lib().bigsi_hip_stats(st.handle, _lib.C.byref(_lib.Stats()), 1))
         check(_lib.lib().bigsi_hip_set_profiling(st.handle, 2))
         for i in range(args.alone_steps):
@@ -1008,47 +1104,49 @@ def run(args):
     off, colours, counts = sh.fetch(batch)
     nk, nu, mk = batch.unique()
     total_unique = int(nu.sum())
-    if stream_steps:          # what the timed steps' call returns for this batch == what the staged batch object returns
+    if stream_steps and args.full:          # what the timed steps' call returns for this batch == what the staged batch object returns
         assert np.array_equal(first_stream[0], nu[: w["batch"]]) and np.array_equal(first_stream[1], off.astype(np.uint64)), "search_stream != batch (offsets)"
         assert np.array_equal(first_stream[2], colours[: int(off[-1])]) and (exact or np.array_equal(first_stream[3], counts[: int(off[-1])])), "search_stream != batch (hits)"
-    wv = -(-my_cols // 64)
-    uniq_rows = 0
-    for i in range(w["batch"]):
-        uniq_rows += np.unique(batch.rows(i, nu[i])).size      # each needed row counted once (reference fetches the union once)
-    # result vector the kernel stores: one bit per sample (AND bitmap / thresholded hit mask); counters only where hits are
-    out_bytes = w["batch"] * wv * 8
-    alg_bytes = uniq_rows * wv * 8 + out_bytes                 # SURVEY.md section 8d, this rank's shard
     # a large batch goes out as several row-AND launches of ~1000 workgroups each: per-launch figures, as rocprofv3 reports them
     launches_per_step = max(stats.and_launches_total, 1) / args.steps
     and_ms = stats.and_ms / max(stats.and_launches, 1)
-    alg_bytes_launch = alg_bytes / launches_per_step
-    overlapped_ms = None
-    if alone_ms:
-        overlapped_ms, and_ms = and_ms, alone_ms
-    achieved = alg_bytes_launch / (and_ms * 1e-3) / 1e9
-    # same-box calibration: bare row streams over this index (no BIGSI code), lists as long as a query's, address-ordered and random
-    cal = None
-    if not use_dist or args.backend == "nccl":
-        rpq = max(int(round(uniq_rows / w["batch"])), 1)
-        cal = {"rows_per_query": rpq}
-        for name, srt in (("sorted", 1), ("random", 0)):
-            g_, m_ = _lib.C.c_double(0), _lib.C.c_double(0)
-            check(_lib.lib().bigsi_hip_probe_rows(st.handle, rpq, 1, srt, 0, 3, _lib.C.byref(g_), _lib.C.byref(m_)))
-            cal[name + "_GBps"], cal[name + "_launch_ms"] = g_.value, m_.value
-        # the exact kernel streams address-ordered lists (K1e) when they are long; everything else sees rows in hash order
-        ordered_lists = exact and not batch.info().one_launch and (w["qlen"] - args.k + 1) * w["hashes"] >= 1024
-        cal["compared_with"] = "sorted" if ordered_lists else "random"
-    per_rank_gbs = [achieved]
-    if use_dist:
-        t = torch.zeros(world, dtype=torch.float64, device=dev)
-        t[rank] = achieved
-        dist.all_reduce(t)
-        per_rank_gbs = [float(x) for x in t.tolist()]
+    # --full: algorithmic bytes of the first staged batch -> the row-AND kernel's achieved GB/s (roofline), same-box calibration
+    alg_bytes = alg_bytes_launch = achieved = overlapped_ms = cal = None
+    per_rank_gbs = []
+    if args.full:
+        wv = -(-my_cols // 64)
+        uniq_rows = 0
+        for i in range(w["batch"]):
+            uniq_rows += np.unique(batch.rows(i, nu[i])).size      # each needed row counted once (reference fetches the union once)
+        # result vector the kernel stores: one bit per sample (AND bitmap / thresholded hit mask); counters only where hits are
+        out_bytes = w["batch"] * wv * 8
+        alg_bytes = uniq_rows * wv * 8 + out_bytes                 # SURVEY.md section 8d, this rank's shard
+        alg_bytes_launch = alg_bytes / launches_per_step
+        if alone_ms:
+            overlapped_ms, and_ms = and_ms, alone_ms
+        achieved = alg_bytes_launch / (and_ms * 1e-3) / 1e9
+        # same-box calibration: bare row streams over this index (no BIGSI code), lists as long as a query's, address-ordered and random
+        if not use_dist or args.backend == "nccl":
+            rpq = max(int(round(uniq_rows / w["batch"])), 1)
+            cal = {"rows_per_query": rpq}
+            for name, srt in (("sorted", 1), ("random", 0)):
+                g_, m_ = _lib.C.c_double(0), _lib.C.c_double(0)
+                check(_lib.lib().bigsi_hip_probe_rows(st.handle, rpq, 1, srt, 0, 3, _lib.C.byref(g_), _lib.C.byref(m_)))
+                cal[name + "_GBps"], cal[name + "_launch_ms"] = g_.value, m_.value
+            # the exact kernel streams address-ordered lists (K1e) when they are long; everything else sees rows in hash order
+            ordered_lists = exact and not batch.info().one_launch and (w["qlen"] - args.k + 1) * w["hashes"] >= 1024
+            cal["compared_with"] = "sorted" if ordered_lists else "random"
+        per_rank_gbs = [achieved]
+        if use_dist:
+            t = torch.zeros(world, dtype=torch.float64, device=dev)
+            t[rank] = achieved
+            dist.all_reduce(t)
+            per_rank_gbs = [float(x) for x in t.tolist()]
 
     # score=True (configs[4]): the scoring leg of a step once more on the first staged batch, its device part timed on its own
     # (events), and the assembled results checked against the oracle's restatement of graph/bigsi.py:211-239 + scoring/score.py
     presence = None
-    if w["score"]:
+    if w["score"] and args.full:
         in_region = dict(scored)
         off_own, col_own, cnt_own = own_hits(batch)
         check(_lib.lib().bigsi_hip_set_profiling(st.handle, 1))
@@ -1083,7 +1181,7 @@ def run(args):
     # PCIe-inclusive rate of the host-buffer boundary (never `value`): sequences in host memory -> batch_reload (H2D) ->
     # run -> fetch_hits (D2H), a few repetitions outside the timed region
     pcie_rate = None
-    if world == 1 and not args.force_dist and args.host_visible:
+    if world == 1 and not args.force_dist and args.host_visible and args.full:
         # a serving loop: two workspaces, reloaded per batch; while one batch runs, the host uploads the next one and
         # downloads the hit lists of the one before (what BIGSI.search_stream does)
         reps = 8 if w["batch"] * w["qlen"] >= (1 << 20) else 200      # (small batches: enough repetitions to time)
@@ -1109,7 +1207,7 @@ def run(args):
     #   stream     ONE bigsi_hip_search_stream call over several of the step's batches (the library pipelines its own chunks)
     #   one_call   bigsi_hip_search_batch latency for the step's first batch (if it is a batch of reads) and for a single query
     host_visible = {"two_workspace_loop_kmer_lookups_per_s": pcie_rate}
-    if world == 1 and not args.force_dist and args.host_visible:
+    if world == 1 and not args.force_dist and args.host_visible and args.full:
         lib_ = _lib.lib()
         # (the library's profiling events -- on since the timed region -- cost a stream 5-7 us per record: the latency figures
         # below are those of a library nobody is profiling, as scripts/call_breakdown.py measures them)
@@ -1204,7 +1302,7 @@ def run(args):
     k5_ratio, k5_line_ratio, traffic_ratio_pmc = None, None, None
     try:
         with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
-            ent = json.load(f).get(wkey)
+            ent = json.load(f).get(wkey) if args.full else None      # (roofline figures: --full)
         if ent:
             # the PMC pass measured launches of ITS shape (--timed resident: whole batches); what carries over to this run's launches --
             # a streamed thresholded batch goes out in two -- is the RATIO of traffic to algorithmic bytes (scaled below, once those are known)
@@ -1220,7 +1318,7 @@ def run(args):
         pass
 
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         # EVERY rank: planted round trip on every shard (the gathered lists are identical on all ranks) + sampled queries against the
         # oracle on the rank's OWN shard (colours, counts; score=True: whole result dicts); rank 0 reports what all ranks found
         from oracle.ref_model import SynthOracle
@@ -1343,7 +1441,7 @@ def run(args):
                     if host_steps else "runs a batch staged in HBM beforehand and leaves its hit lists on the device"),
                 "value_inputs": "host" if host_steps else "resident", "resident_lookups_per_s": resident,
                 "shard_lookups_per_s_sum": rate * world,
-                "aggregate_GBps": sum(per_rank_gbs), "per_rank_GBps": per_rank_gbs,
+                "aggregate_GBps": sum(per_rank_gbs) if per_rank_gbs else None, "per_rank_GBps": per_rank_gbs or None,
                 "parallelism": "column-shard x%d%s" % (world, "" if not use_dist else
                                                       " + ncclAllGather of 1 bit/sample (library-owned RCCL communicator)"
                                                       if sh.exchange == "rccl" else " + torch.distributed(%s) all-gather" % args.backend),
@@ -1352,9 +1450,9 @@ def run(args):
                 "index_fill_s": fill_s, "index_contiguous": bool(stats.index_contiguous), "verified": verified, "presence": presence,
                 "pcie_inclusive_kmer_lookups_per_s": pcie_rate,
                 "host_visible": host_visible,
-                "clocks": {"before_timed_region": clocks_before, "after_timed_region": clocks_after},
+                "clocks": {"before_timed_region": clocks_before, "after_timed_region": clocks_after} if args.full else None,
             },
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "roofline": None if not args.full else {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic_ratio_pmc * alg_bytes_launch if traffic_ratio_pmc else traffic, "traffic_source": traffic_src, "traffic_measured_in_run": False, "pmc_key": wkey,
                          "kernel": "k_reads_fused (K1 + row-AND + K4 in one launch)" if batch.info().one_launch else "k_and_exact" if exact else "k_and_count",
                          "alg_bytes_per_launch": alg_bytes_launch, "kernel_ms": and_ms, "launches_timed": int(stats.and_launches),
@@ -1371,30 +1469,25 @@ def run(args):
                          "concurrent_launches": 3 if batch.info().one_launch and not args.one_stream else 1, "read_launches_repeated": repeated,
                          "rank": 0,
                          # per step, from warmup steps 2..W: K1 (+ row sort on the exact path); K4
-                         "kmerize_ms": warm.kmerize_ms / (args.warmup - 1) if args.warmup > 1 else None,
-                         "compact_ms": warm.compact_ms / (args.warmup - 1) if args.warmup > 1 else None},
+                         "kmerize_ms": warm.kmerize_ms / (warmup - 1) if warmup > 1 else None,
+                         "compact_ms": warm.compact_ms / (warmup - 1) if warmup > 1 else None},
         }
-        if args.cpu_seconds > 0 and world == 1:        # reported at N=1 only
+        if args.full and args.cpu_seconds > 0 and world == 1:        # reported at N=1 only
             line["cpu_baseline"] = cpu_baseline(args, w, my_cols, exact)
     for b_ in batches:
         b_.close()
     sh.close()
     st.delete_all()
-    want_legs = args.also == "all" or (args.also == "auto" and args.workload == "c3" and not [c for c in args.custom if not c.startswith("rows<=")]
-                                       and not args.shard_of and args.scaling == "strong" and not args.force_dist and not args.one_stream)
-    ports = [None] * len(also_legs_for(world))
     if use_dist:
-        if want_legs and world > 1:
-            box = [free_ports(len(ports)) if rank == 0 else None]
-            dist.broadcast_object_list(box, src=0)
-            ports = box[0]
         dist.barrier()
         dist.destroy_process_group()
-    if want_legs:
-        # the other BASELINE configurations, each a short run of this script in fresh processes now that the index is freed
-        legs = run_also_legs(args, world, rank, ports)
-        if rank == 0:
-            line["config"]["also"] = legs
+        if legs is not None and rank == 0:
+            shutil.rmtree(_sync_dir(), ignore_errors=True)      # (every rank is past the legs' last file barrier)
+    if legs is None and want_legs(args):
+        # one GPU: the other BASELINE configurations, each a short run of this script in a fresh process now that the index is freed
+        legs = run_also_legs(args, world, rank)
+    if rank == 0 and legs is not None:
+        line["config"]["also"] = legs
     if rank == 0:
         if args.details:
             os.makedirs(os.path.dirname(os.path.abspath(args.details)) or ".", exist_ok=True)

@@ -11,7 +11,7 @@ res = {l: [] for l in libs}
 for r in range(rounds):
     for l in libs:
         env = dict(os.environ, BIGSI_HIP_LIB=os.path.join(root, "bigsi_amd", "lib%s.so" % l))
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--cpu-seconds", "0", "--no-verify",
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--full", "--cpu-seconds", "0", "--no-verify",
                               "--threshold", thr] + extra, env=env, capture_output=True, text=True).stdout.strip().splitlines()[-1]
         d = json.loads(out)
         res[l].append((d["roofline"]["kernel_ms"], d["ms_per_step"]))

@@ -1,6 +1,6 @@
 cd "${GRAFT_REPO_ROOT:-.}"
 export BIGSI_HIP_LIB=$PWD/bigsi_amd/libbigsi_hip_tuning.so
-B="--cpu-seconds 0 --also none --host-visible 0 --alone-steps 0 --timed resident"
+B="--full --cpu-seconds 0 --also none --host-visible 0 --alone-steps 0 --timed resident"
 for rep in 1 2; do for a in 16 256; do
 echo "== rep $rep align_words=$a"
 for w in "--steps 10 --warmup 3" "--steps 10 --warmup 3 --threshold 0.4" "--workload c4 --shard-of 8 --gpus 1 --steps 100 --warmup 10" "--workload c5 --shard-of 8 --gpus 1 --steps 100 --warmup 10" "--workload northstar --shard-of 8 --gpus 1 --steps 100 --warmup 10"; do

@@ -10,7 +10,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 O=gpurun_out/pmc_attr
 mkdir -p $O
-B="--steps 2 --warmup 1 --no-verify --cpu-seconds 0 --also none"
+B="--steps 2 --warmup 1 --full --no-verify --cpu-seconds 0 --also none"
 declare -A CGRP
 CGRP[utcl1]="TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_REQUEST_sum"
 CGRP[utcl2]="GRBM_UTCL2_BUSY GRBM_GUI_ACTIVE TCP_UTCL1_STALL_UTCL2_REQ_OUT_OF_CREDITS_sum"

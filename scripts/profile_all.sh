@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 R=${ROUND:-r06}
 P=gpurun_out/prof
 mkdir -p $P
-B="--cpu-seconds 0 --also none --host-visible 0 --alone-steps 0"      # (rocprofv3 averages then cover launches of the timed shape only)
+B="--full --cpu-seconds 0 --also none --host-visible 0 --alone-steps 0"      # (rocprofv3 averages then cover launches of the timed shape only)
 [ -f bigsi_amd/libbigsi_hip_tuning.so ] || bash bigsi_amd/csrc/build.sh tuning > /dev/null      # (two legs below A/B through it)
 run() { scripts/prof.sh "$@" > /dev/null; }
 python - <<PYEOF > $P/${R}_build.json
@@ -70,8 +70,8 @@ python scripts/pmc_all.py $P/pmc > $P/${R}_pmc_all.log 2>&1
 # round 6: the request-size classes themselves (no x2 to argue about): calibration on the row-AND kernel, K5 on both c5 legs, the transpose
 python scripts/pmc_requests.py $P/pmc_req c3_exact c5_shard c5_dense transpose > $P/${R}_pmc_requests.log 2>&1
 cp $P/pmc_req/pmc_requests.json $P/${R}_pmc_requests.json
-python bench.py --steps 20 --warmup 5 --details $P/${R}_bench_default_full.json > $P/${R}_bench_default.stdout 2> $P/${R}_bench_default.stderr      # the driver's command: headline + every other config as config.also legs + the CPU baseline
-python bench.py --steps 20 --warmup 5 --threshold 0.4 --also none > $P/${R}_bench_t04.stdout 2> $P/${R}_bench_t04.stderr
+python bench.py --steps 20 --warmup 5 --full --details $P/${R}_bench_default_full.json > $P/${R}_bench_default.stdout 2> $P/${R}_bench_default.stderr      # the default command with --full: headline + every other config as config.also legs + the CPU baseline
+python bench.py --steps 20 --warmup 5 --threshold 0.4 --full --also none > $P/${R}_bench_t04.stdout 2> $P/${R}_bench_t04.stderr
 # round 6: the Python stack's latency, the host-visible build, the transpose A/B against the previous kernel (tuning build), the transposing read's lane map
 python scripts/latency_probe.py > $P/${R}_python_stack_latency.txt 2>&1
 { python scripts/build_bench.py 4000000 16384; python scripts/build_bench.py 1000000 100000; } > $P/${R}_build_bench.jsonl 2>/dev/null

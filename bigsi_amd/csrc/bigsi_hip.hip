@@ -63,11 +63,9 @@ static int read_stream(bigsi_hip_index *ix, hipStream_t *out)
 {
     *out = ix->stream;
     if (ix->stream != ix->own_stream) return BIGSI_OK;       // the caller's own stream (bigsi_hip_set_stream): everything stays on it
-    static const int n_streams = std::min(env_int("BIGSI_HIP_READ_STREAMS", kReadStreamsUsed), kReadStreams);      // A/B: 1 = no overlap
-    if (n_streams <= 1) return BIGSI_OK;
     if (!ix->rd_stream[0])
         for (auto &st : ix->rd_stream) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    *out = ix->rd_stream[ix->rd_next++ % (uint32_t)n_streams];
+    *out = ix->rd_stream[ix->rd_next++ % (uint32_t)kReadStreamsUsed];
     ix->rd_pending = true;
     return BIGSI_OK;
 }
@@ -91,18 +89,9 @@ static int score_stream(bigsi_hip_index *ix, hipStream_t *out)
     *out = ix->stream;
     if (ix->stream != ix->own_stream) return BIGSI_OK;       // the caller's own stream: everything stays on it
     if (!ix->sc_stream) {
-        // (tuning builds: BIGSI_HIP_SCORE_CUS = n > 0 confines the stream to n compute units instead -- a CU-masked stream has no priority)
-        static const int score_cus = env_int("BIGSI_HIP_SCORE_CUS", 0);
-        if (score_cus > 0) {
-            uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            static const int stride = std::max(env_int("BIGSI_HIP_SCORE_CU_STRIDE", 1), 1);
-            for (int i = 0, c = 0; i < score_cus && c < 256; i++, c += stride) mask[c / 32] |= 1u << (c % 32);
-            HIP_TRY(hipExtStreamCreateWithCUMask(&ix->sc_stream, 8, mask));
-        } else {
-            int least = 0, greatest = 0;
-            HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIP_TRY(hipStreamCreateWithPriority(&ix->sc_stream, hipStreamNonBlocking, greatest));
-        }
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&ix->sc_stream, hipStreamNonBlocking, greatest));
     }
     *out = ix->sc_stream;
     return BIGSI_OK;
@@ -131,27 +120,7 @@ static int quiesce_index(bigsi_hip_index *ix)
 
 static uint64_t stride_for(uint64_t cols)
 {
-    static const int align_words = env_int("BIGSI_HIP_ROW_ALIGN_WORDS", 16);      // A/B (tuning builds): 256 = rows at a 2 KB pitch
-    return std::max<uint64_t>(16, round_up(ceil_div(cols, 64), (uint64_t)std::max(align_words, 16)));
-}
-
-// The matrix is an ordinary hipMalloc.  Tuning builds can ask for PHYSICALLY CONTIGUOUS memory instead (BIGSI_HIP_CONTIGUOUS=1:
-// hipDeviceMallocContiguous, largest page-table fragments): the bare-kernel probe measured +4 % on random 12.5 KB rows with it and
-// the counting kernel +0.5 %, but in a process that opens and closes several indexes one after the other it CORRUPTS another
-// buffer -- counters of the last queries of a batch read back as zeros, deterministically, in
-// test_one_launch_read_path_equals_three_launch_path[4-32768] (bisected to this flag alone; the driver appears to move or clear
-// memory under a running process when it makes room for a contiguous block).  Not shipped.
-static hipError_t index_malloc(uint64_t **out, size_t bytes, bool *contiguous)
-{
-    static const int contig = env_int("BIGSI_HIP_CONTIGUOUS", 0);
-    *contiguous = false;
-    if (contig) {
-        hipError_t e = hipExtMallocWithFlags((void **)out, bytes, hipDeviceMallocContiguous);
-        if (e == hipSuccess) { *contiguous = true; return e; }
-        (void)hipGetLastError();          // clear the sticky error: fall back
-        *out = nullptr;
-    }
-    return hipMalloc((void **)out, bytes);
+    return std::max<uint64_t>(16, round_up(ceil_div(cols, 64), 16));
 }
 
 // ------------------------------------------------------------------------------ lifecycle
@@ -193,8 +162,7 @@ static int open_impl(uint64_t num_rows, uint64_t num_cols, uint64_t col_capacity
         // lowest priority: whatever runs here must not delay the workgroups of a row-AND kernel on the index stream
         int least = 0, greatest = 0;
         e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-        static const int pre_prio = env_int("BIGSI_HIP_PRE_PRIORITY", 1);
-        if (e == hipSuccess && pre_prio) e = hipStreamCreateWithPriority(&ix->pre_stream, hipStreamNonBlocking, least);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&ix->pre_stream, hipStreamNonBlocking, least);
         else e = hipStreamCreateWithFlags(&ix->pre_stream, hipStreamNonBlocking);
     }
     if (e != hipSuccess) {
@@ -227,7 +195,7 @@ static int open_impl(uint64_t num_rows, uint64_t num_cols, uint64_t col_capacity
         *out = ix;
         return BIGSI_OK;
     }
-    e = index_malloc(&ix->d_index, bytes, &ix->contiguous);
+    e = hipMalloc((void **)&ix->d_index, bytes);
     if (e != hipSuccess) {
         hipError_t e2 = hipStreamDestroy(ix->own_stream); (void)e2;
         e2 = hipStreamDestroy(ix->pre_stream);
@@ -396,8 +364,7 @@ extern "C" int bigsi_hip_reserve_cols(bigsi_hip_index *ix, uint64_t col_capacity
     TRY(quiesce_index(ix));
     const uint64_t ns = stride_for(col_capacity);
     uint64_t *nd = nullptr;
-    bool nd_contig = false;
-    HIP_TRY(index_malloc(&nd, (size_t)ix->m * ns * 8, &nd_contig));
+    HIP_TRY(hipMalloc((void **)&nd, (size_t)ix->m * ns * 8));
     const uint64_t total = ix->m * ns;
     const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(total, kBlock), 256 * 8 * 4);
     hipLaunchKernelGGL(k_restride, dim3(grid), dim3(kBlock), 0, ix->stream, ix->d_index, ix->stride_words, nd, ns, ix->m);
@@ -405,7 +372,6 @@ extern "C" int bigsi_hip_reserve_cols(bigsi_hip_index *ix, uint64_t col_capacity
     HIP_TRY(hipStreamSynchronize(ix->stream));
     HIP_TRY(hipFree(ix->d_index));
     ix->d_index = nd;
-    ix->contiguous = nd_contig;
     ix->stride_words = ns;
     ix->cap_cols = ns * 64;
     return BIGSI_OK;
@@ -971,60 +937,28 @@ static int transpose_device(bigsi_hip_index *ix, uint64_t col0, uint64_t n, cons
     };
     const uint64_t c_lo = std::min(end, round_up(col0, 128));
     uint64_t n_words = (end - c_lo) / 64, c_hi = c_lo + n_words * 64;
-    static const int tiled = env_int("BIGSI_HIP_TRANSPOSE_TILED", 1);
-    static const int tr_rg = env_int("BIGSI_HIP_TR_RG", 4), tr_cg = env_int("BIGSI_HIP_TR_CG", 1);      // XCD groups: A/B in profiles/r06_transpose_regs_ab.txt
+    // XCD groups of 4 rows x 1 column of supertiles (A/B in profiles/r06_transpose_regs_ab.txt)
+    constexpr uint32_t tr_rg = 4, tr_cg = 1;
     // k_transpose_regs<2>: 1024 rows x 1024 columns per workgroup -- whole 128-byte lines of the filters in (two consecutive loads per
     // lane), 128-byte runs of the rows out.  (RT = 1, 512 rows: 4.4-5.0 TB/s against 4.9-5.4, its half lines shared with another workgroup.)
-    static const int tr_double = env_int("BIGSI_HIP_TR_DOUBLE", 1);
-    bool regs = true;
-    uint64_t rt = tr_double ? 2 : 1, ct = 2;
-#ifdef BIGSI_HIP_TUNING
-    static const int tr_regs = env_int("BIGSI_HIP_TR_REGS", 1), tr_wide = env_int("BIGSI_HIP_TR_WIDE", 1);      // 0: k_transpose_tiles<RT, CT> of rounds 2-6
-    regs = tr_regs != 0;
-    if (!regs) ct = tr_wide ? 2 : 1;
-    static const int tr_cw = env_int("BIGSI_HIP_TR_CW", 1);      // 2: 2048-column tiles (256-byte row runs), 1024 threads, one workgroup per CU
-    if (regs && tr_cw == 2) ct = 4;
-#endif
+    constexpr uint64_t rt = 2, ct = 2;
     // APPENDING (nothing valid at or beyond `end`: the usual build) the tiled kernel also takes the ragged tail: it writes whole 128-byte
     // lines, zeros for the columns that have no filter -- what those bits of the row hold anyway -- instead of leaving up to 63 columns to
     // the column-at-a-time kernel and a partly written line to the memory (round 6: 1 M x 100 000 against 1 M x 98 304: -5 %)
-    if (regs && end >= ix->n_cols && end > c_lo) {
+    if (end >= ix->n_cols && end > c_lo) {
         n_words = std::min<uint64_t>(round_up(ceil_div(end - c_lo, 64), 16), ix->stride_words - c_lo / 64);
         c_hi = end;
     }
     // supertiles of 1024 tiles: 32 wide, narrower (and higher) when the matrix has fewer tile columns than that
     const uint64_t tiles_c = ceil_div(n_words, 8 * ct);
-    static const int tr_supw = env_int("BIGSI_HIP_TR_SUPW", kTransposeSuper);
-    uint32_t sup_w = (uint32_t)tr_supw;
+    uint32_t sup_w = kTransposeSuper;
     while (sup_w > 1 && sup_w / 2 >= tiles_c) sup_w /= 2;
-    const uint32_t sup_h = (uint32_t)(kTransposeSuper * kTransposeSuper) / sup_w, cg_eff = std::min<uint32_t>((uint32_t)tr_cg, sup_w);
+    const uint32_t sup_h = (uint32_t)(kTransposeSuper * kTransposeSuper) / sup_w;
     const uint64_t sup_blocks = ceil_div(ceil_div(ix->m, kTransposeTile * rt), sup_h) * ceil_div(tiles_c, sup_w) * (uint64_t)(kTransposeSuper * kTransposeSuper);
-    if (!tiled || n_words == 0 || bstride % 16 || ((uintptr_t)d_blooms & 15u) || sup_blocks > 0x7FFFFFFFull) return slow(col0, n);
+    if (n_words == 0 || bstride % 16 || ((uintptr_t)d_blooms & 15u) || sup_blocks > 0x7FFFFFFFull) return slow(col0, n);
     TRY(slow(col0, c_lo - col0));
-#define BIGSI_TR_ARGS                                                                                                          \
-    dim3((unsigned)sup_blocks), dim3(kBlock * (unsigned)ct), 0, ix->stream, ix->d_index, ix->stride_words, ix->m, c_lo / 64, n_words,  \
-        d_blooms + (c_lo - col0) * bstride, end - c_lo, bstride, nb, (uint32_t)tr_rg, cg_eff, sup_w
-#define COMMA ,
-#ifdef BIGSI_HIP_TUNING
-    if (regs && ct == 4 && rt == 2) hipLaunchKernelGGL((k_transpose_regs<2 COMMA 2>), BIGSI_TR_ARGS);
-    else if (regs && ct == 4) hipLaunchKernelGGL((k_transpose_regs<1 COMMA 2>), BIGSI_TR_ARGS);
-    else
-#endif
-    if (regs && rt == 2) hipLaunchKernelGGL((k_transpose_regs<2>), BIGSI_TR_ARGS);
-    else if (regs) hipLaunchKernelGGL((k_transpose_regs<1>), BIGSI_TR_ARGS);
-#ifdef BIGSI_HIP_TUNING
-    else {
-        static const int skip = env_int("BIGSI_HIP_TR_SKIP", 0);
-        static bool set = false;
-        if (!set) { const uint32_t v = (uint32_t)skip; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_tr_skip), &v, 4)); set = true; }
-        if (rt == 2 && ct == 2) hipLaunchKernelGGL((k_transpose_tiles<2 COMMA 2>), BIGSI_TR_ARGS);
-        else if (rt == 2) hipLaunchKernelGGL((k_transpose_tiles<2 COMMA 1>), BIGSI_TR_ARGS);
-        else if (ct == 2) hipLaunchKernelGGL((k_transpose_tiles<1 COMMA 2>), BIGSI_TR_ARGS);
-        else hipLaunchKernelGGL((k_transpose_tiles<1 COMMA 1>), BIGSI_TR_ARGS);
-    }
-#endif
-#undef COMMA
-#undef BIGSI_TR_ARGS
+    hipLaunchKernelGGL(k_transpose_regs<2>, dim3((unsigned)sup_blocks), dim3(kBlock * (unsigned)ct), 0, ix->stream, ix->d_index, ix->stride_words,
+                       ix->m, c_lo / 64, n_words, d_blooms + (c_lo - col0) * bstride, end - c_lo, bstride, nb, tr_rg, tr_cg, sup_w);
     HIP_TRY(hipGetLastError());
     return slow(c_hi, end - c_hi);
 }
@@ -1265,7 +1199,7 @@ extern "C" int bigsi_hip_stats(bigsi_hip_index *ix, bigsi_hip_stats_t *out, int 
     TRY(sum(ix->ev_tr, &out->transpose_launches, &out->transpose_ms));
     TRY(sum(ix->ev_ex, &out->exchange_launches, &out->exchange_ms));
     out->presence_bytes = ix->presence_bytes;
-    out->index_contiguous = ix->contiguous ? 1 : 0;
+    out->index_contiguous = 0;
     out->and_launches_total = ix->and_total;
     out->read_launches_repeated = ix->fused_repeats;
     if (reset) {
@@ -1612,11 +1546,9 @@ extern "C" int bigsi_hip_batch_destroy(bigsi_hip_batch *b)
     if (b->pin_out) { e = hipHostFree(b->pin_out); (void)e; }
     if (b->pin_flag) { e = hipHostFree(b->pin_flag); (void)e; }
     b->exp_count.release();
-    if (b->exp_done) { e = hipEventDestroy(b->exp_done); (void)e; }
     if (b->job.h_in) { e = hipHostFree(b->job.h_in); (void)e; }
     if (b->job.h_out) { e = hipHostFree(b->job.h_out); (void)e; }
     if (b->done) { e = hipEventDestroy(b->done); (void)e; }
-    if (b->k1_done) { e = hipEventDestroy(b->k1_done); (void)e; }
     if (b->g_done) { e = hipEventDestroy(b->g_done); (void)e; }
     delete b;
     return BIGSI_OK;
@@ -1656,8 +1588,6 @@ struct CountLaunch {
     uint32_t early_exit;        // BIGSI_RUN_EARLY_EXIT on a hits-only, one-slice run
     uint64_t *partial;          // slices > 1: bit-sliced partial counts of every slice (k_count_combine adds them up)
     uint32_t planes_out;
-    bool half;                  // half the row loads in flight per lane (k_and_count<..., 3>)
-    int vec;                    // 64-column words per lane: 2, or 1 (h = 3 / 4, one slice, not pipelined): `tiles` is computed for it
 };
 
 template <int P, typename CountT>
@@ -1673,17 +1603,9 @@ static void launch_count_wide(bigsi_hip_batch *b, const CountLaunch &c, uint32_t
         c.hit_bitmap, b->wv_pad, c.sparse, c.slices, c.early_exit, c.partial, c.planes_out
 #define COMMA ,
 #define BIGSI_LAUNCH_COUNT(H) hipLaunchKernelGGL((k_and_count<P, H, CountT>), BIGSI_COUNT_ARGS)
-#ifdef BIGSI_HIP_TUNING      // (the one-word-per-lane form: an A/B variant, not in the product library -- DESIGN.md section 7)
-#define BIGSI_LAUNCH_COUNT_VEC1(H)                                                                                          \
-    if (c.vec == 1) hipLaunchKernelGGL((k_and_count<P COMMA H COMMA CountT COMMA 1 COMMA 1>), BIGSI_COUNT_ARGS);          \
-    else if (c.half) hipLaunchKernelGGL((k_and_count<P COMMA H COMMA CountT COMMA 3>), BIGSI_COUNT_ARGS);                  \
-    else
-#else
-#define BIGSI_LAUNCH_COUNT_VEC1(H)
-#endif
 #define BIGSI_LAUNCH_COUNT_DEEP(H)                                                                        \
     if (c.deep) hipLaunchKernelGGL((k_and_count<P COMMA H COMMA CountT COMMA 2>), BIGSI_COUNT_ARGS);       \
-    else BIGSI_LAUNCH_COUNT_VEC1(H) hipLaunchKernelGGL((k_and_count<P, H, CountT>), BIGSI_COUNT_ARGS)
+    else hipLaunchKernelGGL((k_and_count<P, H, CountT>), BIGSI_COUNT_ARGS)
     switch (ix->h) {
     case 1: BIGSI_LAUNCH_COUNT(1); break;
     case 2: BIGSI_LAUNCH_COUNT(2); break;
@@ -1694,7 +1616,6 @@ static void launch_count_wide(bigsi_hip_batch *b, const CountLaunch &c, uint32_t
     }
 #undef BIGSI_LAUNCH_COUNT
 #undef BIGSI_LAUNCH_COUNT_DEEP
-#undef BIGSI_LAUNCH_COUNT_VEC1
 #undef BIGSI_COUNT_ARGS
 #undef COMMA
 }
@@ -1715,35 +1636,13 @@ static int compact(bigsi_hip_batch *b, HitBufs &hb, const void *src, uint32_t n_
 // Reads against a narrow index: K1 + K2 + K4 in one launch (k_reads_fused) when the batch qualifies.
 static bool reads_fusable(const bigsi_hip_batch *b, uint32_t flags)
 {
-    static const int fuse = env_int("BIGSI_HIP_FUSE_READS", 1);
     const bigsi_hip_index *ix = b->ix;
     const bool exact = b->exact;
-    return fuse && b->k == 31 && b->total_pos > 0 && b->max_pos <= 63 && b->n_seqs <= kReadsMaxSeqs && b->wv <= (uint64_t)kBlock * kVec &&
+    return b->k == 31 && b->total_pos > 0 && b->max_pos <= 63 && b->n_seqs <= kReadsMaxSeqs && b->wv <= (uint64_t)kBlock * kVec &&
            ix->h >= 2 && ix->h <= 4 && !b->ext_bitmaps && !b->ext_counts && b->result_cols == 0 &&
            !(flags & (BIGSI_RUN_SKIP_COMPACT | BIGSI_RUN_K1_GLOBAL | BIGSI_RUN_EARLY_EXIT | BIGSI_RUN_NO_SORT)) &&
            (exact || (flags & BIGSI_RUN_SPARSE_COUNTS));     // the fused kernel keeps counters in registers: hits only
 }
-
-#ifdef BIGSI_HIP_TUNING
-uint64_t g_call_trace[16];
-uint64_t g_call_last;
-// tuning builds only: host time per phase of bigsi_hip_search_batch since the last reset (ns sums: stage, run, export, wait,
-// collect; out[15] = calls)
-extern "C" int bigsi_hip_debug_call_trace(uint64_t *out, int reset)
-{
-    if (out) memcpy(out, g_call_trace, sizeof g_call_trace);
-    if (reset) memset(g_call_trace, 0, sizeof g_call_trace);
-    return BIGSI_OK;
-}
-// tuning builds only (not declared in include/bigsi_hip.h): the phase timestamps of the last k_reads_fused launch, 8 per workgroup
-extern "C" int bigsi_hip_debug_phases(bigsi_hip_index *ix, uint64_t *out, uint32_t n_groups)
-{
-    BIGSI_ENTER(ix);
-    HIP_TRY(hipStreamSynchronize(ix->stream));
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), std::min<uint32_t>(n_groups, 1024u) * 64ull));
-    return BIGSI_OK;
-}
-#endif
 
 // Where K1 reads a load's tables and sequences.  Normally the device copies (create / reload / a flushed deferred load).  A one-call
 // search whose input is small reads them straight from the pinned staging (zero copy: scripts/probe/latency_probe.hip prices a 64 KB
@@ -1808,13 +1707,11 @@ static int launch_reads_fused(bigsi_hip_batch *b, hipStream_t st = nullptr, bool
     b->exported_inline = false;
     if (inline_export) {
         TRY(export_prepare(b, st));
-        if (b->exp_flagged) b->exported_inline = true;
-        else b->exp_serial--;          // (tuning builds with the event route: the export kernel as usual)
+        b->exported_inline = true;
     }
     const K1Src src = k1_src(b);
     // one read read in place: its bytes go in the kernel arguments, not over the host link (SeqArg, bigsi_kernels.hpp)
-    static const int arg_env = env_int("BIGSI_HIP_SEQ_BY_ARG", 1);
-    const bool by_arg = arg_env && src.one_len && src.one_len <= kSeqArgRead;
+    const bool by_arg = src.one_len && src.one_len <= kSeqArgRead;
     SeqArg<kSeqArgRead> read_arg;
     if (by_arg) read_arg = src.by_value<kSeqArgRead>();
     else memset(read_arg.w, 0, sizeof read_arg.w);
@@ -1830,29 +1727,14 @@ static int launch_reads_fused(bigsi_hip_batch *b, hipStream_t st = nullptr, bool
     // rows of at most kBlock words, counting: one word per lane (8-byte loads: half the registers -- 8 wavefronts per SIMD instead
     // of 4 -- and twice the lanes that hold columns).  Interleaved A/B at C2: counting 1377 -> 1523 M lookups/s; the exact kernel
     // (6 -> 8 wavefronts per SIMD) 1563 -> 1534 M: stays at two words per lane
-    static const int vec1_exact = env_int("BIGSI_HIP_READS_VEC1_EXACT", 0), vec1_count = env_int("BIGSI_HIP_READS_VEC1_COUNT", 1);
     const bool narrow = b->wv <= (uint64_t)kBlock;
-#ifdef BIGSI_HIP_TUNING
-    static const int reads_unr = env_int("BIGSI_HIP_READS_UNROLL", 16);
-#define BIGSI_READS_UNR(H)                                                                                                          \
-    if (b->exact && reads_unr == 8) hipLaunchKernelGGL((k_reads_fused<H COMMA true COMMA kVec COMMA 8>), BIGSI_READS_ARGS);           \
-    else if (b->exact && reads_unr == 12) hipLaunchKernelGGL((k_reads_fused<H COMMA true COMMA kVec COMMA 12>), BIGSI_READS_ARGS);    \
-    else if (b->exact && reads_unr == 24) hipLaunchKernelGGL((k_reads_fused<H COMMA true COMMA kVec COMMA 24>), BIGSI_READS_ARGS);    \
-    else
-#else
-#define BIGSI_READS_UNR(H)
-#endif
     // a handful of reads (a latency-bound call): the exact route splits each query's rows over the two halves of its workgroup
-    static const int split_max = env_int("BIGSI_HIP_READS_SPLIT_MAX", 64);
-    const bool split = b->wv <= (uint64_t)kBlock && (int)b->n_seqs <= split_max;
+    const bool split = narrow && b->n_seqs <= 64;
 #define BIGSI_READS(H)                                                                              \
-    BIGSI_READS_UNR(H)                                                                              \
     if (split && b->exact) hipLaunchKernelGGL((k_reads_fused<H COMMA true COMMA kVec COMMA 16 COMMA true>), BIGSI_READS_ARGS);     \
     else if (split) hipLaunchKernelGGL((k_reads_fused<H COMMA false COMMA kVec COMMA 16 COMMA true>), BIGSI_READS_ARGS);          \
-    else                                                                                            \
-    if (b->exact && narrow && vec1_exact) hipLaunchKernelGGL((k_reads_fused<H COMMA true COMMA 1>), BIGSI_READS_ARGS);   \
     else if (b->exact) hipLaunchKernelGGL((k_reads_fused<H COMMA true>), BIGSI_READS_ARGS);                \
-    else if (narrow && vec1_count) hipLaunchKernelGGL((k_reads_fused<H COMMA false COMMA 1>), BIGSI_READS_ARGS);       \
+    else if (narrow) hipLaunchKernelGGL((k_reads_fused<H COMMA false COMMA 1>), BIGSI_READS_ARGS);       \
     else hipLaunchKernelGGL((k_reads_fused<H COMMA false>), BIGSI_READS_ARGS)
     switch (ix->h) {
     case 2: BIGSI_READS(2); break;
@@ -1860,7 +1742,6 @@ static int launch_reads_fused(bigsi_hip_batch *b, hipStream_t st = nullptr, bool
     default: BIGSI_READS(4); break;
     }
 #undef BIGSI_READS
-#undef BIGSI_READS_UNR
 #undef BIGSI_READS_ARGS
 #undef COMMA
     HIP_TRY(hipGetLastError());
@@ -1868,23 +1749,41 @@ static int launch_reads_fused(bigsi_hip_batch *b, hipStream_t st = nullptr, bool
     return BIGSI_OK;
 }
 
-// the stream K1 and the row sort run on.  Default: the index stream itself.  BIGSI_HIP_K1_OVERLAP=1 moves them to the pre
-// stream so that they overlap the row-AND kernel of the batch before; measured a LOSS at C3 (exact: K2 1.93 -> 2.12-2.22 ms,
-// the late-placed workgroups break the lock-step sweep of k_and_exact; counts: +-0), kept for A/B runs only
-static hipStream_t k1_stream(const bigsi_hip_index *ix)
+// The launch rule of a large exact batch (one slice, `blocks_per_q` workgroups per query of `wv`-word results): several launches, each
+// a whole number of workgroups per CU (launches of 384 or 640 workgroups measured 0.72-0.78 of peak, 512 / 768 / 1024: 0.82-0.85) with
+// about 1600-2000 LIVE wavefronts: all co-resident, sweeping the address-ordered row lists together, and no more bytes in flight than
+// the memory system schedules well -- 10 M x 100 k (13 live wavefronts per query in 4 workgroups): 512 workgroups per launch 0.853 of
+// peak, 1024: 0.819, 256: 0.68; a 12.5 k-sample shard (2 live wavefronts per workgroup): 1024 workgroups 0.773, 512: 0.581.  Queries
+// per launch a multiple of 8 (the blockIdx -> XCD map).  A batch is cut only from two launches' worth of workgroups on.
+struct ExactLaunch {
+    uint64_t blocks;       // workgroups per launch
+    uint32_t queries;      // queries per launch
+};
+static ExactLaunch exact_launch(uint64_t wv, uint64_t blocks_per_q)
 {
-    static const int overlap = env_int("BIGSI_HIP_K1_OVERLAP", 0);
-    return overlap ? ix->pre_stream : ix->stream;
+    const uint64_t waves_per_q = ceil_div(wv, 64 * kVec);      // wavefronts of a query that hold columns
+    const uint64_t kb = round_up(ceil_div((uint64_t)1600 * blocks_per_q, waves_per_q), 256);
+    return {kb, (uint32_t)std::max<uint64_t>(8, (kb / blocks_per_q) / 8 * 8)};
 }
 
-// see bigsi_internal.hpp; the same arithmetic as the launch rule in bigsi_batch_run below (256-thread workgroups, one slice)
+// small batches: every query's row list is cut into this many slices so that ~2k wavefronts are in flight (see map_block); `waves`:
+// wavefronts that hold columns in the whole batch
+// (one 1 kbp query on 100 k samples, its slices spread over all XCDs (map_block): exact 35 / 14.7 / 16.6 / 22.9 us at
+// 16 / 64 / 128 / 256 slices, counting 59 / 31 / 30 / 32 us; beyond that the atomics that combine the slices show)
+// (counting, round 4: a slice of ~10 k-mers leaves 4 bit-sliced planes instead of 5 for k_count_combine to add up -- one
+// 1 kbp query on 100 k samples at 0.4, the whole call: 60 slices 50.3 us, 96: 47.0, 128: 49.0; exact: 60 -> 36.3, 96 -> 35.8, 128 -> 41)
+static uint32_t row_slices(uint64_t waves, uint64_t max_pos, bool exact)
+{
+    if (waves >= 1024) return 1;
+    return (uint32_t)std::min<uint64_t>({exact ? 64u : 96u, ceil_div(2048, std::max<uint64_t>(waves, 1)), std::max<uint64_t>(max_pos / (exact ? 16 : 10), 1)});
+}
+
+// see bigsi_internal.hpp: bigsi_batch_run's launch rule for 256-thread workgroups
 uint32_t bigsi_exact_launch_queries(const bigsi_hip_index *ix)
 {
     const uint64_t wv = ceil_div(ix->n_cols, 64);
     if (wv == 0) return 8;
-    const uint64_t tiles = ceil_div(wv, (uint64_t)256 * kVec), waves_per_q = ceil_div(wv, (uint64_t)64 * kVec);
-    const uint64_t kb = round_up(ceil_div((uint64_t)1600 * tiles, waves_per_q), 256);
-    return (uint32_t)std::max<uint64_t>(8, (kb / tiles) / 8 * 8);
+    return exact_launch(wv, ceil_div(wv, (uint64_t)256 * kVec)).queries;
 }
 
 enum K1Route { K1_ELEMENTS, K1_WAVE, K1_LDS, K1_GLOBAL };
@@ -1897,17 +1796,14 @@ struct K1Plan {
 static K1Plan k1_plan(const bigsi_hip_batch *b, bool force_global)
 {
     K1Plan p;
-    static const int k1_global = env_int("BIGSI_HIP_K1_GLOBAL", 0);
-    static const int k1_wave = env_int("BIGSI_HIP_K1_WAVE", 1);
     if (b->elements) { p.route = K1_ELEMENTS; return p; }
-    if (!force_global && !k1_global && k1_wave && b->max_pos <= 64) { p.route = K1_WAVE; return p; }
+    if (!force_global && b->max_pos <= 64) { p.route = K1_WAVE; return p; }
     // dedupe table of the LDS route: 4 slots per position when that fits the LDS window (shorter probe chains), else 2
     p.hs_cap = (uint32_t)round_up(std::max<uint64_t>(b->max_pos, 1), 4);
     p.sq_bytes = (uint32_t)round_up(b->max_len + 16, 16);
     // (a handful of queries -- a latency-bound call -- have the LDS to themselves: 8 slots per position, insert phase of one 1 kbp
     // query 2.04 / 1.08 / 0.80 us at 2 / 4 / 8)
-    static const int tab_mult_env = env_int("BIGSI_HIP_K1_TABMULT", 0);      // A/B: 2 = half the LDS per workgroup, longer probe chains
-    p.tab_mult = tab_mult_env == 2 ? 2u : tab_mult_env == 4 ? 4u : (tab_mult_env == 8 || b->n_seqs <= 32) ? 8u : 4u;
+    p.tab_mult = b->n_seqs <= 32 ? 8u : 4u;
     for (;; p.tab_mult /= 2) {
         p.tab_cap = 2;
         while (p.tab_cap < p.tab_mult * b->max_pos && p.tab_cap < (1u << 30)) p.tab_cap <<= 1;
@@ -1915,7 +1811,7 @@ static K1Plan k1_plan(const bigsi_hip_batch *b, bool force_global)
         if (p.lds <= 60 * 1024 || p.tab_mult == 2) break;
     }
     // fused single-launch K1 (dedupe table + sequence in LDS) when every query fits the default 64 KiB dynamic-LDS window
-    p.route = (!force_global && !k1_global && b->max_pos <= kLdsMaxPos && p.lds <= 60 * 1024) ? K1_LDS : K1_GLOBAL;
+    p.route = (!force_global && b->max_pos <= kLdsMaxPos && p.lds <= 60 * 1024) ? K1_LDS : K1_GLOBAL;
     return p;
 }
 
@@ -1933,18 +1829,9 @@ static int run_kmerize(bigsi_hip_batch *b, double threshold, bool force_global =
     const uint64_t ps_words = preset ? preset->words : 0, ps_value = preset ? preset->value : 0;
     bigsi_hip_index *ix = b->ix;
     EventPair ep{};
-    hipStream_t ks = k1_stream(ix);
-    // K1 rewrites arrays the previous run of THIS batch may still be reading (K2/K4 on the index stream, a gathered
-    // compaction on the gather stream); other batches' kernels are not waited for -- that is the overlap
-    if (ks != ix->stream) {
-        if (b->dirty) {
-            HIP_TRY(hipStreamSynchronize(ix->stream));
-            b->dirty = false;
-        } else if (b->done) {
-            HIP_TRY(hipStreamWaitEvent(ks, b->done, 0));
-        }
-    }
-    // (on the index stream itself the callers' own ordering applies, as for every other entry point)
+    hipStream_t ks = ix->stream;
+    // K1 rewrites arrays a gathered compaction of the previous run of THIS batch may still be reading on the gather stream (on the
+    // index stream itself the callers' own ordering applies, as for every other entry point)
     if (b->g_done && b->gstream && b->gstream != ks) HIP_TRY(hipStreamWaitEvent(ks, b->g_done, 0));
     TRY(b->rows.reserve(std::max<uint64_t>(b->total_pos, 1) * ix->h * 8));
     const K1Plan plan = k1_plan(b, force_global);
@@ -1982,8 +1869,7 @@ static int run_kmerize(bigsi_hip_batch *b, double threshold, bool force_global =
     if (plan.route == K1_LDS) {
         // one thread per position for small batches (latency); once there are several queries per CU anyway, smaller
         // workgroups that loop over the positions let more queries overlap their barrier-separated phases
-        static const int k1_block_env = env_int("BIGSI_HIP_K1_BLOCK", 0);
-        const uint32_t block_cap = k1_block_env > 0 ? (uint32_t)k1_block_env : (b->n_seqs >= 1024 ? 256u : 1024u);
+        const uint32_t block_cap = b->n_seqs >= 1024 ? 256u : 1024u;
         uint32_t block = 64;
         while (block < b->max_pos && block < block_cap) block <<= 1;
         if (want_sorted) {
@@ -1993,8 +1879,7 @@ static int run_kmerize(bigsi_hip_batch *b, double threshold, bool force_global =
         TRY(ev_begin(ix, &ep, ks));
         // a handful of gene-length queries (a latency-bound call): the hashing of a query's unique k-mers is spread over several
         // workgroups (k_kmerize_lds, `parts`)
-        static const int parts_env = env_int("BIGSI_HIP_K1_PARTS", 8);
-        const uint32_t parts = (parts_env > 1 && !(parts_env & (parts_env - 1)) && !want_sorted && b->max_pos <= block && b->max_pos >= 256 && (uint64_t)b->n_seqs * parts_env <= 256) ? (uint32_t)parts_env : 1u;
+        const uint32_t parts = (!want_sorted && b->max_pos <= block && b->max_pos >= 256 && b->n_seqs <= 32) ? 8u : 1u;
 #define BIGSI_K1_LDS_(KF, ARGB, SARG)                                                                                           \
     hipLaunchKernelGGL((k_kmerize_lds<KF, ARGB>), dim3(b->n_seqs * parts), dim3(block), lds, ks, src.seqs, src.seq_off,           \
                        src.pos_off, b->k, ix->h, ix->m, threshold, tab_cap, tab_mult, hs_cap, sq_bytes, b->first_pos.as<uint32_t>(), b->tmp.as<uint32_t>(), \
@@ -2002,10 +1887,9 @@ static int run_kmerize(bigsi_hip_batch *b, double threshold, bool force_global =
                        b->num_unique.as<uint32_t>(), b->min_kmers.as<uint32_t>(), want_sorted ? b->rows_sorted.as<uint64_t>() : (uint64_t *)nullptr, \
                        ps_p, ps_words, ps_value, src.pos_off_out, src.one_len, parts, SARG)
         // one sequence read in place (a one-call search): short enough, its bytes go in the kernel arguments (SeqArg)
-        static const int arg_env = env_int("BIGSI_HIP_SEQ_BY_ARG", 1);
 #define BIGSI_K1_LDS(KF)                                                                                   \
-    if (arg_env && src.one_len && src.one_len <= kSeqArgSmall) BIGSI_K1_LDS_(KF, kSeqArgSmall, src.by_value<kSeqArgSmall>());       \
-    else if (arg_env && src.one_len && src.one_len <= kSeqArgLarge) BIGSI_K1_LDS_(KF, kSeqArgLarge, src.by_value<kSeqArgLarge>());  \
+    if (src.one_len && src.one_len <= kSeqArgSmall) BIGSI_K1_LDS_(KF, kSeqArgSmall, src.by_value<kSeqArgSmall>());       \
+    else if (src.one_len && src.one_len <= kSeqArgLarge) BIGSI_K1_LDS_(KF, kSeqArgLarge, src.by_value<kSeqArgLarge>());  \
     else BIGSI_K1_LDS_(KF, 0, SeqArg<0>{})
         if (b->k == 31) BIGSI_K1_LDS(31);
         else BIGSI_K1_LDS(0);
@@ -2063,28 +1947,15 @@ static int run_kmerize(bigsi_hip_batch *b, double threshold, bool force_global =
     return BIGSI_OK;
 }
 
-// K1's outputs become visible to the index stream (K2, K4, lookups): it waits for the pre stream's work of this batch
-static int k1_publish(bigsi_hip_batch *b)
-{
-    bigsi_hip_index *ix = b->ix;
-    if (k1_stream(ix) == ix->stream) return BIGSI_OK;       // same stream: already ordered
-    if (!b->k1_done) HIP_TRY(hipEventCreateWithFlags(&b->k1_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->k1_done, k1_stream(ix)));
-    HIP_TRY(hipStreamWaitEvent(ix->stream, b->k1_done, 0));
-    return BIGSI_OK;
-}
-
 // a deferred load (batch_load): the staged tables and sequences go up now, ahead of this run's first kernel on its stream
 static int flush_upload(bigsi_hip_batch *b, hipStream_t st, bool k1_reads_host = false)
 {
     if (!b->upload_deferred) return BIGSI_OK;
     // a one-call search with a small input: this run's K1 (one of the single-launch routes) reads pin_up itself
-    static const int zc_env = env_int("BIGSI_HIP_ZERO_COPY", 1);
-    b->zero_copy = zc_env && k1_reads_host && b->one_call && b->pin_up_bytes <= kZeroCopyBytes;
+    b->zero_copy = k1_reads_host && b->one_call && b->pin_up_bytes <= kZeroCopyBytes;
     // ... unless many workgroups would each fetch their own few bytes over the link: then one small kernel copies the staging
     // with wide loads first (k_stage_in), and K1 reads the device arrays
-    static const int stage_min = env_int("BIGSI_HIP_STAGE_KERNEL_MIN", 8 << 10);
-    if (b->zero_copy && b->n_seqs > 1 && b->pin_up_bytes >= (size_t)stage_min) {
+    if (b->zero_copy && b->n_seqs > 1 && b->pin_up_bytes >= (size_t)(8 << 10)) {
         const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(b->pin_up_bytes, (uint64_t)kBlock * 16), 64);
         hipLaunchKernelGGL(k_stage_in, dim3(grid), dim3(kBlock), 0, st, static_cast<const uint8_t *>(b->pin_up), b->upload.as<uint8_t>(), (uint64_t)b->pin_up_bytes);
         HIP_TRY(hipGetLastError());
@@ -2141,8 +2012,7 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         TRY(flush_upload(b, st, true));
         TRY(ev_begin(ix, &fe, st, true));
         b->weak_fp = (flags & BIGSI_RUN_WEAK_FINGERPRINT) != 0;
-        static const int inline_env = env_int("BIGSI_HIP_INLINE_EXPORT", 1);
-        TRY(launch_reads_fused(b, st, one_call && inline_env && b->n_seqs == 1));
+        TRY(launch_reads_fused(b, st, one_call && b->n_seqs == 1));
         TRY(ev_end(ix, &fe, ix->ev_and, st));
         b->run_h = ix->h;
         b->fused_run = true;
@@ -2164,32 +2034,17 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     // compaction waits between workgroups, as they do; each kind has the device to its own launches)
     TRY(quiesce_reads(ix));
     b->run_stream = ix->stream;
-    // K1e: address-ordered copy of the row lists for K2 (BIGSI_HIP_SORT_ROWS=0 streams them in hash order instead)
-    static const int sort_rows = env_int("BIGSI_HIP_SORT_ROWS", 1);
-    static const int sort_min_rows = env_int("BIGSI_HIP_SORT_MIN_ROWS", 1024);
+    // K1e: address-ordered copy of the row lists for K2
     // (not for the few queries of a latency-bound call either: their row lists are cut into slices over many workgroups -- see
     // `slices` below -- and the ordering buys nothing, it only lengthens the chain of kernels: 10 us of a 65 us single query)
     // caller-owned result buffers (a shard's slot of a gather buffer): a bitmap can be preset and sliced like the batch's own
     // (the counting path then cuts its hit mask from the slices' summed partial counts, k_count_combine); caller-owned counters are
     // written in place, without presets
     const bool sliceable = !b->ext_counts;
-    const bool few = (uint64_t)b->n_seqs * ceil_div(b->wv, 64 * kVec) < 1024 && sliceable;
-    const bool want_sorted = sort_rows && b->exact && !few && !(flags & BIGSI_RUN_NO_SORT) && b->total_pos && b->max_pos * ix->h >= (uint64_t)sort_min_rows;
-    // small batches: cut every query's row list into slices so that ~2k wavefronts are in flight (see map_block)
-    static const int slices_env = env_int("BIGSI_HIP_SLICES", 0);
-    uint32_t slices = 1;
-    {
-        const uint64_t waves = (uint64_t)b->n_seqs * ceil_div(b->wv, 64 * kVec);
-        if (slices_env > 0) slices = (uint32_t)slices_env;
-        // (one 1 kbp query on 100 k samples, its slices spread over all XCDs (map_block): exact 35 / 14.7 / 16.6 / 22.9 us at
-        // 16 / 64 / 128 / 256 slices, counting 59 / 31 / 30 / 32 us; beyond that the atomics that combine the slices show)
-        // (counting, round 4: a slice of ~10 k-mers leaves 4 bit-sliced planes instead of 5 for k_count_combine to add up -- one
-        // 1 kbp query on 100 k samples at 0.4, the whole call: 60 slices 50.3 us, 96: 47.0, 128: 49.0; exact: 60 -> 36.3, 96 -> 35.8, 128 -> 41)
-        else if (waves < 1024 && b->exact) slices = (uint32_t)std::min<uint64_t>({64, ceil_div(2048, std::max<uint64_t>(waves, 1)), std::max<uint64_t>(b->max_pos / 16, 1)});
-        else if (waves < 1024) slices = (uint32_t)std::min<uint64_t>({96, ceil_div(2048, std::max<uint64_t>(waves, 1)), std::max<uint64_t>(b->max_pos / 10, 1)});
-        if (!sliceable) slices = 1;
-        slices = std::max<uint32_t>(slices, 1);
-    }
+    const uint64_t all_waves = (uint64_t)b->n_seqs * ceil_div(b->wv, 64 * kVec);
+    const bool few = all_waves < 1024 && sliceable;
+    const bool want_sorted = b->exact && !few && !(flags & BIGSI_RUN_NO_SORT) && b->total_pos && b->max_pos * ix->h >= 1024;
+    const uint32_t slices = sliceable ? row_slices(all_waves, b->max_pos, b->exact) : 1;
     // planes needed for the largest possible count = max k-mers of any sequence in the batch
     const uint64_t maxu = b->max_pos;
     const int P = maxu < (1ull << 6) ? 6 : maxu < (1ull << 10) ? 10 : maxu < (1ull << 12) ? 12 : maxu < (1ull << 16) ? 16 : 32;
@@ -2203,11 +2058,11 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     // K1 (its LDS route emits the sorted list itself; the other routes leave that to k_sort_rows below)
     EventPair ep{};
     bool sorted_by_k1 = false;
-    if (!was_idle && b->job.done && b->job.device_work) HIP_TRY(hipStreamWaitEvent(k1_stream(ix), b->job.done, 0));      // (as on the read path above)
+    if (!was_idle && b->job.done && b->job.device_work) HIP_TRY(hipStreamWaitEvent(ix->stream, b->job.done, 0));      // (as on the read path above)
     if (!was_idle && b->done_stale && b->run_stream && b->run_stream != ix->stream) HIP_TRY(hipStreamSynchronize(b->run_stream));      // (a read run of this workspace)
     {
         const K1Route route = k1_plan(b, (flags & BIGSI_RUN_K1_GLOBAL) != 0).route;
-        TRY(flush_upload(b, k1_stream(ix), route == K1_WAVE || route == K1_LDS));
+        TRY(flush_upload(b, ix->stream, route == K1_WAVE || route == K1_LDS));
     }
     TRY(run_kmerize(b, threshold, (flags & BIGSI_RUN_K1_GLOBAL) != 0, want_sorted, &sorted_by_k1, &preset));
     b->dirty = true;        // until `done` is recorded at the end
@@ -2220,68 +2075,52 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         TRY(b->rows_sorted.reserve(std::max<uint64_t>(b->total_pos, 1) * ix->h * 8));
         uint32_t shift = 0;
         while (((ix->m - 1) >> shift) >= (uint64_t)kSortBuckets) shift++;
-        TRY(ev_begin(ix, &ep, k1_stream(ix)));
+        TRY(ev_begin(ix, &ep));
         // 1024 threads per query for long row lists (a 1 kbp query at h=4 has 3880 rows), 256 otherwise
         if (b->max_pos * ix->h >= 2048)
-            hipLaunchKernelGGL((k_sort_rows<1024>), dim3(b->n_seqs), dim3(1024), 0, k1_stream(ix), b->rows.as<uint64_t>(), b->rows_sorted.as<uint64_t>(),
+            hipLaunchKernelGGL((k_sort_rows<1024>), dim3(b->n_seqs), dim3(1024), 0, ix->stream, b->rows.as<uint64_t>(), b->rows_sorted.as<uint64_t>(),
                                b->d_pos_off.as<uint64_t>(), b->num_unique.as<uint32_t>(), ix->h, 1u, shift);
         else
-            hipLaunchKernelGGL((k_sort_rows<kBlock>), dim3(b->n_seqs), dim3(kBlock), 0, k1_stream(ix), b->rows.as<uint64_t>(), b->rows_sorted.as<uint64_t>(),
+            hipLaunchKernelGGL((k_sort_rows<kBlock>), dim3(b->n_seqs), dim3(kBlock), 0, ix->stream, b->rows.as<uint64_t>(), b->rows_sorted.as<uint64_t>(),
                                b->d_pos_off.as<uint64_t>(), b->num_unique.as<uint32_t>(), ix->h, 1u, shift);
         HIP_TRY(hipGetLastError());
-        TRY(ev_end(ix, &ep, ix->ev_km, k1_stream(ix)));
+        TRY(ev_end(ix, &ep, ix->ev_km));
         k2_rows = b->rows_sorted.as<uint64_t>();
     }
-    TRY(k1_publish(b));
     // K2
-    static const int and_block_env = [] { int v = env_int("BIGSI_HIP_AND_BLOCK", 256); return (v >= 64 && v <= 1024 && v % 64 == 0) ? v : 256; }();
     // the counting kernels are compiled for at most 256 threads per workgroup (register budget of the plane arrays)
     // one wavefront per workgroup for batches of a few thousand wavefronts (80 ... 300 gene-length queries on 100 k samples):
     // they are a single launch, a CU's share of it is what bounds it, and 4-wavefront workgroups leave the CUs unevenly loaded
     // (320 / 576 / 800 workgroups on 256 CUs: 0.69 / 0.68 / 0.71 of peak against 0.81 / 0.76 / 0.76 with 64 threads); the large
     // launches, sized in whole workgroups per CU, keep 256 threads (0.85 against 0.79)
     // (exact batches large enough for the launch rule below to cut them -- from 256 such queries on -- are not "mid")
-    const uint64_t all_waves = (uint64_t)b->n_seqs * ceil_div(b->wv, 64 * kVec);
-    bool mid = and_block_env == 256 && all_waves >= 1024 && all_waves < 4096;
+    bool mid = all_waves >= 1024 && all_waves < 4096;
     if (mid) {
-        const uint64_t t256 = ceil_div(b->wv, 256 * kVec), wq = ceil_div(b->wv, 64 * kVec);
-        const uint64_t blocks256 = ceil_div(b->n_seqs, 8) * 8 * t256, kb256 = round_up(ceil_div(1600 * t256, wq), 256);
+        const uint64_t t256 = ceil_div(b->wv, 256 * kVec), blocks256 = ceil_div(b->n_seqs, 8) * 8 * t256;
         // ... nor are batches that already are a whole number of 4-wavefront workgroups per CU (256 queries on a 62.5 k-sample
         // shard: 512 workgroups, 0.80-0.82 either way)
-        if (blocks256 % 256 == 0 || (b->exact && blocks256 >= 2 * kb256)) mid = false;
+        if (blocks256 % 256 == 0 || (b->exact && blocks256 >= 2 * exact_launch(b->wv, t256).blocks)) mid = false;
     }
     // (a sliced exact launch -- a latency-bound call -- in workgroups of two wavefronts: the pieces spread more evenly over the CUs and the
     // stragglers end sooner; one 1 kbp query on 100 k samples, the call: 256 -> 41.9, 128 -> 41.2, 64 -> 41.4 us; counting: no difference)
-    static const int and_block_set = env_int("BIGSI_HIP_AND_BLOCK", 0);
-    const int and_block = mid ? 64 : (slices > 1 && b->exact && !and_block_set) ? 128 : b->exact ? and_block_env : std::min(and_block_env, 256);
+    const int and_block = mid ? 64 : (slices > 1 && b->exact) ? 128 : 256;
     // row loads a lane keeps in flight: 8, or 4 when 8 would put more bytes in flight on the chip (queries of the launch x row bytes x
     // loads) than the memory system schedules well -- the optimum measured at 8-13 MB.  Interleaved A/B: 256 queries per launch on
     // 62.5 k-sample shards (7.8 KB rows: 16 MB at 8 loads): 4 -> +3.3 % (C4 shard 263 -> 272 M lookups/s) / +2.2 % (north-star shard),
     // 6 -> +1.5 %, 2 -> -17 %; unchunked C3 launches of 160-248 queries (16-25 MB): 4 -> +2 ... +9 %.  At 12.8 MB 8 stays: C3's 128-query
     // launches (4: -5 %) and C3 split over 2 / 4 / 8 GPUs -- 256 x 6.3 KB, 512 x 3.1 KB, 1024 x 1.6 KB rows per launch (4: -7 / -10 /
-    // -7 %).  BIGSI_HIP_AND_UNROLL (tuning builds) forces one.
-    static const int and_unroll_env = env_int("BIGSI_HIP_AND_UNROLL", 0);
+    // -7 %).
     const uint32_t tiles = (uint32_t)ceil_div(b->wv, (uint64_t)and_block * kVec);
-    // large exact batches go out as several launches, each a whole number of workgroups per CU (launches of 384 or 640
-    // workgroups measured 0.72-0.78 of peak, 512 / 768 / 1024: 0.82-0.85) with about 1600-2000 LIVE wavefronts: all co-resident,
-    // sweeping the address-ordered row lists together, and no more bytes in flight than the memory system schedules well --
-    // 10 M x 100 k (13 live wavefronts per query in 4 workgroups): 512 workgroups per launch 0.853 of peak, 1024: 0.819, 256:
-    // 0.68; a 12.5 k-sample shard (2 live wavefronts per workgroup): 1024 workgroups 0.773, 512: 0.581.  Queries per launch
-    // a multiple of 8 (the blockIdx -> XCD map).  The counting kernel measured -4 ... 0 % chunked and stays one launch.
-    static const int k2_blocks = env_int("BIGSI_HIP_K2_BLOCKS", 0);          // > 0: workgroups per launch, fixed
-    static const int k2_waves = env_int("BIGSI_HIP_K2_WAVES", 1600);         // live wavefronts a launch should reach at least
+    // large exact batches go out as several launches (exact_launch); the counting kernel measured -4 ... 0 % chunked and stays one launch
     const uint64_t blocks_per_q = (uint64_t)tiles * slices;
     uint32_t chunk_q = b->n_seqs;
     {
         const uint64_t total_blocks = ceil_div(b->n_seqs, 8) * 8 * blocks_per_q;
         if (total_blocks > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "batch too large for one launch (%llu workgroups)", (unsigned long long)total_blocks);
-        uint64_t kb = k2_blocks > 0 ? (uint64_t)k2_blocks : 0;
-        if (!kb && slices == 1) {
-            const uint64_t waves_per_q = ceil_div(b->wv, 64 * kVec);      // wavefronts of a query that hold columns
-            kb = round_up(ceil_div((uint64_t)k2_waves * blocks_per_q, waves_per_q), 256);
+        if (slices == 1 && b->exact) {
+            const ExactLaunch el = exact_launch(b->wv, blocks_per_q);
+            if (total_blocks >= 2 * el.blocks) chunk_q = el.queries;
         }
-        if (kb > 0 && b->exact && total_blocks >= 2 * kb)
-            chunk_q = (uint32_t)std::max<uint64_t>(8, (kb / blocks_per_q) / 8 * 8);
     }
     uint32_t n_launches = 0;
     if (b->exact) {
@@ -2289,7 +2128,6 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         if (!out) { TRY(b->bitmaps.reserve((size_t)b->n_seqs * b->wv_pad * 8)); out = b->bitmaps.as<uint64_t>(); }
         if (slices > 1 && !preset.done) HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)b->n_seqs * b->wv_pad * 8, ix->stream));
         TRY(ev_begin(ix, &ep, nullptr, true));
-        static const int and_nt = env_int("BIGSI_HIP_AND_NT", 1);     // 0: plain loads (A/B against non-temporal)
         for (uint32_t q0 = 0; q0 < b->n_seqs; q0 += chunk_q, n_launches++) {
             const uint32_t q1 = std::min<uint64_t>((uint64_t)q0 + chunk_q, b->n_seqs);
             unsigned grid = (unsigned)((slices > 1 ? (uint64_t)(q1 - q0) : ceil_div(q1 - q0, 8) * 8) * blocks_per_q), l_block = (unsigned)and_block;
@@ -2299,7 +2137,7 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
                 // thousand wavefronts one-wavefront workgroups (see `mid` above), with fewer the sliced launch of a small batch
                 const uint64_t waves_r = (uint64_t)(q1 - q0) * ceil_div(b->wv, 64 * kVec);
                 if (waves_r < 1024) {
-                    l_slices = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({64, ceil_div(2048, std::max<uint64_t>(waves_r, 1)), std::max<uint64_t>(b->max_pos / 16, 1)}));
+                    l_slices = row_slices(waves_r, b->max_pos, true);
                     if (l_slices > 1) HIP_TRY(hipMemsetAsync(out + (uint64_t)q0 * b->wv_pad, 0xFF, (size_t)(q1 - q0) * b->wv_pad * 8, ix->stream));
                     grid = (unsigned)((l_slices > 1 ? (uint64_t)(q1 - q0) : ceil_div(q1 - q0, 8) * 8) * (uint64_t)tiles * l_slices);
                 } else if (grid % 256 != 0) {
@@ -2308,23 +2146,14 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
                     grid = (unsigned)(ceil_div(q1 - q0, 8) * 8 * (uint64_t)l_tiles);
                 }
             }
-#define COMMA ,
 #define BIGSI_LAUNCH_EXACT(U)                                                                                                  \
     hipLaunchKernelGGL((k_and_exact<U>), dim3(grid), dim3(l_block), 0, ix->stream, ix->d_index, ix->stride_words, (uint32_t)b->wv, \
                        ix->n_cols, k2_rows, b->d_pos_off.as<uint64_t>(), b->num_unique.as<uint32_t>(), ix->h, q0,    \
                        q1, l_tiles, out, b->wv_pad, l_slices, (flags & BIGSI_RUN_EARLY_EXIT) ? 1u : 0u)
             const uint64_t in_flight_at_8 = (uint64_t)(q1 - q0) * b->wv * 8 * 8;
-            const int and_unroll = and_unroll_env ? and_unroll_env : (in_flight_at_8 > (29ull << 19) /* 14.5 MB */ && l_slices == 1 ? 4 : 8);
-            if (and_unroll == 4) BIGSI_LAUNCH_EXACT(4);
-#ifdef BIGSI_HIP_TUNING
-            else if (and_unroll == 2) BIGSI_LAUNCH_EXACT(2);
-            else if (and_unroll == 6) BIGSI_LAUNCH_EXACT(6);
-            else if (and_unroll == 16) BIGSI_LAUNCH_EXACT(16);
-#endif
-            else if (!and_nt) BIGSI_LAUNCH_EXACT(8 COMMA false);
+            if (in_flight_at_8 > (29ull << 19) /* 14.5 MB */ && l_slices == 1) BIGSI_LAUNCH_EXACT(4);
             else BIGSI_LAUNCH_EXACT(8);
 #undef BIGSI_LAUNCH_EXACT
-#undef COMMA
         }
         HIP_TRY(hipGetLastError());
         TRY(ev_end(ix, &ep, ix->ev_and, nullptr, n_launches));
@@ -2352,23 +2181,12 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         // fewer than ~3 wavefronts per SIMD in the whole grid (e.g. 128 gene-length queries): the software-pipelined loop,
         // whose wavefronts load the next k-mers' rows while adding the current ones (5.6 -> 6.3 TB/s at 128 x 2-4 kbp; with a
         // full grid other wavefronts already cover the ALU phase and it measured -2 ... +0 %)
-        static const int deep_env = env_int("BIGSI_HIP_COUNT_DEEP", -1);
         const uint64_t grid_waves = (uint64_t)b->n_seqs * tiles * (and_block / 64);
         // (only with >= 12 planes, i.e. queries of >= 1024 k-mers: at 10 planes the ALU phase is short and it measured -2 %)
-        const bool deep = deep_env >= 0 ? deep_env != 0 : (slices == 1 && P >= 12 && grid_waves < 3 * 1024);
+        const bool deep = slices == 1 && P >= 12 && grid_waves < 3 * 1024;
         const uint32_t early = ((flags & BIGSI_RUN_EARLY_EXIT) && sparse && slices == 1) ? 1u : 0u;
-        // one word per lane (8-byte loads, half the plane registers: 8 instead of 4-5 wavefronts per SIMD) -- tuning builds only:
-        // interleaved A/B +-0 at C3 (h = 4), -3.5 % on the north-star shard, -2 % on the C5 shard (h = 3): these kernels are at the
-        // memory system's random-row rate, not short of wavefronts (unlike the read kernel, where the same change is +10 %)
-        static const int count_vec1 = env_int("BIGSI_HIP_COUNT_VEC1", 0);
-        const int vec = (count_vec1 && slices == 1 && !(deep && !early) && (ix->h == 3 || ix->h == 4) && P <= 16) ? 1 : 2;
-        const uint32_t ctiles = vec == 1 ? (uint32_t)ceil_div(b->wv, (uint64_t)and_block) : tiles;
-        if (ceil_div(b->n_seqs, 8) * 8 * (uint64_t)ctiles * slices > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "batch too large for one launch");
-        // half the row loads in flight per lane (tuning builds; what gives the EXACT kernel +2-3 % on 62.5 k-sample shards): -5 % on the
-        // north-star shard at 0.4, +-0 on the C5 shard and at C3 -- the counting kernel keeps 8-12
-        static const int count_half = env_int("BIGSI_HIP_COUNT_HALF", 0);
-        const bool half = count_half == 1 && slices == 1 && !(deep && !early) && (ix->h == 3 || ix->h == 4);
-        const CountLaunch cl{k2_rows, (unsigned)and_block, ctiles, out, cstride, hb, sparse, slices, deep && !early, early, partial, planes_out, half, vec};
+        if (ceil_div(b->n_seqs, 8) * 8 * (uint64_t)tiles * slices > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "batch too large for one launch");
+        const CountLaunch cl{k2_rows, (unsigned)and_block, tiles, out, cstride, hb, sparse, slices, deep && !early, early, partial, planes_out};
         for (uint32_t q0 = 0; q0 < b->n_seqs; q0 += chunk_q, n_launches++)
             launch_count(b, P, cl, q0, (uint32_t)std::min<uint64_t>((uint64_t)q0 + chunk_q, b->n_seqs));
         if (slices > 1) {        // the slices' partial counts -> totals, hit mask, counters
@@ -2439,8 +2257,7 @@ static int compact_ex(bigsi_hip_batch *b, HitBufs &hb, const void *src, bool fro
         // bit vectors (the AND bitmap / the fused count >= min_kmers mask): group totals, then prefix + ordered write
         // (k_hits_totals, k_hits_write: no waiting between workgroups).  `write_only` (the lists overflowed and were grown)
         // runs the write pass again: the totals are still there.
-        static const int k4_groups = env_int("BIGSI_HIP_K4_GROUPS", (int)kHitsMaxGroups);
-        const uint64_t max_groups = (uint64_t)std::min<int>(std::max(k4_groups, 1), (int)kHitsMaxGroups);
+        const uint64_t max_groups = kHitsMaxGroups;
         // a handful of items (one or two gene-length queries: a latency-bound call) go to ONE workgroup, which needs nobody's totals
         const uint32_t ipb = nchunks <= 16 ? (uint32_t)nchunks : (uint32_t)ceil_div(nchunks, max_groups);
         const uint64_t ngroups = ceil_div(nchunks, ipb);
@@ -2449,17 +2266,15 @@ static int compact_ex(bigsi_hip_batch *b, HitBufs &hb, const void *src, bool fro
             hipLaunchKernelGGL(k_hits_totals, dim3((unsigned)ngroups), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv, b->n_seqs,
                                n_shards, chunks, ipb, hb.chunk_hits.as<uint32_t>());
         // a one-call search whose compaction is ONE workgroup (a gene-length query or two): that workgroup exports the results itself
-        static const int k4_export = env_int("BIGSI_HIP_K4_EXPORT", 1);
-        const bool inline_export = k4_export && b->one_call && &hb == &b->hits && !write_only && ngroups == 1 && n_shards == 1 && chunks <= 16 && st == b->ix->stream;
+        const bool inline_export = b->one_call && &hb == &b->hits && !write_only && ngroups == 1 && n_shards == 1 && chunks <= 16 && st == b->ix->stream;
         if (inline_export) {
             TRY(export_prepare(b, st));
-            if (b->exp_flagged) b->exported_inline = true;
-            else b->exp_serial--;          // (tuning builds with the event route: the export kernel as usual)
+            b->exported_inline = true;
         }
         hipLaunchKernelGGL(k_hits_write, dim3((unsigned)ngroups), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv, b->n_seqs,
                            n_shards, chunks, shard_cols, b->num_unique.as<uint32_t>(), ipb, hb.chunk_hits.as<uint32_t>(),
                            hb.hit_off.as<uint64_t>(), hb.col(), hb.cnt(), hb.capacity(), counters, b->count_bytes, b->wv_pad * 64, own_shard,
-                           b->exported_inline && inline_export ? static_cast<uint64_t *>(b->pin_out) : nullptr, b->exp_spec, b->uniq.as<uint32_t>(),
+                           inline_export ? static_cast<uint64_t *>(b->pin_out) : nullptr, b->exp_spec, b->uniq.as<uint32_t>(),
                            (volatile uint64_t *)b->pin_flag, b->exp_serial);
         HIP_TRY(hipGetLastError());
         return BIGSI_OK;
@@ -2888,11 +2703,6 @@ static int presence_begin(bigsi_hip_batch *b, const uint64_t *hit_offsets, const
     std::vector<uint64_t> &hit_pos0 = job.hit_pos0;
     std::vector<PresencePair> pairs;
     std::vector<PresenceWave> waves;          // (k_presence_bits: a wavefront = up to 64 pairs of one query)
-    std::vector<PresenceWave> few;            // (k_presence_bits_sparse: queries with few pairs, one entry each: lanes = k-mers there)
-    // (tuning builds: queries with at most this many pairs go to k_presence_bits_sparse.  Interleaved A/B on the C5 shard, 259 hits in
-    // 256 queries per batch: 245.5 -> 239.5 M lookups/s -- the kernel that wastes no lanes issues its requests faster and takes more
-    // from the row-AND kernel it runs beside (0.974 -> 0.997 ms) than the one-live-lane form that trickles them.  Off.)
-    static const int sparse_max = env_int("BIGSI_HIP_K5_SPARSE_MAX", 0);
     hit_seq.resize(n_hits); hit_q.resize(n_hits); perm.resize(n_hits); hit_pos0.resize(n_hits);
     pairs.clear();
     for (uint64_t t = 0; t < n_hits; t++) perm[t] = (uint32_t)t;
@@ -2934,8 +2744,7 @@ static int presence_begin(bigsi_hip_batch *b, const uint64_t *hit_offsets, const
             perm[lo + r] = src;
             if ((uint64_t)(c >> 6) != last_word) { words++; last_word = c >> 6; }
         }
-        if (sparse_max > 0 && pairs.size() - first_pair <= (size_t)sparse_max) few.push_back(PresenceWave{(uint32_t)first_pair, (uint32_t)(pairs.size() - first_pair)});
-        else for (size_t f = first_pair; f < pairs.size(); f += 64) waves.push_back(PresenceWave{(uint32_t)f, (uint32_t)std::min<size_t>(64, pairs.size() - f)});
+        for (size_t f = first_pair; f < pairs.size(); f += 64) waves.push_back(PresenceWave{(uint32_t)f, (uint32_t)std::min<size_t>(64, pairs.size() - f)});
         max_u = std::max(max_u, b->h_num_unique[q]);
         max_n = std::max(max_n, b->h_num_kmers[q]);
         alg += (uint64_t)b->h_num_unique[q] * b->run_h * words * 8 +
@@ -2957,8 +2766,7 @@ static int presence_begin(bigsi_hip_batch *b, const uint64_t *hit_offsets, const
     const size_t o_str = 0, o_seq = round_up(o_str + (n_hits + 1) * 8, 256);
     const size_t o_perm = round_up(o_seq + n_hits * 4, 256), o_pos0 = round_up(o_perm + n_hits * 4, 256), o_pairs = round_up(o_pos0 + n_hits * 8, 256);
     const size_t o_waves = round_up(o_pairs + pairs.size() * sizeof(PresencePair), 256);
-    const size_t o_few = o_waves + waves.size() * sizeof(PresenceWave);
-    const size_t o_q = round_up(o_few + few.size() * sizeof(PresenceWave), 256), o_hoff = round_up(o_q + n_hits * 4, 256);
+    const size_t o_q = round_up(o_waves + waves.size() * sizeof(PresenceWave), 256), o_hoff = round_up(o_q + n_hits * 4, 256);
     // (K6) per rank: k-mers the hit found, unique k-mers of its sequence
     const size_t o_found = round_up(o_hoff + (nq + 1) * 8ull, 256), o_uniq = round_up(o_found + (packed ? n_hits * 4 : 0), 256);
     const size_t in_bytes = packed ? o_uniq + n_hits * 4 : o_hoff + (nq + 1) * 8ull;
@@ -2972,7 +2780,6 @@ static int presence_begin(bigsi_hip_batch *b, const uint64_t *hit_offsets, const
     memcpy(stage + o_pos0, hit_pos0.data(), n_hits * 8);
     memcpy(stage + o_pairs, pairs.data(), pairs.size() * sizeof(PresencePair));
     memcpy(stage + o_waves, waves.data(), waves.size() * sizeof(PresenceWave));
-    memcpy(stage + o_few, few.data(), few.size() * sizeof(PresenceWave));
     memcpy(stage + o_q, hit_q.data(), n_hits * 4);
     for (uint32_t q = 0; q <= nq; q++) reinterpret_cast<uint64_t *>(stage + o_hoff)[q] = hit_offsets[q] - h0;
     if (packed)
@@ -3008,15 +2815,12 @@ static int presence_begin(bigsi_hip_batch *b, const uint64_t *hit_offsets, const
         b->marks_at = b->pres_desc.p;
     }
     const dim3 grid_a((unsigned)ceil_div(std::max<uint64_t>(waves.size(), 1), kBlock / 64), (unsigned)ceil_div(std::max<uint32_t>(max_u, 1), 16), 1);
-    static const int k5_waves = env_int("BIGSI_HIP_K5_WAVES", 2);
 #define BIGSI_PRESENCE_ARGS                                                                                                        \
     grid_a, dim3(kBlock), 0, ps, ix->d_index, ix->stride_words, b->rows.as<uint64_t>(), b->d_pos_off.as<uint64_t>(),            \
         b->num_unique.as<uint32_t>(), ix->h, (uint32_t)waves.size(), (const PresenceWave *)(din + o_waves), (const PresencePair *)(din + o_pairs),   \
         b->pres_bits.as<uint16_t>(), n_chunks
 #define COMMA ,
-#define BIGSI_PRESENCE(H)                                                                          \
-    if (k5_waves == 4) hipLaunchKernelGGL((k_presence_bits<H COMMA 4>), BIGSI_PRESENCE_ARGS);        \
-    else hipLaunchKernelGGL((k_presence_bits<H COMMA 2>), BIGSI_PRESENCE_ARGS)
+#define BIGSI_PRESENCE(H) hipLaunchKernelGGL((k_presence_bits<H COMMA 2>), BIGSI_PRESENCE_ARGS)
     if (!waves.empty()) switch (ix->h) {
     case 1: BIGSI_PRESENCE(1); break;
     case 2: BIGSI_PRESENCE(2); break;
@@ -3028,25 +2832,6 @@ static int presence_begin(bigsi_hip_batch *b, const uint64_t *hit_offsets, const
 #undef BIGSI_PRESENCE
 #undef BIGSI_PRESENCE_ARGS
 #undef COMMA
-#ifdef BIGSI_HIP_TUNING
-    if (!few.empty()) {
-        // queries with few pairs: lanes = unique k-mers (k_presence_bits_sparse)
-        const dim3 grid_s((unsigned)few.size(), (unsigned)ceil_div(std::max<uint32_t>(max_u, 1), kBlock), 1);
-#define BIGSI_PRESENCE_SPARSE(H)                                                                                                        \
-    hipLaunchKernelGGL((k_presence_bits_sparse<H>), grid_s, dim3(kBlock), 0, ps, ix->d_index, ix->stride_words, b->rows.as<uint64_t>(),   \
-                       b->d_pos_off.as<uint64_t>(), b->num_unique.as<uint32_t>(), ix->h, (const PresenceWave *)(din + o_few),             \
-                       (const PresencePair *)(din + o_pairs), b->pres_bits.as<uint16_t>(), n_chunks)
-        switch (ix->h) {
-        case 1: BIGSI_PRESENCE_SPARSE(1); break;
-        case 2: BIGSI_PRESENCE_SPARSE(2); break;
-        case 3: BIGSI_PRESENCE_SPARSE(3); break;
-        case 4: BIGSI_PRESENCE_SPARSE(4); break;
-        case 5: BIGSI_PRESENCE_SPARSE(5); break;
-        default: BIGSI_PRESENCE_SPARSE(0); break;
-        }
-#undef BIGSI_PRESENCE_SPARSE
-    }
-#endif
     HIP_TRY(hipGetLastError());
     if (packed) {
         // K6: position-ordered bits of every hit and its score record (written at the hit's place in the caller's order)
@@ -3205,19 +2990,15 @@ static int export_prepare(bigsi_hip_batch *b, hipStream_t st)
     const size_t o_uniq = (n + 2ull) * 8, o_col = o_uniq + ((3ull * n + 1) & ~1ull) * 4, bytes = o_col + 8 * spec;
     TRY(pinned_reserve(&b->pin_out, &b->pin_out_cap, bytes));
     // completion: the kernel's last workgroup writes the export's serial into a pinned word the host spins on (no event record, no
-    // hipEventSynchronize: a 1 kbp query's call is ~57 us, of which an event wait is several).  BIGSI_HIP_EXPORT_FLAG=0 (tuning
-    // builds): the event, as before.
-    static const int use_flag = env_int("BIGSI_HIP_EXPORT_FLAG", 1);
-    if (use_flag && !b->pin_flag) {
+    // hipEventSynchronize: a 1 kbp query's call is ~57 us, of which an event wait is several)
+    if (!b->pin_flag) {
         HIP_TRY(hipHostMalloc((void **)&b->pin_flag, 64, hipHostMallocCoherent | hipHostMallocMapped));
         *b->pin_flag = 0;
         TRY(b->exp_count.reserve(256));
         HIP_TRY(hipMemsetAsync(b->exp_count.p, 0, 256, st));
     }
-    if (!use_flag && !b->exp_done) HIP_TRY(hipEventCreateWithFlags(&b->exp_done, hipEventDisableTiming));
     b->exp_spec = (uint32_t)spec;
     b->exp_serial++;
-    b->exp_flagged = use_flag != 0;
     b->exp_stream = st;
     return BIGSI_OK;
 }
@@ -3232,26 +3013,22 @@ int bigsi_batch_export(bigsi_hip_batch *b)
     const uint32_t n = b->n_seqs;
     TRY(export_prepare(b, st));
     const uint64_t spec = b->exp_spec;
-    const bool use_flag = b->exp_flagged;
     if (b->fused_run) {
         // a read run: its export also puts the hit lists in query order (k_export_reads); workgroups own ranges of queries
         // (queries per workgroup, A/B at 1000 reads in one call: 1024 -> 51.2 us, 256 -> 47.7, 64 -> 47.8)
-        static const int per_wg = env_int("BIGSI_HIP_EXPORT_READS_PER_WG", kBlock);
-        const unsigned rgrid = (unsigned)std::min<uint64_t>(ceil_div(n, (uint64_t)std::max(per_wg, 1)), 64);
+        const unsigned rgrid = (unsigned)std::min<uint64_t>(ceil_div(n, (uint64_t)kBlock), 64);
         hipLaunchKernelGGL(k_export_reads, dim3(std::max(rgrid, 1u)), dim3(kBlock), 0, st, hb.q_start.as<uint64_t>(), hb.q_cnt.as<uint32_t>(), n,
                            b->uniq.as<uint32_t>(), hb.col(), hb.cnt(), hb.capacity(), (uint32_t)spec, static_cast<uint64_t *>(b->pin_out), b->exp_count.as<uint32_t>(),
-                           (volatile uint64_t *)(use_flag ? b->pin_flag : nullptr), b->exp_serial);
+                           (volatile uint64_t *)b->pin_flag, b->exp_serial);
         HIP_TRY(hipGetLastError());
-        if (!use_flag) HIP_TRY(hipEventRecord(b->exp_done, st));
         return BIGSI_OK;
     }
     // the hits it carries along speculatively are few: one workgroup unless the batch is large (one workgroup needs no counter)
     const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(std::max<uint64_t>(3ull * n, spec), 4 * kBlock), 64);
     hipLaunchKernelGGL(k_export_results, dim3(std::max(grid, 1u)), dim3(kBlock), 0, st, hb.hit_off.as<uint64_t>(), n, b->fused_run ? 1u : 0u, b->uniq.as<uint32_t>(),
                        hb.col(), hb.cnt(), (uint32_t)spec, static_cast<uint64_t *>(b->pin_out), b->exp_count.as<uint32_t>(),
-                       (volatile uint64_t *)(use_flag ? b->pin_flag : nullptr), b->exp_serial);
+                       (volatile uint64_t *)b->pin_flag, b->exp_serial);
     HIP_TRY(hipGetLastError());
-    if (!use_flag) HIP_TRY(hipEventRecord(b->exp_done, st));
     return BIGSI_OK;
 }
 
@@ -3260,10 +3037,6 @@ int bigsi_batch_export(bigsi_hip_batch *b)
 static int export_wait(bigsi_hip_batch *b)
 {
     if (!b->exp_serial) return fail(BIGSI_ERR_STATE, "internal: nothing exported");
-    if (!b->exp_flagged) {
-        HIP_TRY(hipEventSynchronize(b->exp_done));
-        return BIGSI_OK;
-    }
     volatile uint64_t *f = b->pin_flag;
     const uint64_t want = b->exp_serial;
     for (uint32_t spins = 0; *f != want; spins++) {
@@ -3285,7 +3058,6 @@ int bigsi_batch_collect(bigsi_hip_batch *b, uint32_t *num_kmers, uint32_t *num_u
     if (!b) return fail(BIGSI_ERR_STATE, "internal: nothing exported");
     TRY(use_device(b->ix));
     TRY(export_wait(b));
-    CALL_MARK(4);
     HitBufs &hb = b->hits;
     const uint32_t n = b->n_seqs;
     const uint64_t *off = static_cast<const uint64_t *>(b->pin_out);
@@ -3337,7 +3109,6 @@ extern "C" int bigsi_hip_lookup(bigsi_hip_index *ix, const char *kmers, uint32_t
     bigsi_hip_batch *b = nullptr;
     TRY(bigsi_hip_batch_create(ix, kmers, off.data(), (uint32_t)u, k, &b));
     int rc = run_kmerize(b, 1.0);
-    if (rc == BIGSI_OK) rc = k1_publish(b);
     const uint64_t wv = ix->wv(), rb = ix->rb();
     if (rc == BIGSI_OK) rc = b->scratch.reserve((size_t)u * wv * 8);
     if (rc == BIGSI_OK) {
@@ -3371,7 +3142,6 @@ extern "C" int bigsi_hip_lookup_raw(bigsi_hip_index *ix, const char *blob, const
     bigsi_hip_batch *b = nullptr;
     TRY(bigsi_hip_batch_create_elements(ix, blob, elem_offsets, one.data(), zero.data(), one.data(), (uint32_t)u, &b));
     int rc = run_kmerize(b, 1.0);
-    if (rc == BIGSI_OK) rc = k1_publish(b);
     const uint64_t wv = ix->wv(), rb = ix->rb();
     if (rc == BIGSI_OK) rc = b->scratch.reserve((size_t)u * wv * 8);
     if (rc == BIGSI_OK) {

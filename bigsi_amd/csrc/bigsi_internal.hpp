@@ -38,30 +38,6 @@ int bigsi_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 
 static inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 static inline uint64_t ceil_div(uint64_t x, uint64_t a) { return (x + a - 1) / a; }
 
-// Tuning knobs (A/B measurements: scripts/ab_*.py) are read from the environment only in builds made with
-// -DBIGSI_HIP_TUNING (csrc/build.sh tuning); the product library takes the defaults and never calls getenv.
-static inline int env_int(const char *name, int dflt)
-{
-#ifdef BIGSI_HIP_TUNING
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
-
-// tuning builds: host timestamps inside bigsi_hip_search_batch (scripts/call_breakdown.py), summed per phase; nothing in the product
-#ifdef BIGSI_HIP_TUNING
-#include <time.h>
-extern uint64_t g_call_trace[16];      // [i] = ns spent up to mark i since the mark before, summed over calls; [15] = calls
-extern uint64_t g_call_last;
-static inline uint64_t call_now() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (uint64_t)t.tv_sec * 1000000000ull + (uint64_t)t.tv_nsec; }
-#define CALL_MARK(i) do { const uint64_t n_ = call_now(); if ((i) == 0) g_call_trace[15]++; else g_call_trace[i] += n_ - g_call_last; g_call_last = n_; } while (0)
-#else
-#define CALL_MARK(i) do { } while (0)
-#endif
-
 // ------------------------------------------------------------------------------ device buffer with growth
 struct DevBuf {
     void *p = nullptr;
@@ -97,14 +73,13 @@ struct EventPair {
     uint32_t launches = 1;      // kernel launches bracketed by the pair (large batches go out as several K2 launches)
 };
 
-constexpr int kReadStreams = 4;            // streams created; kReadStreamsUsed of them take launches (tuning builds: BIGSI_HIP_READ_STREAMS)
+constexpr int kReadStreams = 4;            // streams created; kReadStreamsUsed of them take launches
 constexpr int kReadStreamsUsed = 3;
 
 struct bigsi_hip_index {
     int device = 0;
     hipStream_t stream = nullptr, own_stream = nullptr;
     // the sequences of a batch are uploaded here, so that loading one batch does not wait for the kernels of another
-    // (and, with BIGSI_HIP_K1_OVERLAP=1 only, K1 and the row sort run here too: see k1_stream)
     hipStream_t pre_stream = nullptr;
     hipStream_t rd_stream[kReadStreams] = {};      // k_reads_fused launches alternate over these (created at the first one)
     uint32_t rd_next = 0;
@@ -114,11 +89,10 @@ struct bigsi_hip_index {
     hipEvent_t main_ev = nullptr; // end of the last batch run on the index stream (mark_main)
     uint64_t fused_repeats = 0;   // (rounds 2-3: read launches repeated after a bounded wait ran out; nothing waits any more: stays 0)
     struct bigsi_hip_batch *search_ws = nullptr;      // bigsi_hip_search_batch's workspace, created at its first call
-    struct bigsi_hip_batch *stream_ws[6] = {};        // bigsi_hip_search_stream's workspaces (four in use; up to six in tuning builds)
+    struct bigsi_hip_batch *stream_ws[4] = {};        // bigsi_hip_search_stream's workspaces
     uint64_t m = 0, n_cols = 0, cap_cols = 0, stride_words = 0;
     uint32_t h = 0;
     uint64_t *d_index = nullptr;
-    bool contiguous = false;      // d_index is physically contiguous memory (index_malloc)
     // A handle that does not own its matrix: attached to another process's index over hipIpc (bigsi_hip_open_ipc: closed with
     // hipIpcCloseMemHandle) or a second handle of this process onto an open index (bigsi_hip_open_view: nothing to free).  Such a
     // handle is READ-ONLY: every entry point that writes the matrix fails with BIGSI_ERR_STATE (bigsi_writable).
@@ -242,10 +216,8 @@ struct bigsi_hip_batch {
     bool zero_copy = false;                          // this load's tables + sequences are read by K1 straight from pin_up (no upload)
     bool idle = false;                               // nothing of this batch is in flight (its last export was collected)
     bool done_stale = false;                         // the last run did not record `done` (one-call route): wait on its stream instead
-    hipEvent_t exp_done = nullptr;                   // end of the export kernel (only when the flag below is not used)
     uint64_t *pin_flag = nullptr;                    // coherent pinned word the export kernel's last workgroup writes exp_serial to
     uint64_t exp_serial = 0;                         // serial of the last export queued (0: none)
-    bool exp_flagged = false;                        // the last export signals through pin_flag (the host spins on it)
     hipStream_t exp_stream = nullptr;                // the stream it was queued on
     DevBuf exp_count;                                // the export kernel's finished-workgroups counter
     uint32_t exp_spec = 0;                           // hits the export carried along speculatively
@@ -267,7 +239,6 @@ struct bigsi_hip_batch {
     uint32_t run_h = 0;            // num_hashes the row ids of the last K1 were produced with
     hipEvent_t done = nullptr;     // recorded at the end of every run: fetches wait on it, not on the whole stream, so the
                                    // results of one batch can be read while the next batch's kernels are queued behind it
-    hipEvent_t k1_done = nullptr;  // only when K1 runs on the pre stream: recorded after K1 (+ row sort), the index stream waits on it before K2
     hipEvent_t g_done = nullptr;   // recorded on the gather stream after a gathered compaction (it reads K1's per-query arrays)
     bool dirty = false;            // a run was started and its `done` event has not been recorded (error path): full syncs needed
     hipStream_t gstream = nullptr; // stream of the gathered compaction (null: the index's stream)

@@ -441,17 +441,6 @@ __global__ __launch_bounds__(kBlock) void k_kmer_rows(
     }
 }
 
-#ifdef BIGSI_HIP_TUNING
-// tuning builds only: per-workgroup timestamps of the phases of k_reads_fused / k_kmerize_lds (100 MHz wall clock), read by bigsi_hip_debug_phases
-__device__ uint64_t g_phase[1024 * 8];
-#define BIGSI_PHASE(i) do { if (threadIdx.x == 0) g_phase[(blockIdx.x & 1023u) * 8 + (i)] = wall_clock64(); } while (0)
-#define BIGSI_PHASE_AT(group, i) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_phase[(group) * 8 + (i)] = wall_clock64(); } while (0)
-#define BIGSI_PHASE_IF(cond, group, i) do { if (threadIdx.x == 0 && (cond)) g_phase[(group) * 8 + (i)] = wall_clock64(); } while (0)
-#else
-#define BIGSI_PHASE(i) do { } while (0)
-#define BIGSI_PHASE_AT(group, i) do { } while (0)
-#define BIGSI_PHASE_IF(cond, group, i) do { } while (0)
-#endif
 // K1 fused: ONE launch for batches whose longest query has at most kLdsMaxPos k-mer positions (a 4 kbp query; reads
 // and gene-length queries).  One workgroup per query; the sequence and the dedupe table live in LDS (ds_cmpst / ds_min
 // instead of L2 atomics), and the workgroup goes insert -> resolve -> ordered compaction -> hash without leaving the CU.
@@ -521,7 +510,7 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
                       the workgroup (n <= blockDim.x), no sorted copy: every part dedupes the whole query (same table, same ranks: the
                       representative of a k-mer is its smallest position whatever the order of the inserts), then hashes and writes
                       only its share of the unique k-mers.  One CU takes 4 us to hash the ~970 k-mers of a 1 kbp query for 4 seeds
-                      (scripts/ab_k1_phases.py): that part of a latency-bound call is ALU work, and this spreads it over `parts` CUs */,
+                      (profiles/r05_k1_phases.txt): that part of a latency-bound call is ALU work, and this spreads it over `parts` CUs */,
     const SeqArg<ARGB> sarg)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -551,7 +540,6 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
     uint32_t tsize = 2;
     while (tsize < tab_mult * n) tsize <<= 1;            // load factor <= 1/tab_mult: short probe chains
     const uint32_t mask = tsize - 1;
-    BIGSI_PHASE(0);
     for (uint32_t i = threadIdx.x; i < tsize; i += blockDim.x) tab[i] = kEmpty;
     if constexpr (ARGB > 0) {                            // (one_len <= ARGB, zero-padded to a word by the host; sq / sc hold sq_bytes >= that)
         for (uint32_t j = threadIdx.x; j < (len + 3) / 4; j += blockDim.x) {
@@ -578,7 +566,6 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
         }
     }
     __syncthreads();
-    BIGSI_PHASE(1);
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
         if (KF == 31) {
             uint32_t wf[8];
@@ -589,7 +576,6 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
         }
     }
     __syncthreads();
-    BIGSI_PHASE(2);
     // two positions hold the same k-mer iff their bytes are equal; the stored hashes settle almost every comparison with
     // one LDS word instead of a divergent byte loop
     uint32_t my_slot = 0;                                // where this thread's FIRST position ended up
@@ -605,7 +591,6 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
         if (i == threadIdx.x) my_slot = slot;
     }
     __syncthreads();
-    BIGSI_PHASE(3);
     uint32_t *fp = first_pos + P, *ux = uidx + P, *pu = pos_unique + P, *rp = rep_out + P;
     uint64_t *qrows = rows + P * h;
     // (one scan over threads that each take several CONSECUTIVE positions -- fewer barriers -- measured slower: 0.37 against
@@ -619,7 +604,6 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
         const uint32_t c = i < n ? tab[my_slot] : kEmpty;
         const uint32_t flag = (i < n && c == i) ? 1u : 0u;
         const uint32_t pre = block_exclusive_scan_flag(flag != 0, &u, scan);       // (its barrier: every thread has read its table slot)
-        BIGSI_PHASE(4);
         if (flag) {
             hs[pre] = i;
             tab[i] = pre;
@@ -633,7 +617,6 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
             if (flag) ux[i] = pre;
         }
         const uint32_t per_j = (u + parts - 1) >> pshift, j0 = min(u, part * per_j), j1 = min(u, j0 + per_j);
-        BIGSI_PHASE(5);
         for (uint32_t t = threadIdx.x; t < (j1 - j0) * h; t += blockDim.x) {      // a thread per (unique k-mer, seed): the shortest chain
             const uint32_t tj = t / h, j = j0 + tj, sd = t - tj * h, pos = hs[j];
             if (sd == 0) fp[j] = pos;
@@ -645,7 +628,6 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
             const double mk = ceil((double)u * threshold);
             min_kmers[q] = mk > 0.0 ? (uint32_t)mk : 0u;
         }
-        BIGSI_PHASE(6);
         return;
     }
     for (uint32_t base = 0; base < n; base += blockDim.x) {
@@ -677,7 +659,6 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
         u += tot;
     }
     __syncthreads();
-    BIGSI_PHASE(4);
     if (rows_sorted) {
         // K1e fused: counting sort of the u*h row ids by their top bits, the dedupe table's LDS reused as the histogram
         // (tsize >= 2n buckets: about one row per bucket at h <= 4).  Order inside a bucket depends on atomics; K2's result does not.
@@ -729,9 +710,7 @@ __global__ __launch_bounds__(1024) void k_kmerize_lds(
             }
         }
     }
-    BIGSI_PHASE(5);
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) pu[i] = ux[rp[i]];
-    BIGSI_PHASE(6);
     if (threadIdx.x == 0) {
         num_kmers[q] = n;
         num_unique[q] = u;
@@ -961,12 +940,9 @@ __global__ __launch_bounds__(1024) void k_and_exact(
 {
     const TileMap tm = map_block(blockIdx.x, q0, n_seqs, tiles, slices);
     if (!tm.valid) return;
-    BIGSI_PHASE_IF(blockIdx.x == 0, 1001, 0);
-    BIGSI_PHASE_IF(blockIdx.x == gridDim.x - 4, 1002, 0);
     const uint32_t w0 = (tm.tile * blockDim.x + threadIdx.x) * kVec;
     if (w0 >= wv) return;
     const uint64_t Rall = (uint64_t)num_unique[tm.q] * h;
-    BIGSI_PHASE_IF(blockIdx.x == 0, 1001, 1);
     const uint64_t per = (Rall + slices - 1) / slices;
     uint64_t r = (uint64_t)tm.slice * per;
     const uint64_t R = r + per < Rall ? r + per : Rall;
@@ -987,8 +963,6 @@ __global__ __launch_bounds__(1024) void k_and_exact(
     if (Rall == 0) acc = u64x2{0ull, 0ull};
     acc.x &= valid_mask(w0, n_cols);
     acc.y &= valid_mask(w0 + 1, n_cols);
-    BIGSI_PHASE_IF(blockIdx.x == 0 && (acc.x | 1ull), 1001, 2);
-    BIGSI_PHASE_IF(blockIdx.x == gridDim.x - 4 && (acc.x | 1ull), 1002, 2);
     uint64_t *o = out + (uint64_t)tm.q * out_stride_words + w0;
     if (slices > 1) {
         atomicAnd((unsigned long long *)o, (unsigned long long)acc.x);
@@ -1416,7 +1390,6 @@ __global__ __launch_bounds__(kBlock) void k_hits_write(
         // CONSECUTIVE words of a query -- all its loads in flight together, one scan per query instead of one per 256 words
         // (7.5 -> ~4 us for one query on 100 k samples)
         uint64_t base = 0;
-        BIGSI_PHASE_AT(1000, 0);
         // (the block's header numbers: fetched now, beside the words, not in a round trip of their own behind the scans.  What remains of
         // this route's tail is the system-scope release before the flag: 1.5 us by the stamps -- the posted writes' acknowledgement)
         uint32_t hdr = 0;
@@ -1433,9 +1406,7 @@ __global__ __launch_bounds__(kBlock) void k_hits_write(
                 cnt += (uint32_t)__popcll(bits[j]);
             }
             uint32_t tot;
-            BIGSI_PHASE_AT(1000, 1);
             const uint32_t pre = block_exclusive_scan(cnt, &tot, lds);
-            BIGSI_PHASE_AT(1000, 2);
             if (threadIdx.x == 0) {
                 hit_off[q] = base;
                 if (exp_out) exp_out[q] = base;
@@ -1462,7 +1433,6 @@ __global__ __launch_bounds__(kBlock) void k_hits_write(
                 }
             }
         }
-        BIGSI_PHASE_AT(1000, 3);
         if (threadIdx.x == 0) hit_off[n_seqs] = base;
         if (exp_out) {
             if (threadIdx.x == 0) { exp_out[n_seqs] = base; exp_out[n_seqs + 1] = 0; }
@@ -1470,12 +1440,9 @@ __global__ __launch_bounds__(kBlock) void k_hits_write(
             if (!hdr_early)
                 for (uint32_t i = threadIdx.x; i < 3u * n_seqs; i += kBlock) o32[i] = exp_uniq[i];
             else if (threadIdx.x < 3u * n_seqs) o32[threadIdx.x] = hdr;
-            BIGSI_PHASE_AT(1000, 4);
             __threadfence_system();
-            BIGSI_PHASE_AT(1000, 5);
             __syncthreads();
             if (threadIdx.x == 0) *exp_flag = exp_serial;
-            BIGSI_PHASE_AT(1000, 6);
         }
         return;
     }
@@ -1568,7 +1535,6 @@ __global__ __launch_bounds__(kBlock) void k_reads_fused(
     __shared__ uint32_t lds[16];
     __shared__ uint64_t lds64[kBlock / 64];
     const uint32_t q = blockIdx.x;
-    BIGSI_PHASE(0);
     // ---- K1 on two wavefronts, on packed words.  The query's bytes (<= 93) and their complements are staged in LDS once.
     // Wavefront A finds each k-mer's first occurrence (k_kmerize_wave's scheme with a scalar fast path); wavefront B builds
     // the canonical form of EVERY position (forward words against byte-reversed complement words, compared as big-endian
@@ -1595,13 +1561,11 @@ __global__ __launch_bounds__(kBlock) void k_reads_fused(
             }
         }
         __syncthreads();
-        BIGSI_PHASE(4);
         const bool live = lane < n;
         uint32_t wf[8];                                    // the k-mer at position `lane` (kmer31_words)
         if (wave == wave_a || wave == wave_b) kmer31_words(s_seq, lane, wf);
         if (wave == wave_a) {
             const uint32_t fp = live ? kmer31_fingerprint(wf) & fp_mask : 0u;
-            BIGSI_PHASE(5);
             // rep = the first position holding this lane's k-mer.  Branch-free pass: the lowest lane with the same fingerprint
             // (independent v_readlane / compare / select triples, highest lane first so that the lowest match is kept; a serial
             // loop with a scalar early-out ran at 70 ns per position, all dependency stalls), then one word-by-word check
@@ -1631,7 +1595,6 @@ __global__ __launch_bounds__(kBlock) void k_reads_fused(
                     if (eq) rep = j;
                 }
             }
-            BIGSI_PHASE(6);
             const bool first = live && rep == lane;
             const unsigned long long mask = __ballot(first);
             const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
@@ -1654,7 +1617,6 @@ __global__ __launch_bounds__(kBlock) void k_reads_fused(
                 s_u = u;
                 s_min = mn;
             }
-            BIGSI_PHASE(7);
         }
         if (wave == wave_b) {
             uint32_t k1[8];
@@ -1676,7 +1638,6 @@ __global__ __launch_bounds__(kBlock) void k_reads_fused(
     // rows of configs[1] -- so that three times the bytes are in flight measured +-0: with ~1000 workgroups resident the phase
     // already moves 5.7 TB/s of 1.25 KB rows, and the HBM is the limit, not the round trips.)
     const uint32_t u = s_u;
-    BIGSI_PHASE(1);
     const uint32_t w0 = (SPLIT ? (threadIdx.x & (kBlock / 2 - 1)) : threadIdx.x) * VEC;
     const bool live = (!SPLIT || threadIdx.x < kBlock / 2) && w0 < wv;      // the lanes that own the query's words from here on
     uint64_t hitw[VEC];
@@ -1785,7 +1746,6 @@ __global__ __launch_bounds__(kBlock) void k_reads_fused(
             }
         }
     }
-    BIGSI_PHASE(2);
     if (live) {
         uint64_t *o = out_bits + (uint64_t)q * out_stride_words + w0;
 #pragma unroll
@@ -1811,7 +1771,6 @@ __global__ __launch_bounds__(kBlock) void k_reads_fused(
         if (q == 0) alloc[slot ^ 1u] = 0;          // the next launch of this batch (launches of one batch never overlap) starts from zero
     }
     __syncthreads();
-    BIGSI_PHASE(3);
     const uint64_t start = lds64[0];
     if (mine != 0 && start + tot <= capacity) {      // (else the host sees total > capacity, grows the lists and launches again)
         uint64_t o = start + pre;
@@ -2065,66 +2024,6 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_presence_bits(
             for (int t = 0; t < 16; t++) out |= (uint32_t)(((half ? a[t].y : a[t].x) >> bp) & 1ull) << t;
             bits[presence_bits_at(rank, jc, bits_stride)] = (uint16_t)out;
             rank++;
-        }
-    }
-}
-
-// The same bits for queries with FEW pairs (a thresholded search whose queries have a hit or two each -- BASELINE configs[4]: 259 hits in
-// 256 queries): there a wavefront of the kernel above has one live lane, and 259 hits cost 15 800 wavefronts of 48 loads each.
-// Here lane = unique k-mer: a wavefront takes 64 consecutive k-mers of one query (their row ids: coalesced loads), and for every
-// pair of the query ANDs the h rows' 16-byte word pair of its k-mer; a hit's 64 presence bits are one ballot, stored as four
-// 16-bit chunks.  Same layout out (presence_bits_at), h loads per (k-mer, pair) as before, a sixteenth of the instructions.
-template <int H>
-__global__ __launch_bounds__(kBlock) void k_presence_bits_sparse(
-    const uint64_t *__restrict__ index, uint64_t stride_words, const uint64_t *__restrict__ rows, const uint64_t *__restrict__ pos_off,
-    const uint32_t *__restrict__ num_unique, uint32_t h_rt, const PresenceWave *__restrict__ queries /* one per query: all its pairs */,
-    const PresencePair *__restrict__ pairs, uint16_t *__restrict__ bits, uint32_t bits_stride)
-{
-    constexpr int HH = H > 0 ? H : 1;
-    const uint32_t h = H > 0 ? (uint32_t)H : h_rt;
-    const uint32_t jb = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.y * (kBlock / 64) + (threadIdx.x >> 6))), lane = threadIdx.x & 63u;
-    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)queries[blockIdx.x].first);
-    const uint32_t count = (uint32_t)__builtin_amdgcn_readfirstlane((int)queries[blockIdx.x].count);
-    const uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)pairs[first].q);
-    const uint32_t u = num_unique[q];
-    if (jb * 64u >= u) return;
-    const uint32_t j = jb * 64u + lane;
-    const bool live = j < u;
-    const uint64_t *qrows = rows + pos_off[q] * h;
-    uint64_t r[HH];
-    if (H > 0) {
-#pragma unroll
-        for (int sidx = 0; sidx < HH; sidx++) r[sidx] = live ? qrows[(uint64_t)j * H + sidx] : 0ull;
-    }
-    const u64x2 zero = {0ull, 0ull};
-    for (uint32_t p = 0; p < count; p++) {
-        const uint32_t wpair = (uint32_t)__builtin_amdgcn_readfirstlane((int)pairs[first + p].wpair);
-        uint32_t rank = (uint32_t)__builtin_amdgcn_readfirstlane((int)pairs[first + p].base);
-        const uint64_t mask_lo = pairs[first + p].mask_lo, mask_hi = pairs[first + p].mask_hi;
-        const uint32_t woff = wpair * 2u;
-        u64x2 v = zero;
-        if (live) {
-            if (H > 0) {
-                v = load_row_seg(index, r[0], stride_words, woff);
-#pragma unroll
-                for (int sidx = 1; sidx < HH; sidx++) v &= load_row_seg(index, r[sidx], stride_words, woff);
-            } else {
-                v = load_row_seg(index, qrows[(uint64_t)j * h], stride_words, woff);
-                for (uint32_t sidx = 1; sidx < h; sidx++) v &= load_row_seg(index, qrows[(uint64_t)j * h + sidx], stride_words, woff);
-            }
-        }
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            uint64_t m = by_column(half ? mask_hi : mask_lo);
-            const uint64_t word = half ? v.y : v.x;
-            while (m) {
-                const uint32_t c = (uint32_t)__builtin_ctzll(m);
-                m &= m - 1;
-                const uint64_t ball = __ballot(((word >> bit_of_col(c)) & 1ull) != 0);      // bit L: k-mer 64 * jb + L is present in this hit's sample
-                const uint32_t chunk = 4u * jb + lane;
-                if (lane < 4u && chunk * 16u < u) bits[presence_bits_at(rank, chunk, bits_stride)] = (uint16_t)(ball >> (16u * lane));
-                rank++;
-            }
         }
     }
 }
@@ -2549,245 +2448,10 @@ __global__ __launch_bounds__(kBlock) void k_insert_columns(
 
 constexpr int kTransposeTile = 512, kTransposeSuper = 32;      // rows of a tile pass; supertile edge, in tiles
 
-#ifdef BIGSI_HIP_TUNING
-// ROUNDS 2-6's KERNEL, kept in tuning builds only (BIGSI_HIP_TR_REGS=0; scripts/ab_transpose_regs.sh, scripts/probe/transpose_ab.hip)
-// as the other side of the A/B that k_transpose_regs below is measured against.  The product library does not hold it.
-constexpr int kTransposePitch = 72;
-// The transpose as a bandwidth kernel (full 64-column words; k_insert_columns above keeps the ragged edges).
-// A tile is 512 rows x 512 columns: 64 bytes of each of 512 filters in, 64 bytes of each of 512 rows out, as whole runs
-// (16 bytes per lane), so every sector that crosses the memory interface is used in full and nothing is read-modified-written;
-// a workgroup moves 2 x 2 tiles, which makes the runs 128 bytes on both sides (RT, CT below).  In between, the tile is 64 blocks of 64 x 64 bits; a wavefront
-// transposes a block in registers -- lane l holds the 64 row bits of one column, six butterfly steps (exchange with lane
-// l ^ j, j = 32 .. 1) leave lane i holding the 64 column bits of row i -- reading its operands from and writing its results
-// to LDS (pitch 72 bytes: conflict-free 8-byte accesses for 32 lanes at a stride of one LDS row).
-// Bit order: both the filters and the rows keep the reference's byte format (bit 7 - (i & 7) of byte i >> 3), so in a
-// little-endian uint64 element i sits at bit_of_col(i); by_column() turns that into plain order for the butterfly, and lane
-// l is given column bit_of_col(l) of the word, which puts every result bit where the row format wants it.
-
-// 64 x 64 bit transpose across the lanes of a wavefront, on 32-bit halves (64-bit shifts run at a quarter of the rate):
-// after it, bit k of lane i = bit i of (the original value of) lane k.  Step j (32, 16, .. 1) swaps, between lanes l and
-// l ^ j, the off-diagonal j x j blocks.  Each lane ROTATES what its partner needs into place before the exchange (towards
-// the high bits if the lane has bit j set, towards the low bits otherwise: one v_alignbit with a per-lane amount) and
-// merges what it receives under a per-lane mask (one v_bfi).
-// The exchange itself stays in the vector ALUs: lane ^ 1 and ^ 2 are quad permutes, ^ 4 and ^ 8 two row mirrors each (DPP
-// modifiers of a v_mov), ^ 16 and ^ 32 gfx950's v_permlane16_swap / v_permlane32_swap (each checked lane by lane on the
-// hardware) instead of 11 ds_bpermute through the CU's one LDS crossbar.  Neither this nor a variant with 8 x 8 bit blocks in
-// registers (2x fewer VALU operations) moved the kernel: with the butterflies skipped altogether (BIGSI_HIP_TR_SKIP=1 in a
-// tuning build) it runs at the same rate -- the bound is the access pattern: 128-byte runs at large strides on both sides
-// (RT = CT = 2 below) move 3.5-4.1 TB/s, 64-byte runs 3.1, against the 6.3 TB/s the HBM gives a copy.
-__device__ __forceinline__ uint32_t rotl32v(uint32_t x, uint32_t r) { return __builtin_amdgcn_alignbit(x, x, (32u - r) & 31u); }
-
-template <int J> __device__ __forceinline__ uint32_t lane_xor(uint32_t x, uint32_t lane)
-{
-    constexpr int kQuadXor1 = 0xB1, kQuadXor2 = 0x4E, kQuadReverse = 0x1B, kRowMirror = 0x140, kRowHalfMirror = 0x141;
-    if (J == 1) return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, kQuadXor1, 0xF, 0xF, true);
-    if (J == 2) return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, kQuadXor2, 0xF, 0xF, true);
-    if (J == 4)      // i -> 7 - i within 8 lanes is i ^ 7; reversing each quad is ^ 3
-        return (uint32_t)__builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp((int)x, kRowHalfMirror, 0xF, 0xF, true), kQuadReverse, 0xF, 0xF, true);
-    if (J == 8)      // i ^ 15, then i ^ 7
-        return (uint32_t)__builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp((int)x, kRowMirror, 0xF, 0xF, true), kRowHalfMirror, 0xF, 0xF, true);
-    if (J == 16) {   // odd rows (16 lanes) of the first operand <-> even rows of the second
-        const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-        return (lane & 16u) ? r[0] : r[1];
-    }
-    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return (lane & 32u) ? r[0] : r[1];
-}
-
-__device__ __forceinline__ uint64_t transpose64_lanes(uint64_t a64, uint32_t lane)
-{
-    uint32_t lo = (uint32_t)a64, hi = (uint32_t)(a64 >> 32);
-    {   // j = 32: whole halves change lanes
-        const bool s = (lane & 32u) != 0;
-        const uint32_t recv = lane_xor<32>(s ? lo : hi, lane);
-        lo = s ? recv : lo;
-        hi = s ? hi : recv;
-    }
-#define BIGSI_TR_STEP(J, M)                                                                                  \
-    {                                                                                                        \
-        const bool s = (lane & J) != 0;                                                                      \
-        const uint32_t rot = s ? (uint32_t)J : 32u - (uint32_t)J;   /* s: partner wants my bits J higher; else J lower */ \
-        const uint32_t keep = s ? ~(uint32_t)M : (uint32_t)M;       /* the bits of my own value that stay */  \
-        const uint32_t rl = lane_xor<J>(rotl32v(lo, rot), lane);                                             \
-        const uint32_t rh = lane_xor<J>(rotl32v(hi, rot), lane);                                             \
-        lo = (lo & keep) | (rl & ~keep);                                                                     \
-        hi = (hi & keep) | (rh & ~keep);                                                                     \
-    }
-    BIGSI_TR_STEP(16, 0x0000FFFFu)
-    BIGSI_TR_STEP(8, 0x00FF00FFu)
-    BIGSI_TR_STEP(4, 0x0F0F0F0Fu)
-    BIGSI_TR_STEP(2, 0x33333333u)
-    BIGSI_TR_STEP(1, 0x55555555u)
-#undef BIGSI_TR_STEP
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// two independent blocks at once, step by step: the same operations as two calls of transpose64_lanes, written so that the
-// compiler sees the two chains side by side (k_transpose_tiles, phase 2)
-__device__ __forceinline__ void transpose64_lanes_x2(uint64_t &a64, uint64_t &b64, uint32_t lane)
-{
-    uint32_t lo = (uint32_t)a64, hi = (uint32_t)(a64 >> 32), lo2 = (uint32_t)b64, hi2 = (uint32_t)(b64 >> 32);
-    {
-        const bool s = (lane & 32u) != 0;
-        const uint32_t recv = lane_xor<32>(s ? lo : hi, lane), recv2 = lane_xor<32>(s ? lo2 : hi2, lane);
-        lo = s ? recv : lo;
-        hi = s ? hi : recv;
-        lo2 = s ? recv2 : lo2;
-        hi2 = s ? hi2 : recv2;
-    }
-#define BIGSI_TR_STEP2(J, M)                                                                                 \
-    {                                                                                                        \
-        const bool s = (lane & J) != 0;                                                                      \
-        const uint32_t rot = s ? (uint32_t)J : 32u - (uint32_t)J;                                            \
-        const uint32_t keep = s ? ~(uint32_t)M : (uint32_t)M;                                                \
-        const uint32_t rl = lane_xor<J>(rotl32v(lo, rot), lane), rl2 = lane_xor<J>(rotl32v(lo2, rot), lane); \
-        const uint32_t rh = lane_xor<J>(rotl32v(hi, rot), lane), rh2 = lane_xor<J>(rotl32v(hi2, rot), lane); \
-        lo = (lo & keep) | (rl & ~keep);                                                                     \
-        hi = (hi & keep) | (rh & ~keep);                                                                     \
-        lo2 = (lo2 & keep) | (rl2 & ~keep);                                                                  \
-        hi2 = (hi2 & keep) | (rh2 & ~keep);                                                                  \
-    }
-    BIGSI_TR_STEP2(16, 0x0000FFFFu)
-    BIGSI_TR_STEP2(8, 0x00FF00FFu)
-    BIGSI_TR_STEP2(4, 0x0F0F0F0Fu)
-    BIGSI_TR_STEP2(2, 0x33333333u)
-    BIGSI_TR_STEP2(1, 0x55555555u)
-#undef BIGSI_TR_STEP2
-    a64 = ((uint64_t)hi << 32) | lo;
-    b64 = ((uint64_t)hi2 << 32) | lo2;
-}
-
-__device__ uint32_t g_tr_skip = 0;      // experiment (BIGSI_HIP_TR_SKIP=1): move the tiles without transposing them
-// RT = 1: one 512-row tile per workgroup (64-byte filter runs); 2: two stacked tiles, their 128-byte filter runs loaded in one go.
-// CT = 1: 512 columns per workgroup (64-byte row runs); 2: two tiles side by side, each handled by its own 256 threads in its
-// own LDS buffer, their rows stored together as 128-byte runs (half as many DRAM row activations on the write side).
-template <int RT, int CT>
-__global__ __launch_bounds__(kBlock * CT) void k_transpose_tiles(
-    uint64_t *__restrict__ index, uint64_t stride_words, uint64_t m, uint64_t w_first /* first column word written; even */,
-    uint64_t n_words /* whole 64-column words to write */, const uint8_t *__restrict__ blooms /* filter of column 64 * w_first */,
-    uint64_t /* n_filters: k_transpose_regs' argument; here every word has all its filters */,
-    uint64_t bstride /* bytes between filters; multiple of 16 */, uint64_t nb /* valid bytes of a filter: ceil(m / 8) */,
-    uint32_t rg, uint32_t cg /* tiles per XCD group along rows / columns: powers of two, rg * cg <= 128, cg <= sup_w */,
-    uint32_t sup_w /* supertile width in tiles: a power of two <= 32 */)
-{
-    // ONE buffer per 512 x 512 tile: line L holds, before the transpose, the 64 row-bytes of column L and, after it, the 64
-    // column-bytes of row L.  Block (cw, rc) of 64 x 64 bits sits at lines [64 cw, +64), bytes [8 rc, +8) and its transpose
-    // belongs at lines [64 rc, +64), bytes [8 cw, +8) -- the place of block (rc, cw) -- so blocks are transposed in mirrored
-    // pairs, each written where the other was read (37 KB of LDS per tile instead of 74).
-    __shared__ __attribute__((aligned(16))) uint8_t tiles[CT][kTransposeTile * kTransposePitch];
-    constexpr uint32_t kWordsPerBlock = 8 * CT;
-    // workgroup -> tile in SUPERTILES of 1024 tiles, sup_w wide (32, or fewer when the matrix has fewer tile columns: no
-    // workgroups wasted on tiles beyond its edge) and 1024 / sup_w high: the ~1000 workgroups resident at any time then read
-    // long runs of each filter and write long runs of each row, instead of short pieces strided by a whole row or filter
-    const uint64_t tiles_c = (n_words + kWordsPerBlock - 1) / kWordsPerBlock, sup_c = (tiles_c + sup_w - 1) / sup_w;
-    const uint32_t sup_h = (uint32_t)(kTransposeSuper * kTransposeSuper) / sup_w;
-    const uint64_t sup = blockIdx.x / (kTransposeSuper * kTransposeSuper);
-    const uint32_t within = blockIdx.x % (kTransposeSuper * kTransposeSuper);
-    // inside a supertile: groups of rg x cg neighbouring tiles go to the SAME XCD (block b runs on XCD b % 8), one right after
-    // the other: row-neighbours share the 128-byte lines of the filters, column-neighbours those of the rows, and with
-    // consecutive blocks they landed in different L2s (FETCH_SIZE showed every filter line read about twice)
-    const uint32_t gsz = rg * cg, xcd = within & 7u, sl = within >> 3, t = sl % gsz, g = (sl / gsz) * 8u + xcd;
-    const uint32_t gpr = sup_w / cg;                // groups per supertile row of groups
-    const uint64_t tile_r = (sup / sup_c) * sup_h + (g / gpr) * rg + t % rg;
-    const uint64_t tile_c = (sup % sup_c) * sup_w + (g % gpr) * cg + t / rg;
-    if (tile_r * kTransposeTile * RT >= m || tile_c >= tiles_c) return;
-    const uint64_t byte0 = tile_r * (kTransposeTile / 8) * RT;
-    const uint64_t w0 = tile_c * kWordsPerBlock;
-    const uint32_t words_here = (uint32_t)(n_words - w0 < kWordsPerBlock ? n_words - w0 : kWordsPerBlock);
-    // this thread's 512-column tile (of the workgroup's CT) and its place among that tile's 256 threads
-    const uint32_t ct = threadIdx.x / kBlock, tid = threadIdx.x % kBlock;
-    uint8_t *tile = tiles[ct];
-    const uint32_t cols_here = words_here > 8 * ct ? min(words_here - 8 * ct, 8u) * 64u : 0u;
-    // phase 1: 64 bytes of each column's filter -> tile[col][0..64) (columns beyond the last word: zeros).  A 16-byte load
-    // that starts inside the filter's pitch is always in bounds (pitch and offsets are multiples of 16); bytes past
-    // ceil(m / 8), like bits past m inside the last byte, belong to rows >= m, which phase 3 never stores.
-    // (RT = 2: 8 lanes x 16 bytes = one whole 128-byte line per filter and wave instruction; a thread's parts all have the
-    // same index, so its loads all belong to the same one of the two stacked tiles)
-    constexpr int kParts = 4 * RT, kLoads = kTransposeTile * kParts / kBlock;
-    u64x2 ld[kLoads];
-#pragma unroll
-    for (int it = 0; it < kLoads; it++) {
-        const uint32_t item = it * kBlock + tid, col = item / kParts, part = item % kParts;
-        const uint64_t off = byte0 + part * 16;
-        const bool ok = col < cols_here && off + 16 <= bstride && off < nb;
-        const u64x2 *src = reinterpret_cast<const u64x2 *>(blooms + ((w0 + 8 * ct) * 64 + (ok ? col : 0)) * bstride + (ok ? off : 0));
-        ld[it] = ok ? __builtin_nontemporal_load(src) : u64x2{0ull, 0ull};      // (plain loads / stores measured the same)
-    }
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    const uint32_t mycol = bit_of_col(lane);
-#pragma unroll
-    for (int half = 0; half < RT; half++) {
-    const uint64_t r0 = (tile_r * RT + half) * kTransposeTile;
-    if (half) __syncthreads();                          // phase 3 of the first tile has read the buffer
-#pragma unroll
-    for (int it = 0; it < kLoads; it++) {
-        const uint32_t item = it * kBlock + tid, col = item / kParts, part = item % kParts;
-        if ((int)(part >> 2) != half) continue;
-        uint64_t *d = reinterpret_cast<uint64_t *>(tile + col * kTransposePitch + (part & 3u) * 16);
-        d[0] = ld[it].x;
-        d[1] = ld[it].y;
-    }
-    __syncthreads();
-    // phase 2: the 64 blocks of the 8 x 8 grid, two at a time per wavefront -- ALWAYS two, in one basic block, so that the two
-    // butterfly chains (each ~45 dependent vector operations, DPP / permlane exchanges among them) interleave: the two workgroups
-    // of a CU are rarely in this phase together, and with two wavefronts per SIMD a single chain leaves the ALUs waiting for
-    // their own results (round 6: +3 ... +5 % over one pair {(cw, rc), (rc, cw)} per trip with the second block behind a branch).
-    // Trips 0-6 of a wavefront take the off-diagonal pairs {(x, y), (y, x)}, x < y, number `wave + 4 trip` of the 28 (each block
-    // written where its mirror was read: 37 KB of LDS per tile instead of 74); trip 7 takes the diagonal blocks 2 wave and
-    // 2 wave + 1, each transposed in place.
-    if (!(g_tr_skip & 1u))
-#pragma unroll 1
-    for (uint32_t trip = 0; trip < 8; trip++) {
-        uint32_t x, y, xb, yb;                              // block a = (cw = x, rc = y), block b = (cw = xb, rc = yb)
-        if (trip < 7) {
-            const uint32_t oi = wave + (kBlock / 64) * trip;          // oi -> (x, y) with x < y: row y of the strict lower triangle starts at y (y - 1) / 2
-            y = 1;
-            while (y * (y + 1) / 2 <= oi) y++;
-            x = oi - y * (y - 1) / 2;
-            xb = y, yb = x;
-        } else {
-            x = y = 2 * wave;
-            xb = yb = 2 * wave + 1;
-        }
-        uint8_t *pa = tile + (x * 64) * kTransposePitch + y * 8;        // lines of column word x, bytes of row chunk y
-        uint8_t *pb = tile + (xb * 64) * kTransposePitch + yb * 8;
-        uint64_t va = *reinterpret_cast<const uint64_t *>(pa + mycol * kTransposePitch);
-        uint64_t vb = *reinterpret_cast<const uint64_t *>(pb + mycol * kTransposePitch);
-        va = by_column(va);
-        vb = by_column(vb);
-        transpose64_lanes_x2(va, vb, lane);
-        // every lane of the wavefront has read both blocks before any lane overwrites them (the butterflies in between are
-        // wavefront-wide exchanges), and no other wavefront touches these two blocks.  The transpose of block (x, y) belongs at
-        // (y, x): for an off-diagonal pair that is where b was read (and vice versa), for a diagonal block its own place
-        *reinterpret_cast<uint64_t *>(tile + (y * 64 + lane) * kTransposePitch + x * 8) = va;
-        *reinterpret_cast<uint64_t *>(tile + (yb * 64 + lane) * kTransposePitch + xb * 8) = vb;
-    }
-    __syncthreads();
-    // phase 3: tiles[..][row][0 .. 64) -> the rows' words [w_first + w0, +words_here): 4 * CT lanes per row, 16 bytes each
-#pragma unroll
-    for (int it = 0; it < kTransposeTile * 4 / kBlock; it++) {
-        const uint32_t item = it * (kBlock * CT) + threadIdx.x, row = item / (4 * CT), part = item % (4 * CT);
-        const uint64_t r = r0 + row;
-        if (r >= m || part * 2 >= words_here) continue;
-        const uint64_t *sp = reinterpret_cast<const uint64_t *>(tiles[part >> 2] + row * kTransposePitch + (part & 3u) * 16);
-        uint64_t *dst = index + r * stride_words + w_first + w0 + part * 2;
-        if (part * 2 + 1 < words_here) __builtin_nontemporal_store(u64x2{sp[0], sp[1]}, reinterpret_cast<u64x2 *>(dst));
-        else dst[0] = sp[0];
-    }
-    }
-}
-
-// (Round 6 also built the form that takes a workgroup's two column tiles ONE AFTER THE OTHER through one LDS buffer -- 256 threads,
-// 37 KB, four workgroups per CU, the second tile's loads in flight under the first tile's butterflies, the first tile's rows waiting
-// in registers so that both 64-byte halves of a row's run leave in consecutive store instructions: bit-equal, 3.4-3.7 TB/s against
-// 4.1-4.8 for k_transpose_tiles<1,2>, with non-temporal or plain stores alike (profiles/r06_transpose_seq_ab.txt): the halves do not
-// merge on their way out, and a 64-byte write run is what the bare mover prices at 3.7.  Removed.)
-#endif      // BIGSI_HIP_TUNING
-
 // ------------------------------------------------------------------------------ the transpose without lane butterflies (round 6)
-// k_transpose_tiles spends ~90 vector instructions per 64 x 64 bit block on six exchange steps between lanes, and passes every
-// tile through the LDS twice (in, block by block in place, out); with the filters at an aligned pitch the memory side of it moves
-// 5.0-5.2 TB/s and the kernel 4.1-4.4 (profiles/r06_transpose_ab_aligned.txt: "no phase 2").  k_transpose_regs does the BIT
+// The lane-butterfly transpose of rounds 2-6 (k_transpose_tiles, since removed) spent ~90 vector instructions per 64 x 64 bit
+// block on six exchange steps between lanes, and passed every tile through the LDS twice (in, block by block in place, out); with
+// the filters at an aligned pitch the memory side of it moved 5.0-5.2 TB/s and the kernel 4.1-4.4 (profiles/r06_transpose_ab_aligned.txt: "no phase 2").  k_transpose_regs does the BIT
 // level of the transpose between the REGISTERS of a thread and the BYTE level on the way out of the LDS:
 //   1. a thread loads 16 bytes (128 rows) of EIGHT neighbouring filters -- columns 8 g .. 8 g + 7, the columns of ONE byte of
 //      the rows -- and transposes the 8 x 8 bit blocks between its 8 registers, all 16 byte lanes at once: three steps of
@@ -2834,7 +2498,7 @@ __global__ __launch_bounds__(kBlock * 2 * CW) void k_transpose_regs(
     __shared__ __attribute__((aligned(16))) uint64_t image[64 * kPitch];
     constexpr uint32_t kWordsPerBlock = 16 * CW;        // 1024 CW columns
     auto word_at = [](uint32_t line, uint32_t cb) { return line * kPitch + (cb ^ ((cb >> 2) & 8u)); };
-    // workgroup -> tile: as k_transpose_tiles (supertiles of 1024 tiles, groups of rg x cg neighbours on one XCD)
+    // workgroup -> tile: supertiles of 1024 tiles, groups of rg x cg neighbours on one XCD
     const uint64_t tiles_c = (n_words + kWordsPerBlock - 1) / kWordsPerBlock, sup_c = (tiles_c + sup_w - 1) / sup_w;
     const uint32_t sup_h = (uint32_t)(kTransposeSuper * kTransposeSuper) / sup_w;
     const uint64_t sup = blockIdx.x / (kTransposeSuper * kTransposeSuper);

@@ -106,18 +106,13 @@ extern "C" int bigsi_hip_search_batch(bigsi_hip_index *ix, const char *seqs, con
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
     // the index keeps ONE workspace for this entry point (a caller in a loop pays its ~20 device allocations once; the
     // workspace goes with the index, or right away if a call fails)
-    CALL_MARK(0);
     if (ix->search_ws) ix->search_ws->one_call = true;
     TRY(bigsi_batch_stage(ix, &ix->search_ws, seqs, offsets, n_seqs, k));
-    CALL_MARK(1);
     bigsi_hip_batch *b = ix->search_ws;
     b->one_call = true;      // (a small input is then read by K1 straight from the pinned staging, and the run records no event)
     int rc = bigsi_batch_run(b, threshold, (flags & ~BIGSI_RUN_SKIP_COMPACT) | BIGSI_RUN_SPARSE_COUNTS, true);
-    CALL_MARK(2);
     if (rc == BIGSI_OK) rc = bigsi_batch_export(b);
-    CALL_MARK(3);
     if (rc == BIGSI_OK) rc = bigsi_batch_collect(b, num_kmers, num_unique, min_kmers, hit_offsets, colours, counts, hit_capacity);
-    CALL_MARK(5);
     if (rc != BIGSI_OK && rc != BIGSI_ERR_CAPACITY) {      // (a too small hit buffer is the caller's to retry: offsets are filled in)
         ix->search_ws = nullptr;
         bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
@@ -153,24 +148,26 @@ int search_stream_impl(bigsi_hip_index *ix, const char *seqs, const uint64_t *of
     hit_offsets[0] = 0;
     if (so) { so->bit_offsets[0] = 0; *so->bits_needed = 0; }
     if (n_seqs == 0) return BIGSI_OK;
-    constexpr int kMaxSlots = 6;
     // device batches in flight (1 M reads of 61 bp, host-visible, interleaved: 2 -> 1.14, 3 -> 1.47-1.50, 4 -> 1.51-1.53, 6 -> 1.49-1.51 G
     // lookups/s; gene-length and scored streams +-0)
-    static const int kSlots = std::min(std::max(env_int("BIGSI_HIP_STREAM_SLOTS", 4), 2), kMaxSlots);
-    // a batch = at most 2^20 k-mer positions (gene-length queries: ~1000 of 1 kbp) and at most kChunkSeqs sequences (reads).  With the
-    // read kernel that ordered its hit lists inside the launch (rounds 2-3) 2^14 reads per launch measured best; the wait-free kernel
-    // of round 4 prefers smaller launches, more of them in flight: host-visible over 1 M reads of 61 bp 1.04 / 1.41 / 1.51 / 1.45 G
-    // lookups/s at 1024 / 2048 / 4096 / 16384 reads per batch, over 64 k reads 1.01 / 1.36 / 1.39 / 1.27 G (interleaved, twice each)
-    // thresholded searches of gene-length queries take four times that: the counting kernel is ONE launch per chunk (chunked it measured
-    // -4 ... 0 %, bigsi_batch_run), and every launch pays its tail -- 8192 x 1 kbp at 0.4 on 10 M x 100 k: 8 launches of ~1080 queries
-    // 0.774 of peak by the kernel's clock, one launch of 8192 0.80 (round 6); the counters of a chunk are 2 bytes x samples per query
+    constexpr int kSlots = 4;
+    static_assert(kSlots <= sizeof(ix->stream_ws) / sizeof(ix->stream_ws[0]), "a workspace per slot");
+    // a batch = at most 2^20 k-mer positions (gene-length queries: ~1000 of 1 kbp) and at most kChunkSeqs sequences (reads), whichever
+    // limit a chunk reaches first.  With the read kernel that ordered its hit lists inside the launch (rounds 2-3) 2^14 reads per launch
+    // measured best; the wait-free kernel of round 4 prefers smaller launches, more of them in flight: host-visible over 1 M reads of
+    // 61 bp 1.04 / 1.41 / 1.51 / 1.45 G lookups/s at 1024 / 2048 / 4096 / 16384 reads per batch, over 64 k reads 1.01 / 1.36 / 1.39 /
+    // 1.27 G (interleaved, twice each)
+    // thresholded searches of gene-length queries take four times the positions: the counting kernel is ONE launch per chunk (chunked it
+    // measured -4 ... 0 %, bigsi_batch_run), and every launch pays its tail -- 8192 x 1 kbp at 0.4 on 10 M x 100 k: 8 launches of ~1080
+    // queries 0.774 of peak by the kernel's clock, one launch of 8192 0.80 (round 6).  The sequence cap still comes first for them: 4096
+    // queries of 1 kbp are ~4.0 M positions, under 2^22, so 8192 of them go out as two chunks (two launches) of 4096.  The counters of a
+    // chunk are 2 bytes x samples per query
     const uint64_t kChunkPositions = (threshold == 1.0 || so) ? 1ull << 20 : 1ull << 22;      // (scored: K5 + K6 of a chunk run beside the next chunk's row-AND -- more, smaller chunks)
-    static const int chunk_seqs_env = env_int("BIGSI_HIP_STREAM_SEQS", 0);
-    const uint64_t kChunkSeqs = chunk_seqs_env > 0 ? (uint64_t)chunk_seqs_env : 4096;
+    constexpr uint64_t kChunkSeqs = 4096;
     const uint32_t launch_q = bigsi_exact_launch_queries(ix);
     struct Chunk { uint64_t first; uint32_t n; uint64_t hit0, bit0; bool scoring; };
-    Chunk inflight[kMaxSlots] = {};
-    bool busy[kMaxSlots] = {};       // launched, hit lists not collected yet
+    Chunk inflight[kSlots] = {};
+    bool busy[kSlots] = {};       // launched, hit lists not collected yet
     uint64_t total = 0;              // hits so far (global offset of the next chunk's first hit)
     uint64_t bits_total = 0;         // bytes of presence bits so far
     bool overflow = false, bits_overflow = false;

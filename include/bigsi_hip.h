@@ -27,7 +27,7 @@
  *       MEASUREMENT  fill_synthetic, set_profiling, stats (calibration probe and device-resident filters: bigsi_hip_testing.h).
  *     Not advertised here (exported all the same, declared in include/bigsi_hip_testing.h): hooks for hosts that bring their own
  *     collective (torch.distributed over gloo on a one-GPU test box) and the BIGSI_RUN_* flags that force an A/B route.
- *     The library reads no environment variables (tuning knobs exist only in builds made with -DBIGSI_HIP_TUNING).
+ *     The library reads no environment variables.
  *   - ROW FORMAT: a row is the reference's `bitarray.tobytes()` (bigsi/storage/base.py:85-99):
  *     ceil(num_cols/8) bytes, column c at byte c/8 under mask 0x80 >> (c%8), zero pad bits.
  *     The device stores exactly these bytes, zero-extended to a 128-byte-multiple row stride.
@@ -395,8 +395,8 @@ typedef struct {
     uint64_t and_launches_total; /* row-AND launches since the last reset, timed or not (and_launches counts the timed ones) */
     uint64_t read_launches_repeated; /* always 0 since round 4 (rounds 2-3: read launches repeated after a bounded wait between
                                         workgroups ran out; no workgroup of any kernel waits for another any more); kept for the layout */
-    uint64_t index_contiguous;       /* 1: the matrix got physically contiguous device memory (hipDeviceMallocContiguous: largest
-                                        page-table fragments), 0: the ordinary allocation it falls back to */
+    uint64_t index_contiguous;       /* always 0: the matrix is an ordinary hipMalloc (physically contiguous allocation was tried
+                                        and not shipped); kept for the layout */
     uint64_t exchange_launches;      /* bigsi_hip_batch_run_sharded calls timed (profiling level 1) */
     double exchange_ms;              /* their all-gather + gathered compaction + count all-reduce, by events on the communicator's stream */
 } bigsi_hip_stats_t;

@@ -1,5 +1,10 @@
-"""Interleaved A/B of library builds (BIGSI_HIP_LIB cannot change inside a process, so each arm is a subprocess of
-scripts/ab_one.py and rounds alternate arms): median row-AND kernel time per arm."""
+"""Interleaved A/B of library builds: median row-AND kernel time and step time per arm.
+
+    python scripts/ab_libs.py bigsi_hip,bigsi_hip_b THRESHOLD [ROUNDS] [bench.py arguments ...]
+
+Each arm NAME is bigsi_amd/libNAME.so: build the variant from its own branch with bigsi_amd/csrc/build.sh and copy the .so
+there under a second name.  BIGSI_HIP_LIB cannot change inside a process, so every measurement is a bench.py subprocess
+(--full, 20 steps) with BIGSI_HIP_LIB set to the arm's library, and the rounds alternate the arms."""
 import json, os, subprocess, sys
 import numpy as np
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

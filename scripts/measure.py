@@ -243,7 +243,7 @@ def transpose():
         check(L.bigsi_hip_set_profiling(st.handle, 0))
         moved = 2 * ncols * nb
         st.res.written[:] = True
-        for r in (() if os.environ.get("BIGSI_HIP_TR_SKIP") else (0, 1, 511, 512, m // 2 + 3, m - 1)):
+        for r in (0, 1, 511, 512, m // 2 + 3, m - 1):
             bits = ((blooms[:, r >> 3] >> (7 - (r & 7))) & 1).cpu().numpy()
             assert np.array_equal(st.get_rows_packed([r], (ncols + 7) // 8)[0], np.packbits(bits)), r
         emit("transpose_device", m=m, cols=ncols, kernels_ms=s.transpose_ms, bytes_in_plus_out=moved,

@@ -8,7 +8,6 @@ R=${ROUND:-r06}
 P=gpurun_out/prof
 mkdir -p $P
 B="--full --cpu-seconds 0 --also none --host-visible 0 --alone-steps 0"      # (rocprofv3 averages then cover launches of the timed shape only)
-[ -f bigsi_amd/libbigsi_hip_tuning.so ] || bash bigsi_amd/csrc/build.sh tuning > /dev/null      # (two legs below A/B through it)
 run() { scripts/prof.sh "$@" > /dev/null; }
 python - <<PYEOF > $P/${R}_build.json
 import glob, hashlib, json
@@ -23,7 +22,6 @@ run ${R}_c2              -- python bench.py --workload c2 --steps 4000 --warmup 
 run ${R}_c2_t04          -- python bench.py --workload c2 --steps 4000 --warmup 100 $B --threshold 0.4
 run ${R}_c2_one_stream   -- python bench.py --workload c2 --steps 4000 --warmup 100 $B --one-stream      # the read kernel alone on the device: what roofline.frac of read workloads is priced on
 run ${R}_c2_t04_one_stream -- python bench.py --workload c2 --steps 4000 --warmup 100 $B --one-stream --threshold 0.4
-run ${R}_c2_unfused BIGSI_HIP_LIB=$PWD/bigsi_amd/libbigsi_hip_tuning.so BIGSI_HIP_FUSE_READS=0 -- python bench.py --workload c2 --steps 4000 --warmup 100 $B
 run ${R}_c2_32k_reads    -- python bench.py --workload c2 --steps 200 --warmup 16 $B --batch 32768 --distinct-batches 8
 run ${R}_c4_shard        -- python bench.py --workload c4 --shard-of 8 --gpus 1 --steps 200 --warmup 10 $B
 run ${R}_c5_shard        -- python bench.py --workload c5 --shard-of 8 --gpus 1 --steps 200 --warmup 10 $B
@@ -53,10 +51,6 @@ run ${R}_scored_stream   -- python scripts/scored_stream_probe.py
   scripts/probe/row_probe --gb 10 --row-bytes 1250 --rows-per-query 93 --queries 8192 --wgs 2048 --modes random,sorted
   # round 6: the counting kernel's constraint (a k-mer's h rows together) with the k-mers ordered by their first row
   scripts/probe/row_probe --gb 125 --row-bytes 12500 --rows-per-query 3880 --queries 768 --modes random,sorted,kfirst,kpage; } > $P/${R}_row_probe.txt 2>&1
-python scripts/call_breakdown.py > $P/${R}_call_breakdown.txt 2>/dev/null
-BIGSI_HIP_LIB=$PWD/bigsi_amd/libbigsi_hip_tuning.so python scripts/call_breakdown.py 2>/dev/null | grep "inside the call" > $P/${R}_call_trace.txt      # host clock inside the one-call entry point (tuning build)
-BIGSI_HIP_LIB=$PWD/bigsi_amd/libbigsi_hip_tuning.so python scripts/ab_k1_phases.py > $P/${R}_k1_phases.txt 2>/dev/null
-BIGSI_HIP_LIB=$PWD/bigsi_amd/libbigsi_hip_tuning.so python scripts/ab_k1_phases.py 0.4 >> $P/${R}_k1_phases.txt 2>/dev/null
 # the device timeline of a one-call search of one 1 kbp query (kernel durations and gaps), exact and at 0.4
 ( export TMPDIR=/tmp; mkdir -p $P/tl; rocprofv3 --kernel-trace --output-format csv -d $P/tl -o t -- python scripts/one_call_timeline.py run > $P/tl_run.log 2>&1
   python scripts/one_call_timeline.py report $P/tl > $P/${R}_one_call_timeline.txt 2>&1 )
@@ -72,9 +66,8 @@ python scripts/pmc_requests.py $P/pmc_req c3_exact c5_shard c5_dense transpose >
 cp $P/pmc_req/pmc_requests.json $P/${R}_pmc_requests.json
 python bench.py --steps 20 --warmup 5 --full --details $P/${R}_bench_default_full.json > $P/${R}_bench_default.stdout 2> $P/${R}_bench_default.stderr      # the default command with --full: headline + every other config as config.also legs + the CPU baseline
 python bench.py --steps 20 --warmup 5 --threshold 0.4 --full --also none > $P/${R}_bench_t04.stdout 2> $P/${R}_bench_t04.stderr
-# round 6: the Python stack's latency, the host-visible build, the transpose A/B against the previous kernel (tuning build), the transposing read's lane map
+# round 6: the Python stack's latency, the host-visible build, the transposing read's lane map
 python scripts/latency_probe.py > $P/${R}_python_stack_latency.txt 2>&1
 { python scripts/build_bench.py 4000000 16384; python scripts/build_bench.py 1000000 100000; } > $P/${R}_build_bench.jsonl 2>/dev/null
-CFGS="1 1 4 1,0 0 4 1,0 1 4 1" REPS=3 scripts/ab_transpose_regs.sh > $P/${R}_transpose_regs_ab.txt 2>&1
 scripts/probe/tr_probe > $P/${R}_tr_probe.txt 2>&1
 ls $P | wc -l

@@ -2101,15 +2101,17 @@ def test_search_stream_entry_point_equals_batch_runs(hip):
 def test_search_stream_chunks_cut_at_whole_row_and_launches(hip):
     """Round 6: bigsi_hip_search_stream ends an exact chunk of gene-length queries on a multiple of the row-AND launch size (no chunk closes
     with a part launch) and gives thresholded searches four times the positions per chunk.  On 20 000 samples a launch takes 768 queries
-    and 2^20 positions are 2093 queries of 531 bp: exact chunks of 1536, thresholded ones of 8371 -- several of each here, against plain
-    batches (hit lists whole) and the oracle (sampled)."""
+    and 2^20 positions are 2093 queries of 531 bp: exact chunks of 1536.  Thresholded chunks would take 8371 such queries by positions,
+    but the cap of 4096 sequences per chunk comes first: chunks of 4096.  Several chunks of each kind here, hits planted on both sides of
+    every cut, against plain batches (hit lists whole) and the oracle (sampled)."""
     from oracle.ref_model import SynthOracle
     m, n_cols, h = 200_003, 20_000, 3
     c, st = synth_index(hip, m, n_cols, h, 45, draws=1)
     orc = SynthOracle(45, 0, m, n_cols, h, 31, 1)
     rng = np.random.default_rng(9)
     genes = random_seqs(rng, 9000, 531, 531)
-    for col_, i in ((7, 0), (19_999, 1535), (640, 1536), (12_345, 3071), (3, 3072), (9_000, 8370), (9_001, 8371), (5, 8999)):      # either side of every cut
+    for col_, i in ((7, 0), (19_999, 1535), (640, 1536), (12_345, 3071), (3, 3072), (4_444, 4095), (15_000, 4096), (2_222, 8191), (17_777, 8192),
+                    (9_000, 8370), (9_001, 8371), (5, 8999)):      # either side of every cut
         st.insert_kmers(col_, [genes[i]], 31)
         orc.insert_kmers(col_, genes[i])
     for seqs, thr in ((genes[:5000], 1.0), (genes, 0.45)):
@@ -2125,7 +2127,7 @@ def test_search_stream_chunks_cut_at_whole_row_and_launches(hip):
             assert np.array_equal(nk[lo:lo + len(part)], bnk) and np.array_equal(nu[lo:lo + len(part)], bnu)
             assert np.array_equal(off[lo:lo + len(part) + 1].astype(np.int64) - int(off[lo]), boff.astype(np.int64))
             assert np.array_equal(col[int(off[lo]):int(off[lo + len(part)])], bcol) and np.array_equal(cnt[int(off[lo]):int(off[lo + len(part)])], bcnt)
-        for i in [0, 1535, 1536, 3071, 3072, len(seqs) - 1] + ([8370, 8371] if len(seqs) > 8371 else []) + list(range(11, len(seqs), 997)):
+        for i in [0, 1535, 1536, 3071, 3072, 4095, 4096, len(seqs) - 1] + ([8191, 8192, 8370, 8371] if len(seqs) > 8371 else []) + list(range(11, len(seqs), 997)):
             u, want_cnt = orc.counts(seqs[i])
             want = np.flatnonzero(want_cnt >= (u if thr == 1.0 else int(np.ceil(u * thr))))
             assert nu[i] == u and np.array_equal(col[int(off[i]):int(off[i + 1])], want), (thr, i)

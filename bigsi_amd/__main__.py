@@ -15,6 +15,17 @@ from .storage import get_storage
 from .utils import seq_to_kmers
 
 
+def positive_int(text):
+    """argparse type of --limit: an integer >= 1."""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("invalid int value: %r" % text)
+    if n < 1:
+        raise argparse.ArgumentTypeError("must be >= 1, got %d" % n)
+    return n
+
+
 def get_config_from_file(config_file):            # __main__.py:86-94
     config_file = config_file or os.environ.get("BIGSI_CONFIG")
     if not config_file:
@@ -40,16 +51,23 @@ def main(argv=None):
                              "themselves on stdout)")
         return sp
 
-    sp = shardable(common(sub.add_parser("search")))
+    def limited(sp):
+        sp.add_argument("--limit", type=positive_int, default=None, metavar="N",
+                        help="only the first N results of every record (the best N samples: most k-mers found, ties to the lowest colour)")
+        return sp
+
+    sp = limited(shardable(common(sub.add_parser("search"))))
     sp.add_argument("seq")
     sp.add_argument("--threshold", "-t", type=float, default=1.0)
     sp.add_argument("--score", action="store_true")
     sp.add_argument("--format", choices=["json", "csv"], default="json")
-    sp = shardable(common(sub.add_parser("bulk_search")))
+    search_parser = sp
+    sp = limited(shardable(common(sub.add_parser("bulk_search"))))
     sp.add_argument("fasta")
     sp.add_argument("--threshold", "-t", type=float, default=1.0)
     sp.add_argument("--score", action="store_true")
     sp.add_argument("--format", choices=["json", "csv"], default="json")
+    bulk_parser = sp
     sp.add_argument("--stream", action="store_true")
     sp = common(sub.add_parser("variant_search"))
     sp.add_argument("reference")
@@ -81,14 +99,16 @@ def main(argv=None):
     sp = common(sub.add_parser("import-bdb", help="load an existing BerkeleyDB index (v0.3 file, or a v0.1 directory with graph + metadata) into HBM"))
     sp.add_argument("path")
     a = p.parse_args(argv)
+    if getattr(a, "sharded", False) and getattr(a, "limit", None) is not None:
+        (search_parser if a.cmd == "search" else bulk_parser).error("--limit is not available with --sharded (use a single index or storage-config devices)")
     config = get_config_from_file(a.config)
 
     if getattr(a, "sharded", False):
         return sharded_main(a, config)
     if a.cmd == "search":
-        print(search(BIGSI(config), a.seq, a.threshold, a.score, a.format))
+        print(search(BIGSI(config), a.seq, a.threshold, a.score, a.format, limit=a.limit))
     elif a.cmd == "bulk_search":
-        text = bulk_search(BIGSI(config), a.fasta, a.threshold, a.score, a.format, a.stream)
+        text = bulk_search(BIGSI(config), a.fasta, a.threshold, a.score, a.format, a.stream, limit=a.limit)
         if text is not None:
             print(text)
     elif a.cmd == "variant_search":

@@ -107,6 +107,8 @@ SIGNATURES = {
     "bigsi_hip_batch_run": (_i32, [_P, _dbl, _u32]),
     "bigsi_hip_batch_get_info": (_i32, [_P, C.POINTER(BatchInfo)]),
     "bigsi_hip_batch_set_outputs": (_i32, [_P, _P, _P]),
+    "bigsi_hip_batch_set_limit": (_i32, [_P, _u32, _P, _u64]),
+    "bigsi_hip_group_batch_set_limit": (_i32, [_P, _u32, _P, _u64]),
     "bigsi_hip_batch_fetch_unique": (_i32, [_P, _P, _P, _P]),
     "bigsi_hip_batch_fetch_hits": (_i32, [_P, _P, _P, _P, _u64]),
     "bigsi_hip_batch_fetch_counts": (_i32, [_P, _u32, _P]),
@@ -129,6 +131,7 @@ SIGNATURES = {
     "bigsi_hip_batch_set_result_cols": (_i32, [_P, _u64]),
     "bigsi_hip_search_batch": (_i32, [_P, C.c_char_p, _P, _u32, _u32, _dbl, _u32, _P, _P, _P, _P, _P, _P, _u64]),
     "bigsi_hip_search_stream": (_i32, [_P, C.c_char_p, _P, _u64, _u32, _dbl, _u32, _P, _P, _P, _P, _P, _P, _u64]),
+    "bigsi_hip_search_stream_ranked": (_i32, [_P, C.c_char_p, _P, _u64, _u32, _dbl, _u32, _P, _P, _P, _P, _P, _P, _u64, _u32, _P, _u64]),
     "bigsi_hip_search_stream_scored": (_i32, [_P, C.c_char_p, _P, _u64, _u32, _dbl, _u32, _P, _P, _P, _P, _P, _P, _u64, _P, _u64, _P, _P, _P]),
     "bigsi_hip_comm_unique_id": (_i32, [_P]),
     "bigsi_hip_comm_init_rank": (_i32, [_i32, _P, _i32, _i32, C.POINTER(_P)]),
@@ -214,6 +217,11 @@ def device_count():
     n = C.c_int(0)
     check(lib().bigsi_hip_device_count(C.byref(n)))
     return n.value
+
+
+def limit_arg(limit):
+    """A result limit as the C ABI takes it (uint32; a larger limit cannot cut anything a uint32 cannot)."""
+    return min(int(limit), 0xFFFFFFFF)
 
 
 def ptr(a):

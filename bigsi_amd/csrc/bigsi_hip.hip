@@ -1536,7 +1536,7 @@ extern "C" int bigsi_hip_batch_destroy(bigsi_hip_batch *b)
     (void)e;
     b->planes.release();
     for (DevBuf *d : {&b->uniq, &b->upload, &b->pres_desc, &b->elem_seq_off, &b->pres_in, &b->pres_bits, &b->pres_out, &b->rows_sorted, &b->pos_query, &b->hsh, &b->rep, &b->seqs, &b->d_seq_off, &b->d_pos_off, &b->d_tab_off, &b->tab, &b->first_pos, &b->pos_unique, &b->tmp, &b->rows,
-                      &b->num_kmers, &b->num_unique, &b->min_kmers, &b->bitmaps, &b->counts, &b->scratch})
+                      &b->num_kmers, &b->num_unique, &b->min_kmers, &b->bitmaps, &b->counts, &b->scratch, &b->excl_bits, &b->ranked})
         d->release();
     b->hits.release();
     b->ghits.release();
@@ -1562,6 +1562,20 @@ extern "C" int bigsi_hip_batch_set_result_cols(bigsi_hip_batch *b, uint64_t cols
         return fail(BIGSI_ERR_CAPACITY, "result width %llu exceeds col_capacity %llu (call bigsi_hip_reserve_cols)", (unsigned long long)cols,
                     (unsigned long long)b->ix->cap_cols);
     b->result_cols = cols;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_batch_set_limit(bigsi_hip_batch *b, uint32_t limit, const uint32_t *excluded, uint64_t n_excluded)
+{
+    BIGSI_ENTER(b ? b->ix : nullptr);
+    if (!b) return fail(BIGSI_ERR_INVALID, "NULL batch");
+    if (n_excluded && !limit) return fail(BIGSI_ERR_INVALID, "excluded colours are only valid with a limit (limit = 0 is off)");
+    if (n_excluded && !excluded) return fail(BIGSI_ERR_INVALID, "excluded is NULL");
+    if (n_excluded > 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "too many excluded colours");
+    if (limit == b->limit && b->excluded.size() == n_excluded && std::equal(b->excluded.begin(), b->excluded.end(), excluded)) return BIGSI_OK;
+    b->limit = limit;
+    b->excluded.assign(excluded, excluded + n_excluded);
+    b->excl_words = 0;
     return BIGSI_OK;
 }
 
@@ -1632,6 +1646,7 @@ static void launch_count(bigsi_hip_batch *b, int P, const CountLaunch &c, uint32
 }
 
 static int compact(bigsi_hip_batch *b, HitBufs &hb, const void *src, uint32_t n_shards, uint64_t shard_cols, bool write_only);
+static int rank_select(bigsi_hip_batch *b, const void *src, const void *counters, void *dst, hipStream_t st);
 
 // Reads against a narrow index: K1 + K2 + K4 in one launch (k_reads_fused) when the batch qualifies.
 static bool reads_fusable(const bigsi_hip_batch *b, uint32_t flags)
@@ -1639,7 +1654,7 @@ static bool reads_fusable(const bigsi_hip_batch *b, uint32_t flags)
     const bigsi_hip_index *ix = b->ix;
     const bool exact = b->exact;
     return b->k == 31 && b->total_pos > 0 && b->max_pos <= 63 && b->n_seqs <= kReadsMaxSeqs && b->wv <= (uint64_t)kBlock * kVec &&
-           ix->h >= 2 && ix->h <= 4 && !b->ext_bitmaps && !b->ext_counts && b->result_cols == 0 &&
+           ix->h >= 2 && ix->h <= 4 && !b->ext_bitmaps && !b->ext_counts && b->result_cols == 0 && b->limit == 0 &&
            !(flags & (BIGSI_RUN_SKIP_COMPACT | BIGSI_RUN_K1_GLOBAL | BIGSI_RUN_EARLY_EXIT | BIGSI_RUN_NO_SORT)) &&
            (exact || (flags & BIGSI_RUN_SPARSE_COUNTS));     // the fused kernel keeps counters in registers: hits only
 }
@@ -2211,6 +2226,12 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
     b->done_stale = false;
     if (!b->compacted) {
+        // a member of a device group: its slot of the gather buffer goes into the exchange already trimmed to this shard's top N
+        if (b->limit && b->ext_bitmaps) {
+            TRY(ev_begin(ix, &ep));
+            TRY(rank_select(b, b->ext_bitmaps, b->exact ? nullptr : (b->ext_counts ? b->ext_counts : b->counts.p), b->ext_bitmaps, ix->stream));
+            TRY(ev_end(ix, &ep, ix->ev_cp));
+        }
         HIP_TRY(hipEventRecord(b->done, ix->stream));
         TRY(mark_main(ix));
         b->ran = true;
@@ -2234,6 +2255,36 @@ extern "C" int bigsi_hip_batch_run(bigsi_hip_batch *b, double threshold, uint32_
 {
     BIGSI_ENTER(b ? b->ix : nullptr);
     return bigsi_batch_run(b, threshold, flags, false);
+}
+
+// k_rank_select over the batch's hit vectors `src` (counters: the counting run's, null on the exact path) into `dst` (may be `src`),
+// n_seqs x wv_pad words.  The excluded colours' bit vector is built on first use and again whenever the result width outgrew it.
+static int rank_select(bigsi_hip_batch *b, const void *src, const void *counters, void *dst, hipStream_t st)
+{
+    const uint64_t *ex = nullptr;
+    if (!b->excluded.empty()) {
+        if (b->excl_words < b->wv) {
+            std::vector<uint64_t> words(b->wv_pad, 0ull);
+            for (uint32_t c : b->excluded)
+                if (c < b->wv_pad * 64) words[c / 64] |= 1ull << bit_of_col(c % 64);
+            HIP_TRY(hipStreamSynchronize(st));      // (an earlier run of this batch may still read the old vector)
+            TRY(b->excl_bits.reserve(b->wv_pad * 8));
+            HIP_TRY(hipMemcpy(b->excl_bits.p, words.data(), b->wv_pad * 8, hipMemcpyHostToDevice));
+            b->excl_words = b->wv_pad;
+        }
+        ex = b->excl_bits.as<uint64_t>();
+    }
+    if (b->n_seqs == 0) return BIGSI_OK;
+    if (b->count_bytes == 4 && counters)
+        hipLaunchKernelGGL((k_rank_select<uint32_t>), dim3(b->n_seqs), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv,
+                           (const uint32_t *)counters, b->wv_pad * 64, b->num_unique.as<uint32_t>(), b->min_kmers.as<uint32_t>(), ex, b->limit,
+                           (uint64_t *)dst);
+    else
+        hipLaunchKernelGGL((k_rank_select<uint16_t>), dim3(b->n_seqs), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv,
+                           (const uint16_t *)counters, b->wv_pad * 64, b->num_unique.as<uint32_t>(), b->min_kmers.as<uint32_t>(), ex, b->limit,
+                           (uint64_t *)dst);
+    HIP_TRY(hipGetLastError());
+    return BIGSI_OK;
 }
 
 // three compaction passes over [shard][seq][stride]; write_only re-runs just the write pass (after growing buffers).
@@ -2315,6 +2366,14 @@ static int compact(bigsi_hip_batch *b, HitBufs &hb, const void *src, uint32_t n_
     if (&hb == &b->hits) {
         const void *bm = b->ext_bitmaps ? b->ext_bitmaps : b->bitmaps.p;
         const void *counters = b->exact ? nullptr : (b->ext_counts ? b->ext_counts : b->counts.p);
+        if (b->limit) {
+            // a result limit: K4 compacts the trimmed copy; the untrimmed vectors stay for fetch_bitmap / fetch_counts
+            if (!write_only) {
+                TRY(b->ranked.reserve((size_t)b->n_seqs * b->wv_pad * 8));
+                TRY(rank_select(b, bm, counters, b->ranked.p, b->ix->stream));
+            }
+            bm = b->ranked.p;
+        }
         return compact_ex(b, hb, bm, false, counters, 1, shard_cols, write_only, b->ix->stream);
     }
     hipStream_t gst = b->gstream ? b->gstream : b->ix->stream;

@@ -224,6 +224,11 @@ struct bigsi_hip_batch {
     PresJob job;                                     // the K5 / K6 request in flight, its host vectors and pinned staging
     DevBuf pres_in, pres_bits, pres_out, pres_desc;   // K5 at scale (presence_hits): host-built pair lists, presence bits, strings, piece marks
     void *ext_bitmaps = nullptr, *ext_counts = nullptr;
+    // result limit (bigsi_hip_batch_set_limit): k_rank_select trims the hit vectors to the top `limit` between K2/K3 and K4
+    uint32_t limit = 0;                  // 0: off
+    std::vector<uint32_t> excluded;      // colours (of this batch's index) taken out before the selection
+    DevBuf excl_bits, ranked;            // the excluded colours as a row-format bit vector; the trimmed vectors K4 compacts
+    uint64_t excl_words = 0;             // words excl_bits was built for (0: build it at the next limited run)
     HitBufs hits, ghits;
     // state of the last run
     bool ran = false, exact = false, compacted = false, sparse_counts = false;

@@ -1307,6 +1307,160 @@ __global__ __launch_bounds__(kBlock) void k_count_combine(
     }
 }
 
+// ------------------------------------------------------------------------------ K3r: ranked top-N selection (a result limit)
+// search(seq, threshold, score, limit=N) == search(seq, threshold, score)[:N]: the reference orders an exact search's hits by
+// ascending colour (exact_filter, bigsi/graph/bigsi.py:192-205) and a thresholded one by num_kmers_found, descending, with a STABLE
+// sort over ascending colours (inexact_filter, :211-230), then drops deleted samples (:185-190).  So the N results are the hits with
+// the highest counts, ties going to the lowest colours, after the excluded (deleted) colours are taken out.  One workgroup per query
+// trims the query's hit vector (the AND bitmap, or the count >= min_kmers mask) to those N bits; K4, the export kernels and K5 / K6
+// then run unchanged on the trimmed copy (hit lists stay in ascending colour; the host's stable sort restores the reference's order).
+//   pass 0     AND-NOT the excluded colours, popcount.  hits <= N: copy the words through, done (one read of the bitmap).
+//   select     (counting runs) radix select of the cutoff count c* over v = count - min_kmers, 12-bit digits from the top: an LDS
+//              histogram of the digit over the candidates that match the digits chosen so far, a suffix scan over the bins -> the
+//              bin that holds the N-th largest, and how many of it still fit.  One pass while num_unique - min_kmers < 4096 (every
+//              read, every 1 kbp query), two for gene-length queries, three for the 32-bit counters of > 65 535 k-mers.
+//   tie pass   keep count > c*; of the count == c* bits, the first t in colour order: tiles of kBlock consecutive words, the tie
+//              counts scanned across the workgroup (block_exclusive_scan) tile by tile.  Exact runs: every hit ties, t = N.
+// Counters are read only in words that hold hits (in sparse mode the others are stale), 8 at a time: the 8 columns of one byte of
+// the word are 16 B of uint16_t counters (32 B of uint32_t), one vector load.  All loads of the whole-word passes are coalesced
+// (thread t takes words t, t + kBlock, ...).  `out` may be `hits` (a group member trims its slot of the gather buffer in place: every
+// word is read and written by the same thread in the last pass).
+constexpr uint32_t kRankDigitBits = 12, kRankBins = 1u << kRankDigitBits;
+
+// the 8 counters of byte g of word w (columns 64w + 8g .. + 7) as uint32
+template <typename CountT>
+__device__ __forceinline__ void rank_counts8(const CountT *__restrict__ cq, uint32_t w, uint32_t g, uint32_t c[8])
+{
+    const CountT *p = cq + (uint64_t)w * 64 + 8 * g;
+    if (sizeof(CountT) == 2) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(p);
+        c[0] = v.x & 0xFFFFu; c[1] = v.x >> 16; c[2] = v.y & 0xFFFFu; c[3] = v.y >> 16;
+        c[4] = v.z & 0xFFFFu; c[5] = v.z >> 16; c[6] = v.w & 0xFFFFu; c[7] = v.w >> 16;
+    } else {
+        const uint4 lo = *reinterpret_cast<const uint4 *>(p), hi = *reinterpret_cast<const uint4 *>(p + 4);
+        c[0] = lo.x; c[1] = lo.y; c[2] = lo.z; c[3] = lo.w; c[4] = hi.x; c[5] = hi.y; c[6] = hi.z; c[7] = hi.w;
+    }
+}
+
+// the lowest n set bits of m
+__device__ __forceinline__ uint64_t lowest_bits(uint64_t m, uint32_t n)
+{
+    if ((uint32_t)__popcll(m) <= n) return m;
+    uint64_t r = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        r |= m & (0ull - m);
+        m &= m - 1;
+    }
+    return r;
+}
+
+template <typename CountT>
+__global__ __launch_bounds__(kBlock) void k_rank_select(
+    const uint64_t *hits, uint64_t stride_words, uint32_t wv, const CountT *__restrict__ counters /* null: exact run */,
+    uint64_t counter_stride, const uint32_t *__restrict__ num_unique, const uint32_t *__restrict__ min_kmers,
+    const uint64_t *__restrict__ excluded /* null: none; else >= wv words, row format */, uint32_t limit, uint64_t *out)
+{
+    __shared__ uint32_t hist[kRankBins];
+    __shared__ uint32_t lds[16];
+    __shared__ uint32_t pick[2];
+    const uint32_t q = blockIdx.x;
+    const uint64_t *hq = hits + (uint64_t)q * stride_words;
+    uint64_t *oq = out + (uint64_t)q * stride_words;
+    // pass 0
+    uint32_t mine = 0;
+    for (uint32_t w = threadIdx.x; w < wv; w += kBlock) {
+        uint64_t x = hq[w];
+        if (excluded) x &= ~excluded[w];
+        mine += (uint32_t)__popcll(x);
+    }
+    uint32_t total;
+    block_exclusive_scan(mine, &total, lds);
+    if (total <= limit) {
+        if (excluded || oq != hq)
+            for (uint32_t w = threadIdx.x; w < wv; w += kBlock) oq[w] = excluded ? hq[w] & ~excluded[w] : hq[w];
+        return;
+    }
+    // radix select of the cutoff (counting runs): prefix / mask = the digits of c* - min_kmers chosen so far
+    uint32_t prefix = 0, mask = 0, remaining = limit;
+    const uint32_t mk = counters ? min_kmers[q] : 0u;
+    const CountT *cq = counters ? counters + (uint64_t)q * counter_stride : nullptr;
+    if (counters) {
+        const uint32_t range = num_unique[q] > mk ? num_unique[q] - mk : 0u;
+        const uint32_t bits = range ? 32u - (uint32_t)__clz(range) : 1u;
+        for (int shift = (int)(((bits + kRankDigitBits - 1) / kRankDigitBits - 1) * kRankDigitBits); shift >= 0; shift -= (int)kRankDigitBits) {
+            for (uint32_t i = threadIdx.x; i < kRankBins; i += kBlock) hist[i] = 0;
+            __syncthreads();
+            for (uint32_t w = threadIdx.x; w < wv; w += kBlock) {
+                uint64_t x = hq[w];
+                if (excluded) x &= ~excluded[w];
+                for (uint32_t g = 0; g < 8 && (x >> (8 * g)); g++) {
+                    const uint32_t byte = (uint32_t)(x >> (8 * g)) & 0xFFu;
+                    if (!byte) continue;
+                    uint32_t c[8];
+                    rank_counts8(cq, w, g, c);
+#pragma unroll
+                    for (int jj = 0; jj < 8; jj++) {
+                        if (!((byte >> (7 - jj)) & 1u)) continue;      // column 8g + jj sits at bit 8g + 7 - jj
+                        const uint32_t v = c[jj] > mk ? c[jj] - mk : 0u;
+                        if ((v & mask) == prefix) atomicAdd(&hist[(v >> shift) & (kRankBins - 1)], 1u);
+                    }
+                }
+            }
+            __syncthreads();
+            // suffix scan: thread t owns bins [16t, 16t + 16); the bin where the running count from the top reaches `remaining`
+            constexpr uint32_t per = kRankBins / kBlock;
+            uint32_t s = 0;
+            for (uint32_t i = 0; i < per; i++) s += hist[threadIdx.x * per + i];
+            uint32_t tot;
+            const uint32_t pre = block_exclusive_scan(s, &tot, lds);
+            uint32_t above = tot - pre - s;
+            for (int i = (int)per - 1; i >= 0; i--) {
+                const uint32_t bin = threadIdx.x * per + (uint32_t)i, h = hist[bin];
+                if (above < remaining && above + h >= remaining) { pick[0] = bin; pick[1] = remaining - above; }
+                above += h;
+            }
+            __syncthreads();
+            prefix |= pick[0] << shift;
+            mask |= (kRankBins - 1) << shift;
+            remaining = pick[1];
+            __syncthreads();      // (pick and hist are rewritten by the next digit)
+        }
+    }
+    // tie pass: tiles of kBlock consecutive words, colour order across the workgroup
+    uint32_t base = 0;
+    for (uint32_t w0 = 0; w0 < wv; w0 += kBlock) {
+        const uint32_t w = w0 + threadIdx.x;
+        uint64_t x = w < wv ? hq[w] : 0ull;
+        if (excluded && w < wv) x &= ~excluded[w];
+        uint64_t gt = 0, eq = x;
+        if (counters) {
+            eq = 0;
+            for (uint32_t g = 0; g < 8 && (x >> (8 * g)); g++) {
+                const uint32_t byte = (uint32_t)(x >> (8 * g)) & 0xFFu;
+                if (!byte) continue;
+                uint32_t c[8];
+                rank_counts8(cq, w, g, c);
+#pragma unroll
+                for (int jj = 0; jj < 8; jj++) {
+                    if (!((byte >> (7 - jj)) & 1u)) continue;
+                    const uint32_t v = c[jj] > mk ? c[jj] - mk : 0u;
+                    const uint64_t bit = 1ull << (8 * g + 7 - jj);
+                    if (v > prefix) gt |= bit;
+                    else if (v == prefix) eq |= bit;
+                }
+            }
+        }
+        const uint32_t n_eq = (uint32_t)__popcll(eq);
+        uint32_t tot;
+        const uint32_t pre = block_exclusive_scan(n_eq, &tot, lds);
+        const uint32_t before = base + pre, allow = remaining > before ? min(n_eq, remaining - before) : 0u;
+        // the first `allow` ties in COLOUR order: by_column maps the word to column order and back (it is its own inverse)
+        const uint64_t kept = allow == n_eq ? eq : allow ? by_column(lowest_bits(by_column(eq), allow)) : 0ull;
+        if (w < wv) oq[w] = gt | kept;
+        base += tot;
+    }
+}
+
 // ------------------------------------------------------------------------------ K4: threshold + compaction
 // Result buffers are laid out [shard][seq][stride] (n_shards = 1 for a single GPU; > 1 for buffers gathered from column
 // shards); hits come out as (colour, count) in (seq, shard, column) order.  Bit vectors -- every production path -- take

@@ -8,6 +8,7 @@
 #include <unistd.h>
 #include <rccl/rccl.h>      // types and prototypes only: the library is loaded at run time
 
+#include <algorithm>
 #include <cerrno>
 #include <chrono>
 #include <cstdio>
@@ -140,7 +141,8 @@ struct ScoredOut {
 
 int search_stream_impl(bigsi_hip_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
                        uint32_t flags, uint32_t *num_kmers, uint32_t *num_unique, uint32_t *min_kmers, uint64_t *hit_offsets,
-                       uint32_t *colours, uint32_t *counts, uint64_t hit_capacity, const ScoredOut *so)
+                       uint32_t *colours, uint32_t *counts, uint64_t hit_capacity, const ScoredOut *so, uint32_t limit = 0,
+                       const uint32_t *excluded = nullptr, uint64_t n_excluded = 0)
 {
     if (!ix || !offsets || !hit_offsets) return fail(BIGSI_ERR_INVALID, "NULL argument");
     if (k == 0) return fail(BIGSI_ERR_INVALID, "k must be > 0");
@@ -245,6 +247,8 @@ int search_stream_impl(bigsi_hip_index *ix, const char *seqs, const uint64_t *of
         if (rc == BIGSI_OK && so) rc = finish_score(slot);
         if (rc != BIGSI_OK) break;
         rc = bigsi_batch_stage(ix, &ix->stream_ws[slot], seqs, offsets + next, (uint32_t)(end - next), k);
+        // (the workspaces outlive the call: every call sets its own limit, off included)
+        if (rc == BIGSI_OK) rc = bigsi_hip_batch_set_limit(ix->stream_ws[slot], limit, excluded, n_excluded);
         if (rc == BIGSI_OK) rc = bigsi_hip_batch_run(ix->stream_ws[slot], threshold, (flags & ~BIGSI_RUN_SKIP_COMPACT) | BIGSI_RUN_SPARSE_COUNTS);
         if (rc == BIGSI_OK) rc = bigsi_batch_export(ix->stream_ws[slot]);
         if (rc != BIGSI_OK) break;
@@ -283,6 +287,19 @@ extern "C" int bigsi_hip_search_stream(bigsi_hip_index *ix, const char *seqs, co
     BIGSI_ENTER(ix);
     return search_stream_impl(ix, seqs, offsets, n_seqs, k, threshold, flags, num_kmers, num_unique, min_kmers, hit_offsets, colours, counts,
                               hit_capacity, nullptr);
+}
+
+// bigsi_hip_search_stream with a result limit: every device batch of the stream runs k_rank_select before its compaction.
+extern "C" int bigsi_hip_search_stream_ranked(bigsi_hip_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k,
+                                              double threshold, uint32_t flags, uint32_t *num_kmers, uint32_t *num_unique, uint32_t *min_kmers,
+                                              uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t hit_capacity, uint32_t limit,
+                                              const uint32_t *excluded, uint64_t n_excluded)
+{
+    BIGSI_ENTER(ix);
+    if (n_excluded && !limit) return fail(BIGSI_ERR_INVALID, "excluded colours are only valid with a limit (limit = 0 is off)");
+    if (n_excluded && !excluded) return fail(BIGSI_ERR_INVALID, "excluded is NULL");
+    return search_stream_impl(ix, seqs, offsets, n_seqs, k, threshold, flags, num_kmers, num_unique, min_kmers, hit_offsets, colours, counts,
+                              hit_capacity, nullptr, limit, excluded, n_excluded);
 }
 
 // BIGSI.search(..., score=True) for any number of sequences in one call: as above, plus for every hit t (global index into
@@ -476,6 +493,9 @@ extern "C" int bigsi_hip_batch_run_sharded(bigsi_hip_batch *b, double threshold,
     bigsi_hip_comm *c = b->comm;
     if (!c) return fail(BIGSI_ERR_STATE, "no communicator attached (bigsi_hip_batch_set_comm)");
     if (c->group) return fail(BIGSI_ERR_STATE, "this batch belongs to a device group: use bigsi_hip_group_batch_run");
+    if (b->limit)
+        return fail(BIGSI_ERR_INVALID, "a result limit is not available on the one-process-per-GPU sharded path (bigsi_hip_batch_run_sharded): "
+                                       "use a device group (bigsi_hip_group_batch_set_limit) or a single index");
     TRY(bigsi_use_device(b->ix));
     TRY(prepare_slot(b, nullptr));
     TRY(bigsi_hip_batch_run(b, threshold, flags | BIGSI_RUN_SKIP_COMPACT | BIGSI_RUN_SPARSE_COUNTS));
@@ -517,6 +537,7 @@ struct bigsi_hip_group_batch {
     DevBuf shared;                       // loopback groups: the one gather buffer all members write their slot of
     bool ran = false;
     uint64_t reduced_cap = 0;            // hit-buffer capacity the last count reduction covered
+    uint32_t limit = 0;                  // bigsi_hip_group_batch_set_limit: every member trims to its top N, fetch_hits cuts the union to N
 };
 
 __global__ void k_add_counts(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint64_t n)
@@ -1102,11 +1123,69 @@ extern "C" int bigsi_hip_group_batch_fetch_unique(bigsi_hip_group_batch *gb, uin
     return bigsi_hip_batch_fetch_unique(gb->b[0], num_kmers, num_unique, min_kmers);     // K1 is the same on every shard
 }
 
+extern "C" int bigsi_hip_group_batch_set_limit(bigsi_hip_group_batch *gb, uint32_t limit, const uint32_t *excluded, uint64_t n_excluded)
+{
+    if (!gb) return fail(BIGSI_ERR_INVALID, "NULL batch");
+    if (n_excluded && !limit) return fail(BIGSI_ERR_INVALID, "excluded colours are only valid with a limit (limit = 0 is off)");
+    if (n_excluded && !excluded) return fail(BIGSI_ERR_INVALID, "excluded is NULL");
+    bigsi_hip_group *g = gb->g;
+    // global colours -> each shard's own (colour c lives on shard c / shard_cols)
+    std::vector<std::vector<uint32_t>> local(g->n());
+    for (uint64_t i = 0; i < n_excluded; i++) {
+        const uint64_t sh = excluded[i] / g->shard_cols;
+        if (sh < g->n()) local[sh].push_back((uint32_t)(excluded[i] - sh * g->shard_cols));
+    }
+    for (uint32_t i = 0; i < g->n(); i++) TRY(bigsi_hip_batch_set_limit(gb->b[i], limit, local[i].data(), local[i].size()));
+    gb->limit = limit;
+    return BIGSI_OK;
+}
+
+static int group_fetch_all(bigsi_hip_group_batch *gb, uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t capacity);
+
+// A limited group run: the union of the shards' top N lists (at most shards x N hits per query, ascending global colour) cut to the
+// top N by the same rule -- count descending, ties to the lowest colour -- and handed out in ascending colour again.
+static int group_fetch_limited(bigsi_hip_group_batch *gb, uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t capacity)
+{
+    const uint32_t n = gb->b[0]->n_seqs;
+    std::vector<uint64_t> off(n + 1ull);
+    TRY(group_fetch_all(gb, off.data(), nullptr, nullptr, ~0ull));
+    std::vector<uint32_t> col(off[n]), cnt(off[n]), idx;
+    if (off[n]) TRY(group_fetch_all(gb, off.data(), col.data(), cnt.data(), off[n]));
+    uint64_t o = 0;
+    hit_offsets[0] = 0;
+    for (uint32_t q = 0; q < n; q++) {
+        const uint64_t lo = off[q], hi = off[q + 1];
+        idx.resize(hi - lo);
+        for (uint64_t t = lo; t < hi; t++) idx[t - lo] = (uint32_t)(t - lo);
+        if (idx.size() > gb->limit) {
+            std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return cnt[lo + a] > cnt[lo + b]; });
+            idx.resize(gb->limit);
+            std::sort(idx.begin(), idx.end());
+        }
+        for (uint32_t t : idx) {
+            if (o < capacity) {
+                if (colours) colours[o] = col[lo + t];
+                if (counts) counts[o] = cnt[lo + t];
+            }
+            o++;
+        }
+        hit_offsets[q + 1] = o;
+    }
+    if (o > capacity) return fail(BIGSI_ERR_CAPACITY, "hit buffers hold %llu entries, %llu needed", (unsigned long long)capacity, (unsigned long long)o);
+    return BIGSI_OK;
+}
+
 extern "C" int bigsi_hip_group_batch_fetch_hits(bigsi_hip_group_batch *gb, uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t capacity)
 {
     if (!gb) return fail(BIGSI_ERR_INVALID, "NULL batch");
     if (!gb->ran) return fail(BIGSI_ERR_STATE, "bigsi_hip_group_batch_run has not completed for this batch");
     if (!hit_offsets) return fail(BIGSI_ERR_INVALID, "hit_offsets is NULL");
+    if (gb->limit) return group_fetch_limited(gb, hit_offsets, colours, counts, capacity);
+    return group_fetch_all(gb, hit_offsets, colours, counts, capacity);
+}
+
+static int group_fetch_all(bigsi_hip_group_batch *gb, uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t capacity)
+{
     bigsi_hip_group *g = gb->g;
     if (!gb->b[0]->exact) {
         // a fetch with unbounded caller capacity makes every member grow + rewrite its lists if they overflowed (all members

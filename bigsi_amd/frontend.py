@@ -63,12 +63,13 @@ def d_to_csv(d, with_header=True, carriage_return=True):
     return text if carriage_return else text[:-1]
 
 
-def search(bigsi, seq, threshold=1.0, score=False, format="json"):
-    d = search_record(seq, threshold, bigsi.search(seq, threshold, score))
+def search(bigsi, seq, threshold=1.0, score=False, format="json", limit=None):
+    """`limit` = N: the record's results are the first N of the unlimited record's (BIGSI.search(..., limit=N))."""
+    d = search_record(seq, threshold, bigsi.search(seq, threshold, score) if limit is None else bigsi.search(seq, threshold, score, limit=limit))
     return d_to_csv(d) if format == "csv" else json.dumps(d, indent=4)
 
 
-def _bulk_text_native(bigsi, fasta, threshold, format, score=False):
+def _bulk_text_native(bigsi, fasta, threshold, format, score=False, limit=None):
     """The text of a bulk search without a Python object per record: bigsi_hip_fasta_pack -> bigsi_hip_search_stream(_scored) ->
     bigsi_hip_format_results(_scored) (include/bigsi_hip.h, "FRONT-END TEXT").  None when this route does not apply -- text that is
     not plain ASCII (file or sample names), a multi-GPU index, a record on which the reference raises, more scored hits than one
@@ -79,6 +80,8 @@ def _bulk_text_native(bigsi, fasta, threshold, format, score=False):
     st = getattr(bigsi, "storage", None)
     if st is None or not hasattr(st, "search_many_packed") or st.res.is_group or not isinstance(fasta, str):
         return None
+    if limit is not None and score:
+        return None                           # (a limited scored search goes through BIGSI.search_stream's batch route)
     with open(fasta, "rb") as f:
         packed = _lib.fasta_pack(f.read())
     if packed is None:
@@ -97,7 +100,8 @@ def _bulk_text_native(bigsi, fasta, threshold, format, score=False):
             except TooManyHits:
                 return None
         else:
-            nk, nu, off, col, cnt = st.search_many_packed(blob, soff, bigsi.kmer_size, threshold)
+            excluded = bigsi._excluded_colours() if limit is not None else None
+            nk, nu, off, col, cnt = st.search_many_packed(blob, soff, bigsi.kmer_size, threshold, limit=limit, excluded=excluded)
     if len(nu) and int(nu.min()) == 0:
         return None
     if score:
@@ -128,19 +132,26 @@ def _bulk_text_native(bigsi, fasta, threshold, format, score=False):
         raise
 
 
-def bulk_search(bigsi, fasta, threshold=1.0, score=False, format="json", stream=False, out=None):
+def bulk_search(bigsi, fasta, threshold=1.0, score=False, format="json", stream=False, out=None, limit=None):
     """All records of a FASTA file in one device batch.  Returns the combined text (stream=False) or prints one record
-    per line as the reference's streaming branch does and returns None."""
+    per line as the reference's streaming branch does and returns None.  `limit` = N: every record's results are the first N of
+    the unlimited record's."""
+    if limit is not None:
+        from .graph.bigsi import check_limit
+        limit = check_limit(limit)
     if not stream and hasattr(bigsi, "_device_lock"):
-        text = _bulk_text_native(bigsi, fasta, threshold, format, score)
+        text = _bulk_text_native(bigsi, fasta, threshold, format, score, limit)
         if text is not None:
             return text
     seqs = [s for _, s in read_fasta(fasta)]
     if hasattr(bigsi, "search_stream"):       # the C ABI's streaming searches; the text of one slice is assembled while the next one runs
         size = getattr(bigsi, "config", {}).get("batch_size")          # default: slices of ~4M k-mers
-        pairs = bigsi.search_stream(seqs, threshold, score, batch_size=size)
-    else:
+        pairs = bigsi.search_stream(seqs, threshold, score, batch_size=size) if limit is None else \
+            bigsi.search_stream(seqs, threshold, score, batch_size=size, limit=limit)
+    elif limit is None:
         pairs = zip(seqs, bigsi.search_batch(seqs, threshold, score) if seqs else [])
+    else:
+        pairs = zip(seqs, bigsi.search_batch(seqs, threshold, score, limit=limit) if seqs else [])
     if not stream:
         # the reference's text -- json.dumps(list of records, indent=4) / the csv rows of every record -- written record by record: most
         # records of a bulk search have no results, and their text is a constant around the query (json.dumps with indent runs the

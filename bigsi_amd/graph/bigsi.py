@@ -6,6 +6,7 @@ per-sample counts, threshold, compaction -- is ONE device batch (include/bigsi_h
 only assembles result dicts (names, percentages, optional score)."""
 import json
 import logging
+import numbers
 
 import numpy as np
 
@@ -27,6 +28,17 @@ logger = logging.getLogger(__name__)
 DEFAULT_NPROC = 4
 MIN_UNIQUE_KMERS_IN_QUERY = 0
 DEFAULT_CONFIG = {"storage-engine": "hip-hbm", "storage-config": {"name": "default"}, "k": 31, "m": 25 * 10 ** 6, "h": 3}
+
+
+def check_limit(limit):
+    """`limit` of search / search_batch / search_stream: None (every hit) or an int >= 1 -- checked before any device work."""
+    if limit is None:
+        return None
+    if isinstance(limit, bool) or not isinstance(limit, numbers.Integral):
+        raise TypeError("limit must be an int >= 1 or None, got %r" % (limit,))
+    if limit < 1:
+        raise ValueError("limit must be >= 1, got %d" % limit)
+    return int(limit)
 
 
 def validate_build_params(bloomfilters, samples):
@@ -326,6 +338,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
 
     def insert(self, bloomfilter, sample):
         logger.warning("Build and merge is preferable to insert in most cases")
+        self._metadata_changed()
         colour = self.add_sample(sample)
         self.insert_bloom(bloomfilter, colour - 1)
 
@@ -334,6 +347,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         (bigsi_hip_insert_columns) instead of a column-at-a-time loop.  Same result as insert() called for each in turn
         (graph/bigsi.py:244-247)."""
         validate_build_params(bloomfilters, samples)
+        self._metadata_changed()
         col0 = self.num_samples
         self.add_samples(samples)
         nb = (int(self.bloomfilter_size) + 7) // 8
@@ -353,20 +367,52 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         assert self.bloomfilter_size == bigsi.bloomfilter_size
         assert self.num_hashes == bigsi.num_hashes
         assert self.kmer_size == bigsi.kmer_size
+        self._metadata_changed()
         self.merge_indexes(bigsi)
         self.merge_metadata(bigsi)
+
+    def delete_sample(self, sample_name):
+        self._metadata_changed()
+        SampleMetadata.delete_sample(self, sample_name)
+
+    def _metadata_changed(self):
+        self.__dict__.pop("_excluded", None)
+
+    def _excluded_colours(self):
+        """Colours of deleted samples (named DELETION_SPECIAL_SAMPLE_NAME), which a limited search takes out before it ranks: the
+        reference drops them after ordering (graph/bigsi.py:185-190), so the first N of what is left are the same N.  One pass over the
+        colours, kept until the metadata changes through this object."""
+        ex = self.__dict__.get("_excluded")
+        if ex is None:
+            cols = []
+            for c in range(self.num_samples):
+                try:
+                    if self.colour_to_sample(c) == DELETION_SPECIAL_SAMPLE_NAME:
+                        cols.append(c)
+                except KeyError:
+                    pass
+            ex = self.__dict__["_excluded"] = np.asarray(cols, dtype=np.uint32)
+        return ex
+
+    def _set_limit(self, batch, limit):
+        batch.set_limit(limit, self._excluded_colours() if limit else None)
+
+    def _limit_fallback(self, seqs, score, limit):
+        """score=True on a query of ONE k-mer raises the reference's IndexError when it has any hit at all -- deleted samples included,
+        which a limited run takes out before it counts: such a batch runs unlimited and is cut on the host."""
+        return bool(limit and score and any(len(s) - self.kmer_size + 1 == 1 for s in seqs))
 
     # ------------------------------------------------------------------ queries
     def seq_to_kmers(self, seq):
         return seq_to_kmers(seq, self.kmer_size)
 
-    def search(self, seq, threshold=1.0, score=False):
+    def search(self, seq, threshold=1.0, score=False, limit=None):
         if len(seq) - self.kmer_size + 1 <= self.min_unique_kmers_in_query:
             logger.warning("Query string should contain at least %i unique kmers. Your query contained %i unique kmers, "
                            "and as a result the false discovery rate may be high. In future this will become an error."
                            % (self.min_unique_kmers_in_query, max(len(seq) - self.kmer_size + 1, 0)))
         assert threshold <= 1
-        return self.search_batch([seq], threshold, score)[0]
+        return self.search_batch([seq], threshold, score, limit=limit)[0]
 
     def _workspace(self, slot, seqs, ws=None):
         """Batch workspace `slot` (of `ws`, else of this index object), staged with `seqs` (created once, then only reloaded).
@@ -470,36 +516,41 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
             pos.append(j)
         return uniq, pos
 
-    def _search_wide(self, seqs, threshold, score):
+    def _search_wide(self, seqs, threshold, score, limit=None):
         """search_batch for sequences with non-ASCII characters: k-merised here, hashed / fetched / combined on the device."""
         batch = self.storage.new_element_batch([self._elements_of(s) for s in seqs])
         try:
+            self._set_limit(batch, limit)
             self._launch(batch, threshold)
             return self._collect(batch, len(seqs), threshold, score)
         finally:
             batch.close()
 
-    def search_batch(self, seqs, threshold=1.0, score=False):
-        """search() for many sequences in one device batch; a list of result lists in input order."""
+    def search_batch(self, seqs, threshold=1.0, score=False, limit=None):
+        """search() for many sequences in one device batch; a list of result lists in input order.  `limit` = N: each list is
+        search(seq, threshold, score)[:N], and the device selects, exports and scores only those N (k_rank_select)."""
+        limit = check_limit(limit)
         assert threshold <= 1
         with self._device_lock():          # (a search_stream being consumed has a worker thread on this index between yields)
-            return self._search_batch_locked(seqs, threshold, score)
+            return self._search_batch_locked(seqs, threshold, score, limit)
 
-    def _search_batch_locked(self, seqs, threshold, score):
+    def _search_batch_locked(self, seqs, threshold, score, limit=None):
         seqs = list(seqs)
         if not seqs:
             return []
+        if self._limit_fallback(seqs, score, limit):
+            return [r[:limit] for r in self._search_batch_locked(seqs, threshold, score)]
         wide = [i for i, s in enumerate(seqs) if not s.isascii()]
         if wide:
             out = [None] * len(seqs)
             rest = [i for i in range(len(seqs)) if seqs[i].isascii()]
-            for i, r in zip(wide, self._search_wide([seqs[i] for i in wide], threshold, score)):
+            for i, r in zip(wide, self._search_wide([seqs[i] for i in wide], threshold, score, limit)):
                 out[i] = r
             if rest:
-                for i, r in zip(rest, self._search_batch_locked([seqs[i] for i in rest], threshold, score)):
+                for i, r in zip(rest, self._search_batch_locked([seqs[i] for i in rest], threshold, score, limit)):
                     out[i] = r
             return out
-        if not score and sum(map(len, seqs)) <= ONE_CALL_BYTES:
+        if limit is None and not score and sum(map(len, seqs)) <= ONE_CALL_BYTES:
             # unscored (the reference's `search` endpoint, bigsi/__main__.py:195-209): ONE call of the C ABI -- bigsi_hip_search_batch:
             # zero-copy input, results written into pinned memory by the last kernel -- instead of reload + run + two fetches
             # (a 1 kbp query against a 125 GB index: 35 us in the C call against ~90 through the batch object)
@@ -508,6 +559,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
             nk, nu, off, colours, counts = self.storage.search_batch_arrays(seqs, self.kmer_size, threshold, flags, borrow=True)
             return self._collect_end(self._check_degenerate(None, len(seqs), threshold, nk, nu, off, colours, counts))
         batch = self._workspace(0, seqs)
+        self._set_limit(batch, limit)
         self._launch(batch, threshold)
         return self._collect(batch, len(seqs), threshold, score)
 
@@ -523,7 +575,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
             raise UnboundLocalError("local variable 'cumsum' referenced before assignment")
         return (batch, off.astype(np.int64), colours, counts, nu, exact, None), n_seqs
 
-    def search_stream(self, seqs, threshold=1.0, score=False, batch_size=None, batch_kmers=1 << 19, pause_gc=True):
+    def search_stream(self, seqs, threshold=1.0, score=False, batch_size=None, batch_kmers=1 << 19, pause_gc=True, limit=None):
         """Generator over (sequence, results) for an arbitrarily long iterable of sequences (bulk_search, bigsi/__main__.py:261-314,
         runs one BIGSI.search per query in a fork pool).  The sequences go through the C ABI's streaming entry points --
         bigsi_hip_search_stream, or bigsi_hip_search_stream_scored with score=True: one call per slice of about 8 x `batch_kmers`
@@ -536,10 +588,13 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         passes of Python's cyclic garbage collector are deferred until the stream ends (see below); pass False to leave it alone.
         Exhaust the generator or .close() it: while it is suspended the process runs with the short switch interval and (pause_gc)
         without automatic collections; several streams at once share the two settings and the last one to end restores them.
-        A multi-GPU (devices=[...]) index streams through its batch objects instead (_search_stream_batches)."""
+        A multi-GPU (devices=[...]) index streams through its batch objects instead (_search_stream_batches), and so does a scored
+        stream with a `limit` (N: every sequence's results are search(seq, threshold, score)[:N]; unscored, the streaming call
+        bigsi_hip_search_stream_ranked)."""
+        limit = check_limit(limit)
         assert threshold <= 1
-        if self.storage.res.is_group:
-            yield from self._search_stream_batches(seqs, threshold, score, batch_size, batch_kmers)
+        if self.storage.res.is_group or (limit and score):
+            yield from self._search_stream_batches(seqs, threshold, score, batch_size, batch_kmers, limit)
             return
         from concurrent.futures import ThreadPoolExecutor
         from ..storage.hip_hbm import TooManyHits
@@ -560,9 +615,10 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
             with lock:
                 try:
                     if packed is None:                           # rare: answered through search_batch's non-ASCII route
-                        return "done", chunk, self._search_batch_locked(chunk, threshold, score)
+                        return "done", chunk, self._search_batch_locked(chunk, threshold, score, limit)
                     if not score:
-                        return "arrays", chunk, st.search_many_packed(packed[0], packed[1], k, threshold)
+                        excluded = self._excluded_colours() if limit else None
+                        return "arrays", chunk, st.search_many_packed(packed[0], packed[1], k, threshold, limit=limit, excluded=excluded)
                     try:
                         return "arrays", chunk, st.search_many_scored(None, k, threshold, max_bits=SCORE_SLICE_CHARS // 8, packed=packed)
                     except TooManyHits:                          # (a low threshold on a wide index: the batch route scores in slices)
@@ -737,7 +793,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         for s in chunk[prev:]:
             yield s, []
 
-    def _search_stream_batches(self, seqs, threshold=1.0, score=False, batch_size=None, batch_kmers=1 << 19):
+    def _search_stream_batches(self, seqs, threshold=1.0, score=False, batch_size=None, batch_kmers=1 << 19, limit=None):
         """search_stream over this object's own batch workspaces (what a multi-GPU index uses), two workspaces deep: while
         the GPU runs batch i+1 the host fetches and assembles batch i (fetches wait on the batch's own completion event, not
         on the stream).  A device batch closes after `batch_size` sequences if given, else once it holds about
@@ -751,9 +807,10 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
                 plain = "".join(chunk).isascii()           # one pass at C speed
             except TypeError:                             # (bytes among the sequences)
                 plain = all(s.isascii() for s in chunk)
-            if not plain:                                 # rare: answered at once through search_batch's non-ASCII route
-                return [_Done(self.search_batch(chunk, threshold, score)), chunk]
+            if not plain or self._limit_fallback(chunk, score, limit):      # rare: answered at once through search_batch
+                return [_Done(self.search_batch(chunk, threshold, score, limit=limit)), chunk]
             batch = self._workspace(slot, chunk, ws)
+            self._set_limit(batch, limit)
             self._launch(batch, threshold)
             return [batch, chunk]
 

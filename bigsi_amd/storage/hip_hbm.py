@@ -571,9 +571,11 @@ class HipHbmStorage(BaseStorage):
         blob, soff = _lib.pack_seqs(seqs)
         return self.search_many_packed(blob, soff, k, threshold)
 
-    def search_many_packed(self, blob, soff, k, threshold=1.0):
+    def search_many_packed(self, blob, soff, k, threshold=1.0, limit=None, excluded=None):
         """search_many for sequences that are already packed: `blob` (bytes or a uint8 array) holds sequence i at
-        soff[i]:soff[i+1] (uint64, n + 1 entries) -- what bigsi_hip_fasta_pack leaves."""
+        soff[i]:soff[i+1] (uint64, n + 1 entries) -- what bigsi_hip_fasta_pack leaves.  `limit` = N: per sequence only the first N
+        hits of BIGSI.search's order, the colours in `excluded` taken out first (bigsi_hip_search_stream_ranked); lists stay in
+        ascending colour."""
         import ctypes as C
         assert threshold <= 1
         n = len(soff) - 1
@@ -587,8 +589,14 @@ class HipHbmStorage(BaseStorage):
         cap = max(self._search_cap, 1 << 12)
         while True:
             col, cnt = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
-            rc = _lib.lib().bigsi_hip_search_stream(self.handle, text, _lib.ptr(soff), n, int(k), float(threshold), 0, _lib.ptr(nk), _lib.ptr(nu), None,
-                                                    _lib.ptr(off), _lib.ptr(col), _lib.ptr(cnt), cap)
+            if limit:
+                ex = np.ascontiguousarray(excluded if excluded is not None else [], dtype=np.uint32)
+                rc = _lib.lib().bigsi_hip_search_stream_ranked(self.handle, text, _lib.ptr(soff), n, int(k), float(threshold), 0, _lib.ptr(nk),
+                                                               _lib.ptr(nu), None, _lib.ptr(off), _lib.ptr(col), _lib.ptr(cnt), cap,
+                                                               _lib.limit_arg(limit), _lib.ptr(ex) if ex.size else None, ex.size)
+            else:
+                rc = _lib.lib().bigsi_hip_search_stream(self.handle, text, _lib.ptr(soff), n, int(k), float(threshold), 0, _lib.ptr(nk), _lib.ptr(nu), None,
+                                                        _lib.ptr(off), _lib.ptr(col), _lib.ptr(cnt), cap)
             if rc != _lib.ERR_CAPACITY or int(off[-1]) <= cap:
                 break
             cap = self._search_cap = int(off[-1])
@@ -666,6 +674,16 @@ class QueryBatch(object):
         check(self._fn("reload")(self.b, blob, _lib.ptr(off), len(seqs), self.k))
         self.n, self._off = len(seqs), off
         return self
+
+    def set_limit(self, limit, excluded=None):
+        """bigsi_hip_batch_set_limit (or its group twin, over global colours): every later run keeps per sequence only the first
+        `limit` hits of BIGSI.search's order, the colours in `excluded` taken out first; None / 0 turns it off."""
+        ex = np.ascontiguousarray(excluded if (limit and excluded is not None) else [], dtype=np.uint32)
+        key = (_lib.limit_arg(limit) if limit else 0, ex.tobytes())
+        if getattr(self, "_limit", (0, b"")) == key:
+            return
+        check(self._fn("set_limit")(self.b, key[0], _lib.ptr(ex) if ex.size else None, ex.size))
+        self._limit = key
 
     def close(self):
         if self.b is not None:

@@ -229,6 +229,20 @@ int bigsi_hip_batch_destroy(bigsi_hip_batch *b);
  * (two alternating batch objects = upload of one overlaps the row-AND kernel of the other). */
 int bigsi_hip_batch_reload(bigsi_hip_batch *b, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k);
 int bigsi_hip_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags);
+/* Ranked top-N search: BIGSI.search(seq, threshold, score)[:limit] computed on the device.  The reference orders an exact search's
+ * hits by ascending colour (exact_filter, bigsi/graph/bigsi.py:192-205) and a thresholded one by num_kmers_found, descending, with
+ * a STABLE sort -- ties stay in ascending colour (inexact_filter, :211-230) -- and then drops deleted samples (:185-190).  With
+ * limit = N > 0 every later run of this batch keeps, per sequence, only the min(N, hits) hits that come first in that order: the
+ * highest counts, ties to the lowest colours, after the n_excluded colours in `excluded` (e.g. deleted samples) are taken out.
+ * A selection kernel (k_rank_select) trims each sequence's hit vector between the row-AND / counting kernels and the compaction;
+ * hit lists stay in ASCENDING COLOUR, as fetch_hits always returns them (the caller's stable sort restores the reference's
+ * order), and fetch_bitmap / fetch_counts still return the untrimmed vectors.  limit = 0 is off (the default); excluded colours
+ * are only valid with a limit (BIGSI_ERR_INVALID otherwise).  The setting persists across runs and reloads of the batch and is
+ * honoured by every run flag, BIGSI_RUN_EARLY_EXIT and the sliced small-batch route included; with BIGSI_RUN_SKIP_COMPACT it
+ * trims caller-owned result vectors (bigsi_hip_batch_set_outputs) in place.  Scope: a limited run never takes the one-launch
+ * read kernel (bigsi_hip_batch_info.one_launch is 0), and bigsi_hip_batch_run_sharded refuses a limit (BIGSI_ERR_INVALID: use a
+ * device group, include/bigsi_hip_group.h). */
+int bigsi_hip_batch_set_limit(bigsi_hip_batch *b, uint32_t limit, const uint32_t *excluded, uint64_t n_excluded);
 
 typedef struct {
     uint32_t n_seqs;
@@ -336,6 +350,14 @@ int bigsi_hip_search_batch(bigsi_hip_index *ix, const char *seqs, const uint64_t
 int bigsi_hip_search_stream(bigsi_hip_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k,
                             double threshold, uint32_t flags, uint32_t *num_kmers, uint32_t *num_unique, uint32_t *min_kmers,
                             uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t hit_capacity);
+
+/* bigsi_hip_search_stream with a result limit (bigsi_hip_batch_set_limit's meaning: per sequence the first `limit` hits of
+ * BIGSI.search's order, after the excluded colours are taken out, handed out in ascending colour).  Same outputs and capacity
+ * protocol; limit = 0 is bigsi_hip_search_stream. */
+int bigsi_hip_search_stream_ranked(bigsi_hip_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k,
+                                   double threshold, uint32_t flags, uint32_t *num_kmers, uint32_t *num_unique, uint32_t *min_kmers,
+                                   uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t hit_capacity, uint32_t limit,
+                                   const uint32_t *excluded, uint64_t n_excluded);
 
 /* BIGSI.search(..., score=True) (bigsi/graph/bigsi.py:174-190, 232-239 with bigsi/scoring/score.py:96-116) for any number of sequences
  * in ONE call: bigsi_hip_search_stream plus, for every hit t (global index into colours), its presence bits at

@@ -74,6 +74,10 @@ int bigsi_hip_group_batch_create_elements(bigsi_hip_group *g, const char *blob, 
 int bigsi_hip_group_batch_reload(bigsi_hip_group_batch *gb, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k);
 int bigsi_hip_group_batch_destroy(bigsi_hip_group_batch *gb);
 int bigsi_hip_group_batch_run(bigsi_hip_group_batch *gb, double threshold, uint32_t flags); /* asynchronous */
+/* bigsi_hip_batch_set_limit over GLOBAL colours: every shard trims to its own top N (the excluded colours translated to its
+ * own), which contains its part of the global top N; after the exchange fetch_hits cuts each sequence's list of at most
+ * shards x N hits to N by the same rule (count descending, ties to the lowest global colour) and returns it in ascending colour. */
+int bigsi_hip_group_batch_set_limit(bigsi_hip_group_batch *gb, uint32_t limit, const uint32_t *excluded, uint64_t n_excluded);
 int bigsi_hip_group_batch_fetch_unique(bigsi_hip_group_batch *gb, uint32_t *num_kmers, uint32_t *num_unique, uint32_t *min_kmers);
 int bigsi_hip_group_batch_fetch_hits(bigsi_hip_group_batch *gb, uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t capacity);
 int bigsi_hip_group_batch_presence(bigsi_hip_group_batch *gb, uint32_t seq, const uint32_t *colours, uint32_t n_colours, uint8_t *out);

@@ -1589,32 +1589,45 @@ extern "C" int bigsi_hip_batch_set_outputs(bigsi_hip_batch *b, void *d_bitmaps, 
 }
 
 // -------- K2 dispatch
-// one launch of the counting kernel over the queries [q0, q1) of the batch
+// what every launch of the counting kernel over a batch shares (the launches themselves: RowAndPlan::launch, bigsi_launch.hpp)
 struct CountLaunch {
     const uint64_t *k2_rows;
-    unsigned block;
-    uint32_t tiles;             // column tiles per query
     void *out;
     uint64_t out_stride;
     uint64_t *hit_bitmap;
-    uint32_t sparse, slices;
+    uint32_t sparse;
     bool deep;                  // software-pipelined row loads (small grids; h = 3 or 4 only)
     uint32_t early_exit;        // BIGSI_RUN_EARLY_EXIT on a hits-only, one-slice run
     uint64_t *partial;          // slices > 1: bit-sliced partial counts of every slice (k_count_combine adds them up)
     uint32_t planes_out;
 };
 
+// The counter planes `P` of a run -> the template instance <P, CountT> the counting kernels are compiled for: f(Planes<P, CountT>{})
+template <int N, typename T>
+struct Planes {
+    static constexpr int P = N;
+    using CountT = T;
+};
+template <typename F>
+static void with_planes(int P, F &&f)
+{
+    switch (P) {
+    case 6: f(Planes<6, uint16_t>{}); break;
+    case 10: f(Planes<10, uint16_t>{}); break;
+    case 12: f(Planes<12, uint16_t>{}); break;
+    case 16: f(Planes<16, uint16_t>{}); break;
+    default: f(Planes<32, uint32_t>{}); break;
+    }
+}
+
 template <int P, typename CountT>
-static void launch_count_wide(bigsi_hip_batch *b, const CountLaunch &c, uint32_t q0, uint32_t q1)
+static void launch_count_wide(bigsi_hip_batch *b, const CountLaunch &c, const RowAndLaunch &l)
 {
     bigsi_hip_index *ix = b->ix;
-    // (sliced launches map workgroups to queries in plain order -- map_block -- and need no padding to 8 queries: a single sliced query
-    // used to launch 8 x its workgroups, seven eighths of them leaving at once)
-    const unsigned grid = (unsigned)((c.slices > 1 ? (uint64_t)(q1 - q0) : ceil_div(q1 - q0, 8) * 8) * (uint64_t)c.tiles * c.slices);
 #define BIGSI_COUNT_ARGS                                                                                                      \
-    dim3(grid), dim3(c.block), 0, ix->stream, ix->d_index, ix->stride_words, (uint32_t)b->wv, c.k2_rows, b->d_pos_off.as<uint64_t>(), \
-        b->num_unique.as<uint32_t>(), ix->h, q0, q1, c.tiles, (CountT *)c.out, c.out_stride, b->min_kmers.as<uint32_t>(), ix->n_cols,  \
-        c.hit_bitmap, b->wv_pad, c.sparse, c.slices, c.early_exit, c.partial, c.planes_out
+    dim3((unsigned)l.grid), dim3(l.block), 0, ix->stream, ix->d_index, ix->stride_words, (uint32_t)b->wv, c.k2_rows, b->d_pos_off.as<uint64_t>(), \
+        b->num_unique.as<uint32_t>(), ix->h, l.q0, l.q1, l.tiles, (CountT *)c.out, c.out_stride, b->min_kmers.as<uint32_t>(), ix->n_cols,  \
+        c.hit_bitmap, b->wv_pad, c.sparse, l.slices, c.early_exit, c.partial, c.planes_out
 #define COMMA ,
 #define BIGSI_LAUNCH_COUNT(H) hipLaunchKernelGGL((k_and_count<P, H, CountT>), BIGSI_COUNT_ARGS)
 #define BIGSI_LAUNCH_COUNT_DEEP(H)                                                                        \
@@ -1634,15 +1647,9 @@ static void launch_count_wide(bigsi_hip_batch *b, const CountLaunch &c, uint32_t
 #undef COMMA
 }
 
-static void launch_count(bigsi_hip_batch *b, int P, const CountLaunch &c, uint32_t q0, uint32_t q1)
+static void launch_count(bigsi_hip_batch *b, int P, const CountLaunch &c, const RowAndLaunch &l)
 {
-    switch (P) {
-    case 6: launch_count_wide<6, uint16_t>(b, c, q0, q1); break;
-    case 10: launch_count_wide<10, uint16_t>(b, c, q0, q1); break;
-    case 12: launch_count_wide<12, uint16_t>(b, c, q0, q1); break;
-    case 16: launch_count_wide<16, uint16_t>(b, c, q0, q1); break;
-    default: launch_count_wide<32, uint32_t>(b, c, q0, q1); break;
-    }
+    with_planes(P, [&](auto pl) { launch_count_wide<decltype(pl)::P, typename decltype(pl)::CountT>(b, c, l); });
 }
 
 static int compact(bigsi_hip_batch *b, HitBufs &hb, const void *src, uint32_t n_shards, uint64_t shard_cols, bool write_only);
@@ -1764,71 +1771,10 @@ static int launch_reads_fused(bigsi_hip_batch *b, hipStream_t st = nullptr, bool
     return BIGSI_OK;
 }
 
-// The launch rule of a large exact batch (one slice, `blocks_per_q` workgroups per query of `wv`-word results): several launches, each
-// a whole number of workgroups per CU (launches of 384 or 640 workgroups measured 0.72-0.78 of peak, 512 / 768 / 1024: 0.82-0.85) with
-// about 1600-2000 LIVE wavefronts: all co-resident, sweeping the address-ordered row lists together, and no more bytes in flight than
-// the memory system schedules well -- 10 M x 100 k (13 live wavefronts per query in 4 workgroups): 512 workgroups per launch 0.853 of
-// peak, 1024: 0.819, 256: 0.68; a 12.5 k-sample shard (2 live wavefronts per workgroup): 1024 workgroups 0.773, 512: 0.581.  Queries
-// per launch a multiple of 8 (the blockIdx -> XCD map).  A batch is cut only from two launches' worth of workgroups on.
-struct ExactLaunch {
-    uint64_t blocks;       // workgroups per launch
-    uint32_t queries;      // queries per launch
-};
-static ExactLaunch exact_launch(uint64_t wv, uint64_t blocks_per_q)
-{
-    const uint64_t waves_per_q = ceil_div(wv, 64 * kVec);      // wavefronts of a query that hold columns
-    const uint64_t kb = round_up(ceil_div((uint64_t)1600 * blocks_per_q, waves_per_q), 256);
-    return {kb, (uint32_t)std::max<uint64_t>(8, (kb / blocks_per_q) / 8 * 8)};
-}
+// see bigsi_internal.hpp: the launch rule (bigsi_launch.hpp) for 256-thread workgroups
+uint32_t bigsi_exact_launch_queries(const bigsi_hip_index *ix) { return exact_launch_queries(ceil_div(ix->n_cols, 64)); }
 
-// small batches: every query's row list is cut into this many slices so that ~2k wavefronts are in flight (see map_block); `waves`:
-// wavefronts that hold columns in the whole batch
-// (one 1 kbp query on 100 k samples, its slices spread over all XCDs (map_block): exact 35 / 14.7 / 16.6 / 22.9 us at
-// 16 / 64 / 128 / 256 slices, counting 59 / 31 / 30 / 32 us; beyond that the atomics that combine the slices show)
-// (counting, round 4: a slice of ~10 k-mers leaves 4 bit-sliced planes instead of 5 for k_count_combine to add up -- one
-// 1 kbp query on 100 k samples at 0.4, the whole call: 60 slices 50.3 us, 96: 47.0, 128: 49.0; exact: 60 -> 36.3, 96 -> 35.8, 128 -> 41)
-static uint32_t row_slices(uint64_t waves, uint64_t max_pos, bool exact)
-{
-    if (waves >= 1024) return 1;
-    return (uint32_t)std::min<uint64_t>({exact ? 64u : 96u, ceil_div(2048, std::max<uint64_t>(waves, 1)), std::max<uint64_t>(max_pos / (exact ? 16 : 10), 1)});
-}
-
-// see bigsi_internal.hpp: bigsi_batch_run's launch rule for 256-thread workgroups
-uint32_t bigsi_exact_launch_queries(const bigsi_hip_index *ix)
-{
-    const uint64_t wv = ceil_div(ix->n_cols, 64);
-    if (wv == 0) return 8;
-    return exact_launch(wv, ceil_div(wv, (uint64_t)256 * kVec)).queries;
-}
-
-enum K1Route { K1_ELEMENTS, K1_WAVE, K1_LDS, K1_GLOBAL };
-struct K1Plan {
-    K1Route route;
-    uint32_t hs_cap = 0, sq_bytes = 0, tab_mult = 4, tab_cap = 2;
-    size_t lds = 0;
-};
-
-static K1Plan k1_plan(const bigsi_hip_batch *b, bool force_global)
-{
-    K1Plan p;
-    if (b->elements) { p.route = K1_ELEMENTS; return p; }
-    if (!force_global && b->max_pos <= 64) { p.route = K1_WAVE; return p; }
-    // dedupe table of the LDS route: 4 slots per position when that fits the LDS window (shorter probe chains), else 2
-    p.hs_cap = (uint32_t)round_up(std::max<uint64_t>(b->max_pos, 1), 4);
-    p.sq_bytes = (uint32_t)round_up(b->max_len + 16, 16);
-    // (a handful of queries -- a latency-bound call -- have the LDS to themselves: 8 slots per position, insert phase of one 1 kbp
-    // query 2.04 / 1.08 / 0.80 us at 2 / 4 / 8)
-    p.tab_mult = b->n_seqs <= 32 ? 8u : 4u;
-    for (;; p.tab_mult /= 2) {
-        p.tab_cap = 2;
-        while (p.tab_cap < p.tab_mult * b->max_pos && p.tab_cap < (1u << 30)) p.tab_cap <<= 1;
-        p.lds = (size_t)(p.tab_cap + p.tab_cap / 32 + 4) * 4 + 64 + (size_t)p.hs_cap * 4 + 2 * p.sq_bytes;      // table (+ sort pad) | scan | fingerprints | sequence | its complement
-        if (p.lds <= 60 * 1024 || p.tab_mult == 2) break;
-    }
-    // fused single-launch K1 (dedupe table + sequence in LDS) when every query fits the default 64 KiB dynamic-LDS window
-    p.route = (!force_global && b->max_pos <= kLdsMaxPos && p.lds <= 60 * 1024) ? K1_LDS : K1_GLOBAL;
-    return p;
-}
+static K1Plan k1_plan(const bigsi_hip_batch *b, bool force_global) { return k1_plan(b->n_seqs, b->max_pos, b->max_len, b->elements, force_global); }
 
 // K1 for the whole batch (h may have changed since create: the rows buffer is sized for it here)
 struct Preset {              // result words K1 sets for the sliced row-AND launches of a small batch (see k_kmerize_lds)
@@ -1837,7 +1783,7 @@ struct Preset {              // result words K1 sets for the sliced row-AND laun
     bool done = false;       // the K1 route taken did it (the others leave it to a memset)
 };
 
-static int run_kmerize(bigsi_hip_batch *b, double threshold, bool force_global = false, bool want_sorted = false, bool *sorted = nullptr,
+static int run_kmerize(bigsi_hip_batch *b, double threshold, const K1Plan &plan, bool want_sorted = false, bool *sorted = nullptr,
                        Preset *preset = nullptr)
 {
     uint64_t *ps_p = preset ? preset->p : nullptr;
@@ -1849,7 +1795,6 @@ static int run_kmerize(bigsi_hip_batch *b, double threshold, bool force_global =
     // index stream itself the callers' own ordering applies, as for every other entry point)
     if (b->g_done && b->gstream && b->gstream != ks) HIP_TRY(hipStreamWaitEvent(ks, b->g_done, 0));
     TRY(b->rows.reserve(std::max<uint64_t>(b->total_pos, 1) * ix->h * 8));
-    const K1Plan plan = k1_plan(b, force_global);
     const K1Src src = k1_src(b);
     if (plan.route == K1_ELEMENTS) {       // explicit k-mers: only the hashing is left of K1
         TRY(ev_begin(ix, &ep, ks));
@@ -1980,6 +1925,37 @@ static int flush_upload(bigsi_hip_batch *b, hipStream_t st, bool k1_reads_host =
     return BIGSI_OK;
 }
 
+// This batch's own earlier work that the run about to be queued on `st` must not overtake: K1 rewrites arrays it may still be
+// reading.  A batch that `was_idle` (nothing of it in flight: collected since its last run) has no waits to queue.
+// `gather`: a gathered compaction on the gather stream too -- a run whose K1 is run_kmerize leaves that wait to it.
+static int wait_previous(bigsi_hip_batch *b, hipStream_t st, bool was_idle, bool gather)
+{
+    if (was_idle) return BIGSI_OK;
+    // its previous run (one-call runs record no event: bigsi_batch_run)
+    if (b->done_stale && b->run_stream && b->run_stream != st) HIP_TRY(hipStreamSynchronize(b->run_stream));
+    else if (b->done && b->run_stream != st) HIP_TRY(hipStreamWaitEvent(st, b->done, 0));
+    if (gather && b->g_done && b->gstream && b->gstream != st) HIP_TRY(hipStreamWaitEvent(st, b->g_done, 0));
+    // a K5 / K6 request of this batch still in flight on another stream reads what K1 is about to rewrite
+    if (b->job.done && b->job.device_work) HIP_TRY(hipStreamWaitEvent(st, b->job.done, 0));
+    return BIGSI_OK;
+}
+
+// End of a run whose last kernel went out on `st`: the completion event (not for a one-call run: bigsi_batch_run) and, on the
+// index stream, what later read-kernel launches wait for.
+static int finish_run(bigsi_hip_batch *b, hipStream_t st, bool one_call, bool index_stream)
+{
+    b->done_stale = one_call;
+    if (!one_call) {
+        if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(b->done, st));
+    }
+    if (index_stream) TRY(mark_main(b->ix));
+    b->run_stream = st;
+    b->ran = true;
+    b->dirty = false;
+    return BIGSI_OK;
+}
+
 // `one_call`: the caller is bigsi_hip_search_batch, which waits for this run through the export's flag on the same stream: the
 // completion event is not recorded (one HIP call less on a path whose device work is a few microseconds); everything that would
 // wait for it waits for the stream instead (done_stale).
@@ -1991,7 +1967,7 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     // (a shard of a wider index may be empty: its result vectors, result_cols wide, are then all zero)
     if (ix->n_cols == 0 && b->result_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
     TRY(use_device(ix));
-    const bool was_idle = b->idle;      // nothing of this batch in flight (collected since its last run): no waits to queue
+    const bool was_idle = b->idle;
     b->idle = false;
     b->ran = false;
     b->host_counts_valid = false;
@@ -2017,13 +1993,7 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         else if (ix->rd_pending) TRY(quiesce_reads(ix));      // (alone on the device: nothing of the read streams beside it)
         // (the compaction kernel of a gene-length batch waits between workgroups too: such a run is over before read kernels start)
         if (ix->main_ev && st != ix->stream) HIP_TRY(hipStreamWaitEvent(st, ix->main_ev, 0));
-        if (!was_idle) {
-            if (b->done_stale && b->run_stream && b->run_stream != st) HIP_TRY(hipStreamSynchronize(b->run_stream));
-            else if (b->done && b->run_stream != st) HIP_TRY(hipStreamWaitEvent(st, b->done, 0));      // this batch's previous run
-            if (b->g_done && b->gstream && b->gstream != st) HIP_TRY(hipStreamWaitEvent(st, b->g_done, 0));
-            // a K5 / K6 request of this batch still in flight on another stream reads what K1 is about to rewrite
-            if (b->job.done && b->job.device_work) HIP_TRY(hipStreamWaitEvent(st, b->job.done, 0));
-        }
+        TRY(wait_previous(b, st, was_idle, true));
         TRY(flush_upload(b, st, true));
         TRY(ev_begin(ix, &fe, st, true));
         b->weak_fp = (flags & BIGSI_RUN_WEAK_FINGERPRINT) != 0;
@@ -2034,38 +2004,24 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         b->count_bytes = 2;
         b->sparse_counts = !b->exact;
         b->compacted = true;
-        b->done_stale = one_call;
-        if (!one_call) {
-            if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(b->done, st));
-        }
-        b->run_stream = st;
-        b->ran = true;
-        b->dirty = false;
-        return BIGSI_OK;
+        return finish_run(b, st, one_call, false);
     }
 
     // read kernels of other batches still in flight on the read streams: over before this run's kernels start (its hit
     // compaction waits between workgroups, as they do; each kind has the device to its own launches)
     TRY(quiesce_reads(ix));
+    // (with them an earlier run of this batch on a read stream: whatever it ran on last, only its K5 / K6 request is left to wait for)
     b->run_stream = ix->stream;
-    // K1e: address-ordered copy of the row lists for K2
-    // (not for the few queries of a latency-bound call either: their row lists are cut into slices over many workgroups -- see
-    // `slices` below -- and the ordering buys nothing, it only lengthens the chain of kernels: 10 us of a 65 us single query)
-    // caller-owned result buffers (a shard's slot of a gather buffer): a bitmap can be preset and sliced like the batch's own
-    // (the counting path then cuts its hit mask from the slices' summed partial counts, k_count_combine); caller-owned counters are
-    // written in place, without presets
-    const bool sliceable = !b->ext_counts;
-    const uint64_t all_waves = (uint64_t)b->n_seqs * ceil_div(b->wv, 64 * kVec);
-    const bool few = all_waves < 1024 && sliceable;
-    const bool want_sorted = b->exact && !few && !(flags & BIGSI_RUN_NO_SORT) && b->total_pos && b->max_pos * ix->h >= 1024;
-    const uint32_t slices = sliceable ? row_slices(all_waves, b->max_pos, b->exact) : 1;
-    // planes needed for the largest possible count = max k-mers of any sequence in the batch
-    const uint64_t maxu = b->max_pos;
-    const int P = maxu < (1ull << 6) ? 6 : maxu < (1ull << 10) ? 10 : maxu < (1ull << 12) ? 12 : maxu < (1ull << 16) ? 16 : 32;
+    TRY(wait_previous(b, ix->stream, was_idle, false));
+
+    // the plans: K1's route and the row-AND launches (bigsi_launch.hpp)
+    const K1Plan k1 = k1_plan(b, (flags & BIGSI_RUN_K1_GLOBAL) != 0);
+    const RowAndPlan plan = plan_row_and(RowAndInput{b->n_seqs, b->wv, b->max_pos, ix->h, b->exact, (flags & BIGSI_RUN_NO_SORT) != 0,
+                                                     (flags & BIGSI_RUN_EARLY_EXIT) != 0, (flags & BIGSI_RUN_SPARSE_COUNTS) != 0,
+                                                     b->ext_counts != nullptr});
     // the sliced launches combine into preset result words (all ones for the AND, zero counters): K1 sets them on its way
     Preset preset;
-    if (slices > 1 && b->exact) {
+    if (plan.preset) {
         uint64_t *out = (uint64_t *)b->ext_bitmaps;
         if (!out) { TRY(b->bitmaps.reserve((size_t)b->n_seqs * b->wv_pad * 8)); out = b->bitmaps.as<uint64_t>(); }
         preset.p = out; preset.words = b->wv_pad; preset.value = ~0ull;
@@ -2073,20 +2029,11 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     // K1 (its LDS route emits the sorted list itself; the other routes leave that to k_sort_rows below)
     EventPair ep{};
     bool sorted_by_k1 = false;
-    if (!was_idle && b->job.done && b->job.device_work) HIP_TRY(hipStreamWaitEvent(ix->stream, b->job.done, 0));      // (as on the read path above)
-    if (!was_idle && b->done_stale && b->run_stream && b->run_stream != ix->stream) HIP_TRY(hipStreamSynchronize(b->run_stream));      // (a read run of this workspace)
-    {
-        const K1Route route = k1_plan(b, (flags & BIGSI_RUN_K1_GLOBAL) != 0).route;
-        TRY(flush_upload(b, ix->stream, route == K1_WAVE || route == K1_LDS));
-    }
-    TRY(run_kmerize(b, threshold, (flags & BIGSI_RUN_K1_GLOBAL) != 0, want_sorted, &sorted_by_k1, &preset));
-    b->dirty = true;        // until `done` is recorded at the end
+    TRY(flush_upload(b, ix->stream, k1.route == K1_WAVE || k1.route == K1_LDS));
+    TRY(run_kmerize(b, threshold, k1, plan.want_sorted, &sorted_by_k1, &preset));
+    b->dirty = true;        // until finish_run
     const uint64_t *k2_rows = sorted_by_k1 ? b->rows_sorted.as<uint64_t>() : b->rows.as<uint64_t>();
-    // exact path only: there every row can move freely (+4.7 % C3, +7.6 % C4-shard, interleaved A/B); on the counting path a
-    // k-mer's h rows must stay together and ordering k-mers by their first row measured 1.00x
-    // and only for long row lists (>= 1024 rows per query): for read-length queries (C2: 93 rows) the extra launch costs more
-    // than the ordering gains (0.100 vs 0.083 ms per step measured)
-    if (want_sorted && !sorted_by_k1) {
+    if (plan.want_sorted && !sorted_by_k1) {
         TRY(b->rows_sorted.reserve(std::max<uint64_t>(b->total_pos, 1) * ix->h * 8));
         uint32_t shift = 0;
         while (((ix->m - 1) >> shift) >= (uint64_t)kSortBuckets) shift++;
@@ -2102,78 +2049,30 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         TRY(ev_end(ix, &ep, ix->ev_km));
         k2_rows = b->rows_sorted.as<uint64_t>();
     }
-    // K2
-    // the counting kernels are compiled for at most 256 threads per workgroup (register budget of the plane arrays)
-    // one wavefront per workgroup for batches of a few thousand wavefronts (80 ... 300 gene-length queries on 100 k samples):
-    // they are a single launch, a CU's share of it is what bounds it, and 4-wavefront workgroups leave the CUs unevenly loaded
-    // (320 / 576 / 800 workgroups on 256 CUs: 0.69 / 0.68 / 0.71 of peak against 0.81 / 0.76 / 0.76 with 64 threads); the large
-    // launches, sized in whole workgroups per CU, keep 256 threads (0.85 against 0.79)
-    // (exact batches large enough for the launch rule below to cut them -- from 256 such queries on -- are not "mid")
-    bool mid = all_waves >= 1024 && all_waves < 4096;
-    if (mid) {
-        const uint64_t t256 = ceil_div(b->wv, 256 * kVec), blocks256 = ceil_div(b->n_seqs, 8) * 8 * t256;
-        // ... nor are batches that already are a whole number of 4-wavefront workgroups per CU (256 queries on a 62.5 k-sample
-        // shard: 512 workgroups, 0.80-0.82 either way)
-        if (blocks256 % 256 == 0 || (b->exact && blocks256 >= 2 * exact_launch(b->wv, t256).blocks)) mid = false;
-    }
-    // (a sliced exact launch -- a latency-bound call -- in workgroups of two wavefronts: the pieces spread more evenly over the CUs and the
-    // stragglers end sooner; one 1 kbp query on 100 k samples, the call: 256 -> 41.9, 128 -> 41.2, 64 -> 41.4 us; counting: no difference)
-    const int and_block = mid ? 64 : (slices > 1 && b->exact) ? 128 : 256;
-    // row loads a lane keeps in flight: 8, or 4 when 8 would put more bytes in flight on the chip (queries of the launch x row bytes x
-    // loads) than the memory system schedules well -- the optimum measured at 8-13 MB.  Interleaved A/B: 256 queries per launch on
-    // 62.5 k-sample shards (7.8 KB rows: 16 MB at 8 loads): 4 -> +3.3 % (C4 shard 263 -> 272 M lookups/s) / +2.2 % (north-star shard),
-    // 6 -> +1.5 %, 2 -> -17 %; unchunked C3 launches of 160-248 queries (16-25 MB): 4 -> +2 ... +9 %.  At 12.8 MB 8 stays: C3's 128-query
-    // launches (4: -5 %) and C3 split over 2 / 4 / 8 GPUs -- 256 x 6.3 KB, 512 x 3.1 KB, 1024 x 1.6 KB rows per launch (4: -7 / -10 /
-    // -7 %).
-    const uint32_t tiles = (uint32_t)ceil_div(b->wv, (uint64_t)and_block * kVec);
-    // large exact batches go out as several launches (exact_launch); the counting kernel measured -4 ... 0 % chunked and stays one launch
-    const uint64_t blocks_per_q = (uint64_t)tiles * slices;
-    uint32_t chunk_q = b->n_seqs;
-    {
-        const uint64_t total_blocks = ceil_div(b->n_seqs, 8) * 8 * blocks_per_q;
-        if (total_blocks > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "batch too large for one launch (%llu workgroups)", (unsigned long long)total_blocks);
-        if (slices == 1 && b->exact) {
-            const ExactLaunch el = exact_launch(b->wv, blocks_per_q);
-            if (total_blocks >= 2 * el.blocks) chunk_q = el.queries;
-        }
-    }
-    uint32_t n_launches = 0;
+    // K2: the plan's launches
+    if (plan.too_large) return fail(BIGSI_ERR_INVALID, "batch too large for one launch (%llu workgroups)", (unsigned long long)plan.too_large);
     if (b->exact) {
         uint64_t *out = (uint64_t *)b->ext_bitmaps;
         if (!out) { TRY(b->bitmaps.reserve((size_t)b->n_seqs * b->wv_pad * 8)); out = b->bitmaps.as<uint64_t>(); }
-        if (slices > 1 && !preset.done) HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)b->n_seqs * b->wv_pad * 8, ix->stream));
+        if (plan.preset && !preset.done) HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)b->n_seqs * b->wv_pad * 8, ix->stream));
         TRY(ev_begin(ix, &ep, nullptr, true));
-        for (uint32_t q0 = 0; q0 < b->n_seqs; q0 += chunk_q, n_launches++) {
-            const uint32_t q1 = std::min<uint64_t>((uint64_t)q0 + chunk_q, b->n_seqs);
-            unsigned grid = (unsigned)((slices > 1 ? (uint64_t)(q1 - q0) : ceil_div(q1 - q0, 8) * 8) * blocks_per_q), l_block = (unsigned)and_block;
-            uint32_t l_tiles = tiles, l_slices = slices;
-            if (chunk_q < b->n_seqs && q1 - q0 < chunk_q && and_block == 256) {
-                // the last launch of a batch that is not a multiple of the launch size is a batch of its own kind: with a few
-                // thousand wavefronts one-wavefront workgroups (see `mid` above), with fewer the sliced launch of a small batch
-                const uint64_t waves_r = (uint64_t)(q1 - q0) * ceil_div(b->wv, 64 * kVec);
-                if (waves_r < 1024) {
-                    l_slices = row_slices(waves_r, b->max_pos, true);
-                    if (l_slices > 1) HIP_TRY(hipMemsetAsync(out + (uint64_t)q0 * b->wv_pad, 0xFF, (size_t)(q1 - q0) * b->wv_pad * 8, ix->stream));
-                    grid = (unsigned)((l_slices > 1 ? (uint64_t)(q1 - q0) : ceil_div(q1 - q0, 8) * 8) * (uint64_t)tiles * l_slices);
-                } else if (grid % 256 != 0) {
-                    l_block = 64;
-                    l_tiles = (uint32_t)ceil_div(b->wv, 64 * kVec);
-                    grid = (unsigned)(ceil_div(q1 - q0, 8) * 8 * (uint64_t)l_tiles);
-                }
-            }
+        for (uint32_t i = 0; i < plan.n_launches; i++) {
+            const RowAndLaunch l = plan.launch(i);
+            // (a sliced last launch of an unsliced batch: its words alone)
+            if (l.needs_preset && !plan.preset)
+                HIP_TRY(hipMemsetAsync(out + (uint64_t)l.q0 * b->wv_pad, 0xFF, (size_t)(l.q1 - l.q0) * b->wv_pad * 8, ix->stream));
 #define BIGSI_LAUNCH_EXACT(U)                                                                                                  \
-    hipLaunchKernelGGL((k_and_exact<U>), dim3(grid), dim3(l_block), 0, ix->stream, ix->d_index, ix->stride_words, (uint32_t)b->wv, \
-                       ix->n_cols, k2_rows, b->d_pos_off.as<uint64_t>(), b->num_unique.as<uint32_t>(), ix->h, q0,    \
-                       q1, l_tiles, out, b->wv_pad, l_slices, (flags & BIGSI_RUN_EARLY_EXIT) ? 1u : 0u)
-            const uint64_t in_flight_at_8 = (uint64_t)(q1 - q0) * b->wv * 8 * 8;
-            if (in_flight_at_8 > (29ull << 19) /* 14.5 MB */ && l_slices == 1) BIGSI_LAUNCH_EXACT(4);
+    hipLaunchKernelGGL((k_and_exact<U>), dim3((unsigned)l.grid), dim3(l.block), 0, ix->stream, ix->d_index, ix->stride_words, (uint32_t)b->wv, \
+                       ix->n_cols, k2_rows, b->d_pos_off.as<uint64_t>(), b->num_unique.as<uint32_t>(), ix->h, l.q0,    \
+                       l.q1, l.tiles, out, b->wv_pad, l.slices, (flags & BIGSI_RUN_EARLY_EXIT) ? 1u : 0u)
+            if (l.unroll == 4) BIGSI_LAUNCH_EXACT(4);
             else BIGSI_LAUNCH_EXACT(8);
 #undef BIGSI_LAUNCH_EXACT
         }
         HIP_TRY(hipGetLastError());
-        TRY(ev_end(ix, &ep, ix->ev_and, nullptr, n_launches));
+        TRY(ev_end(ix, &ep, ix->ev_and, nullptr, plan.n_launches));
     } else {
-        b->count_bytes = P <= 16 ? 2 : 4;
+        b->count_bytes = plan.count_bytes;
         const uint64_t cstride = b->wv_pad * 64;
         void *out = b->ext_counts;
         if (!out) { TRY(b->counts.reserve((size_t)b->n_seqs * cstride * b->count_bytes)); out = b->counts.p; }
@@ -2182,49 +2081,28 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         uint64_t *hb = b->ext_bitmaps ? (uint64_t *)b->ext_bitmaps : b->bitmaps.as<uint64_t>();
         b->sparse_counts = (flags & BIGSI_RUN_SPARSE_COUNTS) && !b->ext_counts;
         const uint32_t sparse = b->sparse_counts ? 1u : 0u;
-        // a sliced (small) batch: every slice leaves its partial counts bit-sliced in scratch memory -- as many planes as a slice's
-        // k-mers need -- and k_count_combine adds them up, thresholds and expands (no presets, no atomics)
-        uint32_t planes_out = 0;
+        // a sliced (small) batch: every slice leaves its partial counts bit-sliced in scratch memory and k_count_combine adds them up
         uint64_t *partial = nullptr;
-        if (slices > 1) {
-            const uint64_t per_slice = ceil_div(std::max<uint64_t>(b->max_pos, 1), slices);
-            while (planes_out < (uint32_t)P && (per_slice >> planes_out) != 0) planes_out++;
-            TRY(b->planes.reserve((size_t)b->n_seqs * slices * planes_out * b->wv_pad * 8));
+        if (plan.combine) {
+            TRY(b->planes.reserve((size_t)b->n_seqs * plan.slices * plan.planes_out * b->wv_pad * 8));
             partial = b->planes.as<uint64_t>();
         }
         TRY(ev_begin(ix, &ep, nullptr, true));
-        // fewer than ~3 wavefronts per SIMD in the whole grid (e.g. 128 gene-length queries): the software-pipelined loop,
-        // whose wavefronts load the next k-mers' rows while adding the current ones (5.6 -> 6.3 TB/s at 128 x 2-4 kbp; with a
-        // full grid other wavefronts already cover the ALU phase and it measured -2 ... +0 %)
-        const uint64_t grid_waves = (uint64_t)b->n_seqs * tiles * (and_block / 64);
-        // (only with >= 12 planes, i.e. queries of >= 1024 k-mers: at 10 planes the ALU phase is short and it measured -2 %)
-        const bool deep = slices == 1 && P >= 12 && grid_waves < 3 * 1024;
-        const uint32_t early = ((flags & BIGSI_RUN_EARLY_EXIT) && sparse && slices == 1) ? 1u : 0u;
-        if (ceil_div(b->n_seqs, 8) * 8 * (uint64_t)tiles * slices > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "batch too large for one launch");
-        const CountLaunch cl{k2_rows, (unsigned)and_block, tiles, out, cstride, hb, sparse, slices, deep && !early, early, partial, planes_out};
-        for (uint32_t q0 = 0; q0 < b->n_seqs; q0 += chunk_q, n_launches++)
-            launch_count(b, P, cl, q0, (uint32_t)std::min<uint64_t>((uint64_t)q0 + chunk_q, b->n_seqs));
-        if (slices > 1) {        // the slices' partial counts -> totals, hit mask, counters
-            const unsigned grid = (unsigned)(b->n_seqs * ceil_div(b->wv, kBlock / 8));      // 32 words per workgroup, 8 slice groups per word
-#define BIGSI_COMBINE(PP, T)                                                                                                          \
-    hipLaunchKernelGGL((k_count_combine<PP, T>), dim3(grid), dim3(kBlock), 0, ix->stream, partial, slices, planes_out, b->wv_pad, (uint32_t)b->wv, \
-                       b->n_seqs, b->num_unique.as<uint32_t>(), b->min_kmers.as<uint32_t>(), ix->n_cols, hb, (T *)out, cstride, sparse)
-            switch (P) {
-            case 6: BIGSI_COMBINE(6, uint16_t); break;
-            case 10: BIGSI_COMBINE(10, uint16_t); break;
-            case 12: BIGSI_COMBINE(12, uint16_t); break;
-            case 16: BIGSI_COMBINE(16, uint16_t); break;
-            default: BIGSI_COMBINE(32, uint32_t); break;
-            }
-#undef BIGSI_COMBINE
+        const CountLaunch cl{k2_rows, out, cstride, hb, sparse, plan.deep, plan.early ? 1u : 0u, partial, plan.planes_out};
+        for (uint32_t i = 0; i < plan.n_launches; i++) launch_count(b, plan.P, cl, plan.launch(i));
+        if (plan.combine) {        // the slices' partial counts -> totals, hit mask, counters
+            with_planes(plan.P, [&](auto pl) {
+                using CountT = typename decltype(pl)::CountT;
+                hipLaunchKernelGGL((k_count_combine<decltype(pl)::P, CountT>), dim3((unsigned)plan.combine_grid), dim3(kBlock), 0, ix->stream, partial, plan.slices,
+                                   plan.planes_out, b->wv_pad, (uint32_t)b->wv, b->n_seqs, b->num_unique.as<uint32_t>(), b->min_kmers.as<uint32_t>(),
+                                   ix->n_cols, hb, (CountT *)out, cstride, sparse);
+            });
         }
         HIP_TRY(hipGetLastError());
-        TRY(ev_end(ix, &ep, ix->ev_and, nullptr, n_launches));
+        TRY(ev_end(ix, &ep, ix->ev_and, nullptr, plan.n_launches));
     }
 
     b->compacted = !(flags & BIGSI_RUN_SKIP_COMPACT);
-    if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
-    b->done_stale = false;
     if (!b->compacted) {
         // a member of a device group: its slot of the gather buffer goes into the exchange already trimmed to this shard's top N
         if (b->limit && b->ext_bitmaps) {
@@ -2232,23 +2110,14 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
             TRY(rank_select(b, b->ext_bitmaps, b->exact ? nullptr : (b->ext_counts ? b->ext_counts : b->counts.p), b->ext_bitmaps, ix->stream));
             TRY(ev_end(ix, &ep, ix->ev_cp));
         }
-        HIP_TRY(hipEventRecord(b->done, ix->stream));
-        TRY(mark_main(ix));
-        b->ran = true;
-        b->dirty = false;
-        return BIGSI_OK;
+        return finish_run(b, ix->stream, false, true);      // (the group waits for the event, whoever started the run)
     }
     // K4 on this shard's own result
     TRY(ev_begin(ix, &ep));
     const void *src = b->exact ? (b->ext_bitmaps ? b->ext_bitmaps : b->bitmaps.p) : (b->ext_counts ? b->ext_counts : b->counts.p);
     TRY(compact(b, b->hits, src, 1, ix->n_cols, false));
     TRY(ev_end(ix, &ep, ix->ev_cp));
-    b->done_stale = one_call;
-    if (!one_call) HIP_TRY(hipEventRecord(b->done, ix->stream));
-    TRY(mark_main(ix));
-    b->ran = true;
-    b->dirty = false;
-    return BIGSI_OK;
+    return finish_run(b, ix->stream, one_call, true);
 }
 
 extern "C" int bigsi_hip_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags)
@@ -3167,7 +3036,7 @@ extern "C" int bigsi_hip_lookup(bigsi_hip_index *ix, const char *kmers, uint32_t
     for (uint64_t i = 0; i <= u; i++) off[i] = i * k;
     bigsi_hip_batch *b = nullptr;
     TRY(bigsi_hip_batch_create(ix, kmers, off.data(), (uint32_t)u, k, &b));
-    int rc = run_kmerize(b, 1.0);
+    int rc = run_kmerize(b, 1.0, k1_plan(b, false));
     const uint64_t wv = ix->wv(), rb = ix->rb();
     if (rc == BIGSI_OK) rc = b->scratch.reserve((size_t)u * wv * 8);
     if (rc == BIGSI_OK) {
@@ -3200,7 +3069,7 @@ extern "C" int bigsi_hip_lookup_raw(bigsi_hip_index *ix, const char *blob, const
     for (uint64_t i = 0; i <= u; i++) one[i] = i;
     bigsi_hip_batch *b = nullptr;
     TRY(bigsi_hip_batch_create_elements(ix, blob, elem_offsets, one.data(), zero.data(), one.data(), (uint32_t)u, &b));
-    int rc = run_kmerize(b, 1.0);
+    int rc = run_kmerize(b, 1.0, k1_plan(b, false));
     const uint64_t wv = ix->wv(), rb = ix->rb();
     if (rc == BIGSI_OK) rc = b->scratch.reserve((size_t)u * wv * 8);
     if (rc == BIGSI_OK) {

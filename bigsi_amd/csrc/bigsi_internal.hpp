@@ -35,8 +35,7 @@ int bigsi_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 
             return rc_;      \
     } while (0)
 
-static inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-static inline uint64_t ceil_div(uint64_t x, uint64_t a) { return (x + a - 1) / a; }
+#include "bigsi_launch.hpp"      // round_up, ceil_div and the launch rule of a batch run
 
 // ------------------------------------------------------------------------------ device buffer with growth
 struct DevBuf {

@@ -13,13 +13,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bigsi_launch.hpp"      // kBlock, kVec, kLdsMaxPos: shared with the host's launch rule
 #include "bigsi_score.hpp"
 
 namespace bigsi {
 
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr int kBlock = 256;      // 4 wavefronts
-constexpr int kVec = 2;          // uint64 words per lane per row load (16 B/lane, 1 KiB per wave instruction)
 
 // ------------------------------------------------------------------------------ small helpers
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
@@ -445,7 +444,6 @@ __global__ __launch_bounds__(kBlock) void k_kmer_rows(
 // and gene-length queries).  One workgroup per query; the sequence and the dedupe table live in LDS (ds_cmpst / ds_min
 // instead of L2 atomics), and the workgroup goes insert -> resolve -> ordered compaction -> hash without leaving the CU.
 // Same results as the four-kernel path above, which remains the route for longer queries.
-constexpr uint32_t kLdsMaxPos = 4096;
 
 // The bytes of ONE query passed BY VALUE in the kernel arguments (a one-call search of a single sequence).  The runtime writes a
 // launch's arguments into device-visible memory together with the packet, so the kernel's first loads are local instead of a round

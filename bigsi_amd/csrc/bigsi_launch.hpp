@@ -1,0 +1,259 @@
+// bigsi_launch.hpp -- the launch rule of a batch run, host-only: how K1 goes out (k1_plan) and how the row-AND kernels
+// (k_and_exact, k_and_count, k_count_combine) are launched for a batch of queries (plan_row_and).  Pure functions of a handful of
+// integers: no HIP, no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp compiles this header as
+// plain host C++ and tests/test_abi_and_host.py pins the decisions on the CPU.
+//
+// Every constant below was measured on an MI355X; the notes beside them say against what.  A GPU test compares results, and a slip
+// here keeps results right and costs the 3 to 20 % those notes record: change a constant only with a new measurement, and the pinned
+// shapes of the CPU test with it.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+static inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+static inline uint64_t ceil_div(uint64_t x, uint64_t a) { return (x + a - 1) / a; }
+
+namespace bigsi {
+
+constexpr int kBlock = 256;      // 4 wavefronts
+constexpr int kVec = 2;          // uint64 words per lane per row load (16 B/lane, 1 KiB per wave instruction)
+
+// K1 fused (k_kmerize_lds): ONE launch for batches whose longest query has at most kLdsMaxPos k-mer positions (a 4 kbp query)
+constexpr uint32_t kLdsMaxPos = 4096;
+
+// ------------------------------------------------------------------------------ K1
+enum K1Route { K1_ELEMENTS, K1_WAVE, K1_LDS, K1_GLOBAL };
+struct K1Plan {
+    K1Route route;
+    uint32_t hs_cap = 0, sq_bytes = 0, tab_mult = 4, tab_cap = 2;
+    size_t lds = 0;
+};
+
+// `max_pos` / `max_len`: k-mer positions / bytes of the batch's longest query; `elements`: the batch holds explicit k-mers
+static inline K1Plan k1_plan(uint32_t n_seqs, uint64_t max_pos, uint64_t max_len, bool elements, bool force_global)
+{
+    K1Plan p;
+    if (elements) { p.route = K1_ELEMENTS; return p; }
+    if (!force_global && max_pos <= 64) { p.route = K1_WAVE; return p; }
+    // dedupe table of the LDS route: 4 slots per position when that fits the LDS window (shorter probe chains), else 2
+    p.hs_cap = (uint32_t)round_up(std::max<uint64_t>(max_pos, 1), 4);
+    p.sq_bytes = (uint32_t)round_up(max_len + 16, 16);
+    // (a handful of queries -- a latency-bound call -- have the LDS to themselves: 8 slots per position, insert phase of one 1 kbp
+    // query 2.04 / 1.08 / 0.80 us at 2 / 4 / 8)
+    p.tab_mult = n_seqs <= 32 ? 8u : 4u;
+    for (;; p.tab_mult /= 2) {
+        p.tab_cap = 2;
+        while (p.tab_cap < p.tab_mult * max_pos && p.tab_cap < (1u << 30)) p.tab_cap <<= 1;
+        p.lds = (size_t)(p.tab_cap + p.tab_cap / 32 + 4) * 4 + 64 + (size_t)p.hs_cap * 4 + 2 * p.sq_bytes;      // table (+ sort pad) | scan | fingerprints | sequence | its complement
+        if (p.lds <= 60 * 1024 || p.tab_mult == 2) break;
+    }
+    // fused single-launch K1 (dedupe table + sequence in LDS) when every query fits the default 64 KiB dynamic-LDS window
+    p.route = (!force_global && max_pos <= kLdsMaxPos && p.lds <= 60 * 1024) ? K1_LDS : K1_GLOBAL;
+    return p;
+}
+
+// ------------------------------------------------------------------------------ row-AND
+// The launch rule of a large exact batch (one slice, `blocks_per_q` workgroups per query of `wv`-word results): several launches, each
+// a whole number of workgroups per CU (launches of 384 or 640 workgroups measured 0.72-0.78 of peak, 512 / 768 / 1024: 0.82-0.85) with
+// about 1600-2000 LIVE wavefronts: all co-resident, sweeping the address-ordered row lists together, and no more bytes in flight than
+// the memory system schedules well -- 10 M x 100 k (13 live wavefronts per query in 4 workgroups): 512 workgroups per launch 0.853 of
+// peak, 1024: 0.819, 256: 0.68; a 12.5 k-sample shard (2 live wavefronts per workgroup): 1024 workgroups 0.773, 512: 0.581.  Queries
+// per launch a multiple of 8 (the blockIdx -> XCD map).  A batch is cut only from two launches' worth of workgroups on.
+struct ExactLaunch {
+    uint64_t blocks;       // workgroups per launch
+    uint32_t queries;      // queries per launch
+};
+static inline ExactLaunch exact_launch(uint64_t wv, uint64_t blocks_per_q)
+{
+    const uint64_t waves_per_q = ceil_div(wv, 64 * kVec);      // wavefronts of a query that hold columns
+    const uint64_t kb = round_up(ceil_div((uint64_t)1600 * blocks_per_q, waves_per_q), 256);
+    return {kb, (uint32_t)std::max<uint64_t>(8, (kb / blocks_per_q) / 8 * 8)};
+}
+
+// small batches: every query's row list is cut into this many slices so that ~2k wavefronts are in flight (see map_block); `waves`:
+// wavefronts that hold columns in the whole batch
+// (one 1 kbp query on 100 k samples, its slices spread over all XCDs (map_block): exact 35 / 14.7 / 16.6 / 22.9 us at
+// 16 / 64 / 128 / 256 slices, counting 59 / 31 / 30 / 32 us; beyond that the atomics that combine the slices show)
+// (counting, round 4: a slice of ~10 k-mers leaves 4 bit-sliced planes instead of 5 for k_count_combine to add up -- one
+// 1 kbp query on 100 k samples at 0.4, the whole call: 60 slices 50.3 us, 96: 47.0, 128: 49.0; exact: 60 -> 36.3, 96 -> 35.8, 128 -> 41)
+static inline uint32_t row_slices(uint64_t waves, uint64_t max_pos, bool exact)
+{
+    if (waves >= 1024) return 1;
+    return (uint32_t)std::min<uint64_t>({exact ? 64u : 96u, ceil_div(2048, std::max<uint64_t>(waves, 1)), std::max<uint64_t>(max_pos / (exact ? 16 : 10), 1)});
+}
+
+// Queries per launch of a large exact batch in 256-thread workgroups on results of `wv` words: search_stream_impl cuts its chunks
+// at whole launches (bigsi_exact_launch_queries)
+static inline uint32_t exact_launch_queries(uint64_t wv)
+{
+    if (wv == 0) return 8;
+    return exact_launch(wv, ceil_div(wv, (uint64_t)256 * kVec)).queries;
+}
+
+// what the rule reads of a batch, its index and its run
+struct RowAndInput {
+    uint32_t n_seqs;
+    uint64_t wv;                // 64-column words of a result vector
+    uint64_t max_pos;           // k-mer positions of the longest query
+    uint32_t h;                 // rows per k-mer
+    bool exact;                 // k_and_exact (threshold 1.0), else the counting kernels
+    bool no_sort, early_exit, sparse_counts;      // BIGSI_RUN_NO_SORT / _EARLY_EXIT / _SPARSE_COUNTS
+    bool ext_counts;            // caller-owned counters: written in place, so the batch is never sliced and never sparse
+};
+
+// one row-AND launch over the queries [q0, q1)
+struct RowAndLaunch {
+    uint32_t q0, q1;
+    uint64_t grid;              // workgroups
+    uint32_t block;             // threads per workgroup: 64, 128 or 256
+    uint32_t tiles;             // column tiles (workgroups) per query and slice
+    uint32_t slices;
+    uint32_t unroll;            // row loads a lane keeps in flight, k_and_exact<unroll>: 4 or 8 (the counting kernels do not read it: 8)
+    bool needs_preset;          // exact, sliced: the slices AND into the launch's result words, which start as all ones
+};
+
+struct RowAndPlan {
+    uint64_t too_large = 0;     // > 0: the batch does not fit one launch (this many workgroups) and the plan has no launches
+    uint32_t slices = 1;        // of the whole batch (a chunked batch's last launch may differ: launch())
+    bool want_sorted = false;   // K2 reads an address-ordered copy of the row lists (K1's LDS route or k_sort_rows makes it)
+    bool preset = false;        // exact, sliced: ALL result words start as all ones -- K1 sets them on its way, or a memset does
+    int P = 6;                  // counter planes: 6, 10, 12, 16 or 32
+    uint32_t count_bytes = 2;   // of a counter
+    uint32_t planes_out = 0;    // counting, sliced: planes of a slice's partial counts
+    bool combine = false;       // counting, sliced: k_count_combine adds the slices up ...
+    uint64_t combine_grid = 0;  // ... in this many workgroups of kBlock threads
+    bool deep = false;          // counting: the software-pipelined kernel variant (it exists for h = 3 and 4)
+    bool early = false;         // counting: early exit (never together with `deep`)
+    uint32_t n_launches = 0;
+
+    RowAndLaunch launch(uint32_t i) const;
+
+    // the whole batch's shape, and what launch() needs
+    RowAndInput in{};
+    uint32_t block = 256, tiles = 1, chunk_q = 0;
+};
+
+// Workgroups of a launch of `n` queries.  Sliced launches map workgroups to queries in plain order -- map_block -- and need no padding
+// to 8 queries: a single sliced query used to launch 8 x its workgroups, seven eighths of them leaving at once.
+static inline uint64_t row_and_grid(uint64_t n, uint64_t tiles, uint64_t slices)
+{
+    return (slices > 1 ? n : ceil_div(n, 8) * 8) * tiles * slices;
+}
+
+// One-wavefront workgroups for `n` unsliced queries?  Batches of a few thousand wavefronts (80 ... 300 gene-length queries on
+// 100 k samples) are a single launch, a CU's share of it is what bounds it, and 4-wavefront workgroups leave the CUs unevenly loaded
+// (320 / 576 / 800 workgroups on 256 CUs: 0.69 / 0.68 / 0.71 of peak against 0.81 / 0.76 / 0.76 with 64 threads); the large
+// launches, sized in whole workgroups per CU, keep 256 threads (0.85 against 0.79).  Nor is a launch that already is a whole number of
+// 4-wavefront workgroups per CU "mid" (256 queries on a 62.5 k-sample shard: 512 workgroups, 0.80-0.82 either way).
+static inline bool mid_launch(uint64_t n, uint64_t wv, uint64_t waves)
+{
+    return waves >= 1024 && row_and_grid(n, ceil_div(wv, 256 * kVec), 1) % 256 != 0;
+}
+
+static inline RowAndPlan plan_row_and(const RowAndInput &in)
+{
+    RowAndPlan p;
+    p.in = in;
+    const uint64_t waves_per_q = ceil_div(in.wv, 64 * kVec), all_waves = in.n_seqs * waves_per_q;
+    // caller-owned result buffers (a shard's slot of a gather buffer): a bitmap can be preset and sliced like the batch's own
+    // (the counting path then cuts its hit mask from the slices' summed partial counts, k_count_combine); caller-owned counters are
+    // written in place, without presets
+    const bool sliceable = !in.ext_counts;
+    p.slices = sliceable ? row_slices(all_waves, in.max_pos, in.exact) : 1;
+    const bool few = all_waves < 1024 && sliceable;
+    // K1e: address-ordered copy of the row lists for K2
+    // exact path only: there every row can move freely (+4.7 % C3, +7.6 % C4-shard, interleaved A/B); on the counting path a
+    // k-mer's h rows must stay together and ordering k-mers by their first row measured 1.00x
+    // and only for long row lists (>= 1024 rows per query): for read-length queries (C2: 93 rows) the extra launch costs more
+    // than the ordering gains (0.100 vs 0.083 ms per step measured)
+    // (not for the few queries of a latency-bound call either: their row lists are cut into slices over many workgroups and the
+    // ordering buys nothing, it only lengthens the chain of kernels: 10 us of a 65 us single query)
+    p.want_sorted = in.exact && !few && !in.no_sort && in.max_pos * in.h >= 1024;
+    // planes needed for the largest possible count = max k-mers of any sequence in the batch
+    const uint64_t maxu = in.max_pos;
+    p.P = maxu < (1ull << 6) ? 6 : maxu < (1ull << 10) ? 10 : maxu < (1ull << 12) ? 12 : maxu < (1ull << 16) ? 16 : 32;
+    p.count_bytes = p.P <= 16 ? 2 : 4;
+    p.preset = p.slices > 1 && in.exact;
+
+    // the counting kernels are compiled for at most 256 threads per workgroup (register budget of the plane arrays)
+    // one-wavefront workgroups: see mid_launch
+    // (exact batches large enough for exact_launch to cut them -- from 256 such queries on -- are not "mid")
+    const uint64_t t256 = ceil_div(in.wv, 256 * kVec);
+    const bool mid = all_waves < 4096 && mid_launch(in.n_seqs, in.wv, all_waves) &&
+                     !(in.exact && row_and_grid(in.n_seqs, t256, 1) >= 2 * exact_launch(in.wv, t256).blocks);
+    // (a sliced exact launch -- a latency-bound call -- in workgroups of two wavefronts: the pieces spread more evenly over the CUs and the
+    // stragglers end sooner; one 1 kbp query on 100 k samples, the call: 256 -> 41.9, 128 -> 41.2, 64 -> 41.4 us; counting: no difference)
+    p.block = mid ? 64 : p.preset ? 128 : 256;
+    p.tiles = (uint32_t)ceil_div(in.wv, (uint64_t)p.block * kVec);
+
+    // (the bound counts the queries padded to 8, sliced or not)
+    const uint64_t total_blocks = row_and_grid(in.n_seqs, (uint64_t)p.tiles * p.slices, 1);
+    if (total_blocks > 0x7FFFFFFFull) { p.too_large = total_blocks; return p; }
+    // large exact batches go out as several launches (exact_launch); the counting kernel measured -4 ... 0 % chunked and stays one launch
+    p.chunk_q = in.n_seqs;
+    if (p.slices == 1 && in.exact) {
+        const ExactLaunch el = exact_launch(in.wv, p.tiles);
+        if (total_blocks >= 2 * el.blocks) p.chunk_q = el.queries;
+    }
+    p.n_launches = p.chunk_q ? (uint32_t)ceil_div(in.n_seqs, p.chunk_q) : 0;
+
+    if (!in.exact) {
+        // a sliced (small) batch: every slice leaves its partial counts bit-sliced in scratch memory -- as many planes as a slice's
+        // k-mers need -- and k_count_combine adds them up, thresholds and expands (no presets, no atomics)
+        if (p.slices > 1) {
+            const uint64_t per_slice = ceil_div(std::max<uint64_t>(in.max_pos, 1), p.slices);
+            while (p.planes_out < (uint32_t)p.P && (per_slice >> p.planes_out) != 0) p.planes_out++;
+            p.combine = true;
+            p.combine_grid = in.n_seqs * ceil_div(in.wv, kBlock / 8);      // 32 words per workgroup, 8 slice groups per word
+        }
+        p.early = in.early_exit && in.sparse_counts && !in.ext_counts && p.slices == 1;
+        // fewer than ~3 wavefronts per SIMD in the whole grid (e.g. 128 gene-length queries): the software-pipelined loop,
+        // whose wavefronts load the next k-mers' rows while adding the current ones (5.6 -> 6.3 TB/s at 128 x 2-4 kbp; with a
+        // full grid other wavefronts already cover the ALU phase and it measured -2 ... +0 %)
+        const uint64_t grid_waves = (uint64_t)in.n_seqs * p.tiles * (p.block / 64);
+        // (only with >= 12 planes, i.e. queries of >= 1024 k-mers: at 10 planes the ALU phase is short and it measured -2 %)
+        p.deep = p.slices == 1 && p.P >= 12 && grid_waves < 3 * 1024 && !p.early;
+    }
+    return p;
+}
+
+inline RowAndLaunch RowAndPlan::launch(uint32_t i) const
+{
+    RowAndLaunch l;
+    l.q0 = i * chunk_q;
+    l.q1 = (uint32_t)std::min<uint64_t>((uint64_t)l.q0 + chunk_q, in.n_seqs);
+    l.block = block;
+    l.tiles = tiles;
+    l.slices = slices;
+    const uint32_t n = l.q1 - l.q0;
+    if (chunk_q < in.n_seqs && n < chunk_q && block == 256) {
+        // the last launch of a batch that is not a multiple of the launch size is a batch of its own kind: with a few thousand
+        // wavefronts one-wavefront workgroups (mid_launch), with fewer the sliced launch of a small batch.  The rule of a whole
+        // batch, except that
+        //  - a sliced tail keeps the workgroups of 256 threads its batch runs in (a whole batch: 128);
+        //  - a tail is sliced even beside caller-owned counters, which an exact run does not write (a whole batch: never);
+        //  - a tail has no upper bound of 4096 wavefronts (it has fewer than a launch's 1600-2000 anyway, unless its rows are
+        //    wider than 4 M columns, when a launch is the minimum of 8 queries).
+        const uint64_t waves = (uint64_t)n * ceil_div(in.wv, 64 * kVec);
+        if (waves < 1024) l.slices = row_slices(waves, in.max_pos, true);
+        else if (mid_launch(n, in.wv, waves)) {
+            l.block = 64;
+            l.tiles = (uint32_t)ceil_div(in.wv, 64 * kVec);
+        }
+    }
+    l.grid = row_and_grid(n, l.tiles, l.slices);
+    l.needs_preset = in.exact && l.slices > 1;
+    // row loads a lane keeps in flight: 8, or 4 when 8 would put more bytes in flight on the chip (queries of the launch x row bytes x
+    // loads) than the memory system schedules well -- the optimum measured at 8-13 MB.  Interleaved A/B: 256 queries per launch on
+    // 62.5 k-sample shards (7.8 KB rows: 16 MB at 8 loads): 4 -> +3.3 % (C4 shard 263 -> 272 M lookups/s) / +2.2 % (north-star shard),
+    // 6 -> +1.5 %, 2 -> -17 %; unchunked C3 launches of 160-248 queries (16-25 MB): 4 -> +2 ... +9 %.  At 12.8 MB 8 stays: C3's 128-query
+    // launches (4: -5 %) and C3 split over 2 / 4 / 8 GPUs -- 256 x 6.3 KB, 512 x 3.1 KB, 1024 x 1.6 KB rows per launch (4: -7 / -10 /
+    // -7 %).
+    const uint64_t in_flight_at_8 = (uint64_t)n * in.wv * 8 * 8;
+    l.unroll = (in.exact && in_flight_at_8 > (29ull << 19) /* 14.5 MB */ && l.slices == 1) ? 4 : 8;
+    return l;
+}
+
+}  // namespace bigsi

@@ -677,3 +677,137 @@ def test_dense_bench_plants_and_the_oracles_bulk_bookkeeping():
     c_.insert_kmer_masks(c_.rows_of(seq), cols, masks, only)
     assert c_.planted == {r: v for r, v in a.planted.items() if r in set(only.tolist())}
     assert sorted(bench.dense_read_cols(1, 5, 0, 10000)) == sorted(set(bench.dense_read_cols(1, 5, 0, 10000))) and len(bench.dense_read_cols(1, 5, 0, 10000)) == 8
+
+
+# --------------------------------------------------------------------------------------------- the row-AND launch rule, pinned on the CPU
+# bigsi_amd/csrc/bigsi_launch.hpp decides how the row-AND kernels are launched for a batch (slices, workgroup size, tiles, queries per
+# launch, the last partial launch, loads in flight, counter planes).  The GPU suite compares results, which a slip in the rule leaves
+# right; here the header is compiled as host C++ (tests/c_host/launch_host.cpp) and its decisions are pinned.
+HEAD_FIELDS = ("too_large", "slices", "want_sorted", "preset", "P", "count_bytes", "planes_out", "combine", "deep", "early", "n_launches")
+LAUNCH_FIELDS = ("q0", "q1", "grid", "block", "tiles", "slices", "unroll", "needs_preset")
+
+
+def build_launch_host(tmp_path):
+    import ctypes
+    import subprocess
+    so = str(tmp_path / "liblaunch_host.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-Werror",
+                           "-o", so, os.path.join(ROOT, "tests", "c_host", "launch_host.cpp")])
+    lib = ctypes.CDLL(so)
+    lib.launch_host_plan.restype = ctypes.c_uint64
+    lib.launch_host_grid.restype = ctypes.c_uint64
+    lib.launch_host_grid.argtypes = [ctypes.c_uint64] * 3
+    lib.launch_host_exact_launch_queries.restype = ctypes.c_uint32
+    lib.launch_host_exact_launch_queries.argtypes = [ctypes.c_uint64]
+    return lib
+
+
+def plan_on_host(lib, n_seqs, wv, max_pos, h=3, exact=True, no_sort=False, early_exit=False, sparse_counts=False, ext_counts=False):
+    """(head, launches): the plan's fields by name, and one dict per launch."""
+    import ctypes
+    head = np.zeros(len(HEAD_FIELDS), np.uint64)
+    cap = n_seqs // 8 + 2                  # (launches take at least 8 queries)
+    rec = np.zeros((cap, len(LAUNCH_FIELDS)), np.uint64)
+    n = lib.launch_host_plan(ctypes.c_uint32(n_seqs), ctypes.c_uint64(wv), ctypes.c_uint64(max_pos), ctypes.c_uint32(h), int(exact),
+                             int(no_sort), int(early_exit), int(sparse_counts), int(ext_counts), head.ctypes.data_as(ctypes.c_void_p),
+                             rec.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(cap))
+    assert n <= cap
+    return dict(zip(HEAD_FIELDS, map(int, head))), [dict(zip(LAUNCH_FIELDS, map(int, r))) for r in rec[:n]]
+
+
+def test_row_and_launch_rule_pinned_shapes(tmp_path):
+    """The shapes DESIGN.md and the GPU tests' docstrings state, as the planner gives them.  C3: 100 000 samples (1563 result words),
+    1 kbp queries (970 k-mers); the C4 / north-star shard: 62 500 samples (977 words)."""
+    lib = build_launch_host(tmp_path)
+    C3, SHARD, KBP = 1563, 977, 970
+
+    def launch(q0, q1, grid, block, tiles, slices, unroll, needs_preset):
+        return dict(zip(LAUNCH_FIELDS, (q0, q1, grid, block, tiles, slices, unroll, int(needs_preset))))
+
+    # a C3 stream chunk: 8 launches of 128 queries (DESIGN section 5: 64 launches per 8192-query step; 8 loads in flight stay)
+    head, ls = plan_on_host(lib, 1024, C3, KBP)
+    assert (head["slices"], head["want_sorted"], head["preset"], head["too_large"]) == (1, 1, 0, 0)
+    assert ls == [launch(128 * i, 128 * i + 128, 512, 256, 4, 1, 8, False) for i in range(8)]
+    assert lib.launch_host_exact_launch_queries(C3) == 128
+    # 256 queries on the 62.5 k-sample shard: one launch, k_and_exact<4>, not in one-wavefront workgroups
+    head, ls = plan_on_host(lib, 256, SHARD, KBP)
+    assert ls == [launch(0, 256, 512, 256, 2, 1, 4, False)]
+    # 20 000 samples (test_search_stream_chunks_cut_at_whole_row_and_launches)
+    assert lib.launch_host_exact_launch_queries(313) == 768
+    # one 1 kbp query on C3: a latency-bound call, sliced over many small workgroups
+    head, ls = plan_on_host(lib, 1, C3, KBP)
+    assert (head["slices"], head["want_sorted"], head["preset"]) == (60, 0, 1)
+    assert ls == [launch(0, 1, 420, 128, 7, 60, 8, True)]
+    # ... at threshold 0.4: 96 slices of ~10 k-mers, 4 planes each for k_count_combine to add up
+    head, ls = plan_on_host(lib, 1, C3, KBP, exact=False, sparse_counts=True)
+    assert (head["slices"], head["P"], head["planes_out"], head["combine"], head["preset"]) == (96, 10, 4, 1, 0)
+    assert (ls[0]["block"], ls[0]["slices"], ls[0]["needs_preset"]) == (256, 96, 0) and len(ls) == 1
+    # C3 at 0.4: the counting kernel stays one launch
+    head, ls = plan_on_host(lib, 4096, C3, KBP, exact=False, sparse_counts=True)
+    assert (len(ls), head["P"], head["count_bytes"], head["deep"], head["slices"], head["combine"]) == (1, 10, 2, 0, 1, 0)
+    assert (ls[0]["q0"], ls[0]["q1"], ls[0]["block"], ls[0]["tiles"], ls[0]["grid"]) == (0, 4096, 256, 4, 4096 * 4)
+    # 128 queries of 4 kbp: a small grid of long queries takes the software-pipelined kernel
+    head, ls = plan_on_host(lib, 128, C3, 3970, h=4, exact=False, sparse_counts=True)
+    assert (head["P"], head["deep"], head["early"], head["count_bytes"]) == (12, 1, 0, 2)
+    # queries beyond 65 535 k-mers: 4-byte counters
+    head, ls = plan_on_host(lib, 10, C3, 70000, exact=False, sparse_counts=True)
+    assert (head["P"], head["count_bytes"]) == (32, 4)
+    # a chunked batch with a short tail: 57 x 13 = 741 wavefronts, under 1024 -> the tail is sliced, its words preset
+    head, ls = plan_on_host(lib, 1024 + 57, C3, KBP)
+    assert (head["slices"], head["preset"]) == (1, 0)
+    assert ls == [launch(128 * i, 128 * i + 128, 512, 256, 4, 1, 8, False) for i in range(8)] + [launch(1024, 1081, 57 * 4 * 3, 256, 4, 3, 8, True)]
+    # ... and a longer one: 1300 wavefronts in 104 x 4 = 416 workgroups, no whole number per CU -> one-wavefront workgroups
+    head, ls = plan_on_host(lib, 1024 + 100, C3, KBP)
+    assert ls == [launch(128 * i, 128 * i + 128, 512, 256, 4, 1, 8, False) for i in range(8)] + [launch(1024, 1124, 104 * 13, 64, 13, 1, 8, False)]
+
+
+def test_row_and_launch_rule_invariants(tmp_path):
+    """Over a seeded sweep of geometries: the launches cover the batch once and in order, full launches of a chunked batch start at a
+    multiple of 8 queries, every grid is the one formula and fits a launch (or the plan says "too large"), and the enumerated
+    choices stay within their sets."""
+    import random
+    lib = build_launch_host(tmp_path)
+    rng = random.Random(20)
+
+    def log_uniform(lo, hi):
+        return min(hi, max(lo, int(math.exp(rng.uniform(math.log(lo), math.log(hi + 1))))))
+
+    n_plans = n_chunked = n_tails = n_too_large = 0
+    for i in range(4000):
+        n_seqs, wv, max_pos = log_uniform(1, 10000), log_uniform(1, 8000), log_uniform(1, 70000)
+        if i % 100 == 99: n_seqs, wv = rng.randint(3000000, 4000000), rng.randint(390000, 400000)      # beyond one launch: ~2.3e9 to 3.1e9 workgroups
+        h = rng.randint(1, 6)
+        kw = dict(exact=rng.random() < 0.5, no_sort=rng.random() < 0.2, early_exit=rng.random() < 0.3, sparse_counts=rng.random() < 0.5,
+                  ext_counts=rng.random() < 0.2)
+        head, ls = plan_on_host(lib, n_seqs, wv, max_pos, h, **kw)
+        n_plans += 1
+        where = (n_seqs, wv, max_pos, h, kw)
+        assert head["P"] in (6, 10, 12, 16, 32) and head["count_bytes"] == (2 if head["P"] <= 16 else 4), where
+        assert head["planes_out"] <= head["P"], where
+        assert not (head["deep"] and head["early"]), where
+        if head["too_large"]:
+            n_too_large += 1
+            assert head["too_large"] > 2**31 - 1 and ls == [], where
+            continue
+        assert len(ls) == head["n_launches"] >= 1, where
+        assert ls[0]["q0"] == 0 and ls[-1]["q1"] == n_seqs, where
+        for a, b in zip(ls, ls[1:]):
+            assert a["q1"] == b["q0"], where
+        n_chunked += len(ls) > 1
+        n_tails += len(ls) > 1 and (ls[-1]["block"], ls[-1]["slices"]) != (ls[0]["block"], ls[0]["slices"])
+        for j, l in enumerate(ls):
+            assert l["q0"] < l["q1"], where
+            if len(ls) > 1 and j < len(ls) - 1:
+                assert l["q0"] % 8 == 0 and (l["q1"] - l["q0"]) % 8 == 0 and l["q1"] - l["q0"] == ls[0]["q1"], where
+            assert l["grid"] == lib.launch_host_grid(l["q1"] - l["q0"], l["tiles"], l["slices"]) <= 2**31 - 1, where
+            assert l["unroll"] in (4, 8) and l["block"] in (64, 128, 256), where
+            assert l["tiles"] == -(-wv // (l["block"] * 2)), where               # the tiles of a query cover its wv words, 2 per lane
+            assert l["needs_preset"] == (kw["exact"] and l["slices"] > 1), where
+            if not kw["exact"]:
+                assert len(ls) == 1 and l["slices"] == head["slices"] and l["block"] in (64, 256), where
+        assert head["combine"] == (not kw["exact"] and head["slices"] > 1), where
+        assert head["preset"] == (kw["exact"] and head["slices"] > 1), where
+    # the sweep reaches every kind of plan
+    assert n_plans == 4000 and n_chunked > 100 and n_tails > 20 and n_too_large == 40, (n_chunked, n_tails, n_too_large)
+    # the one grid formula: unsliced launches are padded to 8 queries (the blockIdx -> XCD map), sliced ones are not
+    assert lib.launch_host_grid(57, 4, 1) == 64 * 4 and lib.launch_host_grid(57, 4, 3) == 57 * 4 * 3 and lib.launch_host_grid(1, 7, 60) == 420

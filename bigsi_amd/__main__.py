@@ -34,7 +34,8 @@ def get_config_from_file(config_file):            # __main__.py:86-94
         return yaml.safe_load(f)
 
 
-def main(argv=None):
+def build_parser():
+    """(the argument parser, and the sub-parsers of `search` and `bulk_search` for their own error messages)"""
     p = argparse.ArgumentParser(prog="bigsi_amd")
     sub = p.add_subparsers(dest="cmd", required=True)
 
@@ -51,9 +52,8 @@ def main(argv=None):
                              "themselves on stdout)")
         return sp
 
-    def limited(sp):
-        sp.add_argument("--limit", type=positive_int, default=None, metavar="N",
-                        help="only the first N results of every record (the best N samples: most k-mers found, ties to the lowest colour)")
+    def limited(sp, text="only the first N results of every record (the best N samples: most k-mers found, ties to the lowest colour)"):
+        sp.add_argument("--limit", type=positive_int, default=None, metavar="N", help=text)
         return sp
 
     sp = limited(shardable(common(sub.add_parser("search"))))
@@ -98,6 +98,31 @@ def main(argv=None):
     sp.add_argument("--until-eof", action="store_true", help="also exit when stdin ends (a parent process that holds the other end of a pipe)")
     sp = common(sub.add_parser("import-bdb", help="load an existing BerkeleyDB index (v0.3 file, or a v0.1 directory with graph + metadata) into HBM"))
     sp.add_argument("path")
+    sp = common(sub.add_parser("stats", help="how full every sample's Bloom filter is: bits set, fill, the k-mer false-positive rate it implies, estimated distinct k-mers"))
+    sp.add_argument("--format", choices=["json", "csv"], default="json")
+    sp = limited(common(sub.add_parser("similar", help="the samples whose Bloom filters share most with SAMPLE's: bits shared, Jaccard index, containment")),
+                 "only the N most similar samples (highest Jaccard index, ties to the lowest colour)")
+    sp.add_argument("sample")
+    sp.add_argument("--format", choices=["json", "csv"], default="json")
+    return p, search_parser, bulk_parser
+
+
+def stats_text(index, fmt="json"):
+    """`stats`: BIGSI.sample_stats() as JSON, or CSV with a header line."""
+    from .stats import STATS_KEYS, to_csv
+    rows = index.sample_stats()
+    return to_csv(rows, STATS_KEYS) if fmt == "csv" else json.dumps(rows)
+
+
+def similar_text(index, sample, limit=None, fmt="json"):
+    """`similar`: BIGSI.similar_samples(sample, limit) as JSON, or CSV with a header line."""
+    from .stats import SIMILAR_KEYS, to_csv
+    rows = index.similar_samples(sample, limit=limit)
+    return to_csv(rows, SIMILAR_KEYS) if fmt == "csv" else json.dumps(rows)
+
+
+def main(argv=None):
+    p, search_parser, bulk_parser = build_parser()
     a = p.parse_args(argv)
     if getattr(a, "sharded", False) and getattr(a, "limit", None) is not None:
         (search_parser if a.cmd == "search" else bulk_parser).error("--limit is not available with --sharded (use a single index or storage-config devices)")
@@ -148,6 +173,10 @@ def main(argv=None):
             print("rows=%d cols=%d" % bdb.import_index(a.path, dst))
     elif a.cmd == "delete":
         get_storage(config).delete_all()
+    elif a.cmd == "stats":
+        print(stats_text(BIGSI(config), a.format))
+    elif a.cmd == "similar":
+        print(similar_text(BIGSI(config), a.sample, a.limit, a.format))
     elif a.cmd == "hold":
         hold(config, a.handle, a.seconds, a.until_eof)
     return 0

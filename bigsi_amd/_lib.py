@@ -92,6 +92,7 @@ SIGNATURES = {
     "bigsi_hip_bdb_small_records": (_i32, [C.c_char_p, _P, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), _u32]),
     "bigsi_hip_insert_column": (_i32, [_P, _u64, _P]),
     "bigsi_hip_get_column": (_i32, [_P, _u64, _P]),
+    "bigsi_hip_column_popcounts": (_i32, [_P, _P, _P, _u64]),
     "bigsi_hip_insert_columns": (_i32, [_P, _u64, _u64, _P, _u64]),
     "bigsi_hip_insert_columns_device": (_i32, [_P, _u64, _u64, _P, _u64]),
     "bigsi_hip_append_index": (_i32, [_P, _P]),
@@ -155,6 +156,7 @@ SIGNATURES = {
     "bigsi_hip_group_get_rows": (_i32, [_P, _P, _u64, _P, _u64]),
     "bigsi_hip_group_insert_columns": (_i32, [_P, _u64, _u64, _P, _u64]),
     "bigsi_hip_group_get_column": (_i32, [_P, _u64, _P]),
+    "bigsi_hip_group_column_popcounts": (_i32, [_P, _P, _P, _u64]),
     "bigsi_hip_group_insert_kmers": (_i32, [_P, _u64, C.c_char_p, _P, _u32, _u32]),
     "bigsi_hip_group_fill_synthetic": (_i32, [_P, _u64, _u32]),
     "bigsi_hip_group_lookup": (_i32, [_P, C.c_char_p, _u32, _u64, _P]),

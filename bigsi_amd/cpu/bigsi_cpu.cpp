@@ -580,6 +580,23 @@ int bigsi_cpu_get_column(bigsi_cpu_index *ix, uint64_t col, uint8_t *out)
     return BIGSI_OK;
 }
 
+// per column, the rows (of the selected ones) that have its bit: one row at a time, one column at a time
+int bigsi_cpu_column_popcounts(bigsi_cpu_index *ix, const uint8_t *row_mask, uint64_t *out, uint64_t capacity)
+{
+    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    if (!ix || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (capacity < ix->n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "capacity %llu is below num_cols %llu", (unsigned long long)capacity, (unsigned long long)ix->n_cols);
+    for (uint64_t c = 0; c < ix->n_cols; c++) out[c] = 0;
+    for (uint64_t r = 0; r < ix->m; r++) {
+        if (row_mask && !(row_mask[r >> 3] & (0x80u >> (r & 7)))) continue;
+        const uint8_t *row = ix->row(r);
+        for (uint64_t c = 0; c < ix->n_cols; c++)
+            if (row[c >> 3] & (0x80u >> (c & 7))) out[c]++;
+    }
+    return BIGSI_OK;
+}
+
 int bigsi_cpu_insert_kmers(bigsi_cpu_index *ix, uint64_t col, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k)
 {
     if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");

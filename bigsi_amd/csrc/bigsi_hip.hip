@@ -1058,6 +1058,53 @@ extern "C" int bigsi_hip_get_column(bigsi_hip_index *ix, uint64_t col, uint8_t *
     return BIGSI_OK;
 }
 
+// Sample statistics: the vertical popcount (k_col_popcount, launch shape: plan_col_popcount).  The partial counters of the row blocks
+// live for this call only (a few MB for a test index, ~130 MB beside a 125 GB one): statistics are asked for now and then, not in a
+// serving loop, so the handle keeps nothing resident for them.
+namespace {
+struct CallScratch {
+    DevBuf buf;
+    ~CallScratch() { buf.release(); }
+};
+}  // namespace
+
+extern "C" int bigsi_hip_column_popcounts(bigsi_hip_index *ix, const uint8_t *row_mask, uint64_t *out, uint64_t capacity)
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (capacity < ix->n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "capacity %llu is below num_cols %llu", (unsigned long long)capacity, (unsigned long long)ix->n_cols);
+    if (ix->n_cols == 0) return BIGSI_OK;
+    if (ix->m == 0) { memset(out, 0, ix->n_cols * 8); return BIGSI_OK; }
+    TRY(use_device(ix));
+    const ColPopPlan p = plan_col_popcount(ix->m, ix->stride_words);
+    if (p.grid > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "index too large for one popcount launch (%llu workgroups)", (unsigned long long)p.grid);
+    CallScratch partial;
+    TRY(partial.buf.reserve(p.row_blocks * p.partial_stride * 4));
+    TRY(ix->stage_ids.reserve(ix->n_cols * 8));
+    const uint64_t *d_mask = nullptr;
+    if (row_mask) {
+        const uint64_t words = ceil_div(ix->m, 64);
+        TRY(ix->stage.reserve(words * 8));
+        HIP_TRY(hipMemsetAsync(ix->stage.as<uint64_t>() + (words - 1), 0, 8, ix->stream));       // the bytes past ceil(m / 8) of the last word
+        HIP_TRY(hipMemcpyAsync(ix->stage.p, row_mask, ceil_div(ix->m, 8), hipMemcpyHostToDevice, ix->stream));
+        d_mask = ix->stage.as<uint64_t>();
+    }
+    if (d_mask)
+        hipLaunchKernelGGL(k_col_popcount<true>, dim3((unsigned)p.grid), dim3(p.block), 0, ix->stream, ix->d_index, ix->stride_words, ix->m,
+                           p.rows_per_block, (uint32_t)p.seg_groups, p.flush_groups, d_mask, partial.buf.as<uint32_t>(), p.partial_stride);
+    else
+        hipLaunchKernelGGL(k_col_popcount<false>, dim3((unsigned)p.grid), dim3(p.block), 0, ix->stream, ix->d_index, ix->stride_words, ix->m,
+                           p.rows_per_block, (uint32_t)p.seg_groups, p.flush_groups, d_mask, partial.buf.as<uint32_t>(), p.partial_stride);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_col_popcount_sum, dim3((unsigned)ceil_div(ix->n_cols, kBlock)), dim3(kBlock), 0, ix->stream, partial.buf.as<uint32_t>(),
+                       p.partial_stride, p.row_blocks, ix->n_cols, ix->stage_ids.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, ix->stage_ids.p, ix->n_cols * 8, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    return BIGSI_OK;
+}
+
 static int check_offsets(const uint64_t *offsets, uint32_t n_seqs)
 {
     for (uint32_t i = 0; i < n_seqs; i++) {

@@ -2573,6 +2573,156 @@ __global__ __launch_bounds__(kBlock) void k_get_column(
     }
 }
 
+// ------------------------------------------------------------------------------ sample statistics: per-column popcounts
+// The vertical popcount of the matrix: for every column the number of rows that have its bit set -- all rows, or (MASKED) the rows a
+// Bloom-filter-shaped selector names, which is |A AND B_c| for every sample c at once.  Decomposition as K2 (a wavefront owns one
+// 1 KiB column segment, a lane 16 bytes of it; the workgroups of a row block sit side by side over the segments) except that a
+// wavefront walks a contiguous block of rows [rb * rows_per_block, +rows_per_block) instead of a row list: the grid is column
+// segments x row blocks (plan_col_popcount, bigsi_launch.hpp).  kColPopLoads rows are loaded at a time -- independent 16-byte loads,
+// streamed, never reused -- and reduced by a carry-save tree (7 full adders: 8 rows -> one bit each for the planes 1, 2, 4 and a
+// carry into plane 8, rippled up the rest), ~7 bit-ops per row and word against k_and_count's 3 per plane.  The kColPopPlanes
+// bit-sliced planes hold 2^planes - 1 rows: every flush_groups groups (the host's rule keeps flush_groups * kColPopLoads below that)
+// they are expanded -- the row format's permutation, column 8b + jj of a word at bit 8b + 7 - jj -- and added into the wavefront's own
+// 32-bit counters, its 8192 entries of partial[row block][column].  Nobody else writes those, so there are no atomics and no
+// workgroup waits for another; k_col_popcount_sum adds the row blocks up.  A counter sees at most rows_per_block <= 2^31 rows
+// (plan_col_popcount) and the sum is 64 bits wide: nothing wraps for any num_rows.
+// MASKED: `mask` is the selector in the row byte format (bit r = byte r / 8 under 0x80 >> (r % 8): what bigsi_hip_get_column and
+// bigsi_hip_bloom write), zero-padded to whole 64-row words.  A row block starts at a multiple of 64 rows; its mask words are
+// wave-uniform (scalar loads), the wavefront walks their set bits and loads only those rows, 8 at a time; bits at rows >= num_rows are cut off.
+template <bool MASKED>
+__global__ __launch_bounds__(kBlock) void k_col_popcount(
+    const uint64_t *__restrict__ index, uint64_t stride_words, uint64_t num_rows, uint64_t rows_per_block, uint32_t seg_groups,
+    uint32_t flush_groups, const uint64_t *__restrict__ mask, uint32_t *__restrict__ partial, uint64_t partial_stride)
+{
+    constexpr int P = kColPopPlanes, L = kColPopLoads;
+    static_assert(L == 8 && P > 3 && P <= 31, "the carry-save tree below takes 8 rows and feeds plane 3");
+    const uint64_t rb = blockIdx.x / seg_groups;
+    const uint64_t w0 = ((uint64_t)(blockIdx.x - rb * seg_groups) * blockDim.x + threadIdx.x) * kVec;
+    if (w0 >= stride_words) return;        // (the stride is a multiple of 16 words: a lane's two words are inside it or both outside)
+    const uint64_t r0 = rb * rows_per_block;
+    const uint64_t r1 = r0 + rows_per_block < num_rows ? r0 + rows_per_block : num_rows;
+    uint32_t *cnt = partial + rb * partial_stride + w0 * 64;
+
+    u64x2 pl[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) pl[p] = u64x2{0ull, 0ull};
+    uint32_t groups = 0;
+    bool first = true;
+
+    // full adder on bit vectors: s = a ^ b ^ c, carry = majority(a, b, c)
+    auto csa = [](u64x2 &carry, u64x2 &s, u64x2 a, u64x2 b, u64x2 c) {
+        const u64x2 u = a ^ b;
+        carry = (a & b) | (u & c);
+        s = u ^ c;
+    };
+    auto add8 = [&](const u64x2 (&v)[L]) {
+        u64x2 t2a, t2b, t4a, t4b, c8;
+        csa(t2a, pl[0], pl[0], v[0], v[1]);
+        csa(t2b, pl[0], pl[0], v[2], v[3]);
+        csa(t4a, pl[1], pl[1], t2a, t2b);
+        csa(t2a, pl[0], pl[0], v[4], v[5]);
+        csa(t2b, pl[0], pl[0], v[6], v[7]);
+        csa(t4b, pl[1], pl[1], t2a, t2b);
+        csa(c8, pl[2], pl[2], t4a, t4b);
+#pragma unroll
+        for (int p = 3; p < P; p++) {
+            const u64x2 t = pl[p] & c8;
+            pl[p] ^= c8;
+            c8 = t;
+        }
+    };
+    // planes -> this wavefront's counters: 8 consecutive columns (one byte of the row) per pair of 16-byte accesses
+    auto flush = [&]() {
+#pragma unroll
+        for (int e = 0; e < kVec; e++) {
+#pragma unroll
+            for (int b = 0; b < 8; b++) {
+                uint32_t c[8];
+#pragma unroll
+                for (int jj = 0; jj < 8; jj++) {
+                    const int bit = 8 * b + 7 - jj;
+                    uint32_t x = 0;
+#pragma unroll
+                    for (int p = 0; p < P; p++) x |= (uint32_t)(((e ? pl[p].y : pl[p].x) >> bit) & 1ull) << p;
+                    c[jj] = x;
+                }
+                uint4 *o = reinterpret_cast<uint4 *>(cnt + e * 64 + 8 * b);
+                uint4 lo{c[0], c[1], c[2], c[3]}, hi{c[4], c[5], c[6], c[7]};
+                if (!first) {
+                    const uint4 a = o[0], d = o[1];
+                    lo.x += a.x; lo.y += a.y; lo.z += a.z; lo.w += a.w;
+                    hi.x += d.x; hi.y += d.y; hi.z += d.z; hi.w += d.w;
+                }
+                o[0] = lo;
+                o[1] = hi;
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < P; p++) pl[p] = u64x2{0ull, 0ull};
+        first = false;
+        groups = 0;
+    };
+
+    if (MASKED) {
+        // wave-uniform walk over the set bits of the block's mask words: a group takes the next 8 selected rows, across word
+        // boundaries, so only the block's last group is partly filled
+        auto word = [&](uint64_t r) {                      // bit i: row r + i selected
+            const uint64_t s = by_column(mask[r >> 6]);
+            return r1 - r < 64 ? s & ((1ull << (r1 - r)) - 1) : s;
+        };
+        uint64_t r = r0, sel = r0 < r1 ? word(r0) : 0;
+        for (;;) {
+            u64x2 v[L];
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < L; j++) {
+                while (!sel && r + 64 < r1) {
+                    r += 64;
+                    sel = word(r);
+                }
+                if (sel) {
+                    v[j] = load_row_seg(index, r + (uint64_t)__builtin_ctzll(sel), stride_words, (uint32_t)w0);
+                    sel &= sel - 1;
+                    any = true;
+                } else v[j] = u64x2{0ull, 0ull};
+            }
+            if (!any) break;
+            add8(v);
+            if (++groups == flush_groups) flush();
+        }
+    } else {
+        uint64_t r = r0;
+        for (; r + L <= r1; r += L) {
+            u64x2 v[L];
+#pragma unroll
+            for (int j = 0; j < L; j++) v[j] = load_row_seg(index, r + j, stride_words, (uint32_t)w0);
+            add8(v);
+            if (++groups == flush_groups) flush();
+        }
+        if (r < r1) {
+            u64x2 v[L];
+#pragma unroll
+            for (int j = 0; j < L; j++) v[j] = r + j < r1 ? load_row_seg(index, r + j, stride_words, (uint32_t)w0) : u64x2{0ull, 0ull};
+            add8(v);
+            groups++;
+        }
+    }
+    if (groups || first) flush();          // (a wavefront without rows still writes its zeros: the sum reads every row block)
+}
+
+// out[c] = sum over the row blocks of partial[row block][c], for the columns the index has: the pad columns of the stride are
+// never reported, whatever their bits are (bigsi_hip_set_rows can put bits there)
+__global__ __launch_bounds__(kBlock) void k_col_popcount_sum(
+    const uint32_t *__restrict__ partial, uint64_t partial_stride, uint64_t row_blocks, uint64_t n_cols, uint64_t *__restrict__ out)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= n_cols) return;
+    uint64_t s = 0;
+#pragma unroll 8
+    for (uint64_t b = 0; b < row_blocks; b++) s += partial[b * partial_stride + c];
+    out[c] = s;
+}
+
 // transpose (bigsi/matrix/transpose.py:33-43) on the device: n Bloom filters (bloom c at blooms + c*bloom_stride, m bits,
 // row byte format) become columns [col0, col0+n) of the matrix.  One thread per (row, 64-column word); the 8 threads of
 // 8 consecutive rows read the same Bloom byte (one L1 line per wave), the word is read-modified-written once.

@@ -256,4 +256,49 @@ inline RowAndLaunch RowAndPlan::launch(uint32_t i) const
     return l;
 }
 
+// ------------------------------------------------------------------------------ column popcounts (k_col_popcount, k_col_popcount_sum)
+// The vertical popcount sweeps the whole matrix once: a wavefront owns one 1 KiB column segment (kVec words per lane) of a contiguous
+// block of rows, adds the rows kColPopLoads at a time -- that many independent 16-byte loads in flight per lane, as k_and_exact<8>,
+// reduced by a carry-save tree -- into kColPopPlanes bit-sliced planes, and flushes the planes into its own 32-bit counters (its slice
+// of a [row block][column] scratch array) before they can overflow: kColPopPlanes planes hold 2^planes - 1 rows, so a flush is due
+// every flush_groups groups of loads.  k_col_popcount_sum then adds the row blocks of a column up in 64 bits.
+//   - Row blocks supply the parallelism: a 100 k-sample index has 13 column segments, a 62.5 k-sample shard 62, and the sweep wants
+//     about kColPopWaves wavefronts whatever the width, so rows_per_block = rows x segments / kColPopWaves, in whole flush periods:
+//     kColPopFlushRows = 960 rows (<= 2^planes - 1, a multiple of the 64 rows of a mask word and of kColPopLoads), so that every flush
+//     of an unmasked sweep but a block's last carries a full period, and at least two periods.  A flush writes the wavefront's 32 KiB of
+//     counters and every flush but its first reads them back first, the sum reads them once: 64 KiB per 960 KiB of rows, 6.7 % of the
+//     sweep's traffic in the steady state and no more for a minimum block.
+//   - Narrow indexes (fewer than four segments) run one-, two- or three-wavefront workgroups instead of idling wavefronts of four.
+//   - No counter wraps: a wavefront's 32-bit counters see at most rows_per_block <= 2^31 rows (the rule raises the number of row
+//     blocks beyond that), the sum is 64 bits wide.
+constexpr int kColPopLoads = 8;
+constexpr int kColPopPlanes = 10;
+constexpr uint64_t kColPopWaves = 4096;
+constexpr uint64_t kColPopFlushRows = 960;
+static_assert(kColPopFlushRows % 64 == 0 && kColPopFlushRows % kColPopLoads == 0 && kColPopFlushRows < (1ull << kColPopPlanes), "a flush period is whole mask words and whole groups of loads, and fits the planes");
+struct ColPopPlan {
+    uint32_t block = 64;            // threads per workgroup: 64 per segment it covers, at most kBlock
+    uint64_t seg_groups = 0;        // workgroups per row block
+    uint64_t rows_per_block = 0;    // a multiple of kColPopFlushRows, hence of 64
+    uint64_t row_blocks = 0;
+    uint64_t grid = 0;              // seg_groups x row_blocks workgroups
+    uint32_t flush_groups = 0;      // groups of kColPopLoads rows between two flushes
+    uint64_t partial_stride = 0;    // 32-bit counters of one row block in the scratch array: stride_words x 64
+};
+static inline ColPopPlan plan_col_popcount(uint64_t num_rows, uint64_t stride_words)
+{
+    ColPopPlan p;
+    const uint64_t segs = std::max<uint64_t>(ceil_div(stride_words, 64 * kVec), 1);
+    p.block = (uint32_t)std::min<uint64_t>(segs, kBlock / 64) * 64;
+    p.seg_groups = ceil_div(segs, p.block / 64);
+    const uint64_t want_blocks = std::max<uint64_t>(kColPopWaves / segs, 1);
+    p.rows_per_block = round_up(std::max<uint64_t>(ceil_div(num_rows, want_blocks), 2 * kColPopFlushRows), kColPopFlushRows);
+    p.rows_per_block = std::min<uint64_t>(p.rows_per_block, (1ull << 31) / kColPopFlushRows * kColPopFlushRows);
+    p.row_blocks = std::max<uint64_t>(ceil_div(num_rows, p.rows_per_block), 1);
+    p.grid = p.seg_groups * p.row_blocks;
+    p.flush_groups = (uint32_t)(kColPopFlushRows / kColPopLoads);
+    p.partial_stride = stride_words * 64;
+    return p;
+}
+
 }  // namespace bigsi

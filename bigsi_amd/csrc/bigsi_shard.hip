@@ -904,6 +904,19 @@ extern "C" int bigsi_hip_group_get_column(bigsi_hip_group *g, uint64_t col, uint
     return bigsi_hip_get_column(g->ix[i], local, out);
 }
 
+extern "C" int bigsi_hip_group_column_popcounts(bigsi_hip_group *g, const uint8_t *row_mask, uint64_t *out, uint64_t capacity)
+{
+    if (!g || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (capacity < g->n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "capacity %llu is below num_cols %llu", (unsigned long long)capacity, (unsigned long long)g->n_cols);
+    // shard i holds the global colours [i * shard_cols, +cols_of(i)): its counts go straight to their place (an empty shard writes nothing)
+    for (uint32_t i = 0; i < g->n(); i++) {
+        const uint64_t n = g->cols_of(i, g->n_cols);
+        if (n) TRY(bigsi_hip_column_popcounts(g->ix[i], row_mask, out + (uint64_t)i * g->shard_cols, n));
+    }
+    return BIGSI_OK;
+}
+
 extern "C" int bigsi_hip_group_insert_kmers(bigsi_hip_group *g, uint64_t col, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k)
 {
     if (!g) return fail(BIGSI_ERR_INVALID, "NULL group");

@@ -659,6 +659,57 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
                 if pending is not None:
                     pending.result()                             # (the consumer stopped early: let the worker leave the index alone)
 
+    # ------------------------------------------------------------------ sample statistics
+    def _sample_names(self, n):
+        """names[c] for the colours below n: None for a deleted sample or a colour without a record."""
+        names = []
+        for c in range(n):
+            try:
+                name = self.colour_to_sample(c)
+            except KeyError:
+                name = None
+            names.append(None if name == DELETION_SPECIAL_SAMPLE_NAME else name)
+        return names
+
+    def sample_stats(self):
+        """How full every sample's Bloom filter is: [{sample_name, colour, bits_set, fill, kmer_fpr, est_kmers}] in ascending
+        colour, deleted samples dropped (bigsi_amd/stats.py: derive_sample_stats).  One sweep of the matrix on the device; nothing
+        is kept between calls."""
+        from ..stats import derive_sample_stats
+        with self._device_lock():
+            counts = self.storage.column_popcounts()
+        n = min(len(counts), self.num_samples)
+        return derive_sample_stats(counts, int(self.bloomfilter_size), int(self.num_hashes), self._sample_names(n))
+
+    def similar_samples(self, query, limit=None):
+        """The samples whose filters share most with `query` -- a sample name (that sample's own column, the sample itself left
+        out) or a Bloom filter of this index (m bits): [{sample_name, colour, bits_shared, jaccard, containment}] by Jaccard
+        index descending, ties in ascending colour, cut to `limit` (bigsi_amd/stats.py: derive_similar).  Two sweeps on the device,
+        the second reading only the rows where the query filter is set; the ranking of N numbers is the host's."""
+        from ..stats import derive_similar
+        limit = check_limit(limit)
+        m = int(self.bloomfilter_size)
+        with self._device_lock():
+            leave_out = None
+            if isinstance(query, str):
+                colour = self.sample_to_colour(query)
+                if colour is None:
+                    raise KeyError(query)                                        # no such sample, or a deleted one
+                leave_out = colour
+                mask = np.frombuffer(self.storage.get_column(colour), dtype=np.uint8)
+            else:
+                mask = getattr(query, "bitarray", query)
+                if not isinstance(mask, (bytes, bytearray, memoryview, np.ndarray)):
+                    data, nbits = row_bytes_of(mask)
+                    if nbits != m:
+                        raise ValueError("the Bloom filter has %d bits, the index has %d rows" % (nbits, m))
+                    mask = np.frombuffer(data, dtype=np.uint8)
+            masked = self.storage.column_popcounts(mask)
+            counts = self.storage.column_popcounts()
+        bits = np.unpackbits(np.frombuffer(bytes(mask), dtype=np.uint8) if not isinstance(mask, np.ndarray) else mask)[:m]
+        n = min(len(counts), self.num_samples)
+        return derive_similar(counts, int(bits.sum()), masked, self._sample_names(n), leave_out, limit)
+
     def _device_lock(self):
         import threading
         return self.storage.res.__dict__.setdefault("_lock", threading.RLock())

@@ -433,6 +433,39 @@ class HipHbmStorage(BaseStorage):
         check(res.fn("get_column")(res.ix, int(col), _lib.ptr(out)))
         return out.tobytes()
 
+    def column_popcounts(self, mask=None):
+        """np.uint64[num_cols]: per sample (column) the number of rows with its bit set -- the fill of its Bloom filter -- or, with
+        `mask`, the number of those among the rows the mask selects: |mask AND column| for every sample in one sweep of the matrix
+        (bigsi_hip_column_popcounts / its group twin).  `mask`: a Bloom filter of this index as a BitRow / bitarray (num_rows
+        bits), or its bytes / a uint8 array (ceil(num_rows / 8) bytes, the layout get_column returns)."""
+        res = self.res
+        if not res.ensure_open():
+            raise KeyError("number_of_rows:int")
+        nb = (res.m + 7) // 8
+        buf = None
+        if mask is not None:
+            if isinstance(mask, np.ndarray):
+                if mask.dtype != np.uint8:
+                    raise ValueError("a mask array must be uint8, got %s" % mask.dtype)
+                buf = np.ascontiguousarray(mask).reshape(-1)
+            elif isinstance(mask, (bytes, bytearray, memoryview)):
+                buf = np.frombuffer(bytes(mask), dtype=np.uint8)
+            else:
+                mask = getattr(mask, "bitarray", mask)
+                if not (hasattr(mask, "tobytes") and hasattr(mask, "__len__")):
+                    raise TypeError("expected a BitRow/bitarray/bytes/uint8 array, got %r" % type(mask))
+                if len(mask) != res.m:
+                    raise ValueError("the mask has %d bits, the index has %d rows" % (len(mask), res.m))
+                buf = np.frombuffer(mask.tobytes(), dtype=np.uint8)
+            if buf.size != nb:
+                raise ValueError("the mask has %d bytes, an index of %d rows takes %d" % (buf.size, res.m, nb))
+        n = int(res.info().num_cols)
+        out = np.zeros(n, dtype=np.uint64)
+        if n == 0:
+            return out
+        check(res.fn("column_popcounts")(res.ix, None if buf is None else _lib.ptr(buf), _lib.ptr(out), n))
+        return out
+
     def fill_synthetic(self, seed, shard=0, and_draws=2):
         if self.res.is_group:       # shard i of the group is filled as (seed, shard i)
             check(_lib.lib().bigsi_hip_group_fill_synthetic(self.res.ix, int(seed), int(and_draws)))

@@ -48,6 +48,7 @@ int bigsi_cpu_clear(bigsi_cpu_index *ix);
 int bigsi_cpu_insert_column(bigsi_cpu_index *ix, uint64_t col, const uint8_t *bloom);
 int bigsi_cpu_insert_columns(bigsi_cpu_index *ix, uint64_t col0, uint64_t n, const uint8_t *blooms, uint64_t bloom_stride_bytes);
 int bigsi_cpu_get_column(bigsi_cpu_index *ix, uint64_t col, uint8_t *out);
+int bigsi_cpu_column_popcounts(bigsi_cpu_index *ix, const uint8_t *row_mask, uint64_t *out, uint64_t capacity);
 int bigsi_cpu_insert_kmers(bigsi_cpu_index *ix, uint64_t col, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k);
 int bigsi_cpu_fill_synthetic(bigsi_cpu_index *ix, uint64_t seed, uint64_t shard, uint32_t and_draws);
 int bigsi_cpu_bloom(int device, const char *kmers, uint64_t u, uint32_t k, uint64_t m, uint32_t h, uint32_t flags, uint8_t *out);
@@ -93,6 +94,7 @@ int bigsi_cpu_presence(bigsi_cpu_index *ix, const char *seq, uint64_t len, uint3
 #define bigsi_hip_insert_column bigsi_cpu_insert_column
 #define bigsi_hip_insert_columns bigsi_cpu_insert_columns
 #define bigsi_hip_get_column bigsi_cpu_get_column
+#define bigsi_hip_column_popcounts bigsi_cpu_column_popcounts
 #define bigsi_hip_insert_kmers bigsi_cpu_insert_kmers
 #define bigsi_hip_fill_synthetic bigsi_cpu_fill_synthetic
 #define bigsi_hip_bloom bigsi_cpu_bloom

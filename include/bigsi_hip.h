@@ -165,6 +165,14 @@ int bigsi_hip_insert_columns(bigsi_hip_index *ix, uint64_t col0, uint64_t n, con
 int bigsi_hip_append_index(bigsi_hip_index *dst, const bigsi_hip_index *src);
 /* BitMatrix.get_column (bigsi/matrix/bitmatrix.py:50-61): out = ceil(num_rows/8) bytes. */
 int bigsi_hip_get_column(bigsi_hip_index *ix, uint64_t col, uint8_t *out);
+/* Sample statistics (no counterpart in the reference, whose score knows only DB_SIZE, bigsi/scoring/score.py:38-52): the vertical
+ * popcount of the matrix.  out[c] = number of rows r < num_rows with bit (r, c) set and (row_mask == NULL or bit r of row_mask set);
+ * row_mask: ceil(num_rows/8) bytes as bigsi_hip_get_column writes them (bits of its last byte at rows >= num_rows are ignored; the
+ * rows it leaves out are not read); out: capacity >= num_cols entries (BIGSI_ERR_CAPACITY otherwise), the pad columns of the stride
+ * are never counted.  Unmasked: each sample's Bloom-filter fill; masked with a sample's column or a query filter A: |A AND B_c| for
+ * every sample c in one sweep (Jaccard, containment).  Counts are exact for any num_rows (64-bit sums of per-row-block 32-bit
+ * counters).  Read-only: works on ipc / view handles. */
+int bigsi_hip_column_popcounts(bigsi_hip_index *ix, const uint8_t *row_mask, uint64_t *out, uint64_t capacity);
 
 /* Bloom-add every k-mer of every sequence to sample `col` directly on the transposed matrix: OR of
  * BloomFilter.update (bigsi/bloom/bloomfilter.py:25-32) with canonical k-mers (bigsi/graph/bigsi.py:151). */

@@ -44,6 +44,9 @@ int bigsi_hip_group_set_rows(bigsi_hip_group *g, const uint64_t *row_ids, uint64
 int bigsi_hip_group_get_rows(bigsi_hip_group *g, const uint64_t *row_ids, uint64_t n, uint8_t *out, uint64_t row_bytes);
 int bigsi_hip_group_insert_columns(bigsi_hip_group *g, uint64_t col0, uint64_t n, const uint8_t *blooms, uint64_t bloom_stride_bytes);
 int bigsi_hip_group_get_column(bigsi_hip_group *g, uint64_t col, uint8_t *out);
+/* bigsi_hip_column_popcounts over the whole index: every shard counts its own columns, out is in global colour order
+ * (capacity >= the group's num_cols); row_mask as there, the same for every shard */
+int bigsi_hip_group_column_popcounts(bigsi_hip_group *g, const uint8_t *row_mask, uint64_t *out, uint64_t capacity);
 int bigsi_hip_group_insert_kmers(bigsi_hip_group *g, uint64_t col, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k);
 int bigsi_hip_group_fill_synthetic(bigsi_hip_group *g, uint64_t seed, uint32_t and_draws); /* shard i = fill_synthetic(seed, i) */
 /* bigsi_hip_export_ipc / bigsi_hip_open_ipc for a group: n_shards handles of BIGSI_IPC_HANDLE_BYTES bytes each; the attaching process

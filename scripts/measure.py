@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -250,6 +250,37 @@ def transpose():
              GBps=moved / s.transpose_ms / 1e6, frac=moved / s.transpose_ms / 1e6 / PEAK, filter_pitch=pitch,
              note="k_transpose_regs (+ k_insert_columns for ragged edges); filters resident in HBM")
         del blooms
+        st.delete_all()
+
+
+def colpop():
+    """Sample statistics: the full unmasked sweep of column_popcounts over the C3 index and a C4 shard, and a masked sweep at mask
+    density 0.25 (bytes = the selected rows only), beside the box's bare sorted-row stream (bigsi_hip_probe_rows).  Wall-clock
+    time of the whole call (scratch allocation, both kernels, the copy of the counts); kernel times come from the same command
+    under `rocprofv3 --kernel-trace --stats`.  BIGSI_COLPOP_SHAPES="MxN,..." replaces the two shapes."""
+    L = _lib.lib()
+    shapes = ((10_000_000, 100_000, 4), (25_000_000, 62_500, 3))
+    if os.environ.get("BIGSI_COLPOP_SHAPES"):
+        shapes = tuple(tuple(int(x) for x in sh.split("x")) + (3,) for sh in os.environ["BIGSI_COLPOP_SHAPES"].split(","))
+    for m, n, h in shapes:
+        st, fill = open_index("colpop", m, n, h)
+        stride = int(st.res.info().row_stride_bytes)
+        g_, m_ = _lib.C.c_double(0), _lib.C.c_double(0)
+        check(L.bigsi_hip_probe_rows(st.handle, 3880, 1, 1, 0, 3, _lib.C.byref(g_), _lib.C.byref(m_)))
+        rng = np.random.default_rng(5)
+        sel = rng.random(m) < 0.25
+        mask = np.packbits(sel)
+        for name, mk, rows in (("unmasked", None, m), ("masked_0.25", mask, int(sel.sum()))):
+            counts = st.column_popcounts(mk)               # warm
+            reps, ts = 5, []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                counts = st.column_popcounts(mk)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            call = sorted(ts)[reps // 2]
+            emit("column_popcounts_" + name, m=m, cols=n, stride_bytes=stride, rows_read=rows, bytes=rows * stride, call_ms=call,
+                 call_GBps=rows * stride / call / 1e6, box_sorted_GBps=g_.value, counts_sum=int(counts.sum()), counts_max=int(counts.max()),
+                 note="fill %.2f s; median of %d calls, wall clock (allocation + k_col_popcount + k_col_popcount_sum + D2H)" % (fill, reps))
         st.delete_all()
 
 

@@ -107,7 +107,7 @@ SIGNATURES = {
     "bigsi_hip_batch_reload": (_i32, [_P, C.c_char_p, _P, _u32, _u32]),
     "bigsi_hip_batch_run": (_i32, [_P, _dbl, _u32]),
     "bigsi_hip_batch_get_info": (_i32, [_P, C.POINTER(BatchInfo)]),
-    "bigsi_hip_batch_set_outputs": (_i32, [_P, _P, _P]),
+    "bigsi_hip_batch_set_outputs": (_i32, [_P, _P]),
     "bigsi_hip_batch_set_limit": (_i32, [_P, _u32, _P, _u64]),
     "bigsi_hip_group_batch_set_limit": (_i32, [_P, _u32, _P, _u64]),
     "bigsi_hip_batch_fetch_unique": (_i32, [_P, _P, _P, _P]),

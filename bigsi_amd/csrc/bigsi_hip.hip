@@ -1626,12 +1626,11 @@ extern "C" int bigsi_hip_batch_set_limit(bigsi_hip_batch *b, uint32_t limit, con
     return BIGSI_OK;
 }
 
-extern "C" int bigsi_hip_batch_set_outputs(bigsi_hip_batch *b, void *d_bitmaps, void *d_counts)
+extern "C" int bigsi_hip_batch_set_outputs(bigsi_hip_batch *b, void *d_bitmaps)
 {
     BIGSI_ENTER(b ? b->ix : nullptr);
     if (!b) return fail(BIGSI_ERR_INVALID, "NULL batch");
     b->ext_bitmaps = d_bitmaps;
-    b->ext_counts = d_counts;
     return BIGSI_OK;
 }
 
@@ -1699,7 +1698,7 @@ static void launch_count(bigsi_hip_batch *b, int P, const CountLaunch &c, const 
     with_planes(P, [&](auto pl) { launch_count_wide<decltype(pl)::P, typename decltype(pl)::CountT>(b, c, l); });
 }
 
-static int compact(bigsi_hip_batch *b, HitBufs &hb, const void *src, uint32_t n_shards, uint64_t shard_cols, bool write_only);
+static int compact_local(bigsi_hip_batch *b, bool write_only);
 static int rank_select(bigsi_hip_batch *b, const void *src, const void *counters, void *dst, hipStream_t st);
 
 // Reads against a narrow index: K1 + K2 + K4 in one launch (k_reads_fused) when the batch qualifies.
@@ -1708,7 +1707,7 @@ static bool reads_fusable(const bigsi_hip_batch *b, uint32_t flags)
     const bigsi_hip_index *ix = b->ix;
     const bool exact = b->exact;
     return b->k == 31 && b->total_pos > 0 && b->max_pos <= 63 && b->n_seqs <= kReadsMaxSeqs && b->wv <= (uint64_t)kBlock * kVec &&
-           ix->h >= 2 && ix->h <= 4 && !b->ext_bitmaps && !b->ext_counts && b->result_cols == 0 && b->limit == 0 &&
+           ix->h >= 2 && ix->h <= 4 && !b->ext_bitmaps && b->result_cols == 0 && b->limit == 0 &&
            !(flags & (BIGSI_RUN_SKIP_COMPACT | BIGSI_RUN_K1_GLOBAL | BIGSI_RUN_EARLY_EXIT | BIGSI_RUN_NO_SORT)) &&
            (exact || (flags & BIGSI_RUN_SPARSE_COUNTS));     // the fused kernel keeps counters in registers: hits only
 }
@@ -2064,14 +2063,12 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     // the plans: K1's route and the row-AND launches (bigsi_launch.hpp)
     const K1Plan k1 = k1_plan(b, (flags & BIGSI_RUN_K1_GLOBAL) != 0);
     const RowAndPlan plan = plan_row_and(RowAndInput{b->n_seqs, b->wv, b->max_pos, ix->h, b->exact, (flags & BIGSI_RUN_NO_SORT) != 0,
-                                                     (flags & BIGSI_RUN_EARLY_EXIT) != 0, (flags & BIGSI_RUN_SPARSE_COUNTS) != 0,
-                                                     b->ext_counts != nullptr});
+                                                     (flags & BIGSI_RUN_EARLY_EXIT) != 0, (flags & BIGSI_RUN_SPARSE_COUNTS) != 0});
     // the sliced launches combine into preset result words (all ones for the AND, zero counters): K1 sets them on its way
     Preset preset;
     if (plan.preset) {
-        uint64_t *out = (uint64_t *)b->ext_bitmaps;
-        if (!out) { TRY(b->bitmaps.reserve((size_t)b->n_seqs * b->wv_pad * 8)); out = b->bitmaps.as<uint64_t>(); }
-        preset.p = out; preset.words = b->wv_pad; preset.value = ~0ull;
+        if (!b->ext_bitmaps) TRY(b->bitmaps.reserve((size_t)b->n_seqs * b->wv_pad * 8));
+        preset.p = (uint64_t *)b->bit_vectors(); preset.words = b->wv_pad; preset.value = ~0ull;
     }
     // K1 (its LDS route emits the sorted list itself; the other routes leave that to k_sort_rows below)
     EventPair ep{};
@@ -2099,8 +2096,8 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     // K2: the plan's launches
     if (plan.too_large) return fail(BIGSI_ERR_INVALID, "batch too large for one launch (%llu workgroups)", (unsigned long long)plan.too_large);
     if (b->exact) {
-        uint64_t *out = (uint64_t *)b->ext_bitmaps;
-        if (!out) { TRY(b->bitmaps.reserve((size_t)b->n_seqs * b->wv_pad * 8)); out = b->bitmaps.as<uint64_t>(); }
+        if (!b->ext_bitmaps) TRY(b->bitmaps.reserve((size_t)b->n_seqs * b->wv_pad * 8));
+        uint64_t *out = (uint64_t *)b->bit_vectors();
         if (plan.preset && !preset.done) HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)b->n_seqs * b->wv_pad * 8, ix->stream));
         TRY(ev_begin(ix, &ep, nullptr, true));
         for (uint32_t i = 0; i < plan.n_launches; i++) {
@@ -2121,12 +2118,12 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     } else {
         b->count_bytes = plan.count_bytes;
         const uint64_t cstride = b->wv_pad * 64;
-        void *out = b->ext_counts;
-        if (!out) { TRY(b->counts.reserve((size_t)b->n_seqs * cstride * b->count_bytes)); out = b->counts.p; }
+        TRY(b->counts.reserve((size_t)b->n_seqs * cstride * b->count_bytes));
+        void *out = b->counters();
         // the kernel also leaves the thresholded hit bitmap (count >= min_kmers), which is what K4 compacts on a single GPU
         TRY(b->bitmaps.reserve((size_t)b->n_seqs * b->wv_pad * 8));
-        uint64_t *hb = b->ext_bitmaps ? (uint64_t *)b->ext_bitmaps : b->bitmaps.as<uint64_t>();
-        b->sparse_counts = (flags & BIGSI_RUN_SPARSE_COUNTS) && !b->ext_counts;
+        uint64_t *hb = (uint64_t *)b->bit_vectors();
+        b->sparse_counts = (flags & BIGSI_RUN_SPARSE_COUNTS) != 0;
         const uint32_t sparse = b->sparse_counts ? 1u : 0u;
         // a sliced (small) batch: every slice leaves its partial counts bit-sliced in scratch memory and k_count_combine adds them up
         uint64_t *partial = nullptr;
@@ -2154,15 +2151,14 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         // a member of a device group: its slot of the gather buffer goes into the exchange already trimmed to this shard's top N
         if (b->limit && b->ext_bitmaps) {
             TRY(ev_begin(ix, &ep));
-            TRY(rank_select(b, b->ext_bitmaps, b->exact ? nullptr : (b->ext_counts ? b->ext_counts : b->counts.p), b->ext_bitmaps, ix->stream));
+            TRY(rank_select(b, b->ext_bitmaps, b->exact ? nullptr : b->counters(), b->ext_bitmaps, ix->stream));
             TRY(ev_end(ix, &ep, ix->ev_cp));
         }
         return finish_run(b, ix->stream, false, true);      // (the group waits for the event, whoever started the run)
     }
     // K4 on this shard's own result
     TRY(ev_begin(ix, &ep));
-    const void *src = b->exact ? (b->ext_bitmaps ? b->ext_bitmaps : b->bitmaps.p) : (b->ext_counts ? b->ext_counts : b->counts.p);
-    TRY(compact(b, b->hits, src, 1, ix->n_cols, false));
+    TRY(compact_local(b, false));
     TRY(ev_end(ix, &ep, ix->ev_cp));
     return finish_run(b, ix->stream, one_call, true);
 }
@@ -2203,15 +2199,15 @@ static int rank_select(bigsi_hip_batch *b, const void *src, const void *counters
     return BIGSI_OK;
 }
 
-// three compaction passes over [shard][seq][stride]; write_only re-runs just the write pass (after growing buffers).
-// `from_counts`: src is a counter buffer gathered from several shards -> threshold while compacting (k_hits_count);
-// otherwise src is a hit bitmap (the exact AND, or the counting kernel's fused count >= min_kmers mask) and the per-hit
-// count comes from `counters` (null on the exact path: every hit has count == num_unique).
-static int compact_ex(bigsi_hip_batch *b, HitBufs &hb, const void *src, bool from_counts, const void *counters,
-                      uint32_t n_shards, uint64_t shard_cols, bool write_only, hipStream_t st, uint32_t own_shard = kAllShards)
+// K4 over the bit vectors `src`, [n_shards][seq][wv_pad] words (the exact AND, or the counting kernel's fused count >= min_kmers
+// mask): group totals, then prefix + ordered write (k_hits_totals, k_hits_write: no waiting between workgroups).  A hit's count
+// comes from `counters` (null on the exact path: every hit has count == num_unique), which hold shard `own_shard` alone or, with
+// kAllShards, every shard.  `write_only` (the lists overflowed and were grown) runs the write pass again: the totals are still there.
+static int compact_bits(bigsi_hip_batch *b, HitBufs &hb, const void *src, const void *counters, uint32_t n_shards, uint64_t shard_cols,
+                        bool write_only, hipStream_t st, uint32_t own_shard)
 {
-    const uint32_t chunks = !from_counts ? (uint32_t)ceil_div(b->wv, kBlock) : (uint32_t)ceil_div(b->wv_pad * 64, kChunkCols);
-    const uint64_t per_seq = (uint64_t)n_shards * chunks, nchunks = per_seq * b->n_seqs;
+    const uint32_t chunks = (uint32_t)ceil_div(b->wv, kBlock);
+    const uint64_t nchunks = (uint64_t)n_shards * chunks * b->n_seqs;
     if (nchunks > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "too many compaction chunks");
     TRY(hb.hit_off.reserve((b->n_seqs + 1) * 8ull));
     if (hb.cap == 0 && !hb.xcol) {
@@ -2220,82 +2216,49 @@ static int compact_ex(bigsi_hip_batch *b, HitBufs &hb, const void *src, bool fro
         TRY(hb.hit_cnt.reserve(want * 4));
         hb.cap = want;
     }
-    if (!from_counts) {
-        // bit vectors (the AND bitmap / the fused count >= min_kmers mask): group totals, then prefix + ordered write
-        // (k_hits_totals, k_hits_write: no waiting between workgroups).  `write_only` (the lists overflowed and were grown)
-        // runs the write pass again: the totals are still there.
-        const uint64_t max_groups = kHitsMaxGroups;
-        // a handful of items (one or two gene-length queries: a latency-bound call) go to ONE workgroup, which needs nobody's totals
-        const uint32_t ipb = nchunks <= 16 ? (uint32_t)nchunks : (uint32_t)ceil_div(nchunks, max_groups);
-        const uint64_t ngroups = ceil_div(nchunks, ipb);
-        TRY(hb.chunk_hits.reserve(kHitsMaxGroups * 4));
-        if (!write_only && ngroups > 1)
-            hipLaunchKernelGGL(k_hits_totals, dim3((unsigned)ngroups), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv, b->n_seqs,
-                               n_shards, chunks, ipb, hb.chunk_hits.as<uint32_t>());
-        // a one-call search whose compaction is ONE workgroup (a gene-length query or two): that workgroup exports the results itself
-        const bool inline_export = b->one_call && &hb == &b->hits && !write_only && ngroups == 1 && n_shards == 1 && chunks <= 16 && st == b->ix->stream;
-        if (inline_export) {
-            TRY(export_prepare(b, st));
-            b->exported_inline = true;
-        }
-        hipLaunchKernelGGL(k_hits_write, dim3((unsigned)ngroups), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv, b->n_seqs,
-                           n_shards, chunks, shard_cols, b->num_unique.as<uint32_t>(), ipb, hb.chunk_hits.as<uint32_t>(),
-                           hb.hit_off.as<uint64_t>(), hb.col(), hb.cnt(), hb.capacity(), counters, b->count_bytes, b->wv_pad * 64, own_shard,
-                           inline_export ? static_cast<uint64_t *>(b->pin_out) : nullptr, b->exp_spec, b->uniq.as<uint32_t>(),
-                           (volatile uint64_t *)b->pin_flag, b->exp_serial);
-        HIP_TRY(hipGetLastError());
-        return BIGSI_OK;
+    const uint64_t max_groups = kHitsMaxGroups;
+    // a handful of items (one or two gene-length queries: a latency-bound call) go to ONE workgroup, which needs nobody's totals
+    const uint32_t ipb = nchunks <= 16 ? (uint32_t)nchunks : (uint32_t)ceil_div(nchunks, max_groups);
+    const uint64_t ngroups = ceil_div(nchunks, ipb);
+    TRY(hb.chunk_hits.reserve(kHitsMaxGroups * 4));
+    if (!write_only && ngroups > 1)
+        hipLaunchKernelGGL(k_hits_totals, dim3((unsigned)ngroups), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv, b->n_seqs,
+                           n_shards, chunks, ipb, hb.chunk_hits.as<uint32_t>());
+    // a one-call search whose compaction is ONE workgroup (a gene-length query or two): that workgroup exports the results itself
+    const bool inline_export = b->one_call && &hb == &b->hits && !write_only && ngroups == 1 && n_shards == 1 && chunks <= 16 && st == b->ix->stream;
+    if (inline_export) {
+        TRY(export_prepare(b, st));
+        b->exported_inline = true;
     }
-    // gathered dense counters / row-sliced local counters: threshold while compacting, three passes
-    TRY(hb.chunk_hits.reserve(nchunks * 4));
-    TRY(hb.chunk_off.reserve(nchunks * 8));
-    TRY(hb.overflow.reserve(4));
-    const unsigned grid = (unsigned)nchunks;
-    HIP_TRY(hipMemsetAsync(hb.overflow.p, 0, 4, st));
-#define BIGSI_HITS_COMMON                                                                                                        \
-    b->n_seqs, n_shards, chunks, shard_cols, b->min_kmers.as<uint32_t>(), hb.chunk_hits.as<uint32_t>(), hb.chunk_off.as<uint64_t>(), \
-        hb.col(), hb.cnt(), hb.capacity(), hb.overflow.as<uint32_t>()
-    for (int pass = write_only ? 1 : 0; pass < 2; pass++) {
-        if (b->count_bytes == 2) {
-            const uint16_t *c16 = (const uint16_t *)src;
-            if (pass == 0) hipLaunchKernelGGL((k_hits_count<uint16_t, false>), dim3(grid), dim3(kBlock), 0, st, c16, b->wv_pad * 64, (uint32_t)b->wv, BIGSI_HITS_COMMON);
-            else hipLaunchKernelGGL((k_hits_count<uint16_t, true>), dim3(grid), dim3(kBlock), 0, st, c16, b->wv_pad * 64, (uint32_t)b->wv, BIGSI_HITS_COMMON);
-        } else {
-            const uint32_t *c32 = (const uint32_t *)src;
-            if (pass == 0) hipLaunchKernelGGL((k_hits_count<uint32_t, false>), dim3(grid), dim3(kBlock), 0, st, c32, b->wv_pad * 64, (uint32_t)b->wv, BIGSI_HITS_COMMON);
-            else hipLaunchKernelGGL((k_hits_count<uint32_t, true>), dim3(grid), dim3(kBlock), 0, st, c32, b->wv_pad * 64, (uint32_t)b->wv, BIGSI_HITS_COMMON);
-        }
-        HIP_TRY(hipGetLastError());
-        if (pass == 0) {
-            hipLaunchKernelGGL(k_scan_chunks, dim3(1), dim3(kBlock), 0, st, hb.chunk_hits.as<uint32_t>(), nchunks, (uint32_t)per_seq,
-                               b->n_seqs, hb.chunk_off.as<uint64_t>(), hb.hit_off.as<uint64_t>());
-            HIP_TRY(hipGetLastError());
-        }
-    }
-#undef BIGSI_HITS_COMMON
+    hipLaunchKernelGGL(k_hits_write, dim3((unsigned)ngroups), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv, b->n_seqs,
+                       n_shards, chunks, shard_cols, b->num_unique.as<uint32_t>(), ipb, hb.chunk_hits.as<uint32_t>(),
+                       hb.hit_off.as<uint64_t>(), hb.col(), hb.cnt(), hb.capacity(), counters, b->count_bytes, b->wv_pad * 64, own_shard,
+                       inline_export ? static_cast<uint64_t *>(b->pin_out) : nullptr, b->exp_spec, b->uniq.as<uint32_t>(),
+                       (volatile uint64_t *)b->pin_flag, b->exp_serial);
+    HIP_TRY(hipGetLastError());
     return BIGSI_OK;
 }
 
-// this shard's own result (n_shards == 1): always a bitmap; gathered buffers: bitmaps (exact) or counters (counting)
-static int compact(bigsi_hip_batch *b, HitBufs &hb, const void *src, uint32_t n_shards, uint64_t shard_cols, bool write_only)
+// K4 on this shard's own result vectors, into b->hits
+static int compact_local(bigsi_hip_batch *b, bool write_only)
 {
-    if (&hb == &b->hits) {
-        const void *bm = b->ext_bitmaps ? b->ext_bitmaps : b->bitmaps.p;
-        const void *counters = b->exact ? nullptr : (b->ext_counts ? b->ext_counts : b->counts.p);
-        if (b->limit) {
-            // a result limit: K4 compacts the trimmed copy; the untrimmed vectors stay for fetch_bitmap / fetch_counts
-            if (!write_only) {
-                TRY(b->ranked.reserve((size_t)b->n_seqs * b->wv_pad * 8));
-                TRY(rank_select(b, bm, counters, b->ranked.p, b->ix->stream));
-            }
-            bm = b->ranked.p;
+    const void *bm = b->bit_vectors(), *counters = b->exact ? nullptr : b->counters();
+    if (b->limit) {
+        // a result limit: K4 compacts the trimmed copy; the untrimmed vectors stay for fetch_bitmap / fetch_counts
+        if (!write_only) {
+            TRY(b->ranked.reserve((size_t)b->n_seqs * b->wv_pad * 8));
+            TRY(rank_select(b, bm, counters, b->ranked.p, b->ix->stream));
         }
-        return compact_ex(b, hb, bm, false, counters, 1, shard_cols, write_only, b->ix->stream);
+        bm = b->ranked.p;
     }
-    hipStream_t gst = b->gstream ? b->gstream : b->ix->stream;
-    if (!b->exact && b->g_masks)
-        return compact_ex(b, hb, src, false, b->ext_counts ? b->ext_counts : b->counts.p, n_shards, shard_cols, write_only, gst, b->g_own);
-    return compact_ex(b, hb, src, !b->exact, nullptr, n_shards, shard_cols, write_only, gst);
+    return compact_bits(b, b->hits, bm, counters, 1, b->ix->n_cols, write_only, b->ix->stream, kAllShards);
+}
+
+// K4 on the bit vectors gathered from all shards (b->g_*), into b->ghits, on the gather stream
+static int compact_gathered(bigsi_hip_batch *b, bool write_only)
+{
+    return compact_bits(b, b->ghits, b->g_src, b->exact ? nullptr : b->counters(), b->g_shards, b->g_shard_cols, write_only,
+                        b->gstream ? b->gstream : b->ix->stream, b->g_own);
 }
 
 // A one-launch read run leaves every query's hits where its workgroup allocated them (k_reads_fused: no order between queries).
@@ -2346,14 +2309,14 @@ static int fetch_read_hits(bigsi_hip_batch *b, uint64_t *hit_offsets, uint32_t *
 }
 
 // synchronise, make sure the hit lists fit (grow + rewrite if the write pass overflowed), copy them out
-static int fetch_hits_from(bigsi_hip_batch *b, HitBufs &hb, const void *src, uint32_t n_shards, uint64_t shard_cols,
-                           uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t capacity)
+static int fetch_hits_from(bigsi_hip_batch *b, bool gathered, uint64_t *hit_offsets, uint32_t *colours, uint32_t *counts, uint64_t capacity)
 {
-    if (&hb == &b->hits && b->fused_run) return fetch_read_hits(b, hit_offsets, colours, counts, capacity);
-    hipStream_t st = (&hb == &b->ghits && b->gstream) ? b->gstream : b->ix->stream;
+    if (!gathered && b->fused_run) return fetch_read_hits(b, hit_offsets, colours, counts, capacity);
+    HitBufs &hb = gathered ? b->ghits : b->hits;
+    hipStream_t st = (gathered && b->gstream) ? b->gstream : b->ix->stream;
     std::vector<uint64_t> off(b->n_seqs + 2);
     // local hit lists were produced before b->done (already waited for); gathered ones on the gather stream
-    if (&hb == &b->ghits || !b->compacted) HIP_TRY(hipStreamSynchronize(st));
+    if (gathered || !b->compacted) HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(off.data(), hb.hit_off.p, (b->n_seqs + 1) * 8ull, hipMemcpyDeviceToHost));
     const uint64_t total = off[b->n_seqs];
     if (hb.xcol && total > hb.xcap) {
@@ -2364,8 +2327,8 @@ static int fetch_hits_from(bigsi_hip_batch *b, HitBufs &hb, const void *src, uin
         TRY(hb.hit_col.reserve(total * 4));
         TRY(hb.hit_cnt.reserve(total * 4));
         hb.cap = total;
-        TRY(compact(b, hb, src, n_shards, shard_cols, true));
-        if (&hb == &b->ghits && b->comm && !b->exact) TRY(bigsi_reduce_gathered_counts(b));   // every rank takes this branch: totals are identical
+        TRY(gathered ? compact_gathered(b, true) : compact_local(b, true));
+        if (gathered && b->comm && !b->exact) TRY(bigsi_reduce_gathered_counts(b));   // every rank takes this branch: totals are identical
         HIP_TRY(hipStreamSynchronize(st));
     }
     if (hit_offsets) memcpy(hit_offsets, off.data(), (b->n_seqs + 1) * 8ull);
@@ -2420,8 +2383,8 @@ extern "C" int bigsi_hip_batch_get_info(bigsi_hip_batch *b, bigsi_hip_batch_info
     out->total_hits = total;
     out->bitmap_stride_bytes = b->wv_pad * 8;
     out->counts_stride = b->wv_pad * 64;
-    out->d_bitmaps = b->ext_bitmaps ? b->ext_bitmaps : b->bitmaps.p;
-    out->d_counts = b->ext_counts ? b->ext_counts : b->counts.p;
+    out->d_bitmaps = b->bit_vectors();
+    out->d_counts = b->counters();
     out->d_num_unique = b->num_unique.p;
     out->one_launch = b->fused_run ? 1 : 0;
     return BIGSI_OK;
@@ -2442,28 +2405,36 @@ extern "C" int bigsi_hip_batch_fetch_hits(bigsi_hip_batch *b, uint64_t *hit_offs
 {
     BIGSI_ENTER(b ? b->ix : nullptr);
     TRY(need_run(b));
-    const void *src = b->exact ? (b->ext_bitmaps ? b->ext_bitmaps : b->bitmaps.p) : (b->ext_counts ? b->ext_counts : b->counts.p);
     if (!b->compacted) {   // the run skipped K4: do it now
-        TRY(compact(b, b->hits, src, 1, b->ix->n_cols, false));
+        TRY(compact_local(b, false));
         HIP_TRY(hipStreamSynchronize(b->ix->stream));
         b->compacted = true;
     }
-    return fetch_hits_from(b, b->hits, src, 1, b->ix->n_cols, hit_offsets, colours, counts, capacity);
+    return fetch_hits_from(b, false, hit_offsets, colours, counts, capacity);
 }
 
-// gathered compaction is queued behind the batch's run through its `done` event: no host-side wait, so the caller can go on
-// to launch the next batch while this one's row-AND kernel is still running
-static int gather_begin(bigsi_hip_batch *b, hipStream_t st)
+// Both gathered entries (`own_shard` null: bigsi_hip_batch_compact_gathered, which has no counters to fill in).  The compaction is
+// queued behind the batch's run through its `done` event: no host-side wait, so the caller can go on to launch the next batch
+// while this one's row-AND kernel is still running
+static int queue_gathered(bigsi_hip_batch *b, const void *d_gathered, uint32_t n_shards, uint64_t shard_cols, const uint32_t *own_shard)
 {
     if (!b) return fail(BIGSI_ERR_INVALID, "NULL batch");
     if (!b->ran) return fail(BIGSI_ERR_STATE, "bigsi_hip_batch_run has not completed for this batch");
+    if (!b->exact && !own_shard)
+        return fail(BIGSI_ERR_STATE, "the last run was thresholded: its shards exchange hit masks, which bigsi_hip_batch_compact_gathered_masks compacts");
+    if (!d_gathered || n_shards == 0 || (own_shard && *own_shard >= n_shards)) return fail(BIGSI_ERR_INVALID, "bad gathered buffer / shard");
+    if ((uint64_t)n_shards * shard_cols > 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "more than 2^32-1 colours in total");
     TRY(use_device(b->ix));
+    hipStream_t st = b->gstream ? b->gstream : b->ix->stream;
     if (b->done) HIP_TRY(hipStreamWaitEvent(st, b->done, 0));
-    return BIGSI_OK;
-}
-
-static int gather_end(bigsi_hip_batch *b, hipStream_t st)
-{
+    b->g_src = d_gathered;
+    b->g_shards = n_shards;
+    b->g_shard_cols = shard_cols;
+    b->g_own = b->exact ? kAllShards : *own_shard;
+    EventPair ep{};
+    TRY(ev_begin(b->ix, &ep, st));
+    TRY(compact_gathered(b, false));
+    TRY(ev_end(b->ix, &ep, b->ix->ev_cp, st));
     if (!b->g_done) HIP_TRY(hipEventCreateWithFlags(&b->g_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(b->g_done, st));
     return BIGSI_OK;
@@ -2472,45 +2443,14 @@ static int gather_end(bigsi_hip_batch *b, hipStream_t st)
 extern "C" int bigsi_hip_batch_compact_gathered(bigsi_hip_batch *b, const void *d_gathered, uint32_t n_shards, uint64_t shard_cols)
 {
     BIGSI_ENTER(b ? b->ix : nullptr);
-    if (!b) return fail(BIGSI_ERR_INVALID, "NULL batch");
-    hipStream_t gst = b->gstream ? b->gstream : b->ix->stream;
-    TRY(gather_begin(b, gst));
-    if (!d_gathered || n_shards == 0) return fail(BIGSI_ERR_INVALID, "bad gathered buffer");
-    if ((uint64_t)n_shards * shard_cols > 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "more than 2^32-1 colours in total");
-    b->g_src = d_gathered;
-    b->g_shards = n_shards;
-    b->g_shard_cols = shard_cols;
-    b->g_masks = false;
-    EventPair ep{};
-    TRY(ev_begin(b->ix, &ep, b->gstream));
-    TRY(compact(b, b->ghits, d_gathered, n_shards, shard_cols, false));
-    TRY(ev_end(b->ix, &ep, b->ix->ev_cp, b->gstream));
-    TRY(gather_end(b, gst));
-    return BIGSI_OK;
+    return queue_gathered(b, d_gathered, n_shards, shard_cols, nullptr);
 }
 
 extern "C" int bigsi_hip_batch_compact_gathered_masks(bigsi_hip_batch *b, const void *d_gathered_masks, uint32_t n_shards, uint64_t shard_cols,
                                                       uint32_t own_shard)
 {
     BIGSI_ENTER(b ? b->ix : nullptr);
-    if (!b) return fail(BIGSI_ERR_INVALID, "NULL batch");
-    TRY(gather_begin(b, b->gstream ? b->gstream : b->ix->stream));
-    if (!d_gathered_masks || n_shards == 0 || own_shard >= n_shards) return fail(BIGSI_ERR_INVALID, "bad gathered buffer / shard");
-    if ((uint64_t)n_shards * shard_cols > 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "more than 2^32-1 colours in total");
-    if (b->exact) return bigsi_hip_batch_compact_gathered(b, d_gathered_masks, n_shards, shard_cols);
-    b->g_src = d_gathered_masks;
-    b->g_shards = n_shards;
-    b->g_shard_cols = shard_cols;
-    b->g_own = own_shard;
-    b->g_masks = true;
-    hipStream_t st = b->gstream ? b->gstream : b->ix->stream;
-    EventPair ep{};
-    TRY(ev_begin(b->ix, &ep, st));
-    const void *counters = b->ext_counts ? b->ext_counts : b->counts.p;
-    TRY(compact_ex(b, b->ghits, d_gathered_masks, false, counters, n_shards, shard_cols, false, st, own_shard));
-    TRY(ev_end(b->ix, &ep, b->ix->ev_cp, st));
-    TRY(gather_end(b, st));
-    return BIGSI_OK;
+    return queue_gathered(b, d_gathered_masks, n_shards, shard_cols, &own_shard);
 }
 
 extern "C" int bigsi_hip_batch_set_gathered_hit_outputs(bigsi_hip_batch *b, void *d_colours, void *d_counts, uint64_t capacity)
@@ -2537,7 +2477,7 @@ extern "C" int bigsi_hip_batch_fetch_gathered_hits(bigsi_hip_batch *b, uint64_t 
     BIGSI_ENTER(b ? b->ix : nullptr);
     TRY(need_run(b));
     if (!b->g_src) return fail(BIGSI_ERR_STATE, "bigsi_hip_batch_compact_gathered has not been called");
-    return fetch_hits_from(b, b->ghits, b->g_src, b->g_shards, b->g_shard_cols, hit_offsets, colours, counts, capacity);
+    return fetch_hits_from(b, true, hit_offsets, colours, counts, capacity);
 }
 
 extern "C" int bigsi_hip_batch_fetch_counts(bigsi_hip_batch *b, uint32_t seq, uint32_t *out)
@@ -2549,7 +2489,7 @@ extern "C" int bigsi_hip_batch_fetch_counts(bigsi_hip_batch *b, uint32_t seq, ui
     if (b->sparse_counts) return fail(BIGSI_ERR_STATE, "the last run used BIGSI_RUN_SPARSE_COUNTS: only counters of hits were stored");
     if (seq >= b->n_seqs) return fail(BIGSI_ERR_RANGE, "sequence %u out of range", seq);
     const uint64_t n = b->ix->n_cols, cstride = b->wv_pad * 64;
-    const uint8_t *src = (const uint8_t *)(b->ext_counts ? b->ext_counts : b->counts.p) + (uint64_t)seq * cstride * b->count_bytes;
+    const uint8_t *src = (const uint8_t *)b->counters() + (uint64_t)seq * cstride * b->count_bytes;
     if (b->count_bytes == 4) {
         HIP_TRY(hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost));
     } else {
@@ -2567,7 +2507,7 @@ extern "C" int bigsi_hip_batch_fetch_bitmap(bigsi_hip_batch *b, uint32_t seq, ui
     if (!out) return fail(BIGSI_ERR_INVALID, "out is NULL");
     if (!b->exact) return fail(BIGSI_ERR_STATE, "the last run took the counting path");
     if (seq >= b->n_seqs) return fail(BIGSI_ERR_RANGE, "sequence %u out of range", seq);
-    const uint8_t *src = (const uint8_t *)(b->ext_bitmaps ? b->ext_bitmaps : b->bitmaps.p) + (uint64_t)seq * b->wv_pad * 8;
+    const uint8_t *src = (const uint8_t *)b->bit_vectors() + (uint64_t)seq * b->wv_pad * 8;
     HIP_TRY(hipMemcpy(out, src, b->ix->rb(), hipMemcpyDeviceToHost));
     return BIGSI_OK;
 }

@@ -157,7 +157,7 @@ struct bigsi_hip_comm;
 
 // ------------------------------------------------------------------------------ batches
 struct HitBufs {
-    DevBuf chunk_hits, chunk_off, hit_off, hit_col, hit_cnt, overflow;
+    DevBuf chunk_hits, hit_off, hit_col, hit_cnt;       // chunk_hits: the workgroups' hit totals (k_hits_totals -> k_hits_write)
     // k_reads_fused: per query where its hits start in col / cnt and how many they are (no order between queries), and the two
     // allocation counters its launches use alternately
     DevBuf q_start, q_cnt, alloc;
@@ -170,7 +170,7 @@ struct HitBufs {
     uint64_t capacity() const { return xcol ? xcap : cap; }
     void release()
     {
-        chunk_hits.release(); chunk_off.release(); hit_off.release(); hit_col.release(); hit_cnt.release(); overflow.release();
+        chunk_hits.release(); hit_off.release(); hit_col.release(); hit_cnt.release();
         q_start.release(); q_cnt.release(); alloc.release();
     }
 };
@@ -222,7 +222,10 @@ struct bigsi_hip_batch {
     uint32_t exp_spec = 0;                           // hits the export carried along speculatively
     PresJob job;                                     // the K5 / K6 request in flight, its host vectors and pinned staging
     DevBuf pres_in, pres_bits, pres_out, pres_desc;   // K5 at scale (presence_hits): host-built pair lists, presence bits, strings, piece marks
-    void *ext_bitmaps = nullptr, *ext_counts = nullptr;
+    void *ext_bitmaps = nullptr;      // caller-owned bit vectors (bigsi_hip_batch_set_outputs: a shard's slot of a gather buffer)
+    // the result vectors of a run: one bit per sample (the AND, or count >= min_kmers), and the counting path's counters
+    void *bit_vectors() const { return ext_bitmaps ? ext_bitmaps : bitmaps.p; }
+    void *counters() const { return counts.p; }
     // result limit (bigsi_hip_batch_set_limit): k_rank_select trims the hit vectors to the top `limit` between K2/K3 and K4
     uint32_t limit = 0;                  // 0: off
     std::vector<uint32_t> excluded;      // colours (of this batch's index) taken out before the selection
@@ -246,11 +249,12 @@ struct bigsi_hip_batch {
     hipEvent_t g_done = nullptr;   // recorded on the gather stream after a gathered compaction (it reads K1's per-query arrays)
     bool dirty = false;            // a run was started and its `done` event has not been recorded (error path): full syncs needed
     hipStream_t gstream = nullptr; // stream of the gathered compaction (null: the index's stream)
-    const void *g_src = nullptr;   // last gathered buffer handed to compact_gathered
+    // the last gathered compaction: [g_shards][n_seqs][wv_pad] bit vectors (exact: the ANDs; else hit masks, and the counts of shard
+    // g_own's hits come from this rank's counters)
+    const void *g_src = nullptr;
     uint32_t g_shards = 0;
     uint64_t g_shard_cols = 0;
     uint32_t g_own = 0;
-    bool g_masks = false;          // the gathered buffer holds hit masks of a counting run (counts come from this rank's counters)
     std::vector<uint32_t> h_num_unique, h_num_kmers, h_min_kmers;
     bool host_counts_valid = false;
     // column-shard exchange (bigsi_shard.hip)

@@ -7,7 +7,7 @@
 // only applied where set bits become colour ids (compaction, counter expansion).
 //
 // Kernels: K1 k_kmer_insert/resolve/rank/rows, K2/K3a k_and_exact, K2/K3b k_and_count,
-// K4 k_chunk_hits_* / k_scan_chunks / k_write_hits_*, K5 k_presence, plus lookup / storage / build helpers.
+// K4 k_rank_select / k_hits_totals / k_hits_write, K5 k_presence, plus lookup / storage / build helpers.
 // All bitwise, HBM-bound work: no MFMA.  Wavefront = 64 lanes everywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1461,17 +1461,10 @@ __global__ __launch_bounds__(kBlock) void k_rank_select(
 
 // ------------------------------------------------------------------------------ K4: threshold + compaction
 // Result buffers are laid out [shard][seq][stride] (n_shards = 1 for a single GPU; > 1 for buffers gathered from column
-// shards); hits come out as (colour, count) in (seq, shard, column) order.  Bit vectors -- every production path -- take
-// two launches (k_hits_totals, k_hits_write); dense counter buffers take three passes: (a) hits per 2048-column chunk, (b) exclusive scan
-// over chunks, (c) ordered write.  Colours ascend within a sequence
+// shards); hits come out as (colour, count) in (seq, shard, column) order.  The input is always bit vectors (the AND bitmap, or the
+// counting kernel's count >= min_kmers mask) and takes two launches (k_hits_totals, k_hits_write).  Colours ascend within a sequence
 // (exact_filter's np.where order, graph/bigsi.py:193-204; inexact_filter's dict order before its stable sort, :215-229).
 constexpr uint32_t kAllShards = 0xFFFFFFFFu;
-constexpr uint32_t kChunkCols = 2048;   // counting: kBlock threads x 8 columns per chunk; exact: kBlock words (16384 columns)
-
-__device__ __forceinline__ uint64_t chunk_index(uint32_t q, uint32_t shard, uint32_t chunk, uint32_t n_shards, uint32_t chunks)
-{
-    return ((uint64_t)q * n_shards + shard) * chunks + chunk;
-}
 
 // K4 for bit-vector inputs (the AND bitmap of an exact search, the hit mask of a thresholded one) in TWO launches and no
 // waiting between workgroups.  Workgroup g owns the `ipb` consecutive items [g * ipb, +ipb) of the (seq, shard, chunk) order;
@@ -1965,76 +1958,6 @@ __global__ __launch_bounds__(kBlock) void k_reads_fused(
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) *exp_flag = exp_serial;
-}
-
-template <typename CountT, bool WRITE>
-__global__ __launch_bounds__(kBlock) void k_hits_count(
-    const CountT *__restrict__ counts, uint64_t stride, uint32_t /*wv: unused, keeps both K4 signatures alike*/,
-    uint32_t n_seqs, uint32_t n_shards, uint32_t chunks,
-    uint64_t shard_cols, const uint32_t *__restrict__ min_kmers,
-    uint32_t *__restrict__ chunk_hits, const uint64_t *__restrict__ chunk_off,
-    uint32_t *__restrict__ hit_col, uint32_t *__restrict__ hit_cnt, uint64_t capacity, uint32_t *__restrict__ overflow)
-{
-    __shared__ uint32_t lds[16];
-    const uint32_t chunk = blockIdx.x % chunks, sq = blockIdx.x / chunks;
-    const uint32_t shard = sq % n_shards, q = sq / n_shards;
-    const uint64_t c0 = (uint64_t)chunk * kChunkCols + threadIdx.x * 8u;
-    const uint32_t thr = min_kmers[q];
-    uint32_t c[8];
-    uint32_t mine = 0;
-    const CountT *src = counts + ((uint64_t)shard * n_seqs + q) * stride + c0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        c[j] = (c0 + j < shard_cols) ? (uint32_t)src[j] : 0u;
-        if (c0 + j < shard_cols && c[j] >= thr) mine++;
-    }
-    uint32_t tot;
-    const uint32_t pre = block_exclusive_scan(mine, &tot, lds);
-    const uint64_t ci = chunk_index(q, shard, chunk, n_shards, chunks);
-    if (!WRITE) {
-        if (threadIdx.x == 0) chunk_hits[ci] = tot;
-        return;
-    }
-    if (mine == 0) return;
-    uint64_t o = chunk_off[ci] + pre;
-    if (o + mine > capacity) { *overflow = 1; return; }
-    const uint64_t cbase = (uint64_t)shard * shard_cols + c0;
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-        if (c0 + j < shard_cols && c[j] >= thr) { hit_col[o] = (uint32_t)(cbase + j); hit_cnt[o] = c[j]; o++; }
-}
-
-// exclusive scan of chunk_hits (n entries) by one workgroup, kScanItems consecutive entries per thread per round;
-// also hit_off[q] for every sequence and the total.
-constexpr int kScanItems = 16;
-__global__ __launch_bounds__(kBlock) void k_scan_chunks(
-    const uint32_t *__restrict__ chunk_hits, uint64_t n, uint32_t per_seq, uint32_t n_seqs,
-    uint64_t *__restrict__ chunk_off, uint64_t *__restrict__ hit_off)
-{
-    __shared__ uint32_t lds[16];
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < n; base += (uint64_t)kBlock * kScanItems) {
-        const uint64_t i0 = base + (uint64_t)threadIdx.x * kScanItems;
-        uint32_t v[kScanItems], sum = 0;
-#pragma unroll
-        for (int j = 0; j < kScanItems; j++) {
-            v[j] = i0 + j < n ? chunk_hits[i0 + j] : 0u;
-            sum += v[j];
-        }
-        uint32_t tot;
-        uint64_t run = carry + block_exclusive_scan(sum, &tot, lds);
-#pragma unroll
-        for (int j = 0; j < kScanItems; j++) {
-            const uint64_t i = i0 + j;
-            if (i < n) {
-                chunk_off[i] = run;
-                if (i % per_seq == 0) hit_off[i / per_seq] = run;
-            }
-            run += v[j];
-        }
-        carry += tot;
-    }
-    if (threadIdx.x == 0) hit_off[n_seqs] = carry;
 }
 
 // ------------------------------------------------------------------------------ lookup (API parity)

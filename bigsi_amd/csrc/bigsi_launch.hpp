@@ -100,7 +100,6 @@ struct RowAndInput {
     uint32_t h;                 // rows per k-mer
     bool exact;                 // k_and_exact (threshold 1.0), else the counting kernels
     bool no_sort, early_exit, sparse_counts;      // BIGSI_RUN_NO_SORT / _EARLY_EXIT / _SPARSE_COUNTS
-    bool ext_counts;            // caller-owned counters: written in place, so the batch is never sliced and never sparse
 };
 
 // one row-AND launch over the queries [q0, q1)
@@ -157,12 +156,10 @@ static inline RowAndPlan plan_row_and(const RowAndInput &in)
     RowAndPlan p;
     p.in = in;
     const uint64_t waves_per_q = ceil_div(in.wv, 64 * kVec), all_waves = in.n_seqs * waves_per_q;
-    // caller-owned result buffers (a shard's slot of a gather buffer): a bitmap can be preset and sliced like the batch's own
-    // (the counting path then cuts its hit mask from the slices' summed partial counts, k_count_combine); caller-owned counters are
-    // written in place, without presets
-    const bool sliceable = !in.ext_counts;
-    p.slices = sliceable ? row_slices(all_waves, in.max_pos, in.exact) : 1;
-    const bool few = all_waves < 1024 && sliceable;
+    // caller-owned result vectors (a shard's slot of a gather buffer) can be preset and sliced like the batch's own (the counting
+    // path then cuts its hit mask from the slices' summed partial counts, k_count_combine)
+    p.slices = row_slices(all_waves, in.max_pos, in.exact);
+    const bool few = all_waves < 1024;
     // K1e: address-ordered copy of the row lists for K2
     // exact path only: there every row can move freely (+4.7 % C3, +7.6 % C4-shard, interleaved A/B); on the counting path a
     // k-mer's h rows must stay together and ordering k-mers by their first row measured 1.00x
@@ -208,7 +205,7 @@ static inline RowAndPlan plan_row_and(const RowAndInput &in)
             p.combine = true;
             p.combine_grid = in.n_seqs * ceil_div(in.wv, kBlock / 8);      // 32 words per workgroup, 8 slice groups per word
         }
-        p.early = in.early_exit && in.sparse_counts && !in.ext_counts && p.slices == 1;
+        p.early = in.early_exit && in.sparse_counts && p.slices == 1;
         // fewer than ~3 wavefronts per SIMD in the whole grid (e.g. 128 gene-length queries): the software-pipelined loop,
         // whose wavefronts load the next k-mers' rows while adding the current ones (5.6 -> 6.3 TB/s at 128 x 2-4 kbp; with a
         // full grid other wavefronts already cover the ALU phase and it measured -2 ... +0 %)
@@ -233,7 +230,6 @@ inline RowAndLaunch RowAndPlan::launch(uint32_t i) const
         // wavefronts one-wavefront workgroups (mid_launch), with fewer the sliced launch of a small batch.  The rule of a whole
         // batch, except that
         //  - a sliced tail keeps the workgroups of 256 threads its batch runs in (a whole batch: 128);
-        //  - a tail is sliced even beside caller-owned counters, which an exact run does not write (a whole batch: never);
         //  - a tail has no upper bound of 4096 wavefronts (it has fewer than a launch's 1600-2000 anyway, unless its rows are
         //    wider than 4 M columns, when a launch is the minimum of 8 queries).
         const uint64_t waves = (uint64_t)n * ceil_div(in.wv, 64 * kVec);

@@ -192,7 +192,7 @@ class ShardedSearch(object):
                 with self.torch.cuda.stream(self.stream):
                     self._bufs[s] = self.sg.gather_buffer(need, self.device)
             slot = self._bufs[s][self.sg.rank].data_ptr()
-            check(L.bigsi_hip_batch_set_outputs(batch.b, slot, None))
+            check(L.bigsi_hip_batch_set_outputs(batch.b, slot))
             check(L.bigsi_hip_batch_set_gather_stream(batch.b, self.comm_stream.cuda_stream))
             if exact:
                 check(L.bigsi_hip_batch_set_gathered_hit_outputs(batch.b, None, None, 0))

@@ -32,9 +32,10 @@ extern "C" {
  * With a caller-owned stream set, every kernel of the index goes to that one stream (see STREAMS in bigsi_hip.h). */
 int bigsi_hip_set_stream(bigsi_hip_index *ix, void *hip_stream);
 
-/* Write the per-sample result of later runs into caller-owned device memory (e.g. this rank's slot of an
- * RCCL all-gather buffer) instead of the batch's own buffers.  Either may be NULL (= keep own buffer). */
-int bigsi_hip_batch_set_outputs(bigsi_hip_batch *b, void *d_bitmaps, void *d_counts);
+/* Write the per-sample bit vectors of later runs (the exact AND, or the hit mask of a thresholded run) into caller-owned device
+ * memory (e.g. this rank's slot of an all-gather buffer) instead of the batch's own buffer.  NULL = keep the own buffer.
+ * Counters always stay in the batch: they are never exchanged. */
+int bigsi_hip_batch_set_outputs(bigsi_hip_batch *b, void *d_bitmaps);
 /* Width, in columns, of the per-sample result vectors of later runs (default 0 = the index's num_cols).  The shards of one
  * index all set the group's shard width here, so that uneven shards still exchange buffers of ONE geometry (strides, word
  * counts); needs cols <= col_capacity.  Columns beyond the shard's own num_cols read as zero. */
@@ -49,6 +50,8 @@ int bigsi_hip_batch_set_result_cols(bigsi_hip_batch *b, uint64_t cols);
  * the stream the collective is issued under, so that all-gather + compaction of one batch overlap the row-AND kernels of
  * the next batch on the index's stream.  NULL = the index's stream. */
 int bigsi_hip_batch_set_gather_stream(bigsi_hip_batch *b, void *hip_stream);
+/* Exact runs: every hit's count is the query's number of unique k-mers.  After a thresholded run: BIGSI_ERR_STATE, nothing queued
+ * (its exchange is compact_gathered_masks, which accepts exact runs too). */
 int bigsi_hip_batch_compact_gathered(bigsi_hip_batch *b, const void *d_gathered, uint32_t n_shards, uint64_t shard_cols);
 /* Thresholded search over column shards without moving per-sample counters: the counting kernel also leaves each
  * shard's hit mask (1 bit per sample: count >= min_kmers) in the bitmap output (bigsi_hip_batch_set_outputs), which is what

@@ -10,10 +10,10 @@ extern "C" {
 // launches[]: up to `capacity` records of q0, q1, grid, block, tiles, slices, unroll, needs_preset
 // Returns the number of launches of the plan.
 uint64_t launch_host_plan(uint32_t n_seqs, uint64_t wv, uint64_t max_pos, uint32_t h, int exact, int no_sort, int early_exit,
-                          int sparse_counts, int ext_counts, uint64_t *head, uint64_t *launches, uint64_t capacity)
+                          int sparse_counts, uint64_t *head, uint64_t *launches, uint64_t capacity)
 {
     const bigsi::RowAndPlan p = bigsi::plan_row_and(
-        bigsi::RowAndInput{n_seqs, wv, max_pos, h, exact != 0, no_sort != 0, early_exit != 0, sparse_counts != 0, ext_counts != 0});
+        bigsi::RowAndInput{n_seqs, wv, max_pos, h, exact != 0, no_sort != 0, early_exit != 0, sparse_counts != 0});
     const uint64_t hd[11] = {p.too_large, p.slices, p.want_sorted, p.preset, (uint64_t)p.P, p.count_bytes, p.planes_out, p.combine,
                              p.deep, p.early, p.n_launches};
     for (int i = 0; i < 11; i++) head[i] = hd[i];

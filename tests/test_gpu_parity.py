@@ -704,7 +704,9 @@ def test_gathered_compaction_two_shards_on_one_gpu(hip):
     each writing its per-sample bit vector (exact AND bitmap / thresholded hit mask) into its slot of a [shard][seq][stride]
     buffer (bigsi_hip_batch_set_outputs); then, as every rank would, each shard's batch compacts the whole buffer
     (compact_gathered / compact_gathered_masks with its own shard id) and the per-hit counts are summed over "ranks".
-    Hits must equal the oracle's on the concatenated index.  Also the dense variant (gathered uint16 counters)."""
+    Hits must equal the oracle's on the concatenated index.  The exchange carries bit vectors only: compact_gathered refuses a
+    thresholded run (BIGSI_ERR_STATE, naming the masks entry) and leaves nothing behind -- compact_gathered_masks on the same batch
+    then gives the oracle's lists."""
     import torch
     from bigsi_amd import _lib
     from oracle.ref_model import SynthOracle
@@ -729,30 +731,33 @@ def test_gathered_compaction_two_shards_on_one_gpu(hip):
         _lib.check(L.bigsi_hip_batch_fetch_gathered_hits(b.b, _lib.ptr(off), _lib.ptr(col), _lib.ptr(cnt), col.size))
         return off, col[: int(off[-1])], cnt[: int(off[-1])]
 
-    for thr, dense in ((1.0, False), (0.3, False), (0.3, True)):
+    for thr in (1.0, 0.3):
         exact = thr == 1.0
-        stride = wv_pad * 64 * 2 if dense else wv_pad * 8
+        stride = wv_pad * 8
         buf = torch.zeros((world, len(seqs) * stride), dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         batches = []
         for g, st in enumerate(shards):
             b = st.new_batch(seqs, 31)
-            slot = buf[g].data_ptr()
-            _lib.check(L.bigsi_hip_batch_set_outputs(b.b, None if dense else slot, slot if dense else None))
-            b.run(thr, skip_compact=True, sparse_counts=not dense)
+            _lib.check(L.bigsi_hip_batch_set_outputs(b.b, buf[g].data_ptr()))
+            b.run(thr, skip_compact=True, sparse_counts=True)
             _lib.check(L.bigsi_hip_synchronize(st.handle))
             batches.append(b)
         per_rank = []
         for g, b in enumerate(batches):
-            if exact or dense:
+            if exact:
                 _lib.check(L.bigsi_hip_batch_compact_gathered(b.b, buf.data_ptr(), world, shard_cols))
             else:
+                if g == 0:      # the refused call: what follows on this batch is the same as on the other rank's
+                    assert L.bigsi_hip_batch_compact_gathered(b.b, buf.data_ptr(), world, shard_cols) == _lib.ERR_STATE
+                    assert b"bigsi_hip_batch_compact_gathered_masks" in L.bigsi_hip_last_error()
+                    assert L.bigsi_hip_batch_fetch_gathered_hits(b.b, None, None, None, 0) == _lib.ERR_STATE      # (no gathered buffer was taken)
                 _lib.check(L.bigsi_hip_batch_compact_gathered_masks(b.b, buf.data_ptr(), world, shard_cols, g))
             per_rank.append(fetch(b))
         off, col = per_rank[0][0], per_rank[0][1]
         for r in per_rank[1:]:
             assert np.array_equal(r[0], off) and np.array_equal(r[1], col)        # every rank derives the same lists
-        if exact or dense:
+        if exact:
             cnt = per_rank[0][2]
             assert all(np.array_equal(r[2], cnt) for r in per_rank)
         else:
@@ -765,8 +770,8 @@ def test_gathered_compaction_two_shards_on_one_gpu(hip):
             want_cnt = np.concatenate([o.counts(s)[1] for o in orcs])
             want = np.flatnonzero(want_cnt >= (nu[i] if exact else mk[i]))
             lo, hi = int(off[i]), int(off[i + 1])
-            assert np.array_equal(col[lo:hi], want), (thr, dense, i)
-            assert np.array_equal(cnt[lo:hi], want_cnt[want].astype(np.uint32)), (thr, dense, i)
+            assert np.array_equal(col[lo:hi], want), (thr, i)
+            assert np.array_equal(cnt[lo:hi], want_cnt[want].astype(np.uint32)), (thr, i)
         # a shard's own (local) hit list is still available after a skip_compact run
         loff, lcol, lcnt = batches[1].hits()
         c1 = orcs[1].counts(seqs[0])[1]

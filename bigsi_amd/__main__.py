@@ -104,6 +104,14 @@ def build_parser():
                  "only the N most similar samples (highest Jaccard index, ties to the lowest colour)")
     sp.add_argument("sample")
     sp.add_argument("--format", choices=["json", "csv"], default="json")
+    sp = common(sub.add_parser("vacuum", help="remove the columns of deleted samples from the matrix and renumber the samples that stay"))
+    sp.add_argument("--no-shrink", action="store_true", help="keep the row stride (and the HBM) the index had before")
+    sp = common(sub.add_parser("extract", help="a new index, described by TO_CONFIG, of the named samples of this one, in this one's colour order"))
+    sp.add_argument("to_config")
+    sp.add_argument("--samples", "-s", action="append", default=[], metavar="NAME")
+    sp.add_argument("--samples-file", default=None, metavar="FILE", help="one sample name per line")
+    for name in ("vacuum", "extract"):          # (named so that the refusal says why)
+        sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
 
@@ -121,6 +129,32 @@ def similar_text(index, sample, limit=None, fmt="json"):
     return to_csv(rows, SIMILAR_KEYS) if fmt == "csv" else json.dumps(rows)
 
 
+def vacuum_text(index, shrink=True):
+    """`vacuum`: BIGSI.vacuum, then the snapshot (the only thing the next process sees)."""
+    before = index.num_samples
+    removed = index.vacuum(shrink=shrink)
+    if removed:
+        index.storage.sync()
+    return json.dumps({"result": "removed %d of %d samples" % (removed, before), "removed": removed, "num_samples": index.num_samples})
+
+
+def extract_names(a):
+    """The sample names of an `extract` command line: -s NAME ... XOR --samples-file FILE (one name per line)."""
+    if a.samples_file and a.samples:
+        raise ValueError("You can only name samples via --samples-file or -s, but not both")
+    if a.samples_file:
+        with open(a.samples_file) as f:
+            return [line.strip() for line in f if line.strip()]
+    return list(a.samples)
+
+
+def extract_text(index, config_name, to_config_name, names):
+    """`extract`: BIGSI.extract into the index TO_CONFIG describes (it syncs its own snapshot)."""
+    new = index.extract(get_config_from_file(to_config_name), names)
+    return json.dumps({"result": "extracted %d of %d samples from %s into %s." % (new.num_samples, index.num_samples, config_name, to_config_name),
+                       "num_samples": new.num_samples})
+
+
 def main(argv=None):
     p, search_parser, bulk_parser = build_parser()
     a = p.parse_args(argv)
@@ -128,6 +162,8 @@ def main(argv=None):
         (search_parser if a.cmd == "search" else bulk_parser).error("--limit is not available with --sharded (use a single index or storage-config devices)")
     config = get_config_from_file(a.config)
 
+    if getattr(a, "sharded", False) and a.cmd in ("vacuum", "extract"):
+        p.error("%s is not available with --sharded: column shards have a fixed width (use a single index)" % a.cmd)
     if getattr(a, "sharded", False):
         return sharded_main(a, config)
     if a.cmd == "search":
@@ -177,6 +213,10 @@ def main(argv=None):
         print(stats_text(BIGSI(config), a.format))
     elif a.cmd == "similar":
         print(similar_text(BIGSI(config), a.sample, a.limit, a.format))
+    elif a.cmd == "vacuum":
+        print(vacuum_text(BIGSI(config), not a.no_shrink))
+    elif a.cmd == "extract":
+        print(extract_text(BIGSI(config), a.config, a.to_config, extract_names(a)))
     elif a.cmd == "hold":
         hold(config, a.handle, a.seconds, a.until_eof)
     return 0

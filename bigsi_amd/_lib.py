@@ -181,6 +181,13 @@ SIGNATURES = {
     "bigsi_hip_free_text": (None, [_P]),
 }
 
+# every symbol include/bigsi_hip_compact.h declares (column compaction: the maintenance layer)
+COMPACT_SIGNATURES = {
+    "bigsi_hip_compact_columns": (_i32, [_P, _P, C.POINTER(_u64)]),
+    "bigsi_hip_extract_columns": (_i32, [_P, _P, _P]),
+    "bigsi_hip_shrink_to_fit": (_i32, [_P]),
+}
+
 _lib = None
 
 
@@ -201,7 +208,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

@@ -16,6 +16,7 @@
 // BIGSI_CPU_WORD_PARALLEL replaces the last four by 64-bit word operations on the resident rows (same results).
 // Row format = the reference's bitarray.tobytes(): column c at byte c / 8 under mask 0x80 >> (c % 8).
 #include "bigsi_cpu.h"
+#include "bigsi_cpu_compact.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -595,6 +596,55 @@ int bigsi_cpu_column_popcounts(bigsi_cpu_index *ix, const uint8_t *row_mask, uin
             if (row[c >> 3] & (0x80u >> (c & 7))) out[c]++;
     }
     return BIGSI_OK;
+}
+
+// the kept columns of a row, in order, closed up: one bit at a time (dst and src may be the same row: column j is written after
+// column >= j was read)
+static uint64_t select_columns(uint8_t *dst, uint64_t dst_stride, const uint8_t *src, uint64_t n_cols, const uint8_t *keep)
+{
+    uint64_t j = 0;
+    for (uint64_t c = 0; c < n_cols; c++) {
+        if (!(keep[c >> 3] & (0x80u >> (c & 7)))) continue;
+        const bool on = src[c >> 3] & (0x80u >> (c & 7));
+        const uint8_t mask = (uint8_t)(0x80u >> (j & 7));
+        if (on) dst[j >> 3] |= mask;
+        else dst[j >> 3] &= (uint8_t)~mask;
+        j++;
+    }
+    for (uint64_t c = j; c < dst_stride * 8 && (c & 7); c++) dst[c >> 3] &= (uint8_t)~(0x80u >> (c & 7));
+    memset(dst + ceil_div(j, 8), 0, dst_stride - ceil_div(j, 8));
+    return j;
+}
+
+int bigsi_cpu_compact_columns(bigsi_cpu_index *ix, const uint8_t *keep, uint64_t *new_num_cols)
+{
+    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    if (!ix || !keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    uint64_t kept = 0;
+    for (uint64_t c = 0; c < ix->n_cols; c++) kept += (keep[c >> 3] & (0x80u >> (c & 7))) ? 1 : 0;
+    if (kept < ix->n_cols) {          // (every column kept: the rows stay as they are)
+        for (uint64_t r = 0; r < ix->m; r++) select_columns(ix->row(r), ix->stride, ix->row(r), ix->n_cols, keep);
+        ix->n_cols = kept;
+    }
+    if (new_num_cols) *new_num_cols = kept;
+    return BIGSI_OK;
+}
+
+int bigsi_cpu_extract_columns(bigsi_cpu_index *dst, const bigsi_cpu_index *src, const uint8_t *keep)
+{
+    if (dst && dst->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    if (!dst || !src || !keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot extract an index into itself (bigsi_cpu_compact_columns works in place)");
+    if (dst->m != src->m) return fail(BIGSI_ERR_INVALID, "row counts differ (%llu vs %llu)", (unsigned long long)dst->m, (unsigned long long)src->m);
+    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    uint64_t kept = 0;
+    for (uint64_t c = 0; c < src->n_cols; c++) kept += (keep[c >> 3] & (0x80u >> (c & 7))) ? 1 : 0;
+    TRY(bigsi_cpu_reserve_cols(dst, kept));
+    std::vector<uint8_t> tmp, page;
+    const uint64_t rb = src->rb();
+    for (uint64_t r = 0; r < src->m; r++) select_columns(dst->row(r), dst->stride, src->fetch(r, rb, tmp, page), src->n_cols, keep);
+    dst->n_cols = kept;
+    return bdb_read_failed(src);
 }
 
 int bigsi_cpu_insert_kmers(bigsi_cpu_index *ix, uint64_t col, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k)

@@ -1105,6 +1105,89 @@ extern "C" int bigsi_hip_column_popcounts(bigsi_hip_index *ix, const uint8_t *ro
     return BIGSI_OK;
 }
 
+// Column compaction (k_compact_columns; tables and launch shape: plan_compact_columns).  The tables live for this call only, like the
+// statistics' counters: 64 bytes per source word, 100 KB for 100 k columns.  `dst` may be `src` (in place: see the kernel).
+static int compact_launch(bigsi_hip_index *dst, const bigsi_hip_index *src, const CompactPlan &p)
+{
+    if (p.kept == 0) {
+        HIP_TRY(hipMemsetAsync(dst->d_index, 0, (size_t)dst->m * dst->stride_words * 8, dst->stream));
+        HIP_TRY(hipStreamSynchronize(dst->stream));
+        return BIGSI_OK;
+    }
+    CallScratch tab;
+    const uint64_t words_bytes = p.src_words * sizeof(CompactWord), first_bytes = (p.dst_words + 1) * 4;
+    TRY(tab.buf.reserve(words_bytes + first_bytes));
+    HIP_TRY(hipMemcpyAsync(tab.buf.p, p.words.data(), words_bytes, hipMemcpyHostToDevice, dst->stream));
+    HIP_TRY(hipMemcpyAsync(tab.buf.as<uint8_t>() + words_bytes, p.first_src.data(), first_bytes, hipMemcpyHostToDevice, dst->stream));
+    hipLaunchKernelGGL(k_compact_columns, dim3((unsigned)p.grid), dim3(p.block), 0, dst->stream, src->d_index, src->stride_words, dst->d_index,
+                       dst->stride_words, dst->m, tab.buf.as<CompactWord>(), reinterpret_cast<const uint32_t *>(tab.buf.as<uint8_t>() + words_bytes),
+                       p.dst_words);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dst->stream));          // (the tables go out of scope)
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_compact_columns(bigsi_hip_index *ix, const uint8_t *keep, uint64_t *new_num_cols)
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(bigsi_writable(ix));
+    if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_compact_columns: the column count of %d open view(s) would go stale", ix->views.load());
+    const uint64_t kept = count_kept_columns(ix->n_cols, keep);
+    if (kept < ix->n_cols) {          // (every column kept: the matrix stays as it is, byte for byte, and no table is built)
+        const CompactPlan p = plan_compact_columns(ix->n_cols, keep, ix->m);
+        TRY(use_device(ix));
+        TRY(quiesce_index(ix));
+        TRY(compact_launch(ix, ix, p));
+        ix->n_cols = p.kept;
+    }
+    if (new_num_cols) *new_num_cols = kept;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_extract_columns(bigsi_hip_index *dst, const bigsi_hip_index *src, const uint8_t *keep)
+{
+    BIGSI_ENTER(dst);
+    if (!dst || !src || !keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot extract an index into itself (bigsi_hip_compact_columns works in place)");
+    if (dst->m != src->m) return fail(BIGSI_ERR_INVALID, "row counts differ (%llu vs %llu)", (unsigned long long)dst->m, (unsigned long long)src->m);
+    if (dst->device != src->device) return fail(BIGSI_ERR_INVALID, "both indexes must live on the same device");
+    TRY(bigsi_writable(dst));
+    if (dst->d_index == src->d_index) return fail(BIGSI_ERR_INVALID, "src is a view of dst (bigsi_hip_compact_columns works in place)");
+    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_extract_columns: the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    const CompactPlan p = plan_compact_columns(src->n_cols, keep, dst->m);
+    TRY(bigsi_hip_reserve_cols(dst, p.kept));
+    TRY(use_device(dst));
+    TRY(quiesce_index(dst));
+    HIP_TRY(hipStreamSynchronize(src->stream));
+    TRY(compact_launch(dst, src, p));
+    dst->n_cols = p.kept;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_shrink_to_fit(bigsi_hip_index *ix)
+{
+    BIGSI_ENTER(ix);
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
+    const uint64_t ns = stride_for(std::max<uint64_t>(ix->n_cols, 1));
+    if (ns >= ix->stride_words) return BIGSI_OK;
+    TRY(bigsi_writable(ix));          // (as bigsi_hip_reserve_cols: only a call that would really re-stride the matrix needs to own it)
+    if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_shrink_to_fit: re-striding would move the matrix under %d open view(s)", ix->views.load());
+    TRY(use_device(ix));
+    TRY(quiesce_index(ix));
+    uint64_t *nd = nullptr;
+    HIP_TRY(hipMalloc((void **)&nd, (size_t)ix->m * ns * 8));
+    const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(ix->m * ns, kBlock), 256 * 8 * 4);
+    hipLaunchKernelGGL(k_restride, dim3(grid), dim3(kBlock), 0, ix->stream, ix->d_index, ix->stride_words, nd, ns, ix->m);      // (copies min(old, new) words per row)
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    HIP_TRY(hipFree(ix->d_index));
+    ix->d_index = nd;
+    ix->stride_words = ns;
+    ix->cap_cols = ns * 64;
+    return BIGSI_OK;
+}
+
 static int check_offsets(const uint64_t *offsets, uint32_t n_seqs)
 {
     for (uint32_t i = 0; i < n_seqs; i++) {

@@ -1,7 +1,9 @@
 // bigsi_launch.hpp -- the launch rule of a batch run, host-only: how K1 goes out (k1_plan) and how the row-AND kernels
-// (k_and_exact, k_and_count, k_count_combine) are launched for a batch of queries (plan_row_and).  Pure functions of a handful of
-// integers: no HIP, no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp compiles this header as
-// plain host C++ and tests/test_abi_and_host.py pins the decisions on the CPU.
+// (k_and_exact, k_and_count, k_count_combine) are launched for a batch of queries (plan_row_and), the sweep of the column popcounts
+// (plan_col_popcount) and the per-call tables of the column compaction (plan_compact_columns).  Pure functions of a handful of
+// integers (and, for the compaction, of the keep bitmap): no HIP, no batch, no index.  bigsi_hip.hip carries the plans out;
+// tests/c_host/launch_host.cpp and compact_host.cpp compile this header as plain host C++ and tests/test_abi_and_host.py,
+// test_sample_stats_host.py and test_compact_columns_host.py pin the decisions on the CPU.
 //
 // Every constant below was measured on an MI355X; the notes beside them say against what.  A GPU test compares results, and a slip
 // here keeps results right and costs the 3 to 20 % those notes record: change a constant only with a new measurement, and the pinned
@@ -11,6 +13,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <vector>
 
 static inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 static inline uint64_t ceil_div(uint64_t x, uint64_t a) { return (x + a - 1) / a; }
@@ -294,6 +297,108 @@ static inline ColPopPlan plan_col_popcount(uint64_t num_rows, uint64_t stride_wo
     p.grid = p.seg_groups * p.row_blocks;
     p.flush_groups = (uint32_t)(kColPopFlushRows / kColPopLoads);
     p.partial_stride = stride_words * 64;
+    return p;
+}
+
+// ------------------------------------------------------------------------------ column compaction (k_compact_columns)
+// "Keep these columns, in order, and close the gaps": with K = popcount(keep) the j-th kept column of every row becomes column j.
+// The keep mask is the same for all rows, so everything that depends on it alone is worked out HERE, once per call, and the kernel's
+// hot loop is table-driven.  In plain column order (by_column: bit c of word w = column 64 w + c)
+//   - a source word s is compressed to its kept bits -- a software pext, the parallel-suffix network of Hacker's Delight 7-4, whose
+//     six move masks depend on the mask only: words[s].mv.  The device does x &= mask, then six times t = x & mv[i];
+//     x = (x ^ t) | (t >> (1 << i));
+//   - those bits are the kept columns of rank [before, before + popcount(mask)): they land in destination word before / 64 at bit
+//     before % 64 and spill into the next one;
+//   - a destination word o is the OR of the source words first_src[o] .. first_src[o + 1] (both included: a word on the boundary
+//     feeds two), each shifted to its place.  first_src[o] = the first source word that holds a kept column of rank >= 64 o; the
+//     entry behind the last one is the last source word that keeps a column.  first_src[o] >= o: compaction only moves bits towards lower columns,
+//     which is what makes the kernel correct in place (see there).
+// Bits of `keep` at columns >= num_cols are ignored.  Table sizes: 64 bytes per source word and 4 per destination word -- 100 KB for
+// 100 k columns (it stays in the L2 of every XCD), 4 GiB at the ABI's 2^32 - 1 columns.
+// Launch shape: a wavefront owns kCompactRows whole rows at a time (the tables' entries are loaded once for all of them, and the rows'
+// loads are independent: that many 8-byte loads in flight per lane) and strides over the row groups; about kColPopWaves wavefronts
+// whatever the shape, fewer wavefronts per workgroup for a handful of rows.
+constexpr int kCompactRows = 8;
+struct CompactWord {            // per source word, 64 bytes
+    uint64_t mask;              // kept columns of the word, in plain column order
+    uint64_t mv[6];             // move masks of the compress network (unused when mask is all ones or zero)
+    uint32_t before;            // kept columns in front of this word
+    uint32_t count;             // popcount(mask)
+};
+static_assert(sizeof(CompactWord) == 64, "k_compact_columns loads a table entry as four 16-byte pieces");
+struct CompactPlan {
+    uint64_t src_words = 0;     // ceil(num_cols / 64)
+    uint64_t kept = 0;          // K
+    uint64_t dst_words = 0;     // ceil(K / 64)
+    std::vector<CompactWord> words;       // src_words entries
+    std::vector<uint32_t> first_src;      // dst_words + 1 entries
+    uint32_t block = 64;        // threads per workgroup: 64 per row group it covers at once, at most kBlock
+    uint64_t grid = 0;          // workgroups; the wavefronts stride over the row groups
+};
+// software pext with a plan's move masks: what the device does per word (the CPU test drives it against naive selection)
+static inline uint64_t compact_word(uint64_t x, const CompactWord &w)
+{
+    x &= w.mask;
+    for (int i = 0; i < 6; i++) {
+        const uint64_t t = x & w.mv[i];
+        x = (x ^ t) | (t >> (1u << i));
+    }
+    return x;
+}
+// K alone, for a caller that has nothing to do when every column is kept
+static inline uint64_t count_kept_columns(uint64_t num_cols, const uint8_t *keep)
+{
+    uint64_t k = 0;
+    for (uint64_t b = 0; b < num_cols / 8; b++) k += (uint64_t)__builtin_popcount(keep[b]);
+    if (num_cols & 7) k += (uint64_t)__builtin_popcount(keep[num_cols / 8] & (0xFF00u >> (num_cols & 7)) & 0xFFu);
+    return k;
+}
+// `keep`: ceil(num_cols / 8) bytes in the row format (column c at byte c / 8 under 0x80 >> (c % 8))
+static inline CompactPlan plan_compact_columns(uint64_t num_cols, const uint8_t *keep, uint64_t num_rows)
+{
+    CompactPlan p;
+    p.src_words = ceil_div(num_cols, 64);
+    p.words.resize(p.src_words);
+    uint64_t before = 0;
+    for (uint64_t s = 0; s < p.src_words; s++) {
+        CompactWord &w = p.words[s];
+        uint64_t m = 0;
+        for (uint64_t c = s * 64; c < std::min(num_cols, s * 64 + 64); c++)
+            if (keep[c >> 3] & (0x80u >> (c & 7))) m |= 1ull << (c & 63);
+        w.mask = m;
+        w.before = (uint32_t)before;
+        w.count = (uint32_t)__builtin_popcountll(m);
+        // Hacker's Delight 7-4: mk = the bits that have a dropped bit somewhere below them are counted by prefix XORs; mv[i] = the
+        // kept bits that move down by 2^i in step i
+        uint64_t mk = ~m << 1;
+        for (int i = 0; i < 6; i++) {
+            uint64_t mp = mk ^ (mk << 1);
+            mp ^= mp << 2;
+            mp ^= mp << 4;
+            mp ^= mp << 8;
+            mp ^= mp << 16;
+            mp ^= mp << 32;
+            const uint64_t mv = mp & m;
+            w.mv[i] = mv;
+            m = (m ^ mv) | (mv >> (1u << i));
+            mk &= ~mp;
+        }
+        before += w.count;
+    }
+    p.kept = before;
+    p.dst_words = ceil_div(p.kept, 64);
+    // (the entry behind the last destination word: the last source word that keeps anything -- trailing words with empty masks feed
+    // nobody and are not walked)
+    uint64_t last = 0;
+    for (uint64_t s = 0; s < p.src_words; s++)
+        if (p.words[s].count) last = s;
+    p.first_src.assign(p.dst_words + 1, (uint32_t)last);
+    uint64_t o = 0;
+    for (uint64_t s = 0; s < p.src_words && o < p.dst_words; s++)
+        while (o < p.dst_words && (uint64_t)p.words[s].before + p.words[s].count > o * 64) p.first_src[o++] = (uint32_t)s;
+    const uint64_t groups = std::max<uint64_t>(ceil_div(num_rows, kCompactRows), 1);
+    p.block = (uint32_t)std::min<uint64_t>(groups, kBlock / 64) * 64;
+    p.grid = std::min<uint64_t>(ceil_div(groups, p.block / 64), kColPopWaves / (kBlock / 64));
     return p;
 }
 

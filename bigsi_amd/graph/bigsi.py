@@ -710,6 +710,97 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         n = min(len(counts), self.num_samples)
         return derive_similar(counts, int(bits.sum()), masked, self._sample_names(n), leave_out, limit)
 
+    # ------------------------------------------------------------------ column compaction: vacuum / extract
+    def _colour_names(self):
+        """names[c] of every colour, DELETION_SPECIAL_SAMPLE_NAME for a deleted one; the matrix must be as wide as the metadata."""
+        n = self.num_samples
+        cols = int(self.storage.get_integer("number_of_cols"))
+        if cols != n:
+            raise ValueError("the matrix has %d columns and the metadata %d colours" % (cols, n))
+        return [self.colour_to_sample(c) for c in range(n)]
+
+    def vacuum(self, shrink=True):
+        """Remove the columns of deleted samples from the matrix (bigsi_hip_compact_columns, in place on the device) and renumber
+        the samples that stay 0 .. K-1 in their old order: afterwards the index is the one BIGSI.build makes from the kept samples'
+        filters in colour order -- rows, metadata records, search results and scores (which depend on the number of samples).
+        The names of the removed samples can be inserted again.  shrink: also give the freed row stride back
+        (bigsi_hip_shrink_to_fit).  Returns the number of columns removed; 0, without touching the device, when nothing is deleted.
+        The matrix is compacted first and the metadata rewritten after it, in this process's memory; nothing is on disk before the
+        caller's sync().  A process that dies in between loses nothing -- its snapshot is the index before the vacuum -- but an
+        exception between the two steps (none is expected: the second is dictionary writes) would leave THIS object's metadata
+        naming the old colours: drop the resident index and open the snapshot again."""
+        from ..compact import vacuum_plan
+        from .metadata import _COUNT, _k
+        if not isinstance(shrink, bool):
+            raise TypeError("shrink must be a bool, got %r" % (shrink,))
+        with self._device_lock():
+            names = self._colour_names()
+            keep, kept = vacuum_plan(names)
+            removed = len(names) - len(kept)
+            if removed == 0:
+                return 0
+            st = self.storage
+            if st.compact_columns(keep) != len(kept):
+                raise RuntimeError("the device kept another number of columns than the metadata names")
+            for j, name in enumerate(kept):
+                st.set_integer(_k(name), j)
+                st.set_string(_k(j), name)
+            st.delete_records([st.convert_to_string_key(_k(c)) for c in range(len(kept), len(names))])
+            # the tombstones of delete_sample: "<name>:int" = -1
+            st.delete_records([key for key in st.record_keys(_k("")) if key.endswith(":int") and key != st.convert_to_integer_key(_k(_COUNT))
+                               and st[key] == b"-1"])
+            st.set_integer(_k(_COUNT), len(kept))
+            self.bitmatrix.set_num_cols(len(kept))
+            for batch in self.__dict__.pop("_workspaces", {}).values():
+                batch.close()
+            self._metadata_changed()
+            self.scorer = Scorer(self.num_samples)
+            if shrink:
+                st.shrink_to_fit()
+            return removed
+
+    def extract(self, config, samples):
+        """A new index under `config` (same m, h, k, same device; nothing stored under it yet) that holds the named samples of
+        this one, in THIS index's colour order (bigsi_hip_extract_columns: device to device, this index is only read) -- the index
+        BIGSI.build makes from those samples' filters.  A subset that is searched again and again is extracted once and then costs
+        |subset| / N of the bytes per query.  KeyError for a name that is unknown or deleted, ValueError for an empty list or a
+        name given twice.  Returns the new BIGSI."""
+        from ..compact import extract_plan
+        from .index import BLOOMFILTER_SIZE_KEY, NUM_HASH_FUNCTS_KEY
+        if isinstance(samples, (str, bytes)):
+            raise TypeError("samples must be a list of sample names, got %r" % type(samples))
+        samples = list(samples)
+        if not samples or len(set(samples)) != len(samples):
+            extract_plan([], samples)                   # (raises the ValueError, before anything is read)
+        if self.storage.res.is_group:
+            from .._lib import ERR_STATE, BigsiHipError
+            raise BigsiHipError(ERR_STATE, "column extraction is not available for multi-GPU (devices=[...]) indexes")
+        with self._device_lock():
+            keep, picked = extract_plan(self._colour_names(), samples)
+            for key, mine in (("m", self.bloomfilter_size), ("h", self.num_hashes), ("k", self.kmer_size)):
+                if int(config[key]) != int(mine):
+                    raise ValueError("the new index must have this one's %s (%d), its config says %d" % (key, mine, config[key]))
+            storage = get_storage(config)
+            if storage.res is self.storage.res:
+                raise ValueError("the new index needs a storage-config name of its own")
+            if SampleMetadata(storage).num_samples or int(storage.get("number_of_cols:int", b"0")):
+                raise ValueError("the index described by the new config is not empty")
+            try:
+                storage.set_integer(BLOOMFILTER_SIZE_KEY, int(self.bloomfilter_size))
+                storage.set_integer(NUM_HASH_FUNCTS_KEY, int(self.num_hashes))
+                storage.set_integer("number_of_rows", int(self.bloomfilter_size))
+                storage.set_integer("number_of_cols", 0)
+                storage.res.ensure_open()
+                if storage.extract_columns_from(self.storage, keep) != len(picked):
+                    raise RuntimeError("the device extracted another number of columns than the metadata names")
+                SampleMetadata(storage).add_samples(picked)
+                storage.sync()
+            except BaseException:
+                storage.delete_all()          # (it was empty when we came: nothing half-made stays resident under the new name)
+                raise
+            storage.close()
+        return type(self)(config)
+
     def _device_lock(self):
         import threading
         return self.storage.res.__dict__.setdefault("_lock", threading.RLock())

@@ -2,7 +2,8 @@
 
 Records (all under the "metadata:" prefix): "<name>:int" -> colour, "<colour>:string" -> name,
 "colour_count:int" -> number of colours.  Deleting a sample renames its colour to a reserved string; the colour
-itself (a matrix column) stays, so the device kernels keep counting it and results drop it by name."""
+itself (a matrix column) stays, so the device kernels keep counting it and results drop it by name -- until
+BIGSI.vacuum removes the columns of deleted samples from the matrix and renumbers the colours that stay."""
 
 DELETION_SPECIAL_SAMPLE_NAME = "D3L3T3D"
 _PREFIX = "metadata"

@@ -398,9 +398,7 @@ class HipHbmStorage(BaseStorage):
             check(_lib.lib().bigsi_hip_group_insert_columns(res.ix, int(col), 1, _lib.ptr(buf), buf.size))
         else:
             check(_lib.lib().bigsi_hip_insert_column(res.ix, int(col), _lib.ptr(buf)))
-        res.written[:] = True
-        res.lengths_reset()
-        res.kv[b"number_of_cols:int"] = str(int(res.info().num_cols)).encode()
+        self._after_column_move()
 
     def insert_columns(self, col0, blooms):
         """n Bloom filters (uint8[n, >= ceil(m/8)]) -> columns [col0, col0+n): the transpose runs on the device."""
@@ -414,18 +412,61 @@ class HipHbmStorage(BaseStorage):
         if col0 + n > res.info().col_capacity:
             res.reserve_cols(col0 + n)
         check(res.fn("insert_columns")(res.ix, int(col0), n, _lib.ptr(blooms), blooms.shape[1]))
-        res.written[:] = True
-        res.lengths_reset()
-        res.kv[b"number_of_cols:int"] = str(int(res.info().num_cols)).encode()
+        self._after_column_move()
 
     def append_from(self, other):
         """Append every column of another resident hip-hbm index (same device, same m), device to device."""
         if self.res.is_group or other.res.is_group:
             raise BigsiHipError(_lib.ERR_STATE, "merge is not available for multi-GPU (devices=[...]) indexes")
         check(_lib.lib().bigsi_hip_append_index(self.handle, other.handle))
+        self._after_column_move()
+
+    def record_keys(self, prefix=""):
+        """The keys of the host-side records (everything that is not a row) that start with `prefix`, sorted."""
+        pre = self.convert_key_to_bytes(prefix)
+        return sorted(k.decode("utf-8") for k in self.res.kv if k.startswith(pre))
+
+    def delete_records(self, keys):
+        """Remove host-side records (the KV contract has no delete; a vacuum takes the records of the colours it removed away)."""
+        for k in keys:
+            self.res.kv.pop(self.convert_key_to_bytes(k), None)
+
+    def _after_column_move(self):
+        """Every row was rewritten on the device at the index's new width: what insert / merge / compaction leave behind."""
         self.res.written[:] = True
         self.res.lengths_reset()
         self.res.kv[b"number_of_cols:int"] = str(int(self.res.info().num_cols)).encode()
+
+    def compact_columns(self, keep):
+        """Keep the columns `keep` names, in order, and close the gaps, in place on the device (bigsi_hip_compact_columns); returns
+        the new number of columns.  `keep`: a bool array of num_cols entries, or the packed bitmap as a uint8 array / bytes
+        (ceil(num_cols / 8) bytes, column c at byte c // 8 under 0x80 >> (c % 8))."""
+        from ..compact import keep_bytes
+        if self.res.is_group:
+            raise BigsiHipError(_lib.ERR_STATE, "column compaction is not available for multi-GPU (devices=[...]) indexes")
+        buf = keep_bytes(keep, int(self.res.info().num_cols) if self.res.ensure_open() else 0)
+        kept = _lib.C.c_uint64(0)
+        check(_lib.lib().bigsi_hip_compact_columns(self.handle, _lib.ptr(buf), _lib.C.byref(kept)))
+        self._after_column_move()
+        return int(kept.value)
+
+    def extract_columns_from(self, other, keep):
+        """The columns of another resident hip-hbm index (same device, same m) that `keep` names become the columns of this one, which
+        must hold none yet (bigsi_hip_extract_columns); `other` is only read.  Returns the number of columns."""
+        from ..compact import keep_bytes
+        if self.res.is_group or other.res.is_group:
+            raise BigsiHipError(_lib.ERR_STATE, "column extraction is not available for multi-GPU (devices=[...]) indexes")
+        buf = keep_bytes(keep, int(other.res.info().num_cols) if other.res.ensure_open() else 0)
+        check(_lib.lib().bigsi_hip_extract_columns(self.handle, other.handle, _lib.ptr(buf)))
+        self._after_column_move()
+        return int(self.res.info().num_cols)
+
+    def shrink_to_fit(self):
+        """Give back the row stride beyond the columns the index holds (bigsi_hip_shrink_to_fit): the counterpart of reserve_cols."""
+        if self.res.is_group:
+            raise BigsiHipError(_lib.ERR_STATE, "a multi-GPU index keeps the shard width it was opened with")
+        check(_lib.lib().bigsi_hip_shrink_to_fit(self.handle))
+        self._after_column_move()
 
     def get_column(self, col):
         res = self.res

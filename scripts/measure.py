@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -281,6 +281,92 @@ def colpop():
             emit("column_popcounts_" + name, m=m, cols=n, stride_bytes=stride, rows_read=rows, bytes=rows * stride, call_ms=call,
                  call_GBps=rows * stride / call / 1e6, box_sorted_GBps=g_.value, counts_sum=int(counts.sum()), counts_max=int(counts.max()),
                  note="fill %.2f s; median of %d calls, wall clock (allocation + k_col_popcount + k_col_popcount_sum + D2H)" % (fill, reps))
+        st.delete_all()
+
+
+def compact():
+    """Column compaction (k_compact_columns) on the C3 index and a C4 shard at keep densities 0.99 (a vacuum), 0.5 and 0.1 (an
+    extraction), in place and out of place, beside two yardsticks from the same box: the bare sorted-row stream
+    (bigsi_hip_probe_rows) and a bigsi_hip_reserve_cols re-stride of the same matrix -- a pure copy of the same rows, what compaction
+    would cost if the bit work were free.  bytes = the source words read + the destination stride written (the kernel zeroes the
+    row up to its stride).  Wall-clock time of the whole C call: compaction includes its table upload, an extraction goes into a
+    destination reserved beforehand, the re-stride includes the allocation of the copy and the release of the old matrix (the
+    `copy_all_kept` line is the same copy through k_compact_columns without either: an extraction that keeps every column).
+    What does not fit beside the index in device memory is skipped and says so."""
+    import torch
+    L, C = _lib.lib(), _lib.C
+    shapes = ((10_000_000, 100_000), (25_000_000, 62_500))
+
+    def stride_for(cols):
+        return max(16, -(-(-(-cols // 64)) // 16) * 16) * 8
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        check(fn())
+        return (time.perf_counter() - t0) * 1e3
+
+    for m, n in shapes:
+        st, fill = open_index("compact", m, n, 3)
+        stride = int(st.res.info().row_stride_bytes)
+        src_bytes = m * (-(-n // 64)) * 8
+        g_, m_ = C.c_double(0), C.c_double(0)
+        check(L.bigsi_hip_probe_rows(st.handle, 3880, 1, 1, 0, 3, C.byref(g_), C.byref(m_)))
+        rng = np.random.default_rng(9)
+        common = dict(m=m, cols=n, stride_bytes=stride, box_sorted_GBps=g_.value)
+        results = {}
+        for density in (0.99, 0.5, 0.1):
+            flags = rng.random(n) < density
+            keep, k = np.ascontiguousarray(np.packbits(flags)), int(flags.sum())
+            # out of place, into a destination that already has its capacity
+            need = m * stride_for(k)
+            free = torch.cuda.mem_get_info()[0]
+            if need + (2 << 30) > free:
+                emit("compact_extract", density=density, kept=k, skipped="the destination (%d bytes) does not fit beside the index (%d free)" % (need, free), **common)
+            else:
+                dst = C.c_void_p()
+                check(L.bigsi_hip_open(m, 0, k, 3, 0, C.byref(dst)))
+                ms = timed(lambda: L.bigsi_hip_extract_columns(dst, st.handle, _lib.ptr(keep)))
+                moved = src_bytes + need
+                emit("compact_extract", density=density, kept=k, call_ms=ms, bytes=moved, GBps=moved / ms / 1e6, **common)
+                results[("extract", density)] = ms
+                check(L.bigsi_hip_close(dst))
+            # in place; then the index gets its width and its contents back
+            ms = timed(lambda: L.bigsi_hip_compact_columns(st.handle, _lib.ptr(keep), None))
+            moved = src_bytes + m * stride
+            emit("compact_in_place", density=density, kept=k, call_ms=ms, bytes=moved, GBps=moved / ms / 1e6, **common)
+            results[("in_place", density)] = ms
+            check(L.bigsi_hip_set_num_cols(st.handle, n))
+            st.fill_synthetic(SEED, 0, 2)
+        # the copy of every column through k_compact_columns (all masks all ones), then the re-stride: the yardstick
+        free = torch.cuda.mem_get_info()[0]
+        if m * stride + (2 << 30) > free:
+            emit("compact_restride_yardstick", skipped="a second copy of the matrix (%d bytes) does not fit beside it (%d free)" % (m * stride, free), **common)
+        else:
+            dst = C.c_void_p()
+            check(L.bigsi_hip_open(m, 0, n, 3, 0, C.byref(dst)))
+            every = np.full((n + 7) // 8, 0xFF, np.uint8)
+            ms = timed(lambda: L.bigsi_hip_extract_columns(dst, st.handle, _lib.ptr(every)))
+            emit("compact_copy_all_kept", call_ms=ms, bytes=src_bytes + m * stride, GBps=(src_bytes + m * stride) / ms / 1e6, **common)
+            check(L.bigsi_hip_close(dst))
+            ms = timed(lambda: L.bigsi_hip_reserve_cols(st.handle, stride * 8 + 1))
+            new_stride = int(st.res.info().row_stride_bytes)
+            # the call allocates the copy and frees the old matrix around k_restride: the same allocation and release, timed alone,
+            # are taken off, and the ratios are against what is left -- the copy
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            block = torch.cuda.caching_allocator_alloc(m * new_stride)
+            torch.cuda.caching_allocator_delete(block)
+            torch.cuda.empty_cache()
+            torch.cuda.synchronize()
+            alloc_ms = (time.perf_counter() - t0) * 1e3
+            copy_ms = ms - alloc_ms
+            moved = m * (stride + new_stride)
+            emit("compact_restride_yardstick", call_ms=ms, alloc_free_ms=alloc_ms, copy_ms=copy_ms, bytes=moved, GBps=moved / copy_ms / 1e6,
+                 new_stride_bytes=new_stride, in_place_099_over_copy=results[("in_place", 0.99)] / copy_ms,
+                 extract_099_over_copy=(results[("extract", 0.99)] / copy_ms) if ("extract", 0.99) in results else None,
+                 note="bigsi_hip_reserve_cols by one more 128-byte line per row = hipMalloc + k_restride + hipFree; copy_ms = the call less an "
+                      "allocation and release of the same size timed alone (k_restride's own time: the same command under rocprofv3 --kernel-trace --stats)",
+                 **common)
         st.delete_all()
 
 

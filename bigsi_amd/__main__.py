@@ -110,7 +110,15 @@ def build_parser():
     sp.add_argument("to_config")
     sp.add_argument("--samples", "-s", action="append", default=[], metavar="NAME")
     sp.add_argument("--samples-file", default=None, metavar="FILE", help="one sample name per line")
-    for name in ("vacuum", "extract"):          # (named so that the refusal says why)
+    sp = common(sub.add_parser("fold", help="the same index under a Bloom filter of m / FACTOR bits (rows ORed together on the device, no source data needed): "
+                                            "into the index TO_CONFIG describes, or --in-place"))
+    sp.add_argument("to_config", nargs="?", default=None, help="config of the folded index (with --in-place: the config to use from now on)")
+    sp.add_argument("--factor", type=int, required=True, metavar="D", help="a divisor of m (--dry-run lists the ones that exist)")
+    sp.add_argument("--in-place", action="store_true", help="fold this index itself; TO_CONFIG must name the same storage with m = m / D")
+    sp.add_argument("--dry-run", action="store_true", help="touch nothing: print the valid factors near D and the ESTIMATED fill / false-positive rate per sample")
+    sp.add_argument("--no-trim", action="store_true", help="with --in-place: keep the allocation (and the HBM) the index had before")
+    sp.add_argument("--format", choices=["json", "csv"], default="json")
+    for name in ("vacuum", "extract", "fold"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -155,6 +163,56 @@ def extract_text(index, config_name, to_config_name, names):
                        "num_samples": new.num_samples})
 
 
+def fold_dry_run_text(index, factor, fmt="json"):
+    """`fold --dry-run`: nothing is touched.  The valid factors whose folded size is nearest to the one asked for, and per sample the
+    fill and k-mer false-positive rate the balls-in-bins model PREDICTS (fold.fold_estimate) -- estimates, labelled as such; the exact
+    figures are `stats` of the folded index."""
+    from .fold import FOLD_KEYS, divisors_near, fold_estimate_rows
+    from .stats import to_csv
+    m, h = int(index.bloomfilter_size), int(index.num_hashes)
+    valid = factor >= 1 and m % factor == 0
+    near = divisors_near(m, max(m // max(factor, 1), 1))
+    rows = fold_estimate_rows(index.sample_stats(), m, h, factor) if valid else []
+    if fmt == "csv":
+        return to_csv(rows, FOLD_KEYS)
+    return json.dumps({"m": m, "factor": factor, "valid": valid, "new_m": m // factor if valid else None,
+                       "factors_near": [list(fm) for fm in near],
+                       "note": "est_fill and est_kmer_fpr are model estimates (independent bits); `stats` of the folded index gives the exact figures",
+                       "estimate": rows})
+
+
+def fold_check_in_place(config, new_config, factor):
+    """--in-place: the config to use from now on must describe THIS storage under m / factor; checked before anything is touched."""
+    from .fold import fold_plan
+    new_m = fold_plan(int(config["m"]), factor)
+    for key, want in (("m", new_m), ("h", config["h"]), ("k", config["k"])):
+        if int(new_config[key]) != int(want):
+            raise ValueError("the new config must say %s = %d, it says %d" % (key, want, new_config[key]))
+    if new_config.get("storage-engine") != config.get("storage-engine"):
+        raise ValueError("the new config must name the same storage-engine")
+    a, b = dict(config.get("storage-config") or {}), dict(new_config.get("storage-config") or {})
+    for key in ("name", "filename", "device", "devices"):
+        if a.get(key) != b.get(key):
+            raise ValueError("--in-place: the new config must describe the same storage (storage-config %s: %r vs %r)" % (key, a.get(key), b.get(key)))
+    return new_m
+
+
+def fold_text(config, config_name, to_config_name, factor, in_place=False, trim=True):
+    """`fold`: BIGSI.fold_into the index TO_CONFIG describes (it syncs its own snapshot), or --in-place BIGSI.fold and the snapshot."""
+    new_config = get_config_from_file(to_config_name)
+    if in_place:
+        fold_check_in_place(config, new_config, factor)
+        index = BIGSI(config)
+        old_m = int(index.bloomfilter_size)
+        out = index.fold(factor, trim=trim)
+        index.storage.sync()
+        return json.dumps(dict(out, result="folded %s by %d in place: %d rows -> %d rows; use %s from now on." % (config_name, factor, old_m, out["m"], to_config_name)))
+    index = BIGSI(config)
+    new = index.fold_into(new_config, factor)
+    return json.dumps({"result": "folded %s by %d into %s: %d rows -> %d rows." % (config_name, factor, to_config_name, int(index.bloomfilter_size), int(new.bloomfilter_size)),
+                       "m": int(new.bloomfilter_size), "factor": factor, "num_samples": new.num_samples})
+
+
 def main(argv=None):
     p, search_parser, bulk_parser = build_parser()
     a = p.parse_args(argv)
@@ -164,6 +222,10 @@ def main(argv=None):
 
     if getattr(a, "sharded", False) and a.cmd in ("vacuum", "extract"):
         p.error("%s is not available with --sharded: column shards have a fixed width (use a single index)" % a.cmd)
+    if getattr(a, "sharded", False) and a.cmd == "fold":
+        p.error("fold is not available with --sharded: folding column shards is not implemented (use a single index)")
+    if a.cmd == "fold" and not a.dry_run and not a.to_config:
+        p.error("fold needs TO_CONFIG (the config of the folded index) unless --dry-run is given")
     if getattr(a, "sharded", False):
         return sharded_main(a, config)
     if a.cmd == "search":
@@ -217,6 +279,11 @@ def main(argv=None):
         print(vacuum_text(BIGSI(config), not a.no_shrink))
     elif a.cmd == "extract":
         print(extract_text(BIGSI(config), a.config, a.to_config, extract_names(a)))
+    elif a.cmd == "fold":
+        if a.dry_run:
+            print(fold_dry_run_text(BIGSI(config), a.factor, a.format))
+        else:
+            print(fold_text(config, a.config, a.to_config, a.factor, a.in_place, not a.no_trim))
     elif a.cmd == "hold":
         hold(config, a.handle, a.seconds, a.until_eof)
     return 0

@@ -188,6 +188,13 @@ COMPACT_SIGNATURES = {
     "bigsi_hip_shrink_to_fit": (_i32, [_P]),
 }
 
+# every symbol include/bigsi_hip_fold.h declares (row folding: the same index under a smaller Bloom filter)
+FOLD_SIGNATURES = {
+    "bigsi_hip_fold_rows": (_i32, [_P, _u64, C.POINTER(_u64)]),
+    "bigsi_hip_fold_rows_into": (_i32, [_P, _P]),
+    "bigsi_hip_trim_rows": (_i32, [_P]),
+}
+
 _lib = None
 
 
@@ -208,7 +215,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

@@ -17,6 +17,7 @@
 // Row format = the reference's bitarray.tobytes(): column c at byte c / 8 under mask 0x80 >> (c % 8).
 #include "bigsi_cpu.h"
 #include "bigsi_cpu_compact.h"
+#include "bigsi_cpu_fold.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -152,6 +153,7 @@ struct BdbRows {
 
 struct bigsi_cpu_index {
     uint64_t m = 0, n_cols = 0, cap_cols = 0, stride = 0;      // stride: bytes per row, a multiple of 128 like the device's pitch
+    uint64_t alloc_rows = 0;      // rows the table behind `rows` holds: m, or more between bigsi_cpu_fold_rows and bigsi_cpu_trim_rows
     uint32_t h = 0;
     uint8_t *rows = nullptr;
     BdbRows *bdb = nullptr;      // non-null: no table in RAM, every row fetch reads the store's file (read-only index)
@@ -382,6 +384,7 @@ int bigsi_cpu_open(uint64_t num_rows, uint64_t num_cols, uint64_t col_capacity, 
     bigsi_cpu_index *ix = new (std::nothrow) bigsi_cpu_index();
     if (!ix) return fail(BIGSI_ERR_NOMEM, "host allocation failed");
     ix->m = num_rows;
+    ix->alloc_rows = num_rows;
     ix->n_cols = num_cols;
     ix->h = num_hashes;
     ix->stride = stride_for(col_capacity);
@@ -503,6 +506,7 @@ int bigsi_cpu_reserve_cols(bigsi_cpu_index *ix, uint64_t col_capacity)
     for (uint64_t r = 0; r < ix->m; r++) memcpy(grown + r * stride, ix->row(r), ix->stride);
     free(ix->rows);
     ix->rows = grown;
+    ix->alloc_rows = ix->m;
     ix->stride = stride;
     ix->cap_cols = stride * 8;
     return BIGSI_OK;
@@ -645,6 +649,70 @@ int bigsi_cpu_extract_columns(bigsi_cpu_index *dst, const bigsi_cpu_index *src, 
     for (uint64_t r = 0; r < src->m; r++) select_columns(dst->row(r), dst->stride, src->fetch(r, rb, tmp, page), src->n_cols, keep);
     dst->n_cols = kept;
     return bdb_read_failed(src);
+}
+
+// row r of the folded matrix: the OR of the source rows r, r + m_dst, ..., r + (factor - 1) m_dst over the bytes that carry columns,
+// the bits behind the last column cleared and the rest of the destination stride zeroed (dst may be the source's own row r: the j = 0
+// term is read before the row is written)
+static void fold_row(uint8_t *dst, uint64_t dst_stride, const bigsi_cpu_index *src, uint64_t r, uint64_t m_dst, uint64_t factor,
+                     std::vector<uint8_t> &acc, std::vector<uint8_t> &tmp, std::vector<uint8_t> &page)
+{
+    const uint64_t rb = src->rb();
+    acc.assign(rb, 0);
+    for (uint64_t j = 0; j < factor; j++) {
+        const uint8_t *x = src->fetch(r + j * m_dst, rb, tmp, page);
+        for (uint64_t b = 0; b < rb; b++) acc[b] |= x[b];
+    }
+    if (src->n_cols & 7) acc[rb - 1] &= (uint8_t)(0xFF00u >> (src->n_cols & 7));
+    memcpy(dst, acc.data(), rb);
+    memset(dst + rb, 0, dst_stride - rb);
+}
+
+int bigsi_cpu_fold_rows(bigsi_cpu_index *ix, uint64_t factor, uint64_t *new_num_rows)
+{
+    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
+    if (factor == 0 || ix->m % factor)
+        return fail(BIGSI_ERR_INVALID, "fold factor %llu does not divide num_rows %llu", (unsigned long long)factor, (unsigned long long)ix->m);
+    if (factor > 1) {
+        const uint64_t m_dst = ix->m / factor;
+        std::vector<uint8_t> acc, tmp, page;
+        for (uint64_t r = 0; r < m_dst; r++) fold_row(ix->row(r), ix->stride, ix, r, m_dst, factor, acc, tmp, page);
+        ix->m = m_dst;          // (the table keeps its size until bigsi_cpu_trim_rows)
+    }
+    if (new_num_rows) *new_num_rows = ix->m;
+    return BIGSI_OK;
+}
+
+int bigsi_cpu_fold_rows_into(bigsi_cpu_index *dst, const bigsi_cpu_index *src)
+{
+    if (dst && dst->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    if (!dst || !src) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot fold an index into itself (bigsi_cpu_fold_rows works in place)");
+    if (dst->m == 0 || src->m % dst->m)
+        return fail(BIGSI_ERR_INVALID, "the destination's num_rows %llu does not divide the source's %llu", (unsigned long long)dst->m, (unsigned long long)src->m);
+    if (dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
+    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    TRY(bigsi_cpu_reserve_cols(dst, src->n_cols));
+    std::vector<uint8_t> acc, tmp, page;
+    const uint64_t factor = src->m / dst->m;
+    for (uint64_t r = 0; r < dst->m; r++) fold_row(dst->row(r), dst->stride, src, r, dst->m, factor, acc, tmp, page);
+    dst->n_cols = src->n_cols;
+    return bdb_read_failed(src);
+}
+
+int bigsi_cpu_trim_rows(bigsi_cpu_index *ix)
+{
+    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
+    if (ix->alloc_rows <= ix->m) return BIGSI_OK;
+    uint8_t *kept = static_cast<uint8_t *>(malloc(std::max<uint64_t>(ix->m * ix->stride, 1)));
+    if (!kept) return fail(BIGSI_ERR_NOMEM, "cannot allocate %llu x %llu bytes", (unsigned long long)ix->m, (unsigned long long)ix->stride);
+    memcpy(kept, ix->rows, ix->m * ix->stride);
+    free(ix->rows);
+    ix->rows = kept;
+    ix->alloc_rows = ix->m;
+    return BIGSI_OK;
 }
 
 int bigsi_cpu_insert_kmers(bigsi_cpu_index *ix, uint64_t col, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k)

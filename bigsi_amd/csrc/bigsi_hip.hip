@@ -151,6 +151,7 @@ static int open_impl(uint64_t num_rows, uint64_t num_cols, uint64_t col_capacity
     if (!ix) return fail(BIGSI_ERR_NOMEM, "host allocation failed");
     ix->device = device;
     ix->m = num_rows;
+    ix->alloc_rows = num_rows;
     ix->n_cols = num_cols;
     ix->h = num_hashes;
     ix->stride_words = stride_for(col_capacity);
@@ -372,6 +373,7 @@ extern "C" int bigsi_hip_reserve_cols(bigsi_hip_index *ix, uint64_t col_capacity
     HIP_TRY(hipStreamSynchronize(ix->stream));
     HIP_TRY(hipFree(ix->d_index));
     ix->d_index = nd;
+    ix->alloc_rows = ix->m;          // (the new allocation holds the rows the index has: what a fold left behind them is gone)
     ix->stride_words = ns;
     ix->cap_cols = ns * 64;
     return BIGSI_OK;
@@ -1183,8 +1185,122 @@ extern "C" int bigsi_hip_shrink_to_fit(bigsi_hip_index *ix)
     HIP_TRY(hipStreamSynchronize(ix->stream));
     HIP_TRY(hipFree(ix->d_index));
     ix->d_index = nd;
+    ix->alloc_rows = ix->m;          // (the new allocation holds the rows the index has: what a fold left behind them is gone)
     ix->stride_words = ns;
     ix->cap_cols = ns * 64;
+    return BIGSI_OK;
+}
+
+// Row folding (k_fold_rows; launch shape: plan_fold_rows).  `dst` may be `src` (in place: see the kernel); factors below kFoldLoads
+// have a kernel of their own (the factor is a compile-time constant there), every other factor runs the generic one.
+template <int D>
+static void fold_launch_as(const FoldPlan &p, hipStream_t st, const uint64_t *src, uint64_t src_stride, uint64_t *dst, uint64_t dst_stride, uint64_t m_dst,
+                           uint64_t factor, uint64_t words, uint64_t tail_mask)
+{
+    hipLaunchKernelGGL((k_fold_rows<D, kFoldNtLoads>), dim3((unsigned)p.grid), dim3(p.block), 0, st, src, src_stride, dst, dst_stride, m_dst, factor, words,
+                       tail_mask, p.rows_per_block, (uint32_t)p.seg_groups);
+}
+
+static int fold_launch(bigsi_hip_index *dst, const bigsi_hip_index *src, uint64_t m_dst, uint64_t factor, uint64_t n_cols)
+{
+    const uint64_t words = ceil_div(n_cols, 64);
+    if (words > src->stride_words || words > dst->stride_words || src->stride_words % kVec || dst->stride_words % kVec)
+        return fail(BIGSI_ERR_STATE, "internal: %llu column words do not fit the row strides (%llu, %llu)", (unsigned long long)words,
+                    (unsigned long long)src->stride_words, (unsigned long long)dst->stride_words);
+    // the columns of the last word that exist, in the row format: column c of a word at bit 8 (c / 8) + 7 - c % 8
+    uint64_t tail_mask = ~0ull;
+    if (n_cols & 63) {
+        tail_mask = 0;
+        for (uint32_t c = 0; c < (n_cols & 63); c++) tail_mask |= 1ull << bit_of_col(c);
+    }
+    const FoldPlan p = plan_fold_rows(m_dst, factor, dst->stride_words);
+    if (p.grid > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "internal: a fold grid of %llu workgroups", (unsigned long long)p.grid);
+    hipStream_t st = dst->stream;
+#define FOLD_AS(D) fold_launch_as<D>(p, st, src->d_index, src->stride_words, dst->d_index, dst->stride_words, m_dst, factor, words, tail_mask)
+    switch (factor) {
+    case 1: FOLD_AS(1); break;
+    case 2: FOLD_AS(2); break;
+    case 3: FOLD_AS(3); break;
+    case 4: FOLD_AS(4); break;
+    case 5: FOLD_AS(5); break;
+    case 6: FOLD_AS(6); break;
+    case 7: FOLD_AS(7); break;
+    default: FOLD_AS(0); break;
+    }
+#undef FOLD_AS
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_fold_rows(bigsi_hip_index *ix, uint64_t factor, uint64_t *new_num_rows)
+{
+    BIGSI_ENTER(ix);
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
+    if (factor == 0 || ix->m % factor)
+        return fail(BIGSI_ERR_INVALID, "fold factor %llu does not divide num_rows %llu", (unsigned long long)factor, (unsigned long long)ix->m);
+    if (factor > 1) {          // (factor 1: the index stays as it is, and nothing is touched)
+        TRY(bigsi_writable(ix));
+        if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_fold_rows: the row count of %d open view(s) would go stale", ix->views.load());
+        TRY(use_device(ix));
+        TRY(quiesce_index(ix));
+        const uint64_t m_dst = ix->m / factor;
+        TRY(fold_launch(ix, ix, m_dst, factor, ix->n_cols));
+        ix->m = m_dst;          // (alloc_rows stays: bigsi_hip_trim_rows gives the rows behind m back)
+    }
+    if (new_num_rows) *new_num_rows = ix->m;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_fold_rows_into(bigsi_hip_index *dst, const bigsi_hip_index *src)
+{
+    BIGSI_ENTER(dst);
+    if (!dst || !src) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot fold an index into itself (bigsi_hip_fold_rows works in place)");
+    if (dst->m == 0 || src->m % dst->m)
+        return fail(BIGSI_ERR_INVALID, "the destination's num_rows %llu does not divide the source's %llu", (unsigned long long)dst->m, (unsigned long long)src->m);
+    if (dst->device != src->device) return fail(BIGSI_ERR_INVALID, "both indexes must live on the same device");
+    if (dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
+    TRY(bigsi_writable(dst));
+    if (dst->d_index == src->d_index) return fail(BIGSI_ERR_INVALID, "src is a view of dst (bigsi_hip_fold_rows works in place)");
+    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_fold_rows_into: the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    TRY(bigsi_hip_reserve_cols(dst, src->n_cols));
+    TRY(use_device(dst));
+    TRY(quiesce_index(dst));
+    HIP_TRY(hipStreamSynchronize(src->stream));
+    TRY(fold_launch(dst, src, dst->m, src->m / dst->m, src->n_cols));
+    dst->n_cols = src->n_cols;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_trim_rows(bigsi_hip_index *ix)
+{
+    BIGSI_ENTER(ix);
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
+    TRY(bigsi_writable(ix));          // (a handle that does not own the matrix does not know its allocation: refused whatever there is to gain)
+    if (ix->alloc_rows <= ix->m) return BIGSI_OK;
+    if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_trim_rows: trimming would move the matrix under %d open view(s)", ix->views.load());
+    TRY(use_device(ix));
+    TRY(quiesce_index(ix));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    const size_t bytes = (size_t)ix->m * ix->stride_words * 8;
+    uint64_t *nd = nullptr;
+    hipError_t e = hipMalloc((void **)&nd, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();          // (the runtime's last-error slot is sticky: the next launch check of this thread must not inherit it)
+        return fail(e == hipErrorOutOfMemory ? BIGSI_ERR_NOMEM : BIGSI_ERR_HIP, "bigsi_hip_trim_rows: hipMalloc of %zu bytes beside the matrix failed: %s", bytes,
+                    hipGetErrorString(e));
+    }
+    // rows [0, m) are the front of the old allocation, at the same stride: one device-to-device copy
+    e = hipMemcpyAsync(nd, ix->d_index, bytes, hipMemcpyDeviceToDevice, ix->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
+    if (e != hipSuccess) {
+        hipError_t e2 = hipFree(nd); (void)e2;
+        return fail(BIGSI_ERR_HIP, "bigsi_hip_trim_rows: copying the rows failed: %s", hipGetErrorString(e));
+    }
+    HIP_TRY(hipFree(ix->d_index));
+    ix->d_index = nd;
+    ix->alloc_rows = ix->m;
     return BIGSI_OK;
 }
 

@@ -2730,6 +2730,112 @@ __global__ __launch_bounds__(kBlock) void k_compact_columns(
     }
 }
 
+// ------------------------------------------------------------------------------ row folding: the matrix under a smaller Bloom filter
+// dst row r = src row r | src row r + m' | ... | src row r + (factor - 1) m' for r in [0, m'), m' = m_dst: because a row id is
+// floor_mod(hash, m) (row_of_hash) and floor_mod(x, m) mod m' == floor_mod(x, m') for every divisor m' of m, this is bit for bit the
+// matrix the same samples build under m'.  Decomposition as k_col_popcount: a wavefront owns one 1 KiB column segment, a lane 16 bytes
+// of it, and a contiguous block of DESTINATION rows [rb * rows_per_block, +rows_per_block) cut off at m_dst (plan_fold_rows,
+// bigsi_launch.hpp); no LDS, no scratch.
+//   D > 0: factor == D, known at compile time and < kFoldLoads.  A step folds R = ceil(kFoldLoads / D) destination rows: R x D
+//          independent 16-byte loads (8 to 14) are in flight before the first OR.  The rows a block has left over after its whole steps
+//          go one at a time (D loads).
+//   D == 0: any factor (the launcher sends factors >= kFoldLoads here).  One destination row at a time, its source rows in groups of
+//          kFoldLoads independent loads ORed into a running value, the last group predicated (wave-uniform) on the rows that exist.
+// The whole destination stride is written: words [0, words) carry columns (the last one masked by tail_mask: bits at columns
+// >= num_cols, which bigsi_hip_set_rows can put there, do not survive), words [words, dst_stride) are zero and are not loaded.
+// `words` <= src_stride and <= dst_stride; both strides are multiples of kVec words, so a lane's 16 bytes are inside both rows or the
+// lane has returned.
+// Bounds: a destination row is < r1 <= m_dst; a source row is r + j m' <= (m' - 1) + (factor - 1) m' = m_dst factor - 1.  All row and
+// word arithmetic is 64 bits wide: (r + j m') src_stride passes 2^32 words on a 10 M-row index.
+// In place (dst == src, equal strides) this is correct without any ordering between lanes:
+//   - the rows written are [0, m'); row r is read only as the j = 0 term of itself, by the very lane that writes those 16 bytes, and
+//     that lane's store takes its value from that load;
+//   - every other source row is >= m' and nobody writes it;
+//   - wavefronts own disjoint (segment, row) cells.
+// So the result does not depend on the order of execution: no atomics, no barrier, no workgroup waits for another.  (src and dst may
+// alias: no __restrict__.)
+// Loads are streamed (nontemporal) or plain by kFoldNtLoads.  Streamed is what k_col_popcount does for a matrix that is read once; on
+// an MI355X the two flavours were not told apart ("Row folding": their difference is inside the spread between two runs of
+// the same build), so the choice is kept as inherited, not as measured faster.  Stores are plain 16-byte vector stores.
+constexpr bool kFoldNtLoads = true;
+template <bool NT>
+__device__ __forceinline__ u64x2 fold_load(const uint64_t *p)
+{
+    const u64x2 *q = reinterpret_cast<const u64x2 *>(p);
+    if (NT) return __builtin_nontemporal_load(q);
+    return *q;
+}
+
+template <int D, bool NT>
+__global__ __launch_bounds__(kBlock) void k_fold_rows(
+    const uint64_t *src, uint64_t src_stride, uint64_t *dst, uint64_t dst_stride, uint64_t m_dst, uint64_t factor, uint64_t words,
+    uint64_t tail_mask, uint64_t rows_per_block, uint32_t seg_groups)
+{
+    constexpr int L = kFoldLoads, R = D > 0 ? (L + D - 1) / D : 1;
+    static_assert(D >= 0 && D < L && R * (D > 0 ? D : L) <= kFoldMaxLoads, "plan_fold_rows' invariant: at most kFoldMaxLoads loads per lane and step");
+    const uint64_t rb = blockIdx.x / seg_groups;
+    const uint64_t w0 = ((uint64_t)(blockIdx.x - rb * seg_groups) * blockDim.x + threadIdx.x) * kVec;
+    if (w0 >= dst_stride) return;
+    const uint64_t r0 = rb * rows_per_block;
+    if (r0 >= m_dst) return;
+    const uint64_t r1 = m_dst - r0 > rows_per_block ? r0 + rows_per_block : m_dst;
+    uint64_t *out = dst + r0 * dst_stride + w0;
+    if (w0 >= words) {          // the pad of the destination stride: zero, nothing to read
+        for (uint64_t r = r0; r < r1; r++, out += dst_stride) *reinterpret_cast<u64x2 *>(out) = u64x2{0ull, 0ull};
+        return;
+    }
+    const u64x2 keep{w0 + 1 < words ? ~0ull : tail_mask, w0 + 2 < words ? ~0ull : (w0 + 2 == words ? tail_mask : 0ull)};
+    const uint64_t fold = m_dst * src_stride;          // words between two terms of a destination row
+    const uint64_t *in = src + r0 * src_stride + w0;
+    uint64_t r = r0;
+    if (D > 0) {
+        for (; r + R <= r1; r += R, in += R * src_stride, out += R * dst_stride) {
+            u64x2 v[R][D > 0 ? D : 1];
+#pragma unroll
+            for (int i = 0; i < R; i++)
+#pragma unroll
+                for (int j = 0; j < D; j++) v[i][j] = fold_load<NT>(in + i * src_stride + j * fold);
+#pragma unroll
+            for (int i = 0; i < R; i++) {
+                u64x2 acc = v[i][0];
+#pragma unroll
+                for (int j = 1; j < D; j++) acc |= v[i][j];
+                *reinterpret_cast<u64x2 *>(out + i * dst_stride) = acc & keep;
+            }
+        }
+        for (; r < r1; r++, in += src_stride, out += dst_stride) {
+            u64x2 v[D > 0 ? D : 1];
+#pragma unroll
+            for (int j = 0; j < D; j++) v[j] = fold_load<NT>(in + j * fold);
+            u64x2 acc = v[0];
+#pragma unroll
+            for (int j = 1; j < D; j++) acc |= v[j];
+            *reinterpret_cast<u64x2 *>(out) = acc & keep;
+        }
+    } else {
+        for (; r < r1; r++, in += src_stride, out += dst_stride) {
+            u64x2 acc{0ull, 0ull};
+            const uint64_t *q = in;
+            uint64_t j = 0;
+            for (; j + L <= factor; j += L, q += L * fold) {
+                u64x2 v[L];
+#pragma unroll
+                for (int t = 0; t < L; t++) v[t] = fold_load<NT>(q + t * fold);
+#pragma unroll
+                for (int t = 0; t < L; t++) acc |= v[t];
+            }
+            if (j < factor) {          // (wave-uniform)
+                u64x2 v[L];
+#pragma unroll
+                for (int t = 0; t < L; t++) v[t] = j + t < factor ? fold_load<NT>(q + t * fold) : u64x2{0ull, 0ull};
+#pragma unroll
+                for (int t = 0; t < L; t++) acc |= v[t];
+            }
+            *reinterpret_cast<u64x2 *>(out) = acc & keep;
+        }
+    }
+}
+
 // transpose (bigsi/matrix/transpose.py:33-43) on the device: n Bloom filters (bloom c at blooms + c*bloom_stride, m bits,
 // row byte format) become columns [col0, col0+n) of the matrix.  One thread per (row, 64-column word); the 8 threads of
 // 8 consecutive rows read the same Bloom byte (one L1 line per wave), the word is read-modified-written once.

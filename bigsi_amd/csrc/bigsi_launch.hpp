@@ -1,9 +1,10 @@
 // bigsi_launch.hpp -- the launch rule of a batch run, host-only: how K1 goes out (k1_plan) and how the row-AND kernels
 // (k_and_exact, k_and_count, k_count_combine) are launched for a batch of queries (plan_row_and), the sweep of the column popcounts
-// (plan_col_popcount) and the per-call tables of the column compaction (plan_compact_columns).  Pure functions of a handful of
-// integers (and, for the compaction, of the keep bitmap): no HIP, no batch, no index.  bigsi_hip.hip carries the plans out;
-// tests/c_host/launch_host.cpp and compact_host.cpp compile this header as plain host C++ and tests/test_abi_and_host.py,
-// test_sample_stats_host.py and test_compact_columns_host.py pin the decisions on the CPU.
+// (plan_col_popcount), the per-call tables of the column compaction (plan_compact_columns) and the sweep of the row folding
+// (plan_fold_rows).  Pure functions of a handful of integers (and, for the compaction, of the keep bitmap): no HIP, no batch, no
+// index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp, compact_host.cpp and fold_host.cpp compile this header as
+// plain host C++ and tests/test_abi_and_host.py, test_sample_stats_host.py, test_compact_columns_host.py and test_fold_rows_host.py
+// pin the decisions on the CPU.
 //
 // Every constant below was measured on an MI355X; the notes beside them say against what.  A GPU test compares results, and a slip
 // here keeps results right and costs the 3 to 20 % those notes record: change a constant only with a new measurement, and the pinned
@@ -399,6 +400,52 @@ static inline CompactPlan plan_compact_columns(uint64_t num_cols, const uint8_t 
     const uint64_t groups = std::max<uint64_t>(ceil_div(num_rows, kCompactRows), 1);
     p.block = (uint32_t)std::min<uint64_t>(groups, kBlock / 64) * 64;
     p.grid = std::min<uint64_t>(ceil_div(groups, p.block / 64), kColPopWaves / (kBlock / 64));
+    return p;
+}
+
+// ------------------------------------------------------------------------------ row folding (k_fold_rows)
+// Destination row r = the OR of the source rows r, r + m', ..., r + (factor - 1) m' (m' = m_dst = m / factor): the matrix of the same
+// samples under a Bloom filter of m' bits.  One streaming pass, decomposed as the column popcounts: a wavefront owns one 1 KiB column
+// segment (kVec words per lane) of a contiguous block of DESTINATION rows, the grid is segments x row blocks.
+//   - Loads in flight: a step of the kernel takes rows_per_step destination rows at once, rows_per_step x factor independent 16-byte
+//     loads per lane, for factor < kFoldLoads (ceil(kFoldLoads / factor) rows: 8 to 14 loads); for factor >= kFoldLoads it takes one
+//     destination row and its source rows in groups of kFoldLoads, ORed into a running value.
+//     INVARIANT (the kernel's register budget): rows_per_step x min(factor, kFoldLoads) <= kFoldMaxLoads = 16 loads of 4 VGPRs each,
+//     64 VGPRs of row data per lane; the kernel's arrays are sized by it and tests/test_fold_rows_host.py checks it for every plan.
+//   - Row blocks: about kFoldWaves wavefronts whatever the shape.  The figure is INHERITED from the column popcounts' sweep
+//     (kColPopWaves, measured there), not measured for this kernel.  A block is a whole number of steps, and at least kFoldMinRows
+//     rows (a wavefront that folds fewer has more launch than work), so only a matrix of fewer than kFoldMinRows x (wanted blocks) rows
+//     runs fewer wavefronts.  No block is empty: row_blocks = ceil(m_dst / rows_per_block), the last one is ragged.
+//   - The grid is seg_groups x row_blocks <= max(2^17, 4 x kFoldWaves) workgroups for any stride the ABI allows (2^32 - 1 columns
+//     = 2^26 words = 2^19 segments): it fits 31 bits.
+constexpr int kFoldLoads = 8;
+constexpr int kFoldMaxLoads = 16;
+constexpr uint64_t kFoldWaves = kColPopWaves;
+constexpr uint64_t kFoldMinRows = 64;
+struct FoldPlan {
+    uint32_t block = 64;            // threads per workgroup: 64 per segment it covers, at most kBlock
+    uint64_t seg_groups = 0;        // workgroups per row block
+    uint32_t rows_per_step = 1;     // destination rows a lane folds at once
+    uint64_t rows_per_block = 0;    // a multiple of rows_per_step
+    uint64_t row_blocks = 0;
+    uint64_t grid = 0;              // seg_groups x row_blocks workgroups
+};
+static inline uint32_t fold_rows_per_step(uint64_t factor)
+{
+    return factor >= (uint64_t)kFoldLoads ? 1u : (uint32_t)ceil_div(kFoldLoads, std::max<uint64_t>(factor, 1));
+}
+// `stride_words`: the DESTINATION's row stride (every word of it is written)
+static inline FoldPlan plan_fold_rows(uint64_t m_dst, uint64_t factor, uint64_t stride_words)
+{
+    FoldPlan p;
+    const uint64_t segs = std::max<uint64_t>(ceil_div(stride_words, 64 * kVec), 1);
+    p.block = (uint32_t)std::min<uint64_t>(segs, kBlock / 64) * 64;
+    p.seg_groups = ceil_div(segs, p.block / 64);
+    p.rows_per_step = fold_rows_per_step(factor);
+    const uint64_t want_blocks = std::max<uint64_t>(kFoldWaves / segs, 1);
+    p.rows_per_block = round_up(std::max<uint64_t>(ceil_div(m_dst, want_blocks), kFoldMinRows), p.rows_per_step);
+    p.row_blocks = std::max<uint64_t>(ceil_div(m_dst, p.rows_per_block), 1);
+    p.grid = p.seg_groups * p.row_blocks;
     return p;
 }
 

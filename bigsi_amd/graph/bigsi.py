@@ -801,6 +801,91 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
             storage.close()
         return type(self)(config)
 
+    # ------------------------------------------------------------------ row folding: the same index under a smaller Bloom filter
+    def _refuse_group_fold(self):
+        if self.storage.res.is_group:
+            from .._lib import ERR_STATE, BigsiHipError
+            raise BigsiHipError(ERR_STATE, "row folding is not available for multi-GPU (devices=[...]) indexes")
+
+    def fold(self, factor, trim=True):
+        """Fold the index in place to m' = m / factor rows (bigsi_hip_fold_rows: row r becomes the OR of the rows r, r + m', ...,
+        r + (factor - 1) m').  Because a k-mer's row is floor_mod(hash, m) and m' divides m, the result is bit for bit the index
+        BIGSI.build makes from the same samples under a config with m = m': rows, search results, counts and scores; no false
+        negative appears, the false-positive rate rises (sample_stats() of the folded index says to what; fold.fold_estimate
+        predicts it).  The stored bloomfilter_size and number_of_rows follow; from now on the index is described by a config with
+        m = m'.  trim: also give the freed rows back (bigsi_hip_trim_rows) -- that needs room for the smaller copy beside the
+        matrix, and a trim that finds none leaves the allocation as it is and reports trimmed: False.  Nothing is on disk before
+        the caller's sync().  Returns {"m": m', "factor": factor, "trimmed": bool}."""
+        from .._lib import ERR_NOMEM, BigsiHipError
+        from ..fold import fold_plan
+        from .index import BLOOMFILTER_SIZE_KEY
+        if not isinstance(trim, bool):
+            raise TypeError("trim must be a bool, got %r" % (trim,))
+        new_m = fold_plan(int(self.bloomfilter_size), factor)
+        self._refuse_group_fold()
+        with self._device_lock():
+            st = self.storage
+            trimmed = False
+            if factor > 1:
+                for batch in self.__dict__.pop("_workspaces", {}).values():
+                    batch.close()
+                if st.fold_rows(factor) != new_m:
+                    raise RuntimeError("the device folded to another number of rows than the host worked out")
+                st.set_integer(BLOOMFILTER_SIZE_KEY, new_m)
+                st.set_integer("number_of_rows", new_m)
+                self.bloomfilter_size = new_m
+                self.bitmatrix._rows = new_m
+                if isinstance(self.config, dict) and "m" in self.config:
+                    self.config = dict(self.config, m=new_m)
+                self._metadata_changed()
+                if trim:
+                    try:
+                        st.trim_rows()
+                        trimmed = True
+                    except BigsiHipError as e:
+                        if e.code != ERR_NOMEM:
+                            raise
+            return {"m": new_m, "factor": int(factor), "trimmed": trimmed}
+
+    def fold_into(self, config, factor):
+        """A new index under `config` (m = this index's m / factor, same h and k, same device, a storage-config name of its own,
+        nothing stored under it yet) that holds this index folded by `factor` (bigsi_hip_fold_rows_into: device to device, this
+        index is only read) -- the index BIGSI.build makes from the same samples under `config`.  The sample metadata is copied
+        unchanged: same colours, and deleted samples stay deleted.  On any failure the new storage is emptied again.  Returns the
+        new BIGSI."""
+        from ..fold import fold_plan
+        from .index import BLOOMFILTER_SIZE_KEY, NUM_HASH_FUNCTS_KEY
+        from .metadata import _k
+        new_m = fold_plan(int(self.bloomfilter_size), factor)
+        for key, mine in (("m", new_m), ("h", self.num_hashes), ("k", self.kmer_size)):
+            if int(config[key]) != int(mine):
+                raise ValueError("the new index must have %s = %d, its config says %d" % (key, mine, config[key]))
+        self._refuse_group_fold()
+        with self._device_lock():
+            storage = get_storage(config)
+            if storage.res is self.storage.res:
+                raise ValueError("the new index needs a storage-config name of its own")
+            if SampleMetadata(storage).num_samples or int(storage.get("number_of_cols:int", b"0")):
+                raise ValueError("the index described by the new config is not empty")
+            try:
+                storage.set_integer(BLOOMFILTER_SIZE_KEY, new_m)
+                storage.set_integer(NUM_HASH_FUNCTS_KEY, int(self.num_hashes))
+                storage.set_integer("number_of_rows", new_m)
+                storage.set_integer("number_of_cols", 0)
+                storage.res.ensure_open()
+                cols = int(self.storage.get_integer("number_of_cols"))
+                if storage.fold_rows_from(self.storage) != cols:
+                    raise RuntimeError("the device folded another number of columns than the index holds")
+                mine = self.storage
+                for key in mine.record_keys(_k("")):          # colours, names and the tombstones of deleted samples, as they are
+                    storage[key] = mine[key]
+                storage.sync()
+            except BaseException:
+                storage.delete_all()          # (it was empty when we came: nothing half-made stays resident under the new name)
+                raise
+            storage.close()
+        return type(self)(config)
+
     def _device_lock(self):
         import threading
         return self.storage.res.__dict__.setdefault("_lock", threading.RLock())

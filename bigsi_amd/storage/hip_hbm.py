@@ -269,6 +269,12 @@ class HipHbmStorage(BaseStorage):
                 pass                                   # a handle onto the index another process holds resident
             elif fn and os.path.exists(fn):
                 _load_snapshot(res, fn, int(self.storage_config.get("io_threads", 0)))
+                want = self.storage_config.get("m")
+                if want is not None and res.m is not None and int(want) != res.m:
+                    # (a snapshot of an index folded to fewer rows, opened under the config from before the fold)
+                    have = res.m
+                    HipHbmStorage.drop(self.name)
+                    raise BigsiHipError(_lib.ERR_INVALID, "number_of_rows %d differs from the index in the snapshot %s (%d rows)" % (int(want), fn, have))
                 if self.storage_config.get("export"):
                     _export_attach(res, self.storage_config["export"])
         self.res = res
@@ -467,6 +473,54 @@ class HipHbmStorage(BaseStorage):
             raise BigsiHipError(_lib.ERR_STATE, "a multi-GPU index keeps the shard width it was opened with")
         check(_lib.lib().bigsi_hip_shrink_to_fit(self.handle))
         self._after_column_move()
+
+    def _after_row_fold(self):
+        """The index has fewer rows now, every one of them rewritten on the device at the index's width: the host-side records follow."""
+        res = self.res
+        res.m = int(res.info().num_rows)
+        res.written = np.ones(res.m, dtype=bool)
+        res.lengths_reset()
+        res.cfg["m"] = res.m          # (the name now describes an index of m' rows: a config that still says m is another index's)
+        self.storage_config["m"] = res.m
+        res.kv[b"number_of_rows:int"] = str(res.m).encode()
+        res.kv[b"number_of_cols:int"] = str(int(res.info().num_cols)).encode()
+
+    def fold_rows(self, factor):
+        """Fold the resident index in place to num_rows / factor rows (bigsi_hip_fold_rows): row r becomes the OR of the rows
+        r, r + m', ..., r + (factor - 1) m' -- the matrix of the same samples under a Bloom filter of m' bits.  Returns m'.  The
+        allocation keeps its size until trim_rows()."""
+        from ..fold import fold_plan
+        if self.res.is_group:
+            raise BigsiHipError(_lib.ERR_STATE, "row folding is not available for multi-GPU (devices=[...]) indexes")
+        if not self.res.ensure_open():
+            raise KeyError("number_of_rows:int")
+        fold_plan(int(self.res.m), factor)
+        new = _lib.C.c_uint64(0)
+        check(_lib.lib().bigsi_hip_fold_rows(self.handle, int(factor), _lib.C.byref(new)))
+        if factor > 1:
+            self._after_row_fold()
+        return int(new.value)
+
+    def fold_rows_from(self, other):
+        """Another resident hip-hbm index (same device, same h), folded by other's rows / this one's rows, becomes the content of
+        this one, which must hold no columns yet (bigsi_hip_fold_rows_into); `other` is only read.  Returns the number of columns."""
+        if self.res.is_group or other.res.is_group:
+            raise BigsiHipError(_lib.ERR_STATE, "row folding is not available for multi-GPU (devices=[...]) indexes")
+        if not (self.res.ensure_open() and other.res.ensure_open()):
+            raise KeyError("number_of_rows:int")
+        check(_lib.lib().bigsi_hip_fold_rows_into(self.handle, other.handle))
+        self._after_column_move()
+        return int(self.res.info().num_cols)
+
+    def trim_rows(self):
+        """Give back the rows of the allocation behind num_rows (bigsi_hip_trim_rows): the counterpart of fold_rows, as
+        shrink_to_fit is of compact_columns.  Needs room for the smaller copy while it runs (BigsiHipError with code ERR_NOMEM
+        otherwise, the index unchanged)."""
+        if self.res.is_group:
+            raise BigsiHipError(_lib.ERR_STATE, "a multi-GPU index keeps the rows it was opened with")
+        if not self.res.ensure_open():
+            raise KeyError("number_of_rows:int")
+        check(_lib.lib().bigsi_hip_trim_rows(self.handle))
 
     def get_column(self, col):
         res = self.res

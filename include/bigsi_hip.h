@@ -24,6 +24,7 @@
  *       MULTI-GPU  bigsi_hip_comm_* / batch_set_comm / batch_run_sharded (one process per GPU): the RCCL exchange is issued by
  *                  the library.  One process driving N GPUs: bigsi_hip_group_* in include/bigsi_hip_group.h.
  *       MAINTENANCE  removing or extracting samples physically (column compaction, the capacity trim): include/bigsi_hip_compact.h.
+ *                  The same index under a smaller Bloom filter size (row folding, the row trim): include/bigsi_hip_fold.h.
  *       SHARING    export_ipc / open_ipc (another process) and open_view (another thread): read-only handles onto ONE resident matrix.
  *       MEASUREMENT  fill_synthetic, set_profiling, stats (calibration probe and device-resident filters: bigsi_hip_testing.h).
  *     Not advertised here (exported all the same, declared in include/bigsi_hip_testing.h): hooks for hosts that bring their own

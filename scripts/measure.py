@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -366,6 +366,120 @@ def compact():
                  extract_099_over_copy=(results[("extract", 0.99)] / copy_ms) if ("extract", 0.99) in results else None,
                  note="bigsi_hip_reserve_cols by one more 128-byte line per row = hipMalloc + k_restride + hipFree; copy_ms = the call less an "
                       "allocation and release of the same size timed alone (k_restride's own time: the same command under rocprofv3 --kernel-trace --stats)",
+                 **common)
+        st.delete_all()
+
+
+def fold():
+    """Row folding (k_fold_rows) on the C3 index -- by 2 out of place, by 2 in place, by 8 in place -- and on a C4 shard (by 2 in place
+    only: a second matrix does not fit beside 198 GB), beside two yardsticks from the same run on the same box: the bare sorted-row
+    stream (bigsi_hip_probe_rows) and a bigsi_hip_reserve_cols re-stride of the same matrix, k_restride's pure copy.  bytes = what the
+    kernel reads (factor x m' rows, the 16-byte pieces that carry columns) + what it writes (m' rows at the destination stride);
+    wall-clock time of the whole C call.  Before every fold the source rows of 64 seeded destination rows are fetched with get_rows,
+    and afterwards the folded rows are checked against their OR: the only place the 64-bit row arithmetic meets a real size.  What
+    does not fit beside the index in device memory is skipped and says so.  BIGSI_FOLD_SHAPES="MxN,..." replaces the two shapes (the
+    first runs everything, the others the in-place fold by 2)."""
+    import torch
+    L, C = _lib.lib(), _lib.C
+    shapes = ((10_000_000, 100_000), (25_000_000, 62_500))
+    if os.environ.get("BIGSI_FOLD_SHAPES"):
+        shapes = tuple(tuple(int(x) for x in sh.split("x")) for sh in os.environ["BIGSI_FOLD_SHAPES"].split(","))
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        check(fn())
+        return (time.perf_counter() - t0) * 1e3
+
+    def get_rows(handle, ids, rb):
+        out = np.zeros((ids.size, rb), np.uint8)
+        check(L.bigsi_hip_get_rows(handle, _lib.ptr(ids), ids.size, _lib.ptr(out), rb))
+        return out
+
+    def expectation(handle, m, n, d, seed):
+        """(64 seeded destination rows -- the first, the last and one either side of 2^32 words among them --, the OR of their sources)"""
+        new_m, stride = m // d, int(info(handle).row_stride_bytes)
+        rng = np.random.default_rng(seed)
+        edge = (1 << 32) // (stride // 8)                      # the row whose first word is word 2^32 of the matrix
+        picks = [0, new_m - 1] + [r % new_m for r in (edge - 1, edge, edge + 1)] + [int(x) for x in rng.integers(0, new_m, 59)]
+        dst = np.unique(np.array(picks, np.uint64))
+        src = (dst[None, :] + (np.arange(d, dtype=np.uint64) * np.uint64(new_m))[:, None]).reshape(-1)
+        rows = get_rows(handle, src, stride).reshape(d, dst.size, stride)
+        want = np.bitwise_or.reduce(rows, axis=0)
+        bits = np.unpackbits(want, axis=1)
+        bits[:, n:] = 0
+        return dst, np.packbits(bits, axis=1)
+
+    def info(handle):
+        inf = _lib.Info()
+        check(L.bigsi_hip_get_info(handle, C.byref(inf)))
+        return inf
+
+    def moved_bytes(m, n, d, dst_stride):
+        return m * (-(-(-(-n // 64)) // 2) * 2) * 8 + (m // d) * dst_stride
+
+    for si, (m, n) in enumerate(shapes):
+        st, fill = open_index("fold", m, n, 3)
+        stride = int(st.res.info().row_stride_bytes)
+        g_, m_ = C.c_double(0), C.c_double(0)
+        check(L.bigsi_hip_probe_rows(st.handle, 3880, 1, 1, 0, 3, C.byref(g_), C.byref(m_)))
+        common = dict(m=m, cols=n, stride_bytes=stride, box_sorted_GBps=g_.value, lib=os.path.basename(_lib.LIB_PATH))
+        results = {}
+        if si == 0:
+            # out of place by 2, into a destination that already has its capacity
+            need = (m // 2) * stride
+            free = torch.cuda.mem_get_info()[0]
+            if need + (2 << 30) > free:
+                emit("fold_into", factor=2, skipped="the destination (%d bytes) does not fit beside the index (%d free)" % (need, free), **common)
+            else:
+                ids, want = expectation(st.handle, m, n, 2, 1)
+                dst = C.c_void_p()
+                check(L.bigsi_hip_open(m // 2, 0, n, 3, 0, C.byref(dst)))
+                ms = timed(lambda: L.bigsi_hip_fold_rows_into(dst, st.handle))
+                ok = bool(np.array_equal(get_rows(dst, ids, stride), want))
+                moved = moved_bytes(m, n, 2, int(info(dst).row_stride_bytes))
+                emit("fold_into", factor=2, call_ms=ms, bytes=moved, GBps=moved / ms / 1e6, rows_checked=int(ids.size), rows_ok=ok, **common)
+                results["into2"] = moved / ms
+                check(L.bigsi_hip_close(dst))
+                assert ok
+        for d in ((2, 8) if si == 0 else (2,)):
+            if m % d:
+                emit("fold_in_place", factor=d, skipped="%d does not divide %d" % (d, m), **common)
+                continue
+            ids, want = expectation(st.handle, m, n, d, 2 + d)
+            ms = timed(lambda: L.bigsi_hip_fold_rows(st.handle, d, None))
+            ok = bool(np.array_equal(get_rows(st.handle, ids, stride), want)) and int(info(st.handle).num_rows) == m // d
+            moved = moved_bytes(m, n, d, stride)
+            emit("fold_in_place", factor=d, call_ms=ms, bytes=moved, GBps=moved / ms / 1e6, rows_checked=int(ids.size), rows_ok=ok, **common)
+            results["in_place%d" % d] = moved / ms
+            assert ok
+            st.delete_all()                                    # (the index has m / d rows now: a fresh one for what follows)
+            st, fill = open_index("fold", m, n, 3)
+        # the yardstick: a re-stride of the same matrix, a pure copy of the same rows
+        free = torch.cuda.mem_get_info()[0]
+        if m * (stride + 128) + (2 << 30) > free:
+            emit("fold_restride_yardstick", skipped="a second copy of the matrix (%d bytes) does not fit beside it (%d free)" % (m * (stride + 128), free),
+                 fold_by_2_in_place_over_box=results["in_place2"] / 1e6 / g_.value if "in_place2" in results else None, **common)
+        else:
+            ms = timed(lambda: L.bigsi_hip_reserve_cols(st.handle, stride * 8 + 1))
+            new_stride = int(st.res.info().row_stride_bytes)
+            # The call is hipMalloc + k_restride + hipFree, and for 125 GB the two runtime calls take seconds where the kernel takes
+            # tens of milliseconds.  Both are timed alone here, through the very runtime the library calls (the same hipMalloc /
+            # hipFree, the same size), and BOTH figures are printed: call_ms is what was measured, call_less_alloc_ms is the
+            # difference of two terms of seconds and carries their noise (it can come out negative).  k_restride's own time is the
+            # kernel trace's: this command under `rocprofv3 --kernel-trace --stats`, where k_fold_rows' times stand beside it.
+            hip = C.CDLL(next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64.so" in line))
+            block = C.c_void_p()
+            t0 = time.perf_counter()
+            assert hip.hipMalloc(C.byref(block), C.c_size_t(m * new_stride)) == 0
+            assert hip.hipFree(block) == 0
+            alloc_ms = (time.perf_counter() - t0) * 1e3
+            moved = m * (stride + new_stride)
+            emit("fold_restride_yardstick", call_ms=ms, alloc_free_ms=alloc_ms, call_less_alloc_ms=ms - alloc_ms, bytes=moved, new_stride_bytes=new_stride,
+                 fold_GBps={k: v / 1e6 for k, v in results.items()},
+                 **{"fold_%s_rate_over_box" % k: v / 1e6 / g_.value for k, v in results.items()},
+                 note="bigsi_hip_reserve_cols by one more 128-byte line per row = hipMalloc + k_restride + hipFree; alloc_free_ms = a hipMalloc + hipFree "
+                      "of the new matrix's size timed alone through the same runtime; call_less_alloc_ms is NOT a kernel time (a difference of two "
+                      "terms of seconds); k_restride's copy time: the kernel trace of this command (rocprofv3 --kernel-trace --stats)",
                  **common)
         st.delete_all()
 

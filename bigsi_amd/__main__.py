@@ -118,7 +118,14 @@ def build_parser():
     sp.add_argument("--dry-run", action="store_true", help="touch nothing: print the valid factors near D and the ESTIMATED fill / false-positive rate per sample")
     sp.add_argument("--no-trim", action="store_true", help="with --in-place: keep the allocation (and the HBM) the index had before")
     sp.add_argument("--format", choices=["json", "csv"], default="json")
-    for name in ("vacuum", "extract", "fold"):          # (named so that the refusal says why)
+    sp = common(sub.add_parser("prevalence", help="for every k-mer position of SEQ (or of every record of a FASTA file): how many samples hold the k-mer, "
+                                                  "and how many of the named samples"))
+    sp.add_argument("seq", nargs="?", default=None)
+    sp.add_argument("--fasta", default=None, metavar="FILE", help="the queries: every record of a FASTA file")
+    sp.add_argument("--samples", "-s", action="append", default=[], metavar="NAME", help="also count among these samples only")
+    sp.add_argument("--samples-file", default=None, metavar="FILE", help="one sample name per line")
+    sp.add_argument("--format", choices=["json", "csv"], default="json")
+    for name in ("vacuum", "extract", "fold", "prevalence"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -161,6 +168,31 @@ def extract_text(index, config_name, to_config_name, names):
     new = index.extract(get_config_from_file(to_config_name), names)
     return json.dumps({"result": "extracted %d of %d samples from %s into %s." % (new.num_samples, index.num_samples, config_name, to_config_name),
                        "num_samples": new.num_samples})
+
+
+# k-mer positions of one device call of `prevalence --fasta` (a few bounded batches instead of one of any size: the device keeps a
+# partial count and a result per position)
+PREVALENCE_BATCH_POSITIONS = 1 << 20
+
+
+def prevalence_text(index, queries, samples=None, fmt="json"):
+    """`prevalence`: BIGSI.kmer_prevalence_many over the queries, in device calls of at most PREVALENCE_BATCH_POSITIONS k-mer
+    positions (a single longer query is a call of its own).  JSON: the dicts, each with its "query" first; CSV:
+    record,pos,kmer,samples,in_subset with one line per k-mer position."""
+    from .prevalence import to_csv
+    k = int(index.kmer_size)
+    records, chunk, load = [], [], 0
+    for q in list(queries) + [None]:
+        n = 0 if q is None else max(len(q) - k + 1, 0)
+        if chunk and (q is None or load + n > PREVALENCE_BATCH_POSITIONS):
+            records.extend(index.kmer_prevalence_many(chunk, samples=samples))
+            chunk, load = [], 0
+        if q is not None:
+            chunk.append(q)
+            load += n
+    if fmt == "csv":
+        return to_csv(records, queries, k)
+    return json.dumps([dict({"query": q}, **r) for q, r in zip(queries, records)])
 
 
 def fold_dry_run_text(index, factor, fmt="json"):
@@ -224,6 +256,10 @@ def main(argv=None):
         p.error("%s is not available with --sharded: column shards have a fixed width (use a single index)" % a.cmd)
     if getattr(a, "sharded", False) and a.cmd == "fold":
         p.error("fold is not available with --sharded: folding column shards is not implemented (use a single index)")
+    if getattr(a, "sharded", False) and a.cmd == "prevalence":
+        p.error("prevalence is not available with --sharded: the per-shard sweep plus a host sum is not implemented (use a single index)")
+    if a.cmd == "prevalence" and (a.seq is None) == (a.fasta is None):
+        p.error("prevalence takes SEQ or --fasta FILE (one of them)")
     if a.cmd == "fold" and not a.dry_run and not a.to_config:
         p.error("fold needs TO_CONFIG (the config of the folded index) unless --dry-run is given")
     if getattr(a, "sharded", False):
@@ -284,6 +320,10 @@ def main(argv=None):
             print(fold_dry_run_text(BIGSI(config), a.factor, a.format))
         else:
             print(fold_text(config, a.config, a.to_config, a.factor, a.in_place, not a.no_trim))
+    elif a.cmd == "prevalence":
+        queries = [a.seq] if a.fasta is None else [s for _, s in read_fasta(a.fasta)]
+        names = extract_names(a)
+        print(prevalence_text(BIGSI(config), queries, names or None, a.format))
     elif a.cmd == "hold":
         hold(config, a.handle, a.seconds, a.until_eof)
     return 0

@@ -195,6 +195,12 @@ FOLD_SIGNATURES = {
     "bigsi_hip_trim_rows": (_i32, [_P]),
 }
 
+# every symbol include/bigsi_hip_prevalence.h declares (k-mer prevalence: per-position sample counts of a query)
+PREVALENCE_SIGNATURES = {
+    "bigsi_hip_kmer_prevalence": (_i32, [_P, C.c_char_p, _P, _u32, _u32, _P, _P, _P, _P, _P, _u64]),
+    "bigsi_hip_batch_kmer_prevalence": (_i32, [_P, _P, _P, _P, _P, _u64]),
+}
+
 _lib = None
 
 
@@ -215,7 +221,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

@@ -18,6 +18,7 @@
 #include "bigsi_cpu.h"
 #include "bigsi_cpu_compact.h"
 #include "bigsi_cpu_fold.h"
+#include "bigsi_cpu_prevalence.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -847,6 +848,62 @@ int bigsi_cpu_presence(bigsi_cpu_index *ix, const char *seq, uint64_t len, uint3
             bool present = true;
             for (uint32_t t = 0; t < ix->h && present; t++) present = (ix->fetch(r[t], ix->rb(), tmp, page)[c >> 3] & (0x80u >> (c & 7))) != 0;
             out[(uint64_t)j * n + i] = present ? '1' : '0';
+        }
+    }
+    return bdb_read_failed(ix);
+}
+
+// per k-mer position the number of samples that hold the k-mer: every unique k-mer string of a sequence is swept once (the AND of
+// its h rows, byte by byte, under the universe and the subset masks, the bits behind the last column cut off) and the two numbers are
+// expanded over the positions that carry it
+int bigsi_cpu_kmer_prevalence(bigsi_cpu_index *ix, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k,
+                              const uint8_t *universe, const uint8_t *subset, uint64_t *pos_offsets, uint32_t *total, uint32_t *in_subset,
+                              uint64_t capacity)
+{
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_seqs(seqs, offsets, n_seqs, k));
+    if (!pos_offsets) return fail(BIGSI_ERR_INVALID, "pos_offsets is NULL");
+    if (!total) return fail(BIGSI_ERR_INVALID, "total is NULL");
+    if (in_subset && !subset) return fail(BIGSI_ERR_INVALID, "in_subset given without a subset mask");
+    if (subset && !in_subset) return fail(BIGSI_ERR_INVALID, "a subset mask given without in_subset");
+    pos_offsets[0] = 0;
+    for (uint32_t i = 0; i < n_seqs; i++) {
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        pos_offsets[i + 1] = pos_offsets[i] + (len >= k ? len - k + 1 : 0);
+    }
+    if (capacity < pos_offsets[n_seqs])
+        return fail(BIGSI_ERR_CAPACITY, "prevalence buffers hold %llu entries, %llu needed", (unsigned long long)capacity, (unsigned long long)pos_offsets[n_seqs]);
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    const uint64_t rb = ix->rb();
+    const uint8_t last = (ix->n_cols & 7) ? (uint8_t)(0xFF00u >> (ix->n_cols & 7)) : (uint8_t)0xFF;
+    QueryKmers q;
+    std::string canon;
+    std::vector<uint64_t> r(ix->h);
+    std::vector<uint8_t> acc(rb), tmp, page;
+    std::vector<uint32_t> n_all, n_sub;
+    for (uint32_t i = 0; i < n_seqs; i++) {
+        const char *s = seqs + offsets[i];
+        unique_kmers(s, offsets[i + 1] - offsets[i], k, q);
+        n_all.assign(q.first_pos.size(), 0);
+        n_sub.assign(q.first_pos.size(), 0);
+        for (size_t j = 0; j < q.first_pos.size(); j++) {
+            canonical(s + q.first_pos[j], k, canon);
+            rows_of(canon, ix->h, ix->m, r.data());
+            std::fill(acc.begin(), acc.end(), 0xFF);
+            for (uint32_t t = 0; t < ix->h; t++) {
+                const uint8_t *x = ix->fetch(r[t], rb, tmp, page);
+                for (uint64_t b = 0; b < rb; b++) acc[b] &= x[b];
+            }
+            acc[rb - 1] &= last;
+            for (uint64_t b = 0; b < rb; b++) {
+                const uint8_t a = universe ? (uint8_t)(acc[b] & universe[b]) : acc[b];
+                n_all[j] += (uint32_t)__builtin_popcount(a);
+                if (subset) n_sub[j] += (uint32_t)__builtin_popcount(a & subset[b]);
+            }
+        }
+        for (size_t p = 0; p < q.pos_unique.size(); p++) {
+            total[pos_offsets[i] + p] = n_all[q.pos_unique[p]];
+            if (subset) in_subset[pos_offsets[i] + p] = n_sub[q.pos_unique[p]];
         }
     }
     return bdb_read_failed(ix);

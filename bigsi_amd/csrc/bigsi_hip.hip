@@ -292,6 +292,10 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
     }
     for (auto &w : ix->stream_ws)
         if (w) { bigsi_hip_batch_destroy(w); w = nullptr; }
+    if (ix->prevalence_ws) {
+        bigsi_hip_batch_destroy(ix->prevalence_ws);
+        ix->prevalence_ws = nullptr;
+    }
     hipError_t e = hipSetDevice(ix->device);
     e = hipStreamSynchronize(ix->stream);
     if (ix->pre_stream) e = hipStreamSynchronize(ix->pre_stream);
@@ -2772,6 +2776,128 @@ extern "C" int bigsi_hip_batch_presence(bigsi_hip_batch *b, uint32_t seq, const 
     HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n_colours * n, hipMemcpyDeviceToHost, ix->stream));
     HIP_TRY(hipStreamSynchronize(ix->stream));
     return BIGSI_OK;
+}
+
+// K-mer prevalence (k_kmer_prevalence + k_kmer_prevalence_sum; launch shape: plan_kmer_prevalence): per k-mer position of a batch that
+// has run, the number of samples that hold the k-mer, under a universe mask and, with `subset`, a second count under a subset mask.
+// The batch's scratch holds, for this call only: the two device masks (universe AND valid columns; subset AND that), zero-padded to
+// whole 1 KiB segments, the slices' partial counts and the per-position results that are copied out.  Both kernels go to the index
+// stream and are timed with the presence kernels (bigsi_hip_set_profiling / bigsi_hip_stats: presence_ms).
+template <int H>
+static void prevalence_launch_as(const PrevalencePlan &p, bigsi_hip_batch *b, bool with_subset, const uint64_t *umask, const uint64_t *smask, uint32_t *partial)
+{
+    bigsi_hip_index *ix = b->ix;
+#define BIGSI_PREVALENCE(SUBSET)                                                                                                        \
+    hipLaunchKernelGGL((k_kmer_prevalence<H, SUBSET>), dim3((unsigned)p.grid), dim3(p.block), 0, ix->stream, ix->d_index, ix->stride_words, ix->wv(), \
+                       b->rows.as<uint64_t>(), b->d_pos_off.as<uint64_t>(), b->num_unique.as<uint32_t>(), b->n_seqs, b->total_pos, ix->h, umask, smask, \
+                       p.slices, p.segs_per_slice, p.segs, p.waves_per_slice, partial, p.partial_stride)
+    if (with_subset) BIGSI_PREVALENCE(true);
+    else BIGSI_PREVALENCE(false);
+#undef BIGSI_PREVALENCE
+}
+
+static int prevalence_launch(bigsi_hip_batch *b, const uint8_t *universe, const uint8_t *subset, uint32_t *total, uint32_t *in_subset)
+{
+    bigsi_hip_index *ix = b->ix;
+    if (b->total_pos == 0) return BIGSI_OK;
+    if (b->run_h != ix->h) return fail(BIGSI_ERR_STATE, "num_hashes changed since this batch ran (%u then, %u now): run it again", b->run_h, ix->h);
+    if (ix->wv() > ix->stride_words || ix->stride_words % kVec)
+        return fail(BIGSI_ERR_STATE, "internal: %llu column words do not fit the row stride %llu", (unsigned long long)ix->wv(), (unsigned long long)ix->stride_words);
+    TRY(host_counts(b));
+    uint64_t total_unique = 0;
+    for (uint32_t v : b->h_num_unique) total_unique += v;
+    const PrevalencePlan p = plan_kmer_prevalence(b->total_pos, total_unique, ix->wv(), ix->h);
+    const uint64_t sum_grid = ceil_div(b->total_pos, kBlock);
+    if (p.grid == 0 || p.grid > 0x7FFFFFFFull || sum_grid > 0x7FFFFFFFull)
+        return fail(BIGSI_ERR_INVALID, "batch too large for one prevalence launch (%llu positions)", (unsigned long long)b->total_pos);
+    // the masks in the row format: byte i < row_bytes = universe (all ones without one), the bits behind the last column cleared;
+    // everything from there to the end of the last segment zero
+    const uint64_t rb = ix->rb(), mask_bytes = (uint64_t)p.segs * 64 * kVec * 8, n_masks = subset ? 2 : 1;
+    std::vector<uint8_t> masks(n_masks * mask_bytes, 0);
+    for (uint64_t i = 0; i < rb; i++) masks[i] = universe ? universe[i] : 0xFF;
+    if (ix->n_cols & 7) masks[rb - 1] &= (uint8_t)(0xFF00u >> (ix->n_cols & 7));
+    if (subset)
+        for (uint64_t i = 0; i < rb; i++) masks[mask_bytes + i] = subset[i] & masks[i];
+    const uint64_t per = subset ? 2 : 1;
+    const size_t o_partial = round_up(n_masks * mask_bytes, 256), o_total = round_up(o_partial + p.partial_entries * per * 4, 256);
+    const size_t o_sub = round_up(o_total + b->total_pos * 4, 256), bytes = o_sub + (subset ? b->total_pos * 4 : 0);
+    TRY(b->scratch.reserve(bytes));
+    uint8_t *d = b->scratch.as<uint8_t>();
+    const uint64_t *umask = reinterpret_cast<const uint64_t *>(d), *smask = subset ? reinterpret_cast<const uint64_t *>(d + mask_bytes) : nullptr;
+    uint32_t *partial = reinterpret_cast<uint32_t *>(d + o_partial), *d_total = reinterpret_cast<uint32_t *>(d + o_total);
+    uint32_t *d_sub = subset ? reinterpret_cast<uint32_t *>(d + o_sub) : nullptr;
+    HIP_TRY(hipMemcpyAsync(d, masks.data(), masks.size(), hipMemcpyHostToDevice, ix->stream));
+    EventPair ep{};
+    TRY(bigsi_ev_begin(ix, &ep));
+    switch (ix->h) {
+    case 1: prevalence_launch_as<1>(p, b, subset != nullptr, umask, smask, partial); break;
+    case 2: prevalence_launch_as<2>(p, b, subset != nullptr, umask, smask, partial); break;
+    case 3: prevalence_launch_as<3>(p, b, subset != nullptr, umask, smask, partial); break;
+    case 4: prevalence_launch_as<4>(p, b, subset != nullptr, umask, smask, partial); break;
+    case 5: prevalence_launch_as<5>(p, b, subset != nullptr, umask, smask, partial); break;
+    case 6: prevalence_launch_as<6>(p, b, subset != nullptr, umask, smask, partial); break;
+    case 7: prevalence_launch_as<7>(p, b, subset != nullptr, umask, smask, partial); break;
+    default: prevalence_launch_as<0>(p, b, subset != nullptr, umask, smask, partial); break;
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_kmer_prevalence_sum, dim3((unsigned)sum_grid), dim3(kBlock), 0, ix->stream, partial, p.partial_stride, p.slices,
+                       b->d_pos_off.as<uint64_t>(), b->n_seqs, b->pos_unique.as<uint32_t>(), b->total_pos, d_total, d_sub);
+    HIP_TRY(hipGetLastError());
+    TRY(bigsi_ev_end(ix, &ep, ix->ev_pr, nullptr, 2));
+    HIP_TRY(hipMemcpyAsync(total, d_total, b->total_pos * 4, hipMemcpyDeviceToHost, ix->stream));
+    if (subset) HIP_TRY(hipMemcpyAsync(in_subset, d_sub, b->total_pos * 4, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));          // (`masks` is read by its copy until here)
+    return BIGSI_OK;
+}
+
+static int check_prevalence_args(const uint8_t *subset, const uint32_t *total, const uint32_t *in_subset)
+{
+    if (!total) return fail(BIGSI_ERR_INVALID, "total is NULL");
+    if (in_subset && !subset) return fail(BIGSI_ERR_INVALID, "in_subset given without a subset mask");
+    if (subset && !in_subset) return fail(BIGSI_ERR_INVALID, "a subset mask given without in_subset");
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_batch_kmer_prevalence(bigsi_hip_batch *b, const uint8_t *universe, const uint8_t *subset, uint32_t *total,
+                                               uint32_t *in_subset, uint64_t capacity)
+{
+    BIGSI_ENTER(b ? b->ix : nullptr);
+    TRY(need_run(b));
+    TRY(check_prevalence_args(subset, total, in_subset));
+    if (b->elements) return fail(BIGSI_ERR_STATE, "k-mer prevalence is not available for a batch of explicit k-mers");
+    if (capacity < b->total_pos)
+        return fail(BIGSI_ERR_CAPACITY, "prevalence buffers hold %llu entries, %llu needed", (unsigned long long)capacity, (unsigned long long)b->total_pos);
+    return prevalence_launch(b, universe, subset, total, in_subset);
+}
+
+// The sequences are staged into a workspace of the index and run as an exact search: the exact row-AND is the cheapest run that leaves
+// K1's arrays behind on every K1 route, and bigsi_batch_run stays as it is (a K1-only run is the follow-up: DESIGN.md).
+extern "C" int bigsi_hip_kmer_prevalence(bigsi_hip_index *ix, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k,
+                                         const uint8_t *universe, const uint8_t *subset, uint64_t *pos_offsets, uint32_t *total,
+                                         uint32_t *in_subset, uint64_t capacity)
+{
+    BIGSI_ENTER(ix);
+    TRY(check_batch_args(ix, seqs, offsets, n_seqs, k));
+    if (!pos_offsets) return fail(BIGSI_ERR_INVALID, "pos_offsets is NULL");
+    TRY(check_prevalence_args(subset, total, in_subset));
+    pos_offsets[0] = 0;
+    for (uint32_t i = 0; i < n_seqs; i++) {
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        pos_offsets[i + 1] = pos_offsets[i] + (len >= k ? len - k + 1 : 0);
+    }
+    if (capacity < pos_offsets[n_seqs])
+        return fail(BIGSI_ERR_CAPACITY, "prevalence buffers hold %llu entries, %llu needed", (unsigned long long)capacity, (unsigned long long)pos_offsets[n_seqs]);
+    // (the workspace is never a one-call batch: its run uploads the staging and records its event, so K1 leaves the device copy of pos_off)
+    TRY(bigsi_batch_stage(ix, &ix->prevalence_ws, seqs, offsets, n_seqs, k));
+    bigsi_hip_batch *b = ix->prevalence_ws;
+    int rc = bigsi_batch_run(b, 1.0, 0, false);
+    if (rc == BIGSI_OK) rc = need_run(b);
+    if (rc == BIGSI_OK) rc = prevalence_launch(b, universe, subset, total, in_subset);
+    if (rc != BIGSI_OK) {
+        ix->prevalence_ws = nullptr;
+        bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
+    }
+    return rc;
 }
 
 // K5 at scale: the presence strings of all hits of the batch (see k_presence_bits).  The host sorts each sequence's hits by

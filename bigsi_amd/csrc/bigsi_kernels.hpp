@@ -2836,6 +2836,173 @@ __global__ __launch_bounds__(kBlock) void k_fold_rows(
     }
 }
 
+// ------------------------------------------------------------------------------ k-mer prevalence: per-k-mer sample counts
+// For every unique k-mer of a batch, how many samples hold it: the popcount of the AND of its h rows over the whole width, under a
+// mask -- the horizontal twin of k_col_popcount.  K1 of any route has left rows[slot * h .. +h), pos_off and num_unique behind; slot t
+// of the batch's positions [0, total_pos) is a unique k-mer of its sequence q iff t - pos_off[q] < num_unique[q], and the other slots
+// cost the search for q and that test.  Decomposition (plan_kmer_prevalence, bigsi_launch.hpp): wavefront w owns slice w % slices --
+// the 1 KiB column segments [slice * segs_per_slice, +segs_per_slice) cut off at `segs` -- and the slots w / slices,
+// + waves_per_slice, ...; a lane owns kVec words of a segment.  Everything that names a slot is wave-uniform (the wavefront's number
+// goes through readfirstlane): the search of pos_off and the row ids are scalar loads, the row addresses scalar arithmetic, 64 bits
+// wide (row x stride_words passes 2^32 on a 10 M-row index).
+//   H > 0: h == H < kPrevLoads.  A step takes S = ceil(kPrevLoads / H) segments: S x H independent streamed 16-byte loads (8 to 14)
+//          are in flight before the first AND.
+//   H == 0: any h (the launcher sends h >= kPrevLoads here).  One segment at a time, its rows in groups of kPrevLoads independent
+//          loads ANDed into a running value, the last group predicated (wave-uniform) on the rows that exist.
+// A slice's whole steps run without a predicate; what is left of it is ONE more step in which a lane loads only the words below
+// `wlim` = the end of the slice or of the words that carry columns (wv), whichever comes first: words from wv to the stride are not
+// loaded, and a load of the word pair that holds word wv - 1 stays inside the row (the stride is a multiple of kVec words).
+// `umask` is universe AND valid columns, `smask` subset AND umask, both built by the host in the row format (popcount is invariant
+// under the format's bit permutation: no by_column anywhere), zero from the last column to segs x 128 words: the bits behind
+// num_cols, which bigsi_hip_set_rows can put into the matrix, are never counted, and a mask load never leaves the buffer.  They are
+// read by every wavefront and stay in L2 (plain loads).
+// A lane counts into 32-bit accumulators (at most 128 x segs <= 2^26 per k-mer); at the end of the slice one wave reduction on the DPP
+// path of the block scans, and the last lane stores the slice's partial -- one uint32, or {total, in_subset} as one 8-byte store --
+// into partial[slice][slot].  Nobody else writes that entry and nobody reads an entry that was not written (k_kmer_prevalence_sum
+// reads unique slots only): no atomics, no zeroed array, no LDS, no scratch, and no workgroup waits for another.
+// Bounds: slot t < total_pos, so rows[t * h + j] is inside K1's array of total_pos x h ids, each < num_rows; a loaded word pair
+// starts below wv <= stride_words.
+__device__ __forceinline__ uint32_t wave_sum_last_lane(uint32_t v)      // lane 63 returns the sum over the wavefront
+{
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);      // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);      // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);      // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);      // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);      // row_bcast:15 into rows 1 and 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
+// the sequence that owns position p: the largest q with pos_off[q] <= p (p < pos_off[n_seqs]; sequences without positions own none)
+__device__ __forceinline__ uint32_t prevalence_owner(const uint64_t *__restrict__ pos_off, uint32_t n_seqs, uint64_t p)
+{
+    uint32_t lo = 0, hi = n_seqs;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (pos_off[mid] <= p) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <int H, bool SUBSET>
+__global__ __launch_bounds__(kBlock) void k_kmer_prevalence(
+    const uint64_t *__restrict__ index, uint64_t stride_words, uint64_t wv, const uint64_t *__restrict__ rows,
+    const uint64_t *__restrict__ pos_off, const uint32_t *__restrict__ num_unique, uint32_t n_seqs, uint64_t total_pos, uint32_t h,
+    const uint64_t *__restrict__ umask, const uint64_t *__restrict__ smask, uint32_t slices, uint32_t segs_per_slice, uint32_t segs,
+    uint64_t waves_per_slice, uint32_t *__restrict__ partial, uint64_t partial_stride)
+{
+    constexpr int L = kPrevLoads, G = H > 0 ? H : L, S = H > 0 ? (L + H - 1) / H : 1;
+    constexpr uint64_t SEG = 64 * kVec;          // words of a segment
+    static_assert(H >= 0 && H < L && S * G <= kPrevMaxLoads, "plan_kmer_prevalence's invariant: at most kPrevMaxLoads loads per lane and step");
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wave >= waves_per_slice * slices) return;
+    const uint32_t slice = (uint32_t)(wave % slices);
+    const uint64_t s0 = (uint64_t)slice * segs_per_slice;
+    const uint64_t s1 = s0 + segs_per_slice < segs ? s0 + segs_per_slice : segs;
+    const uint64_t wlim = s1 * SEG < wv ? s1 * SEG : wv;
+
+    for (uint64_t t = wave / slices; t < total_pos; t += waves_per_slice) {
+        const uint32_t q = prevalence_owner(pos_off, n_seqs, t);
+        if (t - pos_off[q] >= num_unique[q]) continue;          // a duplicate's slot: K1 left no rows here
+        const uint64_t *__restrict__ rp = rows + t * h;
+        uint64_t rid[G];
+        if (H > 0) {
+#pragma unroll
+            for (int j = 0; j < G; j++) rid[j] = rp[j];
+        }
+        uint32_t tot = 0, sub = 0;
+        auto count = [&](u64x2 a, uint64_t w) {
+            const u64x2 u = *reinterpret_cast<const u64x2 *>(umask + w);
+            tot += (uint32_t)__popcll(a.x & u.x) + (uint32_t)__popcll(a.y & u.y);
+            if (SUBSET) {
+                const u64x2 s = *reinterpret_cast<const u64x2 *>(smask + w);
+                sub += (uint32_t)__popcll(a.x & s.x) + (uint32_t)__popcll(a.y & s.y);
+            }
+        };
+        // the AND of all h rows at the lane's words [w, w + kVec) (H == 0: in groups of L loads)
+        auto and_rows = [&](uint64_t w) {
+            u64x2 a{~0ull, ~0ull};
+            for (uint32_t g = 0; g < h; g += L) {
+                u64x2 v[L];
+#pragma unroll
+                for (int j = 0; j < L; j++) v[j] = g + j < h ? load_row_seg(index, rp[g + j], stride_words, (uint32_t)w) : u64x2{~0ull, ~0ull};
+#pragma unroll
+                for (int j = 0; j < L; j++) a &= v[j];
+            }
+            return a;
+        };
+        uint64_t wb = s0 * SEG;          // first word of the step's first segment
+        if (H > 0) {
+            for (; wb + S * SEG <= wlim; wb += S * SEG) {
+                u64x2 v[S][G];
+#pragma unroll
+                for (int i = 0; i < S; i++)
+#pragma unroll
+                    for (int j = 0; j < G; j++) v[i][j] = load_row_seg(index, rid[j], stride_words, (uint32_t)(wb + i * SEG + lane * kVec));
+#pragma unroll
+                for (int i = 0; i < S; i++) {
+                    u64x2 a = v[i][0];
+#pragma unroll
+                    for (int j = 1; j < G; j++) a &= v[i][j];
+                    count(a, wb + i * SEG + lane * kVec);
+                }
+            }
+            if (wb < wlim) {          // (wave-uniform) the rest of the slice: fewer than S segments, the last one maybe part of one
+                u64x2 v[S][G];
+#pragma unroll
+                for (int i = 0; i < S; i++) {
+                    const uint64_t w = wb + i * SEG + lane * kVec;
+#pragma unroll
+                    for (int j = 0; j < G; j++) v[i][j] = w < wlim ? load_row_seg(index, rid[j], stride_words, (uint32_t)w) : u64x2{0ull, 0ull};
+                }
+#pragma unroll
+                for (int i = 0; i < S; i++) {
+                    const uint64_t w = wb + i * SEG + lane * kVec;
+                    u64x2 a = v[i][0];
+#pragma unroll
+                    for (int j = 1; j < G; j++) a &= v[i][j];
+                    if (w < wlim) count(a, w);
+                }
+            }
+        } else {
+            for (; wb + SEG <= wlim; wb += SEG) count(and_rows(wb + lane * kVec), wb + lane * kVec);
+            if (wb + lane * kVec < wlim) count(and_rows(wb + lane * kVec), wb + lane * kVec);
+        }
+        tot = wave_sum_last_lane(tot);
+        if (SUBSET) sub = wave_sum_last_lane(sub);
+        if (lane == 63) {
+            const uint64_t e = (uint64_t)slice * partial_stride + t;
+            if (SUBSET) *reinterpret_cast<uint2 *>(partial + 2 * e) = uint2{tot, sub};
+            else partial[e] = tot;
+        }
+    }
+}
+
+// A thread per POSITION p of the batch: out[p] = the sum over the slices of the partials of the position's unique k-mer, slot
+// pos_off[q] + pos_unique[p] -- where duplicates are expanded, as the presence strings expand them.  `out_sub` non-null: the partials
+// are {total, in_subset} pairs.
+__global__ __launch_bounds__(kBlock) void k_kmer_prevalence_sum(
+    const uint32_t *__restrict__ partial, uint64_t partial_stride, uint32_t slices, const uint64_t *__restrict__ pos_off, uint32_t n_seqs,
+    const uint32_t *__restrict__ pos_unique, uint64_t total_pos, uint32_t *__restrict__ out_total, uint32_t *__restrict__ out_sub)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= total_pos) return;
+    const uint64_t slot = pos_off[prevalence_owner(pos_off, n_seqs, p)] + pos_unique[p];
+    uint32_t tot = 0, sub = 0;
+    for (uint32_t s = 0; s < slices; s++) {
+        const uint64_t e = (uint64_t)s * partial_stride + slot;
+        if (out_sub) {
+            const uint2 v = *reinterpret_cast<const uint2 *>(partial + 2 * e);
+            tot += v.x;
+            sub += v.y;
+        } else tot += partial[e];
+    }
+    out_total[p] = tot;
+    if (out_sub) out_sub[p] = sub;
+}
+
 // transpose (bigsi/matrix/transpose.py:33-43) on the device: n Bloom filters (bloom c at blooms + c*bloom_stride, m bits,
 // row byte format) become columns [col0, col0+n) of the matrix.  One thread per (row, 64-column word); the 8 threads of
 // 8 consecutive rows read the same Bloom byte (one L1 line per wave), the word is read-modified-written once.

@@ -1,10 +1,11 @@
 // bigsi_launch.hpp -- the launch rule of a batch run, host-only: how K1 goes out (k1_plan) and how the row-AND kernels
 // (k_and_exact, k_and_count, k_count_combine) are launched for a batch of queries (plan_row_and), the sweep of the column popcounts
-// (plan_col_popcount), the per-call tables of the column compaction (plan_compact_columns) and the sweep of the row folding
-// (plan_fold_rows).  Pure functions of a handful of integers (and, for the compaction, of the keep bitmap): no HIP, no batch, no
-// index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp, compact_host.cpp and fold_host.cpp compile this header as
-// plain host C++ and tests/test_abi_and_host.py, test_sample_stats_host.py, test_compact_columns_host.py and test_fold_rows_host.py
-// pin the decisions on the CPU.
+// (plan_col_popcount), the per-call tables of the column compaction (plan_compact_columns), the sweep of the row folding
+// (plan_fold_rows) and the sweep of the k-mer prevalence (plan_kmer_prevalence).  Pure functions of a handful of integers (and, for
+// the compaction, of the keep bitmap): no HIP, no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp,
+// compact_host.cpp, fold_host.cpp and prevalence_host.cpp compile this header as plain host C++ and tests/test_abi_and_host.py,
+// test_sample_stats_host.py, test_compact_columns_host.py, test_fold_rows_host.py and test_kmer_prevalence_host.py pin the decisions
+// on the CPU.
 //
 // Every constant below was measured on an MI355X; the notes beside them say against what.  A GPU test compares results, and a slip
 // here keeps results right and costs the 3 to 20 % those notes record: change a constant only with a new measurement, and the pinned
@@ -446,6 +447,64 @@ static inline FoldPlan plan_fold_rows(uint64_t m_dst, uint64_t factor, uint64_t 
     p.rows_per_block = round_up(std::max<uint64_t>(ceil_div(m_dst, want_blocks), kFoldMinRows), p.rows_per_step);
     p.row_blocks = std::max<uint64_t>(ceil_div(m_dst, p.rows_per_block), 1);
     p.grid = p.seg_groups * p.row_blocks;
+    return p;
+}
+
+// ------------------------------------------------------------------------------ k-mer prevalence (k_kmer_prevalence)
+// For every unique k-mer of a batch the popcount of the AND of its h rows over the whole width (under a mask): the horizontal twin of
+// the column popcounts.  A work item is (slot, slice): a slot is a k-mer position of the batch (slot t of sequence q is a unique
+// k-mer iff t - pos_off[q] < num_unique[q]; the others cost their test), a slice a run of segs_per_slice 1 KiB column segments.  A
+// wavefront owns one slice and strides over the slots; a lane owns kVec words of a segment.
+//   - Slices: one per k-mer once the batch has kPrevWaves unique k-mers; fewer k-mers are cut into enough slices to reach that many
+//     items, never more than there are segments (one 1 kbp query on 13 segments: 5 slices).  No slice is empty:
+//     slices = ceil(segs / segs_per_slice), the last one is ragged.  A one-segment index has one slice.
+//   - Wavefronts: about kPrevWaves.  The figure is INHERITED from the column popcounts' sweep (kColPopWaves, measured there), not
+//     measured for this kernel.  A batch whose slots are at most twice the wavefronts of a slice gets one wavefront per slot (at most
+//     2 x kPrevWaves in all: striding would leave half of them a second slot while the others are done).
+//   - Loads in flight: a step takes segs_per_step segments x the k-mer's rows for h < kPrevLoads (ceil(kPrevLoads / h) segments: 8 to
+//     14 independent 16-byte loads per lane), for h >= kPrevLoads one segment and its rows in groups of kPrevLoads ANDed into a running
+//     value.  INVARIANT (the kernel's register budget, the fold planner's): at most kPrevMaxLoads = 16 loads of 4 VGPRs each per lane
+//     and step; the kernel's arrays are sized by it and tests/test_kmer_prevalence_host.py checks it for every plan.
+//   - Workgroups: as many wavefronts as the index has segments, at most kBlock / 64 (narrow indexes: as plan_col_popcount).  The
+//     wavefronts of a workgroup are consecutive slices of the same slot, then the next slot.  grid <= 2 x kPrevWaves.
+//   - The partial array: partial[slice][slot], slices x partial_stride entries (of one uint32, or two with a subset).
+constexpr int kPrevLoads = 8;
+constexpr int kPrevMaxLoads = 16;
+constexpr uint64_t kPrevWaves = kColPopWaves;
+struct PrevalencePlan {
+    uint32_t block = 64;             // threads per workgroup
+    uint32_t segs = 1;               // 1 KiB column segments that carry columns (at least 1)
+    uint32_t slices = 1;             // per k-mer
+    uint32_t segs_per_slice = 1;
+    uint64_t waves_per_slice = 0;    // wavefronts that stride over the slots of one slice
+    uint64_t waves = 0;              // slices x waves_per_slice
+    uint64_t grid = 0;               // workgroups (0: nothing to sweep)
+    uint32_t segs_per_step = 1;      // segments a lane takes at once
+    uint32_t loads_per_step = 1;     // independent 16-byte loads a lane has in flight in a step
+    uint64_t partial_stride = 0;     // entries per slice: one per slot
+    uint64_t partial_entries = 0;    // slices x partial_stride
+};
+static inline uint32_t prevalence_segs_per_step(uint32_t h)
+{
+    return h >= (uint32_t)kPrevLoads ? 1u : (uint32_t)ceil_div(kPrevLoads, std::max<uint32_t>(h, 1));
+}
+// `wv`: 64-column words that carry columns; `total_pos` slots, `total_unique` of them unique k-mers
+static inline PrevalencePlan plan_kmer_prevalence(uint64_t total_pos, uint64_t total_unique, uint64_t wv, uint32_t h)
+{
+    PrevalencePlan p;
+    p.segs = (uint32_t)std::max<uint64_t>(ceil_div(wv, 64 * kVec), 1);
+    p.block = (uint32_t)std::min<uint64_t>(p.segs, kBlock / 64) * 64;
+    const uint64_t want_slices = std::min<uint64_t>(ceil_div(kPrevWaves, std::max<uint64_t>(total_unique, 1)), p.segs);
+    p.segs_per_slice = (uint32_t)ceil_div(p.segs, want_slices);
+    p.slices = (uint32_t)ceil_div(p.segs, p.segs_per_slice);
+    p.waves_per_slice = std::min<uint64_t>(total_pos, std::max<uint64_t>(kPrevWaves / p.slices, 1));
+    if (total_pos <= 2 * p.waves_per_slice) p.waves_per_slice = total_pos;
+    p.waves = p.waves_per_slice * p.slices;
+    p.grid = ceil_div(p.waves, p.block / 64);
+    p.segs_per_step = prevalence_segs_per_step(h);
+    p.loads_per_step = std::min<uint32_t>(std::max<uint32_t>(h, 1), kPrevLoads) * std::min<uint32_t>(p.segs_per_step, p.segs_per_slice);
+    p.partial_stride = total_pos;
+    p.partial_entries = p.slices * p.partial_stride;
     return p;
 }
 

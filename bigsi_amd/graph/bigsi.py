@@ -377,6 +377,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
 
     def _metadata_changed(self):
         self.__dict__.pop("_excluded", None)
+        self.__dict__.pop("_names", None)
 
     def _excluded_colours(self):
         """Colours of deleted samples (named DELETION_SPECIAL_SAMPLE_NAME), which a limited search takes out before it ranks: the
@@ -709,6 +710,46 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         bits = np.unpackbits(np.frombuffer(bytes(mask), dtype=np.uint8) if not isinstance(mask, np.ndarray) else mask)[:m]
         n = min(len(counts), self.num_samples)
         return derive_similar(counts, int(bits.sum()), masked, self._sample_names(n), leave_out, limit)
+
+    # ------------------------------------------------------------------ k-mer prevalence
+    def kmer_prevalence_many(self, seqs, samples=None):
+        """For every k-mer position of every sequence, how many samples hold the k-mer -- the transposed question of a search --
+        and, with samples=[names], how many of THOSE samples: one dict per sequence,
+            {"num_kmers": n, "num_unique": u (distinct window strings, counted on the host), "num_samples": |universe|, "subset_size": |subset| or None,
+             "samples_with_kmer": [n ints], "subset_with_kmer": [n ints] or None}
+        The universe is every sample that is not deleted.  ONE device call for all sequences (bigsi_hip_kmer_prevalence: a k-mer is
+        swept once, its rows never leave the device); masks and records are bigsi_amd/prevalence.py's.  A sequence shorter than k
+        gives num_kmers 0 and empty lists.  ValueError for a name that is unknown or deleted and for sequences with non-ASCII
+        characters; multi-GPU (devices=[...]) indexes are refused."""
+        from ..prevalence import assemble, subset_mask, universe_mask
+        if isinstance(seqs, (str, bytes)):
+            raise TypeError("seqs must be a list of sequences, got %r" % type(seqs))
+        seqs = list(seqs)
+        if self.storage.res.is_group:
+            from .._lib import ERR_STATE, BigsiHipError
+            raise BigsiHipError(ERR_STATE, "k-mer prevalence is not available for multi-GPU (devices=[...]) indexes")
+        for s in seqs:
+            if not s.isascii():
+                raise ValueError("k-mer prevalence takes ASCII sequences (queries with other characters are out of scope)")
+        k = int(self.kmer_size)
+        with self._device_lock():
+            # masks as wide as the MATRIX (it may hold columns the metadata has no record of: they are in no universe)
+            n_cols = int(self.storage.get_integer("number_of_cols"))
+            names = self.__dict__.get("_names")          # one pass over the colours, kept until the metadata changes through this object
+            if names is None or len(names) != self.num_samples:
+                names = self.__dict__["_names"] = self._sample_names(self.num_samples)
+            universe, n_universe = universe_mask(n_cols, names)
+            subset = n_subset = None
+            if samples is not None:
+                subset, n_subset = subset_mask(n_cols, names, samples)
+            if not seqs:
+                return []
+            pos, total, in_subset = self.storage.kmer_prevalence(seqs, k, universe, subset)
+        return assemble(seqs, k, pos, total, in_subset, n_universe, n_subset)
+
+    def kmer_prevalence(self, seq, samples=None):
+        """kmer_prevalence_many for one sequence: its dict."""
+        return self.kmer_prevalence_many([seq], samples)[0]
 
     # ------------------------------------------------------------------ column compaction: vacuum / extract
     def _colour_names(self):

@@ -561,6 +561,41 @@ class HipHbmStorage(BaseStorage):
         check(res.fn("column_popcounts")(res.ix, None if buf is None else _lib.ptr(buf), _lib.ptr(out), n))
         return out
 
+    def kmer_prevalence(self, seqs, k, universe=None, subset=None):
+        """For every k-mer position of every sequence, the number of samples that hold the k-mer (bigsi_hip_kmer_prevalence: ONE
+        device call; a k-mer is swept once and only its popcount leaves the device).  universe / subset: masks in the row format
+        (ceil(num_cols / 8) bytes as uint8 arrays or bytes; bits at columns >= num_cols are ignored).  Returns (pos_offsets
+        np.uint64[n + 1], total np.uint32[positions], in_subset np.uint32[positions] or None): total counts the samples of the
+        universe (all without one), in_subset those that are also in the subset."""
+        res = self.res
+        if res.is_group:
+            raise BigsiHipError(_lib.ERR_STATE, "k-mer prevalence is not available for multi-GPU (devices=[...]) indexes")
+        if not res.ensure_open():
+            raise KeyError("number_of_rows:int")
+        seqs = list(seqs)
+        if not seqs:
+            return np.zeros(1, np.uint64), np.zeros(0, np.uint32), None
+        nb = (int(res.info().num_cols) + 7) // 8
+
+        def mask_bytes(mask, what):
+            if mask is None:
+                return None
+            buf = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1) if isinstance(mask, np.ndarray) else np.frombuffer(bytes(mask), dtype=np.uint8)
+            if buf.size < nb:
+                raise ValueError("the %s mask has %d bytes, an index of %d columns takes %d" % (what, buf.size, int(res.info().num_cols), nb))
+            return buf
+        uni, sub = mask_bytes(universe, "universe"), mask_bytes(subset, "subset")
+        blob, off = _lib.pack_seqs(seqs)
+        k = int(k)
+        pos = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        cap = sum(max(len(s) - k + 1, 0) for s in seqs)
+        total = np.zeros(max(cap, 1), dtype=np.uint32)
+        in_sub = None if sub is None else np.zeros(max(cap, 1), dtype=np.uint32)
+        check(_lib.lib().bigsi_hip_kmer_prevalence(self.handle, blob, _lib.ptr(off), len(seqs), k, None if uni is None else _lib.ptr(uni),
+                                                   None if sub is None else _lib.ptr(sub), _lib.ptr(pos), _lib.ptr(total),
+                                                   None if in_sub is None else _lib.ptr(in_sub), cap))
+        return pos, total[:cap], None if in_sub is None else in_sub[:cap]
+
     def fill_synthetic(self, seed, shard=0, and_draws=2):
         if self.res.is_group:       # shard i of the group is filled as (seed, shard i)
             check(_lib.lib().bigsi_hip_group_fill_synthetic(self.res.ix, int(seed), int(and_draws)))

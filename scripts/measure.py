@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -481,6 +481,89 @@ def fold():
                       "of the new matrix's size timed alone through the same runtime; call_less_alloc_ms is NOT a kernel time (a difference of two "
                       "terms of seconds); k_restride's copy time: the kernel trace of this command (rocprofv3 --kernel-trace --stats)",
                  **common)
+        st.delete_all()
+
+
+def prevalence():
+    """K-mer prevalence (bigsi_hip_kmer_prevalence): one 1 kbp query and 8192 x 1 kbp on the C3 index, 256 x 1 kbp on a C4 shard.
+    Per workload: the sweep's algorithmic bytes (unique k-mers x h x ceil(N / 64) x 8), the sweep by the library's HIP events on the
+    index stream (k_kmer_prevalence + k_kmer_prevalence_sum: presence_ms of bigsi_hip_stats), the exact run in front of it (K1 +
+    row-AND + K4), the whole call by the wall clock, and the box's bare random-row and sorted-row streams of the same run
+    (bigsi_hip_probe_rows).  The yardstick is the RANDOM-row rate: a k-mer's h rows meet in one lane, so the list cannot be
+    address-ordered.  On the first shape, 64 k-mers -- three of them with a row next to the one whose word offset passes 2^32 -- are
+    checked against the popcounts of bigsi_hip_lookup's rows.  BIGSI_PREVALENCE_SHAPES="MxNxHxQ,..." replaces the workloads."""
+    L, C = _lib.lib(), _lib.C
+    work = ((10_000_000, 100_000, 4, (1, 8192)), (25_000_000, 62_500, 3, (256,)))
+    if os.environ.get("BIGSI_PREVALENCE_SHAPES"):
+        work = tuple((int(a), int(b), int(c), (int(d),)) for a, b, c, d in (sh.split("x") for sh in os.environ["BIGSI_PREVALENCE_SHAPES"].split(",")))
+    first = True
+    for m, n, h, sizes in work:
+        st, fill = open_index("prevalence", m, n, h)
+        wv = -(-n // 64)
+        box = {}
+        for name, srt in (("box_random_GBps", 0), ("box_sorted_GBps", 1)):
+            g_, m_ = C.c_double(0), C.c_double(0)
+            check(L.bigsi_hip_probe_rows(st.handle, 3880, 1, srt, 0, 3, C.byref(g_), C.byref(m_)))
+            box[name] = g_.value
+        rng = np.random.default_rng(11)
+        for q in sizes:
+            seqs = rand_seqs(rng, q, 1000)
+            unique = sum(len({s[i:i + 31] for i in range(970)}) for s in seqs)
+            ab = unique * h * wv * 8
+            reps = 3 if ab < 50e9 else 1
+            if reps > 1:
+                st.kmer_prevalence(seqs, 31)            # warm (a single pass of hundreds of GB is its own steady state)
+            check(L.bigsi_hip_set_profiling(st.handle, 1))
+            stats(st)
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                pos, total, _ = st.kmer_prevalence(seqs, 31)
+            call = (time.perf_counter() - t0) / reps * 1e3
+            s_ = stats(st)
+            check(L.bigsi_hip_set_profiling(st.handle, 0))
+            sweep = s_.presence_ms / reps
+            emit("kmer_prevalence", m=m, cols=n, h=h, n_seqs=q, unique_kmers=unique, alg_bytes=ab, sweep_ms=sweep, sweep_GBps=ab / sweep / 1e6,
+                 sweep_over_box_random=ab / sweep / 1e6 / box["box_random_GBps"], exact_run_ms=(s_.and_ms + s_.kmerize_ms + s_.compact_ms) / reps,
+                 call_ms=call, total_sum=int(total.sum(dtype=np.uint64)), total_max=int(total.max()),
+                 note="fill %.2f s; mean of %d call(s); sweep = both kernels by HIP events, exact run = K1 + row-AND + K4 by HIP events" % (fill, reps), **box)
+        if first:
+            first = False
+            # k-mers with a row id next to the row where row x stride_words passes 2^32 words: K1 on a narrow index of the same m finds them
+            stride_words = int(st.res.info().row_stride_bytes) // 8
+            edge = (1 << 32) // stride_words
+            hits = {}          # row id -> the text of a k-mer that has it
+            if edge + 1 < m:
+                small, _ = open_index("prevalence_ids", m, 64, h)
+                for _ in range(16):
+                    long_seqs = rand_seqs(rng, 4096, 1000)
+                    b = small.new_batch(long_seqs, 31)
+                    b.run(1.0)
+                    _, nu, _ = b.unique()
+                    for i, s in enumerate(long_seqs):
+                        rows = b.rows(i, nu[i])
+                        for r in (edge - 1, edge, edge + 1):
+                            j = np.flatnonzero((rows == r).any(axis=1))
+                            if len(j) and r not in hits:
+                                seen, order = set(), []          # unique k-mer j[0] of the sequence, in first-occurrence order
+                                for p in range(len(s) - 30):
+                                    if s[p:p + 31] not in seen:
+                                        seen.add(s[p:p + 31])
+                                        order.append(p)
+                                hits[r] = s[order[int(j[0])]:order[int(j[0])] + 31]
+                    b.close()
+                    if len(hits) == 3:
+                        break
+                small.delete_all()
+            kmers = list(hits.values()) + rand_seqs(rng, 64 - len(hits), 31)
+            pos, total, _ = st.kmer_prevalence(kmers, 31)
+            rb = (n + 7) // 8
+            out = np.zeros((len(kmers), rb), np.uint8)
+            check(L.bigsi_hip_lookup(st.handle, "".join(kmers).encode(), 31, len(kmers), _lib.ptr(out)))
+            if n % 8:
+                out[:, -1] &= (0xFF00 >> (n % 8)) & 0xFF
+            want = np.unpackbits(out, axis=1).sum(axis=1, dtype=np.uint64)
+            emit("kmer_prevalence_vs_lookup", m=m, cols=n, kmers=len(kmers), edge_row=edge, edge_rows_found=sorted(int(r) for r in hits),
+                 equal=bool(np.array_equal(want, total.astype(np.uint64))), total_min=int(total.min()), total_max=int(total.max()))
         st.delete_all()
 
 

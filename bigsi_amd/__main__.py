@@ -125,7 +125,12 @@ def build_parser():
     sp.add_argument("--samples", "-s", action="append", default=[], metavar="NAME", help="also count among these samples only")
     sp.add_argument("--samples-file", default=None, metavar="FILE", help="one sample name per line")
     sp.add_argument("--format", choices=["json", "csv"], default="json")
-    for name in ("vacuum", "extract", "fold", "prevalence"):          # (named so that the refusal says why)
+    sp = common(sub.add_parser("collapse", help="a new index, described by TO_CONFIG, in which every group of samples of this one is one column: "
+                                                "the OR of its members (the small index that is searched first)"))
+    sp.add_argument("to_config")
+    sp.add_argument("--groups", required=True, metavar="FILE", help="sample<TAB>group lines; a group's colour follows its first appearance")
+    sp.add_argument("--keep-others", action="store_true", help="samples the file does not name stay, each as a group of its own, after the named groups")
+    for name in ("vacuum", "extract", "fold", "prevalence", "collapse"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -168,6 +173,35 @@ def extract_text(index, config_name, to_config_name, names):
     new = index.extract(get_config_from_file(to_config_name), names)
     return json.dumps({"result": "extracted %d of %d samples from %s into %s." % (new.num_samples, index.num_samples, config_name, to_config_name),
                        "num_samples": new.num_samples})
+
+
+def collapse_groups(path):
+    """The (sample, group) pairs of a `collapse --groups FILE`: one sample<TAB>group per line, blank lines skipped."""
+    pairs = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            cells = line.split("\t")
+            if len(cells) != 2 or not cells[0].strip() or not cells[1].strip():
+                raise ValueError("%s line %d: expected sample<TAB>group, got %r" % (path, no, line))
+            pairs.append((cells[0].strip(), cells[1].strip()))
+    return pairs
+
+
+def collapse_text(index, config_name, to_config_name, pairs, keep_others=False):
+    """`collapse`: BIGSI.collapse into the index TO_CONFIG describes (it syncs its own snapshot); the report names the membership."""
+    from .collapse import DROPPED, collapse_plan
+    new = index.collapse(get_config_from_file(to_config_name), pairs, keep_others=keep_others)
+    names = [index.colour_to_sample(c) for c in range(index.num_samples)]
+    group_of, group_names, members = collapse_plan(names, pairs, keep_others)
+    from .graph.metadata import DELETION_SPECIAL_SAMPLE_NAME
+    live = sum(1 for n in names if n != DELETION_SPECIAL_SAMPLE_NAME)          # (deleted samples are not counted as dropped: they were gone)
+    moved = int((group_of != DROPPED).sum())
+    return json.dumps({"result": "collapsed %d of %d samples from %s into %d groups in %s." % (moved, live, config_name, len(group_names), to_config_name),
+                       "groups": len(group_names), "samples_in": live, "samples_dropped": live - moved, "num_samples": new.num_samples,
+                       "members": dict(zip(group_names, members))})
 
 
 # k-mer positions of one device call of `prevalence --fasta` (a few bounded batches instead of one of any size: the device keeps a
@@ -252,7 +286,7 @@ def main(argv=None):
         (search_parser if a.cmd == "search" else bulk_parser).error("--limit is not available with --sharded (use a single index or storage-config devices)")
     config = get_config_from_file(a.config)
 
-    if getattr(a, "sharded", False) and a.cmd in ("vacuum", "extract"):
+    if getattr(a, "sharded", False) and a.cmd in ("vacuum", "extract", "collapse"):
         p.error("%s is not available with --sharded: column shards have a fixed width (use a single index)" % a.cmd)
     if getattr(a, "sharded", False) and a.cmd == "fold":
         p.error("fold is not available with --sharded: folding column shards is not implemented (use a single index)")
@@ -315,6 +349,8 @@ def main(argv=None):
         print(vacuum_text(BIGSI(config), not a.no_shrink))
     elif a.cmd == "extract":
         print(extract_text(BIGSI(config), a.config, a.to_config, extract_names(a)))
+    elif a.cmd == "collapse":
+        print(collapse_text(BIGSI(config), a.config, a.to_config, collapse_groups(a.groups), a.keep_others))
     elif a.cmd == "fold":
         if a.dry_run:
             print(fold_dry_run_text(BIGSI(config), a.factor, a.format))

@@ -195,6 +195,11 @@ FOLD_SIGNATURES = {
     "bigsi_hip_trim_rows": (_i32, [_P]),
 }
 
+# every symbol include/bigsi_hip_collapse.h declares (column collapse: OR the columns of a group of samples into one)
+COLLAPSE_SIGNATURES = {
+    "bigsi_hip_collapse_columns_into": (_i32, [_P, _P, _P, _u64]),
+}
+
 # every symbol include/bigsi_hip_prevalence.h declares (k-mer prevalence: per-position sample counts of a query)
 PREVALENCE_SIGNATURES = {
     "bigsi_hip_kmer_prevalence": (_i32, [_P, C.c_char_p, _P, _u32, _u32, _P, _P, _P, _P, _P, _u64]),
@@ -221,7 +226,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

@@ -16,6 +16,7 @@
 // BIGSI_CPU_WORD_PARALLEL replaces the last four by 64-bit word operations on the resident rows (same results).
 // Row format = the reference's bitarray.tobytes(): column c at byte c / 8 under mask 0x80 >> (c % 8).
 #include "bigsi_cpu.h"
+#include "bigsi_cpu_collapse.h"
 #include "bigsi_cpu_compact.h"
 #include "bigsi_cpu_fold.h"
 #include "bigsi_cpu_prevalence.h"
@@ -649,6 +650,36 @@ int bigsi_cpu_extract_columns(bigsi_cpu_index *dst, const bigsi_cpu_index *src, 
     const uint64_t rb = src->rb();
     for (uint64_t r = 0; r < src->m; r++) select_columns(dst->row(r), dst->stride, src->fetch(r, rb, tmp, page), src->n_cols, keep);
     dst->n_cols = kept;
+    return bdb_read_failed(src);
+}
+
+// Column collapse: destination column g = the OR of the source columns of group g, one row and one column at a time
+int bigsi_cpu_collapse_columns_into(bigsi_cpu_index *dst, const bigsi_cpu_index *src, const uint32_t *group_of, uint64_t num_groups)
+{
+    if (dst && dst->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    if (!dst || !src || !group_of) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (num_groups == 0 || num_groups >= 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "num_groups %llu is not in [1, 2^32 - 1)", (unsigned long long)num_groups);
+    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot collapse an index into itself (there is no in-place form)");
+    if (dst->m != src->m) return fail(BIGSI_ERR_INVALID, "row counts differ (%llu vs %llu)", (unsigned long long)dst->m, (unsigned long long)src->m);
+    if (dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
+    for (uint64_t c = 0; c < src->n_cols; c++)
+        if (group_of[c] != BIGSI_COLLAPSE_DROPPED && group_of[c] >= num_groups)
+            return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither a group id below %llu nor BIGSI_COLLAPSE_DROPPED", (unsigned long long)c, group_of[c],
+                        (unsigned long long)num_groups);
+    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    TRY(bigsi_cpu_reserve_cols(dst, num_groups));
+    std::vector<uint8_t> tmp, page;
+    const uint64_t rb = src->rb();
+    for (uint64_t r = 0; r < src->m; r++) {
+        const uint8_t *x = src->fetch(r, rb, tmp, page);
+        uint8_t *y = dst->row(r);
+        memset(y, 0, dst->stride);
+        for (uint64_t c = 0; c < src->n_cols; c++) {
+            const uint32_t g = group_of[c];
+            if (g != BIGSI_COLLAPSE_DROPPED && (x[c >> 3] & (0x80u >> (c & 7)))) y[g >> 3] |= (uint8_t)(0x80u >> (g & 7));
+        }
+    }
+    dst->n_cols = num_groups;
     return bdb_read_failed(src);
 }
 

@@ -1195,6 +1195,53 @@ extern "C" int bigsi_hip_shrink_to_fit(bigsi_hip_index *ix)
     return BIGSI_OK;
 }
 
+// Column collapse (k_collapse_columns; tables, launch shape and destination window: plan_collapse_columns).  The tables live for this
+// call only, like the compaction's: 4 bytes per source column and 8 per source word, 412 KB for 100 k columns.
+extern "C" int bigsi_hip_collapse_columns_into(bigsi_hip_index *dst, const bigsi_hip_index *src, const uint32_t *group_of, uint64_t num_groups)
+{
+    BIGSI_ENTER(dst);
+    BusyGuard src_guard(src);          // (both handles are held: the source's matrix must not move or change under the sweep)
+    if (!src_guard.ok) return fail(BIGSI_ERR_STATE, "the source index handle is in use by another host thread (one handle = one thread at a time)");
+    if (!dst || !src || !group_of) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (num_groups == 0 || num_groups >= 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "num_groups %llu is not in [1, 2^32 - 1)", (unsigned long long)num_groups);
+    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot collapse an index into itself (there is no in-place form)");
+    if (dst->m != src->m) return fail(BIGSI_ERR_INVALID, "row counts differ (%llu vs %llu)", (unsigned long long)dst->m, (unsigned long long)src->m);
+    if (dst->device != src->device) return fail(BIGSI_ERR_INVALID, "both indexes must live on the same device");
+    if (dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
+    const uint64_t bad = collapse_first_bad(src->n_cols, group_of, num_groups);
+    if (bad < src->n_cols)
+        return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither a group id below %llu nor BIGSI_COLLAPSE_DROPPED", (unsigned long long)bad, group_of[bad],
+                    (unsigned long long)num_groups);
+    TRY(bigsi_writable(dst));
+    if (dst->d_index == src->d_index) return fail(BIGSI_ERR_INVALID, "src is a view of dst (there is no in-place form)");
+    if (dst->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_collapse_columns_into: the column count of %d open view(s) of the destination would go stale", dst->views.load());
+    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_collapse_columns_into: the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    const CollapsePlan p = plan_collapse_columns(src->n_cols, group_of, num_groups, dst->m);
+    TRY(bigsi_hip_reserve_cols(dst, num_groups));
+    if (p.table_words > src->stride_words || round_up(p.dst_words, 2) > dst->stride_words || src->stride_words % kVec || dst->stride_words % kVec ||
+        p.lds_bytes > kCollapseLdsBytes || p.image_words % 2 || p.grid == 0 || p.grid > 0x7FFFFFFFull)
+        return fail(BIGSI_ERR_STATE, "internal: a collapse plan of %llu source and %llu destination words does not fit the row strides (%llu, %llu) or the LDS (%llu bytes)",
+                    (unsigned long long)p.table_words, (unsigned long long)p.dst_words, (unsigned long long)src->stride_words,
+                    (unsigned long long)dst->stride_words, (unsigned long long)p.lds_bytes);
+    TRY(use_device(dst));
+    TRY(quiesce_index(dst));
+    HIP_TRY(hipStreamSynchronize(src->stream));
+    CallScratch tab;
+    const uint64_t bit_bytes = std::max<uint64_t>(p.dst_bit.size() * 4, 16), live_bytes = std::max<uint64_t>(p.live.size() * 8, 16);
+    TRY(tab.buf.reserve(bit_bytes + live_bytes));          // (bit_bytes is a multiple of 16: live is read 16 bytes at a time)
+    if (!p.dst_bit.empty()) {
+        HIP_TRY(hipMemcpyAsync(tab.buf.p, p.dst_bit.data(), p.dst_bit.size() * 4, hipMemcpyHostToDevice, dst->stream));
+        HIP_TRY(hipMemcpyAsync(tab.buf.as<uint8_t>() + bit_bytes, p.live.data(), p.live.size() * 8, hipMemcpyHostToDevice, dst->stream));
+    }
+    hipLaunchKernelGGL(k_collapse_columns, dim3((unsigned)p.grid), dim3(p.block), (size_t)p.lds_bytes, dst->stream, src->d_index, src->stride_words, dst->d_index,
+                       dst->stride_words, dst->m, tab.buf.as<uint32_t>(), reinterpret_cast<const uint64_t *>(tab.buf.as<uint8_t>() + bit_bytes), p.table_words,
+                       p.dst_words, p.window_words, (uint32_t)p.image_words);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dst->stream));          // (the tables go out of scope)
+    dst->n_cols = num_groups;
+    return BIGSI_OK;
+}
+
 // Row folding (k_fold_rows; launch shape: plan_fold_rows).  `dst` may be `src` (in place: see the kernel); factors below kFoldLoads
 // have a kernel of their own (the factor is a compile-time constant there), every other factor runs the generic one.
 template <int D>

@@ -2,6 +2,7 @@
 // (bigsi_hip.hip: single-shard C ABI; bigsi_shard.hip: RCCL exchange, device groups, one-call search).
 #pragma once
 #include "bigsi_hip.h"
+#include "bigsi_hip_collapse.h"
 #include "bigsi_hip_compact.h"
 #include "bigsi_hip_fold.h"
 #include "bigsi_hip_group.h"

@@ -2730,6 +2730,115 @@ __global__ __launch_bounds__(kBlock) void k_compact_columns(
     }
 }
 
+// ------------------------------------------------------------------------------ column collapse: OR columns into groups
+// Destination column g of every row is the OR of the source columns c with group_of[c] == g; everything from column G to the end of the
+// destination stride is zero afterwards.  All that depends on the map alone comes from the host (plan_collapse_columns,
+// bigsi_launch.hpp), in terms of bits as they lie in memory: live[w] = the bits of source word w that have a destination, dst_bit[a] =
+// the destination bit address of source bit address a.  No by_column here: the row format's permutation is inside the tables.
+// Source-driven: a wavefront owns whole rows, one at a time, and an image of the destination row -- or of one WINDOW of it -- in LDS
+// (image_words 64-bit words at smem + wavefront-in-workgroup x image_words).  Per row and window:
+//   - each lane streams the source row with coalesced 16-byte loads, kCollapseLoads independent ones (and as many of `live`) in flight,
+//     ANDs with live, and walks the set bits that are left 32 at a time: b = ctz(x); x &= x - 1.  An all-zero word costs its load;
+//   - the dst_bit gathers have L2 latency, so they go in batches: up to kCollapseGathers bit positions are collected, that many loads
+//     are issued, then that many LDS ORs (ds_or_b32 without return: bit address a is bit a % 32 of 32-bit word a / 32, in the table, in
+//     the source and in the image alike).  A bit whose destination lies outside the window [lo, lo + span) is passed over; the next
+//     pass over the row, which then comes from L2, takes it.  Nothing assumes that a destination row fits in LDS;
+//   - the image is written out with plain coalesced 16-byte vector stores and cleared for the next window or row.  The last pair may
+//     hold one word past ceil(G / 64): nobody ORs into it, it is stored as the zero it is.  The padding words up to the destination
+//     stride are stored as zeros without an image behind them.
+// ORDER: the image belongs to ONE wavefront, whose LDS instructions execute in program order, and OR is commutative, so the result does
+// not depend on the order of execution: no global atomics, no workgroup waits for another, no __syncthreads, no separate zeroing
+// launch.  What has to be kept is the COMPILER's order between the ORs of all lanes and the read-out, and between the clear and the
+// next ORs: a wavefront-scope fence and a wave barrier at both places (collapse_image_fence).
+// Work is proportional to the set bits that move, not to N x G.  All row addressing is 64 bits wide (row x stride passes 2^32 words on
+// a 10 M-row index); bit addresses are 32 bits wide (at most 2^32 - 1 columns either side, and the window test wraps correctly).
+// Bounds: a source piece p < table_words / 2 and table_words <= src_stride; a destination pair ends at or before
+// round_up(ceil(G / 64), 2) <= dst_stride (both strides are multiples of 16 words; the launcher checks the three).
+// Loads of the source are plain (several windows read a row again); streamed loads for the one-window case were not tried.
+__device__ __forceinline__ void collapse_image_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// the set bits of 32 source bits: tab = the dst_bit entries of those 32 bit addresses
+__device__ __forceinline__ void collapse_walk(uint32_t x, const uint32_t *__restrict__ tab, uint32_t *img, uint32_t lo, uint32_t span)
+{
+    constexpr int B = kCollapseGathers;
+    while (x) {
+        uint32_t d[B];
+        bool on[B];
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            on[k] = x != 0u;
+            const uint32_t b = on[k] ? (uint32_t)__builtin_ctz(x) : 0u;
+            x &= x - 1u;
+            d[k] = on[k] ? tab[b] : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            const uint32_t a = d[k] - lo;          // (wraps for a destination below the window: then a >= span)
+            if (on[k] && a < span) atomicOr(&img[a >> 5], 1u << (a & 31u));
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_collapse_columns(
+    const uint64_t *__restrict__ src, uint64_t src_stride, uint64_t *__restrict__ dst, uint64_t dst_stride, uint64_t m,
+    const uint32_t *__restrict__ dst_bit, const uint64_t *__restrict__ live, uint64_t table_words, uint64_t dst_words, uint64_t window_words,
+    uint32_t image_words)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr int U = kCollapseLoads;
+    const uint32_t lane = threadIdx.x & 63u, wave_in_block = threadIdx.x >> 6, waves_per_block = blockDim.x >> 6;
+    const uint64_t wave = (uint64_t)blockIdx.x * waves_per_block + wave_in_block, n_waves = (uint64_t)gridDim.x * waves_per_block;
+    uint32_t *img = reinterpret_cast<uint32_t *>(smem) + (size_t)wave_in_block * image_words * 2u;
+    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+    for (uint32_t i = lane * 2u; i < image_words; i += 128u) *reinterpret_cast<uint4 *>(img + 2u * i) = zero;
+    collapse_image_fence();
+    const uint64_t pieces = table_words / 2;          // 16-byte pieces of a source row that carry columns
+    const uint4 *live4 = reinterpret_cast<const uint4 *>(live);
+    for (uint64_t row = wave; row < m; row += n_waves) {
+        const uint4 *srow = reinterpret_cast<const uint4 *>(src + row * src_stride);
+        uint64_t *drow = dst + row * dst_stride;
+        for (uint64_t win0 = 0; win0 < dst_words; win0 += window_words) {          // (wave-uniform)
+            const uint64_t win_n = dst_words - win0 < window_words ? dst_words - win0 : window_words;
+            const uint32_t lo = (uint32_t)(win0 * 64), span = (uint32_t)(win_n * 64);
+            for (uint64_t p0 = 0; p0 < pieces; p0 += 64 * U) {
+                // (a lane past the row's last piece loads that last piece again and walks nothing: a predicated 16-byte load would be
+                // split into four 4-byte ones)
+                uint4 v[U], lv[U];
+                uint64_t p[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint64_t q = p0 + (uint64_t)u * 64 + lane;
+                    p[u] = q < pieces ? q : pieces - 1;
+                    v[u] = srow[p[u]];
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) lv[u] = live4[p[u]];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const bool mine = p0 + (uint64_t)u * 64 + lane < pieces;
+                    const uint32_t *tab = dst_bit + p[u] * 128;
+                    collapse_walk(mine ? v[u].x & lv[u].x : 0u, tab, img, lo, span);
+                    collapse_walk(mine ? v[u].y & lv[u].y : 0u, tab + 32, img, lo, span);
+                    collapse_walk(mine ? v[u].z & lv[u].z : 0u, tab + 64, img, lo, span);
+                    collapse_walk(mine ? v[u].w & lv[u].w : 0u, tab + 96, img, lo, span);
+                }
+            }
+            collapse_image_fence();          // every lane's ORs of this window are in the image
+            for (uint64_t i = lane * 2u; i < win_n; i += 128) {
+                uint4 *q = reinterpret_cast<uint4 *>(img + 2 * i);
+                *reinterpret_cast<uint4 *>(drow + win0 + i) = *q;
+                *q = zero;
+            }
+            collapse_image_fence();          // the image is clear before anybody's next OR
+        }
+        for (uint64_t w = (dst_words + 1) / 2 * 2 + lane * 2u; w < dst_stride; w += 128) *reinterpret_cast<uint4 *>(drow + w) = zero;
+    }
+}
+
 // ------------------------------------------------------------------------------ row folding: the matrix under a smaller Bloom filter
 // dst row r = src row r | src row r + m' | ... | src row r + (factor - 1) m' for r in [0, m'), m' = m_dst: because a row id is
 // floor_mod(hash, m) (row_of_hash) and floor_mod(x, m) mod m' == floor_mod(x, m') for every divisor m' of m, this is bit for bit the

@@ -1,11 +1,12 @@
 // bigsi_launch.hpp -- the launch rule of a batch run, host-only: how K1 goes out (k1_plan) and how the row-AND kernels
 // (k_and_exact, k_and_count, k_count_combine) are launched for a batch of queries (plan_row_and), the sweep of the column popcounts
 // (plan_col_popcount), the per-call tables of the column compaction (plan_compact_columns), the sweep of the row folding
-// (plan_fold_rows) and the sweep of the k-mer prevalence (plan_kmer_prevalence).  Pure functions of a handful of integers (and, for
-// the compaction, of the keep bitmap): no HIP, no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp,
-// compact_host.cpp, fold_host.cpp and prevalence_host.cpp compile this header as plain host C++ and tests/test_abi_and_host.py,
-// test_sample_stats_host.py, test_compact_columns_host.py, test_fold_rows_host.py and test_kmer_prevalence_host.py pin the decisions
-// on the CPU.
+// (plan_fold_rows), the sweep of the k-mer prevalence (plan_kmer_prevalence) and the per-call tables, launch shape and destination
+// window of the column collapse (plan_collapse_columns).  Pure functions of a handful of integers (and, for the compaction and the
+// collapse, of the keep bitmap / the group map): no HIP, no batch, no index.  bigsi_hip.hip carries the plans out;
+// tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp, prevalence_host.cpp and collapse_host.cpp compile this header as
+// plain host C++ and tests/test_abi_and_host.py, test_sample_stats_host.py, test_compact_columns_host.py, test_fold_rows_host.py,
+// test_kmer_prevalence_host.py and test_collapse_columns_host.py pin the decisions on the CPU.
 //
 // Every constant below was measured on an MI355X; the notes beside them say against what.  A GPU test compares results, and a slip
 // here keeps results right and costs the 3 to 20 % those notes record: change a constant only with a new measurement, and the pinned
@@ -505,6 +506,93 @@ static inline PrevalencePlan plan_kmer_prevalence(uint64_t total_pos, uint64_t t
     p.loads_per_step = std::min<uint32_t>(std::max<uint32_t>(h, 1), kPrevLoads) * std::min<uint32_t>(p.segs_per_step, p.segs_per_slice);
     p.partial_stride = total_pos;
     p.partial_entries = p.slices * p.partial_stride;
+    return p;
+}
+
+// ------------------------------------------------------------------------------ column collapse (k_collapse_columns)
+// "OR these columns together": group_of[c] names the destination column of source column c (kCollapseDropped: none), and destination
+// column g of every row is the OR of the source columns of group g.  The map is the same for all rows, so everything that depends on
+// it alone is worked out HERE, once per call -- the row format's bit permutation included, so the kernel never maps a word to column
+// order and back.  The tables speak of bits AS THEY LIE IN MEMORY: bit b of the little-endian 64-bit word w of a row is column
+// 64 w + 8 (b / 8) + 7 - b % 8 (collapse_mem_bit is that permutation, and its own inverse).
+//   - dst_bit[64 w + b]: the destination bit address 64 w' + b' of source bit (w, b), or kCollapseDropped.  4 bytes per source column
+//     (400 KB at 100 k columns: resident in every XCD's L2).  The kernel reads it 32 bits at a time -- bit address a lies in the
+//     little-endian 32-bit word a / 32 at bit a % 32 --, for the source's loads and for the LDS image's ORs alike.
+//   - live[w]: the bits of source word w that have a destination.  The kernel ANDs a loaded word with it first, so dropped columns
+//     and stray bits behind num_cols cost nothing and dst_bit is consulted only for bits that move.  live is what decides: a dst_bit
+//     entry is never compared with kCollapseDropped on the device (the bit address of column 2^32 - 8 IS that value).
+//     Both tables are padded to an even number of source words (the kernel's 16-byte loads; the padding is zero / dropped).
+// Launch shape: a wavefront owns whole rows, one at a time, and an image of the destination row in LDS; about kCollapseWaves
+// wavefronts stride over the rows.  The figure is INHERITED from the column popcounts' sweep (kColPopWaves, measured there), not
+// measured for this kernel.  A handful of rows gets fewer wavefronts per workgroup.
+// Window: the image is bounded by kCollapseWindowWords 64-bit words per wavefront (2048 = 16 KiB = 131 072 groups: the 100 k-sample
+// index takes one pass; 4 wavefronts x 16 KiB = 64 KiB per workgroup, two workgroups per CU.  UNMEASURED starting values).  A wider
+// destination is done in ceil(dst_words / window) windows per row: each pass over the source row keeps the bits whose destination lies
+// in the window [win0, win0 + window) and the row comes from L2 after the first pass.  A narrow destination takes a smaller image
+// (more workgroups per CU).  INVARIANTS (tests/test_collapse_columns_host.py checks them over seeded shapes): image_words is even and
+// <= window_words; lds_bytes = image_words x 8 x wavefronts per workgroup <= kCollapseLdsBytes; the windows tile [0, dst_words)
+// without gap or overlap.
+constexpr uint32_t kCollapseDropped = 0xFFFFFFFFu;
+constexpr uint64_t kCollapseWaves = kColPopWaves;
+constexpr uint64_t kCollapseWindowWords = 2048;
+constexpr uint64_t kCollapseLdsBytes = 64 * 1024;
+constexpr int kCollapseLoads = 4;            // independent 16-byte loads a lane has in flight
+constexpr int kCollapseGathers = 8;          // dst_bit gathers issued together, then that many LDS ORs
+static_assert(kCollapseWindowWords % 2 == 0 && kCollapseWindowWords * 8 * (kBlock / 64) <= kCollapseLdsBytes, "the images of a workgroup fit its LDS");
+static inline uint32_t collapse_mem_bit(uint32_t c) { return ((c >> 3) & 7u) * 8u + 7u - (c & 7u); }
+struct CollapsePlan {
+    uint64_t src_words = 0;          // ceil(num_cols / 64)
+    uint64_t table_words = 0;        // src_words rounded up to even: live has that many entries, dst_bit 64 times as many
+    uint64_t dst_words = 0;          // ceil(num_groups / 64)
+    uint64_t window_words = 0;       // destination words per window
+    uint64_t windows = 1;            // passes per row (at least 1)
+    uint64_t image_words = 0;        // 64-bit words of one wavefront's LDS image
+    uint32_t block = 64;             // threads per workgroup
+    uint64_t grid = 0;               // workgroups; the wavefronts stride over the rows
+    uint64_t lds_bytes = 0;          // dynamic LDS per workgroup
+    uint64_t moved = 0;              // source columns that have a destination
+    std::vector<uint32_t> dst_bit;   // 64 x table_words
+    std::vector<uint64_t> live;      // table_words
+};
+// the first column whose entry is neither a group id nor kCollapseDropped, or num_cols
+static inline uint64_t collapse_first_bad(uint64_t num_cols, const uint32_t *group_of, uint64_t num_groups)
+{
+    for (uint64_t c = 0; c < num_cols; c++)
+        if (group_of[c] != kCollapseDropped && group_of[c] >= num_groups) return c;
+    return num_cols;
+}
+// window j of a plan: destination words [first, first + count)
+static inline void collapse_window(const CollapsePlan &p, uint64_t j, uint64_t *first, uint64_t *count)
+{
+    *first = j * p.window_words;
+    *count = std::min<uint64_t>(p.window_words, p.dst_words - std::min(p.dst_words, *first));
+}
+// `group_of`: num_cols entries, each < num_groups or kCollapseDropped (collapse_first_bad); 0 < num_groups < 2^32 - 1
+static inline CollapsePlan plan_collapse_columns(uint64_t num_cols, const uint32_t *group_of, uint64_t num_groups, uint64_t num_rows,
+                                                 uint64_t window_words = kCollapseWindowWords)
+{
+    CollapsePlan p;
+    p.src_words = ceil_div(num_cols, 64);
+    p.table_words = round_up(p.src_words, 2);
+    p.dst_words = ceil_div(num_groups, 64);
+    p.window_words = window_words;
+    p.windows = std::max<uint64_t>(ceil_div(p.dst_words, p.window_words), 1);
+    p.image_words = std::min<uint64_t>(p.window_words, round_up(std::max<uint64_t>(p.dst_words, 1), 2));
+    p.dst_bit.assign(p.table_words * 64, kCollapseDropped);
+    p.live.assign(p.table_words, 0ull);
+    for (uint64_t c = 0; c < num_cols; c++) {
+        const uint32_t g = group_of[c];
+        if (g == kCollapseDropped) continue;
+        const uint32_t b = collapse_mem_bit((uint32_t)(c & 63));
+        p.dst_bit[(c & ~63ull) + b] = (g & ~63u) + collapse_mem_bit(g & 63u);
+        p.live[c >> 6] |= 1ull << b;
+        p.moved++;
+    }
+    const uint64_t rows = std::max<uint64_t>(num_rows, 1);
+    const uint64_t waves_per_block = std::min<uint64_t>(rows, kBlock / 64);
+    p.block = (uint32_t)waves_per_block * 64;
+    p.grid = std::min<uint64_t>(ceil_div(rows, waves_per_block), kCollapseWaves / (kBlock / 64));
+    p.lds_bytes = p.image_words * 8 * waves_per_block;
     return p;
 }
 

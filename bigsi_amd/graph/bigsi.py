@@ -842,6 +842,50 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
             storage.close()
         return type(self)(config)
 
+    # ------------------------------------------------------------------ column collapse: groups of samples ORed into one column each
+    def collapse(self, config, groups, keep_others=False):
+        """A new index under `config` (same m, h, k, same device; a storage-config name of its own, nothing stored under it yet) in
+        which every GROUP of samples of this one is one column: the OR of its members' columns (bigsi_hip_collapse_columns_into:
+        device to device, this index is only read).  The Bloom filter of a union of k-mer sets is the OR of the members' filters, so
+        the new index is bit for bit the one BIGSI.build makes from the OR-ed filters under the group names, and every exact hit of
+        a member is a hit of its group: the small index that is searched first, at |groups| / N of the bytes per query.
+        groups: an ordered mapping group name -> [sample names], or (sample, group) pairs; the new colours follow the order of a
+        group's first appearance, so singleton groups REORDER samples.  Deleted samples are dropped; unlisted samples are dropped, or
+        with keep_others each stays as a group of its own under its own name, after the named groups.  KeyError / ValueError as
+        collapse.collapse_plan says (which also gives the membership: collapse_plan(names, groups, keep_others)[2]).  Returns the
+        new BIGSI."""
+        from ..collapse import check_groups, collapse_plan
+        from .index import BLOOMFILTER_SIZE_KEY, NUM_HASH_FUNCTS_KEY
+        check_groups(groups, keep_others)               # (whatever it raises, it raises before anything is read)
+        if self.storage.res.is_group:
+            from .._lib import ERR_STATE, BigsiHipError
+            raise BigsiHipError(ERR_STATE, "column collapse is not available for multi-GPU (devices=[...]) indexes")
+        with self._device_lock():
+            group_of, group_names, _ = collapse_plan(self._colour_names(), groups, keep_others)
+            for key, mine in (("m", self.bloomfilter_size), ("h", self.num_hashes), ("k", self.kmer_size)):
+                if int(config[key]) != int(mine):
+                    raise ValueError("the new index must have this one's %s (%d), its config says %d" % (key, mine, config[key]))
+            storage = get_storage(config)
+            if storage.res is self.storage.res:
+                raise ValueError("the new index needs a storage-config name of its own")
+            if SampleMetadata(storage).num_samples or int(storage.get("number_of_cols:int", b"0")):
+                raise ValueError("the index described by the new config is not empty")
+            try:
+                storage.set_integer(BLOOMFILTER_SIZE_KEY, int(self.bloomfilter_size))
+                storage.set_integer(NUM_HASH_FUNCTS_KEY, int(self.num_hashes))
+                storage.set_integer("number_of_rows", int(self.bloomfilter_size))
+                storage.set_integer("number_of_cols", 0)
+                storage.res.ensure_open()
+                if self.storage.collapse_columns_into(storage, group_of, len(group_names)) != len(group_names):
+                    raise RuntimeError("the device made another number of columns than there are groups")
+                SampleMetadata(storage).add_samples(group_names)
+                storage.sync()
+            except BaseException:
+                storage.delete_all()          # (it was empty when we came: nothing half-made stays resident under the new name)
+                raise
+            storage.close()
+        return type(self)(config)
+
     # ------------------------------------------------------------------ row folding: the same index under a smaller Bloom filter
     def _refuse_group_fold(self):
         if self.storage.res.is_group:

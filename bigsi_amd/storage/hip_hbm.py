@@ -467,6 +467,19 @@ class HipHbmStorage(BaseStorage):
         self._after_column_move()
         return int(self.res.info().num_cols)
 
+    def collapse_columns_into(self, dst, group_of, num_groups):
+        """Column g of `dst` -- another resident hip-hbm index on the same device with the same m and h, which must hold no columns
+        yet -- becomes the OR of this index's columns c with group_of[c] == g (bigsi_hip_collapse_columns_into); this index is only
+        read.  group_of: one unsigned 32-bit entry per column, a group id below num_groups or collapse.DROPPED.  Returns the number of
+        columns of dst (num_groups)."""
+        from ..collapse import group_ids
+        if self.res.is_group or dst.res.is_group:
+            raise BigsiHipError(_lib.ERR_STATE, "column collapse is not available for multi-GPU (devices=[...]) indexes")
+        buf = group_ids(group_of, int(self.res.info().num_cols) if self.res.ensure_open() else 0, num_groups)
+        check(_lib.lib().bigsi_hip_collapse_columns_into(dst.handle, self.handle, _lib.ptr(buf), int(num_groups)))
+        dst._after_column_move()
+        return int(dst.res.info().num_cols)
+
     def shrink_to_fit(self):
         """Give back the row stride beyond the columns the index holds (bigsi_hip_shrink_to_fit): the counterpart of reserve_cols."""
         if self.res.is_group:

@@ -25,6 +25,7 @@
  *                  the library.  One process driving N GPUs: bigsi_hip_group_* in include/bigsi_hip_group.h.
  *       MAINTENANCE  removing or extracting samples physically (column compaction, the capacity trim): include/bigsi_hip_compact.h.
  *                  The same index under a smaller Bloom filter size (row folding, the row trim): include/bigsi_hip_fold.h.
+ *                  Groups of samples ORed into one column each of a new index (column collapse): include/bigsi_hip_collapse.h.
  *       PREVALENCE for every k-mer position of a query the number of samples that hold the k-mer: include/bigsi_hip_prevalence.h.
  *       SHARING    export_ipc / open_ipc (another process) and open_view (another thread): read-only handles onto ONE resident matrix.
  *       MEASUREMENT  fill_synthetic, set_profiling, stats (calibration probe and device-resident filters: bigsi_hip_testing.h).

@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -565,6 +565,89 @@ def prevalence():
             emit("kmer_prevalence_vs_lookup", m=m, cols=n, kmers=len(kmers), edge_row=edge, edge_rows_found=sorted(int(r) for r in hits),
                  equal=bool(np.array_equal(want, total.astype(np.uint64))), total_min=int(total.min()), total_max=int(total.max()))
         st.delete_all()
+
+
+def collapse():
+    """Column collapse (k_collapse_columns) on the C3 index: (a) the identity map, (b) 100 000 -> 1000 groups at random, (c) a
+    dereplication -- 1 % of the columns merged in pairs, the rest singletons -- beside two figures from the same run: an extraction that
+    keeps every column (the same copy through k_compact_columns) and the bare sorted-row stream (bigsi_hip_probe_rows).  Wall-clock
+    time of the whole C call (table upload included) into a destination reserved beforehand; bytes = the source words read + the
+    destination stride written; bits = the set bits of the columns that move (bigsi_hip_column_popcounts).  Before each call 64 seeded
+    rows are fetched -- the rows either side of row 2 739 137, where row x stride_words passes 2^32, among them -- and checked against
+    numpy afterwards.  What does not fit beside the index in device memory is skipped and says so."""
+    import torch
+    L, C = _lib.lib(), _lib.C
+    m, n = 10_000_000, 100_000
+    DROPPED = 0xFFFFFFFF
+
+    def stride_for(cols):
+        return max(16, -(-(-(-cols // 64)) // 16) * 16) * 8
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        check(fn())
+        return (time.perf_counter() - t0) * 1e3
+
+    def rows_of(handle, ids, rb):
+        out = np.zeros((ids.size, rb), np.uint8)
+        check(L.bigsi_hip_get_rows(handle, _lib.ptr(ids), ids.size, _lib.ptr(out), rb))
+        return out
+
+    st, fill = open_index("collapse", m, n, 3)
+    stride = int(st.res.info().row_stride_bytes)
+    src_bytes = m * (-(-n // 64)) * 8
+    g_, m_ = C.c_double(0), C.c_double(0)
+    check(L.bigsi_hip_probe_rows(st.handle, 3880, 1, 1, 0, 3, C.byref(g_), C.byref(m_)))
+    counts = np.zeros(n, np.uint64)
+    check(L.bigsi_hip_column_popcounts(st.handle, None, _lib.ptr(counts), n))
+    rng = np.random.default_rng(10)
+    edge = (1 << 32) // (stride // 8)          # the first row whose offset in words is >= 2^32
+    ids = np.unique(np.concatenate([rng.integers(0, m, 61).astype(np.uint64), np.array([edge - 1, edge, edge + 1], np.uint64)]))
+    before = np.unpackbits(rows_of(st.handle, ids, (n + 7) // 8), axis=1)[:, :n]
+    common = dict(m=m, cols=n, stride_bytes=stride, box_sorted_GBps=g_.value, fill_density=float(counts.sum()) / (m * n), edge_row=int(edge))
+    # the yardstick of the same run: the copy of every column through k_compact_columns
+    copy_ms = None
+    free = torch.cuda.mem_get_info()[0]
+    if m * stride + (2 << 30) > free:
+        emit("collapse_copy_all_kept_yardstick", skipped="a second copy of the matrix (%d bytes) does not fit beside it (%d free)" % (m * stride, free), **common)
+    else:
+        dst = C.c_void_p()
+        check(L.bigsi_hip_open(m, 0, n, 3, 0, C.byref(dst)))
+        every = np.full((n + 7) // 8, 0xFF, np.uint8)
+        copy_ms = timed(lambda: L.bigsi_hip_extract_columns(dst, st.handle, _lib.ptr(every)))
+        emit("collapse_copy_all_kept_yardstick", call_ms=copy_ms, bytes=src_bytes + m * stride, GBps=(src_bytes + m * stride) / copy_ms / 1e6, **common)
+        check(L.bigsi_hip_close(dst))
+    identity = np.arange(n, dtype=np.uint32)
+    thousand = rng.integers(0, 1000, n).astype(np.uint32)
+    derep = np.zeros(n, np.uint32)
+    pairs = rng.choice(n, 1000, replace=False)          # 1 % of the columns, merged in pairs: the second of a pair takes the first's group
+    second = np.zeros(n, bool)
+    second[pairs[1::2]] = True
+    derep[~second] = np.arange(int((~second).sum()), dtype=np.uint32)
+    derep[pairs[1::2]] = derep[pairs[0::2]]
+    for name, group_of, groups in (("identity", identity, n), ("random_1000", thousand, 1000), ("dereplicate_1pct", derep, int((~second).sum()))):
+        need = m * stride_for(groups)
+        free = torch.cuda.mem_get_info()[0]
+        if need + (2 << 30) > free:
+            emit("collapse_" + name, groups=groups, skipped="the destination (%d bytes) does not fit beside the index (%d free)" % (need, free), **common)
+            continue
+        dst = C.c_void_p()
+        check(L.bigsi_hip_open(m, 0, groups, 3, 0, C.byref(dst)))
+        ms = timed(lambda: L.bigsi_hip_collapse_columns_into(dst, st.handle, _lib.ptr(group_of), groups))
+        want = np.zeros((groups, ids.size), np.uint8)
+        cols = np.flatnonzero(group_of != DROPPED)
+        np.maximum.at(want, group_of[cols].astype(np.int64), before[:, cols].T)
+        got = rows_of(dst, ids, need // m)
+        exp = np.zeros_like(got)
+        packed = np.packbits(want.T, axis=1)
+        exp[:, :packed.shape[1]] = packed
+        bits = int(counts[cols].sum())
+        emit("collapse_" + name, groups=groups, call_ms=ms, bytes=src_bytes + need, GBps=(src_bytes + need) / ms / 1e6, bits_moved=bits,
+             Gbits_per_s=bits / ms / 1e6, over_copy_all_kept=(ms / copy_ms) if copy_ms else None, rows_checked=int(ids.size),
+             rows_equal=bool(np.array_equal(got, exp)), source_unchanged=bool(np.array_equal(np.unpackbits(rows_of(st.handle, ids, (n + 7) // 8), axis=1)[:, :n], before)),
+             **common)
+        check(L.bigsi_hip_close(dst))
+    st.delete_all()
 
 
 if __name__ == "__main__":

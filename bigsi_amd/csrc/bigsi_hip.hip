@@ -1052,7 +1052,8 @@ extern "C" int bigsi_hip_get_column(bigsi_hip_index *ix, uint64_t col, uint8_t *
 {
     BIGSI_ENTER(ix);
     if (!ix || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
-    if (col >= ix->cap_cols) return fail(BIGSI_ERR_RANGE, "column %llu beyond col_capacity", (unsigned long long)col);
+    // (a column the index does not have is refused, as the CPU twin refuses it: what the stride holds behind num_cols is no sample's filter)
+    if (col >= ix->n_cols) return fail(BIGSI_ERR_RANGE, "column %llu out of range [0,%llu)", (unsigned long long)col, (unsigned long long)ix->n_cols);
     TRY(use_device(ix));
     const uint64_t nb = ceil_div(ix->m, 8);
     TRY(ix->stage.reserve(nb));

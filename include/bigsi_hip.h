@@ -162,12 +162,19 @@ int bigsi_hip_save_rows_file(bigsi_hip_index *ix, const char *path, uint64_t fil
 int bigsi_hip_insert_column(bigsi_hip_index *ix, uint64_t col, const uint8_t *bloom);
 /* transpose + BitMatrix.create (bigsi/matrix/transpose.py:33-43, bigsi/graph/index.py:27-40), on the device: n Bloom
  * filters (filter i at blooms + i*bloom_stride_bytes, ceil(num_rows/8) bytes each) become columns [col0, col0+n).
- * col0 <= num_cols; num_cols grows to col0+n if that is larger.  Needs col0+n <= col_capacity. */
+ * col0 <= num_cols; num_cols grows to col0+n if that is larger.  Needs col0+n <= col_capacity.
+ * Only the first num_rows bits of a filter are read: the rest of its last byte and the bytes up to bloom_stride_bytes may hold
+ * anything.  An overwrite (col0+n < num_cols) changes columns [col0, col0+n) and no other bit of a row; a call that reaches or
+ * passes num_cols relies on the rows being zero behind num_cols (every call of this library leaves them so; bigsi_hip_set_rows
+ * with bytes behind num_cols is the caller's way to break it) and leaves them zero behind col0+n. */
 int bigsi_hip_insert_columns(bigsi_hip_index *ix, uint64_t col0, uint64_t n, const uint8_t *blooms, uint64_t bloom_stride_bytes);
 /* KmerSignatureIndex.merge_indexes (bigsi/graph/index.py:54-60): append all columns of src after dst's, device to
- * device (same device, same num_rows); dst's capacity grows as needed. */
+ * device (same device, same num_rows); dst's capacity grows as needed.  Only columns [0, src num_cols) of src are read: bits
+ * its rows hold behind them do not reach dst, whose rows are zero behind the appended columns; src is not changed. */
 int bigsi_hip_append_index(bigsi_hip_index *dst, const bigsi_hip_index *src);
-/* BitMatrix.get_column (bigsi/matrix/bitmatrix.py:50-61): out = ceil(num_rows/8) bytes. */
+/* BitMatrix.get_column (bigsi/matrix/bitmatrix.py:50-61): out = ceil(num_rows/8) bytes, the bits of the last byte behind row
+ * num_rows - 1 zero.  col < num_cols: a column the index does not have -- behind num_cols, inside the capacity or not -- is
+ * BIGSI_ERR_RANGE and out is not written (as bigsi_cpu_get_column). */
 int bigsi_hip_get_column(bigsi_hip_index *ix, uint64_t col, uint8_t *out);
 /* Sample statistics (no counterpart in the reference, whose score knows only DB_SIZE, bigsi/scoring/score.py:38-52): the vertical
  * popcount of the matrix.  out[c] = number of rows r < num_rows with bit (r, c) set and (row_mask == NULL or bit r of row_mask set);

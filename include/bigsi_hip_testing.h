@@ -66,7 +66,9 @@ int bigsi_hip_batch_set_gathered_hit_outputs(bigsi_hip_batch *b, void *d_colours
 
 /* MEASUREMENT (bench.py, scripts/measure.py).
  * bigsi_hip_insert_columns with the filters already in device memory (no staging copy: what prices the transpose kernel alone).
- * A 16-byte aligned pointer and pitch take the tiled transpose; anything else the column-at-a-time route. */
+ * A 16-byte aligned pointer and pitch take the tiled transpose; anything else the column-at-a-time route.  d_blooms spans
+ * n * bloom_stride_bytes bytes: the tiled route loads 16 bytes at a time, inside a filter's pitch but up to 15 bytes behind its
+ * ceil(num_rows/8); what those bytes, and the bits of the last byte behind row num_rows - 1, hold reaches no row. */
 int bigsi_hip_insert_columns_device(bigsi_hip_index *ix, uint64_t col0, uint64_t n, const void *d_blooms, uint64_t bloom_stride_bytes);
 /* Same-box calibration: achieved GB/s of bare row streams over this index's matrix -- a kernel with no BIGSI code, the load
  * pattern of the row-AND kernels (one wavefront per 1 KiB column segment, 16 B per lane, 8 loads in flight) -- over n_queries

@@ -187,6 +187,38 @@ int bdb_read_failed(const bigsi_cpu_index *ix)
              : BIGSI_OK;
 }
 
+// BIGSI_OK, or the refusal of every call that would write to a BerkeleyDB-backed index or sweep all of its rows (NULL passes: the
+// caller's own check names it)
+int read_only(const bigsi_cpu_index *ix)
+{
+    if (ix && ix->bdb)
+        return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    return BIGSI_OK;
+}
+
+// The calls that make one index from another (extract_columns, collapse_columns_into, fold_rows_into): what the two must have in
+// common, in the order of the device library's check_derive (no devices, handles or views here).  An entry point checks its own
+// arguments before this.
+struct DeriveRule {
+    const char *in_place;      // the in-place form a caller may have meant, or nullptr: there is none
+    bool rows_divide;          // the destination's num_rows divides the source's (a fold); otherwise the two are equal
+    bool same_hashes;
+};
+
+int check_derive(const DeriveRule &r, const bigsi_cpu_index *dst, const bigsi_cpu_index *src)
+{
+    TRY(read_only(dst));
+    if (!dst || !src) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (dst == src)
+        return fail(BIGSI_ERR_INVALID, "dst and src are the same index (%s%s)", r.in_place ? r.in_place : "there is no in-place form", r.in_place ? " works in place" : "");
+    if (r.rows_divide ? (dst->m == 0 || src->m % dst->m) : dst->m != src->m)
+        return fail(BIGSI_ERR_INVALID, r.rows_divide ? "the destination's num_rows %llu does not divide the source's %llu" : "row counts differ (%llu vs %llu)",
+                    (unsigned long long)dst->m, (unsigned long long)src->m);
+    if (r.same_hashes && dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
+    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    return BIGSI_OK;
+}
+
 int check_seqs(const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k)
 {
     if (!offsets) return fail(BIGSI_ERR_INVALID, "NULL argument");
@@ -499,7 +531,7 @@ int bigsi_cpu_set_num_hashes(bigsi_cpu_index *ix, uint32_t num_hashes)
 
 int bigsi_cpu_reserve_cols(bigsi_cpu_index *ix, uint64_t col_capacity)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
     if (col_capacity <= ix->cap_cols) return BIGSI_OK;
     const uint64_t stride = stride_for(col_capacity);
@@ -518,7 +550,7 @@ int bigsi_cpu_synchronize(bigsi_cpu_index *ix) { return ix ? BIGSI_OK : fail(BIG
 
 int bigsi_cpu_set_rows(bigsi_cpu_index *ix, const uint64_t *row_ids, uint64_t n, const uint8_t *bytes, uint64_t row_bytes)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix || (n && (!row_ids || !bytes))) return fail(BIGSI_ERR_INVALID, "NULL argument");
     if (row_bytes > ix->stride) return fail(BIGSI_ERR_CAPACITY, "row_bytes %llu exceeds the row stride %llu", (unsigned long long)row_bytes, (unsigned long long)ix->stride);
     for (uint64_t i = 0; i < n; i++)
@@ -544,7 +576,7 @@ int bigsi_cpu_get_rows(bigsi_cpu_index *ix, const uint64_t *row_ids, uint64_t n,
 
 int bigsi_cpu_clear(bigsi_cpu_index *ix)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
     memset(ix->rows, 0, ix->m * ix->stride);
     return BIGSI_OK;
@@ -557,7 +589,7 @@ int bigsi_cpu_insert_column(bigsi_cpu_index *ix, uint64_t col, const uint8_t *bl
 
 int bigsi_cpu_insert_columns(bigsi_cpu_index *ix, uint64_t col0, uint64_t n, const uint8_t *blooms, uint64_t bloom_stride_bytes)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix || (n && !blooms)) return fail(BIGSI_ERR_INVALID, "NULL argument");
     if (col0 > ix->n_cols) return fail(BIGSI_ERR_RANGE, "col0 %llu beyond num_cols %llu", (unsigned long long)col0, (unsigned long long)ix->n_cols);
     if (col0 + n > ix->cap_cols) return fail(BIGSI_ERR_CAPACITY, "columns [%llu, %llu) exceed col_capacity %llu", (unsigned long long)col0, (unsigned long long)(col0 + n), (unsigned long long)ix->cap_cols);
@@ -578,7 +610,7 @@ int bigsi_cpu_insert_columns(bigsi_cpu_index *ix, uint64_t col0, uint64_t n, con
 
 int bigsi_cpu_get_column(bigsi_cpu_index *ix, uint64_t col, uint8_t *out)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
     if (col >= ix->n_cols) return fail(BIGSI_ERR_RANGE, "column %llu out of range", (unsigned long long)col);
     memset(out, 0, ceil_div(ix->m, 8));
@@ -590,7 +622,7 @@ int bigsi_cpu_get_column(bigsi_cpu_index *ix, uint64_t col, uint8_t *out)
 // per column, the rows (of the selected ones) that have its bit: one row at a time, one column at a time
 int bigsi_cpu_column_popcounts(bigsi_cpu_index *ix, const uint8_t *row_mask, uint64_t *out, uint64_t capacity)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
     if (capacity < ix->n_cols)
         return fail(BIGSI_ERR_CAPACITY, "capacity %llu is below num_cols %llu", (unsigned long long)capacity, (unsigned long long)ix->n_cols);
@@ -624,7 +656,7 @@ static uint64_t select_columns(uint8_t *dst, uint64_t dst_stride, const uint8_t 
 
 int bigsi_cpu_compact_columns(bigsi_cpu_index *ix, const uint8_t *keep, uint64_t *new_num_cols)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix || !keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
     uint64_t kept = 0;
     for (uint64_t c = 0; c < ix->n_cols; c++) kept += (keep[c >> 3] & (0x80u >> (c & 7))) ? 1 : 0;
@@ -638,11 +670,8 @@ int bigsi_cpu_compact_columns(bigsi_cpu_index *ix, const uint8_t *keep, uint64_t
 
 int bigsi_cpu_extract_columns(bigsi_cpu_index *dst, const bigsi_cpu_index *src, const uint8_t *keep)
 {
-    if (dst && dst->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
-    if (!dst || !src || !keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
-    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot extract an index into itself (bigsi_cpu_compact_columns works in place)");
-    if (dst->m != src->m) return fail(BIGSI_ERR_INVALID, "row counts differ (%llu vs %llu)", (unsigned long long)dst->m, (unsigned long long)src->m);
-    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    if (!keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_derive({/*in_place*/ "bigsi_cpu_compact_columns", /*rows_divide*/ false, /*same_hashes*/ false}, dst, src));
     uint64_t kept = 0;
     for (uint64_t c = 0; c < src->n_cols; c++) kept += (keep[c >> 3] & (0x80u >> (c & 7))) ? 1 : 0;
     TRY(bigsi_cpu_reserve_cols(dst, kept));
@@ -656,17 +685,13 @@ int bigsi_cpu_extract_columns(bigsi_cpu_index *dst, const bigsi_cpu_index *src, 
 // Column collapse: destination column g = the OR of the source columns of group g, one row and one column at a time
 int bigsi_cpu_collapse_columns_into(bigsi_cpu_index *dst, const bigsi_cpu_index *src, const uint32_t *group_of, uint64_t num_groups)
 {
-    if (dst && dst->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
     if (!dst || !src || !group_of) return fail(BIGSI_ERR_INVALID, "NULL argument");
     if (num_groups == 0 || num_groups >= 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "num_groups %llu is not in [1, 2^32 - 1)", (unsigned long long)num_groups);
-    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot collapse an index into itself (there is no in-place form)");
-    if (dst->m != src->m) return fail(BIGSI_ERR_INVALID, "row counts differ (%llu vs %llu)", (unsigned long long)dst->m, (unsigned long long)src->m);
-    if (dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
+    TRY(check_derive({/*in_place*/ nullptr, /*rows_divide*/ false, /*same_hashes*/ true}, dst, src));
     for (uint64_t c = 0; c < src->n_cols; c++)
         if (group_of[c] != BIGSI_COLLAPSE_DROPPED && group_of[c] >= num_groups)
             return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither a group id below %llu nor BIGSI_COLLAPSE_DROPPED", (unsigned long long)c, group_of[c],
                         (unsigned long long)num_groups);
-    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
     TRY(bigsi_cpu_reserve_cols(dst, num_groups));
     std::vector<uint8_t> tmp, page;
     const uint64_t rb = src->rb();
@@ -702,7 +727,7 @@ static void fold_row(uint8_t *dst, uint64_t dst_stride, const bigsi_cpu_index *s
 
 int bigsi_cpu_fold_rows(bigsi_cpu_index *ix, uint64_t factor, uint64_t *new_num_rows)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
     if (factor == 0 || ix->m % factor)
         return fail(BIGSI_ERR_INVALID, "fold factor %llu does not divide num_rows %llu", (unsigned long long)factor, (unsigned long long)ix->m);
@@ -718,13 +743,7 @@ int bigsi_cpu_fold_rows(bigsi_cpu_index *ix, uint64_t factor, uint64_t *new_num_
 
 int bigsi_cpu_fold_rows_into(bigsi_cpu_index *dst, const bigsi_cpu_index *src)
 {
-    if (dst && dst->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
-    if (!dst || !src) return fail(BIGSI_ERR_INVALID, "NULL argument");
-    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot fold an index into itself (bigsi_cpu_fold_rows works in place)");
-    if (dst->m == 0 || src->m % dst->m)
-        return fail(BIGSI_ERR_INVALID, "the destination's num_rows %llu does not divide the source's %llu", (unsigned long long)dst->m, (unsigned long long)src->m);
-    if (dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
-    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    TRY(check_derive({/*in_place*/ "bigsi_cpu_fold_rows", /*rows_divide*/ true, /*same_hashes*/ true}, dst, src));
     TRY(bigsi_cpu_reserve_cols(dst, src->n_cols));
     std::vector<uint8_t> acc, tmp, page;
     const uint64_t factor = src->m / dst->m;
@@ -735,7 +754,7 @@ int bigsi_cpu_fold_rows_into(bigsi_cpu_index *dst, const bigsi_cpu_index *src)
 
 int bigsi_cpu_trim_rows(bigsi_cpu_index *ix)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
     if (ix->alloc_rows <= ix->m) return BIGSI_OK;
     uint8_t *kept = static_cast<uint8_t *>(malloc(std::max<uint64_t>(ix->m * ix->stride, 1)));
@@ -749,7 +768,7 @@ int bigsi_cpu_trim_rows(bigsi_cpu_index *ix)
 
 int bigsi_cpu_insert_kmers(bigsi_cpu_index *ix, uint64_t col, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
     if (n_seqs == 0) return BIGSI_OK;
     TRY(check_seqs(seqs, offsets, n_seqs, k));
@@ -770,7 +789,7 @@ int bigsi_cpu_insert_kmers(bigsi_cpu_index *ix, uint64_t col, const char *seqs, 
 
 int bigsi_cpu_fill_synthetic(bigsi_cpu_index *ix, uint64_t seed, uint64_t shard, uint32_t and_draws)
 {
-    if (ix && ix->bdb) return fail(BIGSI_ERR_STATE, "this index serves its rows from a BerkeleyDB file (bigsi_cpu_open_bdb): read-only, search / lookup / get_rows / presence only");
+    TRY(read_only(ix));
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
     const uint64_t base = mix64(seed + shard * 0x632BE59BD9B4E019ull), words = ix->stride / 8;
     for (uint64_t r = 0; r < ix->m; r++) {

@@ -131,6 +131,102 @@ int bigsi_writable(const bigsi_hip_index *ix)
     return BIGSI_OK;
 }
 
+// ------------------------------------------------------------------------------ shared guards of the calls that change an index
+// What a call that rewrites a matrix in place needs before it touches it (compact_columns, fold_rows, shrink_to_fit, trim_rows and a
+// reserve_cols that re-strides): the handle owns the matrix, no view of it is open (`stale`: what would happen to the views), its device
+// is current and nothing reads the matrix on another stream.  A call's no-op returns come before this: a view may ask for nothing.
+static int begin_rewrite(bigsi_hip_index *ix, const char *who, const char *stale)
+{
+    TRY(bigsi_writable(ix));
+    if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "%s: %d view(s) of this index are open: %s", who, ix->views.load(), stale);
+    TRY(use_device(ix));
+    return quiesce_index(ix);
+}
+
+// The matrix moves to an allocation of its own size, num_rows rows of `new_stride` words: through k_restride when the stride changes
+// (min(old, new) words of every row, zeros behind them), as one device-to-device copy of the front of the old allocation when it
+// does not (bigsi_hip_trim_rows).  The second matrix has to fit beside the first (BIGSI_ERR_NOMEM); on any failure the index is as it
+// was, nothing is leaked and the runtime's sticky last-error slot is clear for this thread's next launch check.
+static int replace_matrix(bigsi_hip_index *ix, uint64_t new_stride, const char *who)
+{
+    const size_t bytes = (size_t)ix->m * new_stride * 8;
+    uint64_t *nd = nullptr;
+    hipError_t e = hipMalloc((void **)&nd, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? BIGSI_ERR_NOMEM : BIGSI_ERR_HIP, "%s: hipMalloc of %zu bytes beside the matrix failed: %s", who, bytes,
+                    hipGetErrorString(e));
+    }
+    if (new_stride != ix->stride_words) {
+        const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(ix->m * new_stride, kBlock), 256 * 8 * 4);
+        hipLaunchKernelGGL(k_restride, dim3(grid), dim3(kBlock), 0, ix->stream, ix->d_index, ix->stride_words, nd, new_stride, ix->m);
+        e = hipGetLastError();
+    } else
+        e = hipMemcpyAsync(nd, ix->d_index, bytes, hipMemcpyDeviceToDevice, ix->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        hipError_t e2 = hipFree(nd); (void)e2;
+        return fail(BIGSI_ERR_HIP, "%s: copying the rows failed: %s", who, hipGetErrorString(e));
+    }
+    HIP_TRY(hipFree(ix->d_index));
+    ix->d_index = nd;
+    ix->alloc_rows = ix->m;          // (the new allocation holds the rows the index has: what a fold left behind them is gone)
+    ix->stride_words = new_stride;
+    ix->cap_cols = new_stride * 64;
+    return BIGSI_OK;
+}
+
+// The calls that make or grow one index from another (extract_columns, fold_rows_into, collapse_columns_into, append_index): what the
+// two handles must have in common, checked in one order for all of them.  An entry point checks its own arguments before this.
+namespace {
+struct DeriveRule {
+    const char *name;          // the entry point, for messages
+    const char *in_place;      // the in-place form a caller may have meant, or nullptr: there is none
+    bool rows_divide;          // the destination's num_rows divides the source's (a fold); otherwise the two are equal
+    bool same_hashes;          // num_hashes must match
+    bool into_empty;           // the destination holds no columns and has no views open (append_index grows it, as insert_columns does)
+};
+}  // namespace
+
+static int check_derive(const DeriveRule &r, const bigsi_hip_index *dst, const bigsi_hip_index *src)
+{
+    if (!dst || !src) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    const std::string hint = r.in_place ? std::string(r.in_place) + " works in place" : std::string("there is no in-place form");
+    if (dst == src) return fail(BIGSI_ERR_INVALID, "%s: dst and src are the same index (%s)", r.name, hint.c_str());
+    if (r.rows_divide ? (dst->m == 0 || src->m % dst->m) : dst->m != src->m)
+        return fail(BIGSI_ERR_INVALID, r.rows_divide ? "the destination's num_rows %llu does not divide the source's %llu" : "row counts differ (%llu vs %llu)",
+                    (unsigned long long)dst->m, (unsigned long long)src->m);
+    if (dst->device != src->device) return fail(BIGSI_ERR_INVALID, "both indexes must live on the same device");
+    if (r.same_hashes && dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
+    TRY(bigsi_writable(dst));
+    if (dst->d_index == src->d_index) return fail(BIGSI_ERR_INVALID, "%s: src is a view of dst (%s)", r.name, hint.c_str());
+    if (!r.into_empty) return BIGSI_OK;
+    if (dst->views.load() > 0)
+        return fail(BIGSI_ERR_STATE, "%s: %d view(s) of the destination are open: their column count would go stale", r.name, dst->views.load());
+    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "%s: the destination already holds %llu column(s)", r.name, (unsigned long long)dst->n_cols);
+    return BIGSI_OK;
+}
+
+// Both handles are held for the whole call: the source's matrix must not be re-strided, folded, compacted or closed by another host
+// thread under the kernel that reads it.
+#define BIGSI_ENTER_DERIVE(dstp, srcp)                                                                                             \
+    BIGSI_ENTER(dstp);                                                                                                             \
+    BusyGuard src_guard_(srcp);                                                                                                    \
+    if (!src_guard_.ok)                                                                                                            \
+        return fail(BIGSI_ERR_STATE, "the source index handle is in use by another host thread (one handle = one thread at a time)")
+
+// ... and what they do once the checks are through: room for `cols` columns in the destination, nothing reading it on another
+// stream, and the source's stream drained (streams of different handles are not ordered with each other)
+static int begin_derive(bigsi_hip_index *dst, const bigsi_hip_index *src, uint64_t cols)
+{
+    TRY(bigsi_hip_reserve_cols(dst, cols));
+    TRY(use_device(dst));
+    TRY(quiesce_index(dst));
+    HIP_TRY(hipStreamSynchronize(src->stream));
+    return BIGSI_OK;
+}
+
 // the matrix of a new handle: allocated and zeroed here (ipc == nullptr && view == nullptr), another process's allocation mapped
 // into this one (ipc), or another handle's pointer (view)
 static int open_impl(uint64_t num_rows, uint64_t num_cols, uint64_t col_capacity, uint32_t num_hashes, int device, const hipIpcMemHandle_t *ipc,
@@ -361,26 +457,10 @@ extern "C" int bigsi_hip_reserve_cols(bigsi_hip_index *ix, uint64_t col_capacity
 {
     BIGSI_ENTER(ix);
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
-    if (col_capacity <= ix->cap_cols) return BIGSI_OK;
-    TRY(bigsi_writable(ix));          // (only a call that would really re-stride the matrix needs to own it)
+    if (col_capacity <= ix->cap_cols) return BIGSI_OK;          // (only a call that would really re-stride the matrix needs to own it)
     if (col_capacity > 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "col_capacity exceeds 2^32-1");
-    if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_reserve_cols: re-striding would move the matrix under %d open view(s)", ix->views.load());
-    TRY(use_device(ix));
-    TRY(quiesce_index(ix));
-    const uint64_t ns = stride_for(col_capacity);
-    uint64_t *nd = nullptr;
-    HIP_TRY(hipMalloc((void **)&nd, (size_t)ix->m * ns * 8));
-    const uint64_t total = ix->m * ns;
-    const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(total, kBlock), 256 * 8 * 4);
-    hipLaunchKernelGGL(k_restride, dim3(grid), dim3(kBlock), 0, ix->stream, ix->d_index, ix->stride_words, nd, ns, ix->m);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ix->stream));
-    HIP_TRY(hipFree(ix->d_index));
-    ix->d_index = nd;
-    ix->alloc_rows = ix->m;          // (the new allocation holds the rows the index has: what a fold left behind them is gone)
-    ix->stride_words = ns;
-    ix->cap_cols = ns * 64;
-    return BIGSI_OK;
+    TRY(begin_rewrite(ix, "bigsi_hip_reserve_cols", "re-striding would move the matrix under them"));
+    return replace_matrix(ix, stride_for(col_capacity), "bigsi_hip_reserve_cols");
 }
 
 extern "C" int bigsi_hip_set_stream(bigsi_hip_index *ix, void *hip_stream)
@@ -1027,17 +1107,10 @@ extern "C" int bigsi_hip_insert_columns_device(bigsi_hip_index *ix, uint64_t col
 
 extern "C" int bigsi_hip_append_index(bigsi_hip_index *dst, const bigsi_hip_index *src)
 {
-    BIGSI_ENTER(dst);
-    TRY(bigsi_writable(dst));
-    if (!dst || !src) return fail(BIGSI_ERR_INVALID, "NULL argument");
-    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot append an index to itself");
-    if (dst->m != src->m) return fail(BIGSI_ERR_INVALID, "row counts differ (%llu vs %llu)", (unsigned long long)dst->m, (unsigned long long)src->m);
-    if (dst->device != src->device) return fail(BIGSI_ERR_INVALID, "both indexes must live on the same device");
+    BIGSI_ENTER_DERIVE(dst, src);
+    TRY(check_derive({"bigsi_hip_append_index", /*in_place*/ nullptr, /*rows_divide*/ false, /*same_hashes*/ false, /*into_empty*/ false}, dst, src));
     if (src->n_cols == 0) return BIGSI_OK;
-    TRY(bigsi_hip_reserve_cols(dst, dst->n_cols + src->n_cols));
-    TRY(use_device(dst));
-    TRY(quiesce_index(dst));
-    HIP_TRY(hipStreamSynchronize(src->stream));
+    TRY(begin_derive(dst, src, dst->n_cols + src->n_cols));
     const uint64_t per_row = ceil_div(dst->n_cols + src->n_cols, 64) - (dst->n_cols >> 6);
     const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(dst->m * per_row, kBlock), 256 * 64);
     hipLaunchKernelGGL(k_append_columns, dim3(grid), dim3(kBlock), 0, dst->stream, dst->d_index, dst->stride_words, dst->n_cols,
@@ -1138,13 +1211,10 @@ extern "C" int bigsi_hip_compact_columns(bigsi_hip_index *ix, const uint8_t *kee
 {
     BIGSI_ENTER(ix);
     if (!ix || !keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
-    TRY(bigsi_writable(ix));
-    if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_compact_columns: the column count of %d open view(s) would go stale", ix->views.load());
+    TRY(begin_rewrite(ix, "bigsi_hip_compact_columns", "their column count would go stale"));          // (a view is refused whatever `keep` says)
     const uint64_t kept = count_kept_columns(ix->n_cols, keep);
     if (kept < ix->n_cols) {          // (every column kept: the matrix stays as it is, byte for byte, and no table is built)
         const CompactPlan p = plan_compact_columns(ix->n_cols, keep, ix->m);
-        TRY(use_device(ix));
-        TRY(quiesce_index(ix));
         TRY(compact_launch(ix, ix, p));
         ix->n_cols = p.kept;
     }
@@ -1154,19 +1224,11 @@ extern "C" int bigsi_hip_compact_columns(bigsi_hip_index *ix, const uint8_t *kee
 
 extern "C" int bigsi_hip_extract_columns(bigsi_hip_index *dst, const bigsi_hip_index *src, const uint8_t *keep)
 {
-    BIGSI_ENTER(dst);
-    if (!dst || !src || !keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
-    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot extract an index into itself (bigsi_hip_compact_columns works in place)");
-    if (dst->m != src->m) return fail(BIGSI_ERR_INVALID, "row counts differ (%llu vs %llu)", (unsigned long long)dst->m, (unsigned long long)src->m);
-    if (dst->device != src->device) return fail(BIGSI_ERR_INVALID, "both indexes must live on the same device");
-    TRY(bigsi_writable(dst));
-    if (dst->d_index == src->d_index) return fail(BIGSI_ERR_INVALID, "src is a view of dst (bigsi_hip_compact_columns works in place)");
-    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_extract_columns: the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
+    BIGSI_ENTER_DERIVE(dst, src);
+    if (!keep) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_derive({"bigsi_hip_extract_columns", /*in_place*/ "bigsi_hip_compact_columns", /*rows_divide*/ false, /*same_hashes*/ false, /*into_empty*/ true}, dst, src));
     const CompactPlan p = plan_compact_columns(src->n_cols, keep, dst->m);
-    TRY(bigsi_hip_reserve_cols(dst, p.kept));
-    TRY(use_device(dst));
-    TRY(quiesce_index(dst));
-    HIP_TRY(hipStreamSynchronize(src->stream));
+    TRY(begin_derive(dst, src, p.kept));
     TRY(compact_launch(dst, src, p));
     dst->n_cols = p.kept;
     return BIGSI_OK;
@@ -1177,56 +1239,30 @@ extern "C" int bigsi_hip_shrink_to_fit(bigsi_hip_index *ix)
     BIGSI_ENTER(ix);
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
     const uint64_t ns = stride_for(std::max<uint64_t>(ix->n_cols, 1));
-    if (ns >= ix->stride_words) return BIGSI_OK;
-    TRY(bigsi_writable(ix));          // (as bigsi_hip_reserve_cols: only a call that would really re-stride the matrix needs to own it)
-    if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_shrink_to_fit: re-striding would move the matrix under %d open view(s)", ix->views.load());
-    TRY(use_device(ix));
-    TRY(quiesce_index(ix));
-    uint64_t *nd = nullptr;
-    HIP_TRY(hipMalloc((void **)&nd, (size_t)ix->m * ns * 8));
-    const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(ix->m * ns, kBlock), 256 * 8 * 4);
-    hipLaunchKernelGGL(k_restride, dim3(grid), dim3(kBlock), 0, ix->stream, ix->d_index, ix->stride_words, nd, ns, ix->m);      // (copies min(old, new) words per row)
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ix->stream));
-    HIP_TRY(hipFree(ix->d_index));
-    ix->d_index = nd;
-    ix->alloc_rows = ix->m;          // (the new allocation holds the rows the index has: what a fold left behind them is gone)
-    ix->stride_words = ns;
-    ix->cap_cols = ns * 64;
-    return BIGSI_OK;
+    if (ns >= ix->stride_words) return BIGSI_OK;          // (as bigsi_hip_reserve_cols: only a call that would really re-stride the matrix needs to own it)
+    TRY(begin_rewrite(ix, "bigsi_hip_shrink_to_fit", "re-striding would move the matrix under them"));
+    return replace_matrix(ix, ns, "bigsi_hip_shrink_to_fit");
 }
 
 // Column collapse (k_collapse_columns; tables, launch shape and destination window: plan_collapse_columns).  The tables live for this
 // call only, like the compaction's: 4 bytes per source column and 8 per source word, 412 KB for 100 k columns.
 extern "C" int bigsi_hip_collapse_columns_into(bigsi_hip_index *dst, const bigsi_hip_index *src, const uint32_t *group_of, uint64_t num_groups)
 {
-    BIGSI_ENTER(dst);
-    BusyGuard src_guard(src);          // (both handles are held: the source's matrix must not move or change under the sweep)
-    if (!src_guard.ok) return fail(BIGSI_ERR_STATE, "the source index handle is in use by another host thread (one handle = one thread at a time)");
+    BIGSI_ENTER_DERIVE(dst, src);
     if (!dst || !src || !group_of) return fail(BIGSI_ERR_INVALID, "NULL argument");
     if (num_groups == 0 || num_groups >= 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "num_groups %llu is not in [1, 2^32 - 1)", (unsigned long long)num_groups);
-    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot collapse an index into itself (there is no in-place form)");
-    if (dst->m != src->m) return fail(BIGSI_ERR_INVALID, "row counts differ (%llu vs %llu)", (unsigned long long)dst->m, (unsigned long long)src->m);
-    if (dst->device != src->device) return fail(BIGSI_ERR_INVALID, "both indexes must live on the same device");
-    if (dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
+    TRY(check_derive({"bigsi_hip_collapse_columns_into", /*in_place*/ nullptr, /*rows_divide*/ false, /*same_hashes*/ true, /*into_empty*/ true}, dst, src));
     const uint64_t bad = collapse_first_bad(src->n_cols, group_of, num_groups);
     if (bad < src->n_cols)
         return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither a group id below %llu nor BIGSI_COLLAPSE_DROPPED", (unsigned long long)bad, group_of[bad],
                     (unsigned long long)num_groups);
-    TRY(bigsi_writable(dst));
-    if (dst->d_index == src->d_index) return fail(BIGSI_ERR_INVALID, "src is a view of dst (there is no in-place form)");
-    if (dst->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_collapse_columns_into: the column count of %d open view(s) of the destination would go stale", dst->views.load());
-    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_collapse_columns_into: the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
     const CollapsePlan p = plan_collapse_columns(src->n_cols, group_of, num_groups, dst->m);
-    TRY(bigsi_hip_reserve_cols(dst, num_groups));
+    TRY(begin_derive(dst, src, num_groups));
     if (p.table_words > src->stride_words || round_up(p.dst_words, 2) > dst->stride_words || src->stride_words % kVec || dst->stride_words % kVec ||
         p.lds_bytes > kCollapseLdsBytes || p.image_words % 2 || p.grid == 0 || p.grid > 0x7FFFFFFFull)
         return fail(BIGSI_ERR_STATE, "internal: a collapse plan of %llu source and %llu destination words does not fit the row strides (%llu, %llu) or the LDS (%llu bytes)",
                     (unsigned long long)p.table_words, (unsigned long long)p.dst_words, (unsigned long long)src->stride_words,
                     (unsigned long long)dst->stride_words, (unsigned long long)p.lds_bytes);
-    TRY(use_device(dst));
-    TRY(quiesce_index(dst));
-    HIP_TRY(hipStreamSynchronize(src->stream));
     CallScratch tab;
     const uint64_t bit_bytes = std::max<uint64_t>(p.dst_bit.size() * 4, 16), live_bytes = std::max<uint64_t>(p.live.size() * 8, 16);
     TRY(tab.buf.reserve(bit_bytes + live_bytes));          // (bit_bytes is a multiple of 16: live is read 16 bytes at a time)
@@ -1292,10 +1328,7 @@ extern "C" int bigsi_hip_fold_rows(bigsi_hip_index *ix, uint64_t factor, uint64_
     if (factor == 0 || ix->m % factor)
         return fail(BIGSI_ERR_INVALID, "fold factor %llu does not divide num_rows %llu", (unsigned long long)factor, (unsigned long long)ix->m);
     if (factor > 1) {          // (factor 1: the index stays as it is, and nothing is touched)
-        TRY(bigsi_writable(ix));
-        if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_fold_rows: the row count of %d open view(s) would go stale", ix->views.load());
-        TRY(use_device(ix));
-        TRY(quiesce_index(ix));
+        TRY(begin_rewrite(ix, "bigsi_hip_fold_rows", "their row count would go stale"));
         const uint64_t m_dst = ix->m / factor;
         TRY(fold_launch(ix, ix, m_dst, factor, ix->n_cols));
         ix->m = m_dst;          // (alloc_rows stays: bigsi_hip_trim_rows gives the rows behind m back)
@@ -1306,20 +1339,9 @@ extern "C" int bigsi_hip_fold_rows(bigsi_hip_index *ix, uint64_t factor, uint64_
 
 extern "C" int bigsi_hip_fold_rows_into(bigsi_hip_index *dst, const bigsi_hip_index *src)
 {
-    BIGSI_ENTER(dst);
-    if (!dst || !src) return fail(BIGSI_ERR_INVALID, "NULL argument");
-    if (dst == src) return fail(BIGSI_ERR_INVALID, "cannot fold an index into itself (bigsi_hip_fold_rows works in place)");
-    if (dst->m == 0 || src->m % dst->m)
-        return fail(BIGSI_ERR_INVALID, "the destination's num_rows %llu does not divide the source's %llu", (unsigned long long)dst->m, (unsigned long long)src->m);
-    if (dst->device != src->device) return fail(BIGSI_ERR_INVALID, "both indexes must live on the same device");
-    if (dst->h != src->h) return fail(BIGSI_ERR_INVALID, "num_hashes differ (%u vs %u)", dst->h, src->h);
-    TRY(bigsi_writable(dst));
-    if (dst->d_index == src->d_index) return fail(BIGSI_ERR_INVALID, "src is a view of dst (bigsi_hip_fold_rows works in place)");
-    if (dst->n_cols != 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_fold_rows_into: the destination already holds %llu column(s)", (unsigned long long)dst->n_cols);
-    TRY(bigsi_hip_reserve_cols(dst, src->n_cols));
-    TRY(use_device(dst));
-    TRY(quiesce_index(dst));
-    HIP_TRY(hipStreamSynchronize(src->stream));
+    BIGSI_ENTER_DERIVE(dst, src);
+    TRY(check_derive({"bigsi_hip_fold_rows_into", /*in_place*/ "bigsi_hip_fold_rows", /*rows_divide*/ true, /*same_hashes*/ true, /*into_empty*/ true}, dst, src));
+    TRY(begin_derive(dst, src, src->n_cols));
     TRY(fold_launch(dst, src, dst->m, src->m / dst->m, src->n_cols));
     dst->n_cols = src->n_cols;
     return BIGSI_OK;
@@ -1331,29 +1353,8 @@ extern "C" int bigsi_hip_trim_rows(bigsi_hip_index *ix)
     if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
     TRY(bigsi_writable(ix));          // (a handle that does not own the matrix does not know its allocation: refused whatever there is to gain)
     if (ix->alloc_rows <= ix->m) return BIGSI_OK;
-    if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_trim_rows: trimming would move the matrix under %d open view(s)", ix->views.load());
-    TRY(use_device(ix));
-    TRY(quiesce_index(ix));
-    HIP_TRY(hipStreamSynchronize(ix->stream));
-    const size_t bytes = (size_t)ix->m * ix->stride_words * 8;
-    uint64_t *nd = nullptr;
-    hipError_t e = hipMalloc((void **)&nd, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();          // (the runtime's last-error slot is sticky: the next launch check of this thread must not inherit it)
-        return fail(e == hipErrorOutOfMemory ? BIGSI_ERR_NOMEM : BIGSI_ERR_HIP, "bigsi_hip_trim_rows: hipMalloc of %zu bytes beside the matrix failed: %s", bytes,
-                    hipGetErrorString(e));
-    }
-    // rows [0, m) are the front of the old allocation, at the same stride: one device-to-device copy
-    e = hipMemcpyAsync(nd, ix->d_index, bytes, hipMemcpyDeviceToDevice, ix->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
-    if (e != hipSuccess) {
-        hipError_t e2 = hipFree(nd); (void)e2;
-        return fail(BIGSI_ERR_HIP, "bigsi_hip_trim_rows: copying the rows failed: %s", hipGetErrorString(e));
-    }
-    HIP_TRY(hipFree(ix->d_index));
-    ix->d_index = nd;
-    ix->alloc_rows = ix->m;
-    return BIGSI_OK;
+    TRY(begin_rewrite(ix, "bigsi_hip_trim_rows", "trimming would move the matrix under them"));
+    return replace_matrix(ix, ix->stride_words, "bigsi_hip_trim_rows");          // rows [0, m) are the front of the old allocation, at the same stride
 }
 
 static int check_offsets(const uint64_t *offsets, uint32_t n_seqs)

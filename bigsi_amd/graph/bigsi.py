@@ -725,9 +725,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         if isinstance(seqs, (str, bytes)):
             raise TypeError("seqs must be a list of sequences, got %r" % type(seqs))
         seqs = list(seqs)
-        if self.storage.res.is_group:
-            from .._lib import ERR_STATE, BigsiHipError
-            raise BigsiHipError(ERR_STATE, "k-mer prevalence is not available for multi-GPU (devices=[...]) indexes")
+        self._refuse_group("k-mer prevalence")
         for s in seqs:
             if not s.isascii():
                 raise ValueError("k-mer prevalence takes ASCII sequences (queries with other characters are out of scope)")
@@ -807,40 +805,20 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         |subset| / N of the bytes per query.  KeyError for a name that is unknown or deleted, ValueError for an empty list or a
         name given twice.  Returns the new BIGSI."""
         from ..compact import extract_plan
-        from .index import BLOOMFILTER_SIZE_KEY, NUM_HASH_FUNCTS_KEY
         if isinstance(samples, (str, bytes)):
             raise TypeError("samples must be a list of sample names, got %r" % type(samples))
         samples = list(samples)
         if not samples or len(set(samples)) != len(samples):
             extract_plan([], samples)                   # (raises the ValueError, before anything is read)
-        if self.storage.res.is_group:
-            from .._lib import ERR_STATE, BigsiHipError
-            raise BigsiHipError(ERR_STATE, "column extraction is not available for multi-GPU (devices=[...]) indexes")
+        self._refuse_group("column extraction")
         with self._device_lock():
             keep, picked = extract_plan(self._colour_names(), samples)
-            for key, mine in (("m", self.bloomfilter_size), ("h", self.num_hashes), ("k", self.kmer_size)):
-                if int(config[key]) != int(mine):
-                    raise ValueError("the new index must have this one's %s (%d), its config says %d" % (key, mine, config[key]))
-            storage = get_storage(config)
-            if storage.res is self.storage.res:
-                raise ValueError("the new index needs a storage-config name of its own")
-            if SampleMetadata(storage).num_samples or int(storage.get("number_of_cols:int", b"0")):
-                raise ValueError("the index described by the new config is not empty")
-            try:
-                storage.set_integer(BLOOMFILTER_SIZE_KEY, int(self.bloomfilter_size))
-                storage.set_integer(NUM_HASH_FUNCTS_KEY, int(self.num_hashes))
-                storage.set_integer("number_of_rows", int(self.bloomfilter_size))
-                storage.set_integer("number_of_cols", 0)
-                storage.res.ensure_open()
+
+            def fill(storage):
                 if storage.extract_columns_from(self.storage, keep) != len(picked):
                     raise RuntimeError("the device extracted another number of columns than the metadata names")
                 SampleMetadata(storage).add_samples(picked)
-                storage.sync()
-            except BaseException:
-                storage.delete_all()          # (it was empty when we came: nothing half-made stays resident under the new name)
-                raise
-            storage.close()
-        return type(self)(config)
+            return self._derive(config, self.bloomfilter_size, fill)
 
     # ------------------------------------------------------------------ column collapse: groups of samples ORed into one column each
     def collapse(self, config, groups, keep_others=False):
@@ -855,30 +833,47 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         collapse.collapse_plan says (which also gives the membership: collapse_plan(names, groups, keep_others)[2]).  Returns the
         new BIGSI."""
         from ..collapse import check_groups, collapse_plan
-        from .index import BLOOMFILTER_SIZE_KEY, NUM_HASH_FUNCTS_KEY
         check_groups(groups, keep_others)               # (whatever it raises, it raises before anything is read)
-        if self.storage.res.is_group:
-            from .._lib import ERR_STATE, BigsiHipError
-            raise BigsiHipError(ERR_STATE, "column collapse is not available for multi-GPU (devices=[...]) indexes")
+        self._refuse_group("column collapse")
         with self._device_lock():
             group_of, group_names, _ = collapse_plan(self._colour_names(), groups, keep_others)
-            for key, mine in (("m", self.bloomfilter_size), ("h", self.num_hashes), ("k", self.kmer_size)):
-                if int(config[key]) != int(mine):
-                    raise ValueError("the new index must have this one's %s (%d), its config says %d" % (key, mine, config[key]))
+
+            def fill(storage):
+                if self.storage.collapse_columns_into(storage, group_of, len(group_names)) != len(group_names):
+                    raise RuntimeError("the device made another number of columns than there are groups")
+                SampleMetadata(storage).add_samples(group_names)
+            return self._derive(config, self.bloomfilter_size, fill)
+
+    # ------------------------------------------------------------------ what extract, collapse and fold_into share
+    def _refuse_group(self, what):
+        if self.storage.res.is_group:
+            from .._lib import ERR_STATE, BigsiHipError
+            raise BigsiHipError(ERR_STATE, "%s is not available for multi-GPU (devices=[...]) indexes" % what)
+
+    def _check_derived_config(self, config, new_m):
+        for key, want in (("m", new_m), ("h", self.num_hashes), ("k", self.kmer_size)):
+            if int(config[key]) != int(want):
+                raise ValueError("the new index must have %s = %d, its config says %d" % (key, want, config[key]))
+
+    def _derive(self, config, new_m, fill):
+        """The index under `config` (m = new_m, this index's h and k, a storage-config name of its own, nothing stored under it yet)
+        made from this one by fill(storage): the device call into the opened, empty storage and the sample metadata that goes with
+        it.  On any failure the new storage is emptied again.  Returns the new BIGSI."""
+        from .index import BLOOMFILTER_SIZE_KEY, NUM_HASH_FUNCTS_KEY
+        self._check_derived_config(config, new_m)
+        with self._device_lock():
             storage = get_storage(config)
             if storage.res is self.storage.res:
                 raise ValueError("the new index needs a storage-config name of its own")
             if SampleMetadata(storage).num_samples or int(storage.get("number_of_cols:int", b"0")):
                 raise ValueError("the index described by the new config is not empty")
             try:
-                storage.set_integer(BLOOMFILTER_SIZE_KEY, int(self.bloomfilter_size))
+                storage.set_integer(BLOOMFILTER_SIZE_KEY, int(new_m))
                 storage.set_integer(NUM_HASH_FUNCTS_KEY, int(self.num_hashes))
-                storage.set_integer("number_of_rows", int(self.bloomfilter_size))
+                storage.set_integer("number_of_rows", int(new_m))
                 storage.set_integer("number_of_cols", 0)
                 storage.res.ensure_open()
-                if self.storage.collapse_columns_into(storage, group_of, len(group_names)) != len(group_names):
-                    raise RuntimeError("the device made another number of columns than there are groups")
-                SampleMetadata(storage).add_samples(group_names)
+                fill(storage)
                 storage.sync()
             except BaseException:
                 storage.delete_all()          # (it was empty when we came: nothing half-made stays resident under the new name)
@@ -887,11 +882,6 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         return type(self)(config)
 
     # ------------------------------------------------------------------ row folding: the same index under a smaller Bloom filter
-    def _refuse_group_fold(self):
-        if self.storage.res.is_group:
-            from .._lib import ERR_STATE, BigsiHipError
-            raise BigsiHipError(ERR_STATE, "row folding is not available for multi-GPU (devices=[...]) indexes")
-
     def fold(self, factor, trim=True):
         """Fold the index in place to m' = m / factor rows (bigsi_hip_fold_rows: row r becomes the OR of the rows r, r + m', ...,
         r + (factor - 1) m').  Because a k-mer's row is floor_mod(hash, m) and m' divides m, the result is bit for bit the index
@@ -907,7 +897,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         if not isinstance(trim, bool):
             raise TypeError("trim must be a bool, got %r" % (trim,))
         new_m = fold_plan(int(self.bloomfilter_size), factor)
-        self._refuse_group_fold()
+        self._refuse_group("row folding")
         with self._device_lock():
             st = self.storage
             trimmed = False
@@ -939,37 +929,18 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         unchanged: same colours, and deleted samples stay deleted.  On any failure the new storage is emptied again.  Returns the
         new BIGSI."""
         from ..fold import fold_plan
-        from .index import BLOOMFILTER_SIZE_KEY, NUM_HASH_FUNCTS_KEY
         from .metadata import _k
         new_m = fold_plan(int(self.bloomfilter_size), factor)
-        for key, mine in (("m", new_m), ("h", self.num_hashes), ("k", self.kmer_size)):
-            if int(config[key]) != int(mine):
-                raise ValueError("the new index must have %s = %d, its config says %d" % (key, mine, config[key]))
-        self._refuse_group_fold()
-        with self._device_lock():
-            storage = get_storage(config)
-            if storage.res is self.storage.res:
-                raise ValueError("the new index needs a storage-config name of its own")
-            if SampleMetadata(storage).num_samples or int(storage.get("number_of_cols:int", b"0")):
-                raise ValueError("the index described by the new config is not empty")
-            try:
-                storage.set_integer(BLOOMFILTER_SIZE_KEY, new_m)
-                storage.set_integer(NUM_HASH_FUNCTS_KEY, int(self.num_hashes))
-                storage.set_integer("number_of_rows", new_m)
-                storage.set_integer("number_of_cols", 0)
-                storage.res.ensure_open()
-                cols = int(self.storage.get_integer("number_of_cols"))
-                if storage.fold_rows_from(self.storage) != cols:
-                    raise RuntimeError("the device folded another number of columns than the index holds")
-                mine = self.storage
-                for key in mine.record_keys(_k("")):          # colours, names and the tombstones of deleted samples, as they are
-                    storage[key] = mine[key]
-                storage.sync()
-            except BaseException:
-                storage.delete_all()          # (it was empty when we came: nothing half-made stays resident under the new name)
-                raise
-            storage.close()
-        return type(self)(config)
+        self._check_derived_config(config, new_m)          # (a config that does not fit is a bad argument: said before the storage is looked at)
+        self._refuse_group("row folding")
+
+        def fill(storage):
+            mine = self.storage
+            if storage.fold_rows_from(mine) != int(mine.get_integer("number_of_cols")):
+                raise RuntimeError("the device folded another number of columns than the index holds")
+            for key in mine.record_keys(_k("")):          # colours, names and the tombstones of deleted samples, as they are
+                storage[key] = mine[key]
+        return self._derive(config, new_m, fill)
 
     def _device_lock(self):
         import threading

@@ -390,9 +390,7 @@ class HipHbmStorage(BaseStorage):
 
     def insert_column(self, col, bloom_bytes):
         """BitMatrix.insert_column on the device (bigsi/matrix/bitmatrix.py:67-75)."""
-        res = self.res
-        if not res.ensure_open():
-            raise KeyError("number_of_rows:int")
+        res = self._opened()
         if col >= res.info().col_capacity:
             res.reserve_cols(max(col + 1, 2 * int(res.info().col_capacity)))
         buf = np.frombuffer(bytes(bloom_bytes), dtype=np.uint8)
@@ -408,9 +406,7 @@ class HipHbmStorage(BaseStorage):
 
     def insert_columns(self, col0, blooms):
         """n Bloom filters (uint8[n, >= ceil(m/8)]) -> columns [col0, col0+n): the transpose runs on the device."""
-        res = self.res
-        if not res.ensure_open():
-            raise KeyError("number_of_rows:int")
+        res = self._opened()
         blooms = np.ascontiguousarray(blooms, dtype=np.uint8)
         n, need = blooms.shape[0], (res.m + 7) // 8
         if blooms.shape[1] < need:
@@ -422,8 +418,7 @@ class HipHbmStorage(BaseStorage):
 
     def append_from(self, other):
         """Append every column of another resident hip-hbm index (same device, same m), device to device."""
-        if self.res.is_group or other.res.is_group:
-            raise BigsiHipError(_lib.ERR_STATE, "merge is not available for multi-GPU (devices=[...]) indexes")
+        self._single_gpu("merge", other)
         check(_lib.lib().bigsi_hip_append_index(self.handle, other.handle))
         self._after_column_move()
 
@@ -437,6 +432,17 @@ class HipHbmStorage(BaseStorage):
         for k in keys:
             self.res.kv.pop(self.convert_key_to_bytes(k), None)
 
+    def _opened(self):
+        """The resident index, opened; the KeyError of a store that has no number_of_rows yet otherwise."""
+        if not self.res.ensure_open():
+            raise KeyError("number_of_rows:int")
+        return self.res
+
+    def _single_gpu(self, what, *others, why=None):
+        """The maintenance calls work on one device's matrix: a multi-GPU index, here or among `others`, is refused."""
+        if any(st.res.is_group for st in (self,) + others):
+            raise BigsiHipError(_lib.ERR_STATE, why or "%s is not available for multi-GPU (devices=[...]) indexes" % what)
+
     def _after_column_move(self):
         """Every row was rewritten on the device at the index's new width: what insert / merge / compaction leave behind."""
         self.res.written[:] = True
@@ -448,8 +454,7 @@ class HipHbmStorage(BaseStorage):
         the new number of columns.  `keep`: a bool array of num_cols entries, or the packed bitmap as a uint8 array / bytes
         (ceil(num_cols / 8) bytes, column c at byte c // 8 under 0x80 >> (c % 8))."""
         from ..compact import keep_bytes
-        if self.res.is_group:
-            raise BigsiHipError(_lib.ERR_STATE, "column compaction is not available for multi-GPU (devices=[...]) indexes")
+        self._single_gpu("column compaction")
         buf = keep_bytes(keep, int(self.res.info().num_cols) if self.res.ensure_open() else 0)
         kept = _lib.C.c_uint64(0)
         check(_lib.lib().bigsi_hip_compact_columns(self.handle, _lib.ptr(buf), _lib.C.byref(kept)))
@@ -460,8 +465,7 @@ class HipHbmStorage(BaseStorage):
         """The columns of another resident hip-hbm index (same device, same m) that `keep` names become the columns of this one, which
         must hold none yet (bigsi_hip_extract_columns); `other` is only read.  Returns the number of columns."""
         from ..compact import keep_bytes
-        if self.res.is_group or other.res.is_group:
-            raise BigsiHipError(_lib.ERR_STATE, "column extraction is not available for multi-GPU (devices=[...]) indexes")
+        self._single_gpu("column extraction", other)
         buf = keep_bytes(keep, int(other.res.info().num_cols) if other.res.ensure_open() else 0)
         check(_lib.lib().bigsi_hip_extract_columns(self.handle, other.handle, _lib.ptr(buf)))
         self._after_column_move()
@@ -473,8 +477,7 @@ class HipHbmStorage(BaseStorage):
         read.  group_of: one unsigned 32-bit entry per column, a group id below num_groups or collapse.DROPPED.  Returns the number of
         columns of dst (num_groups)."""
         from ..collapse import group_ids
-        if self.res.is_group or dst.res.is_group:
-            raise BigsiHipError(_lib.ERR_STATE, "column collapse is not available for multi-GPU (devices=[...]) indexes")
+        self._single_gpu("column collapse", dst)
         buf = group_ids(group_of, int(self.res.info().num_cols) if self.res.ensure_open() else 0, num_groups)
         check(_lib.lib().bigsi_hip_collapse_columns_into(dst.handle, self.handle, _lib.ptr(buf), int(num_groups)))
         dst._after_column_move()
@@ -482,8 +485,7 @@ class HipHbmStorage(BaseStorage):
 
     def shrink_to_fit(self):
         """Give back the row stride beyond the columns the index holds (bigsi_hip_shrink_to_fit): the counterpart of reserve_cols."""
-        if self.res.is_group:
-            raise BigsiHipError(_lib.ERR_STATE, "a multi-GPU index keeps the shard width it was opened with")
+        self._single_gpu("shrink_to_fit", why="a multi-GPU index keeps the shard width it was opened with")
         check(_lib.lib().bigsi_hip_shrink_to_fit(self.handle))
         self._after_column_move()
 
@@ -503,11 +505,8 @@ class HipHbmStorage(BaseStorage):
         r, r + m', ..., r + (factor - 1) m' -- the matrix of the same samples under a Bloom filter of m' bits.  Returns m'.  The
         allocation keeps its size until trim_rows()."""
         from ..fold import fold_plan
-        if self.res.is_group:
-            raise BigsiHipError(_lib.ERR_STATE, "row folding is not available for multi-GPU (devices=[...]) indexes")
-        if not self.res.ensure_open():
-            raise KeyError("number_of_rows:int")
-        fold_plan(int(self.res.m), factor)
+        self._single_gpu("row folding")
+        fold_plan(int(self._opened().m), factor)
         new = _lib.C.c_uint64(0)
         check(_lib.lib().bigsi_hip_fold_rows(self.handle, int(factor), _lib.C.byref(new)))
         if factor > 1:
@@ -517,10 +516,7 @@ class HipHbmStorage(BaseStorage):
     def fold_rows_from(self, other):
         """Another resident hip-hbm index (same device, same h), folded by other's rows / this one's rows, becomes the content of
         this one, which must hold no columns yet (bigsi_hip_fold_rows_into); `other` is only read.  Returns the number of columns."""
-        if self.res.is_group or other.res.is_group:
-            raise BigsiHipError(_lib.ERR_STATE, "row folding is not available for multi-GPU (devices=[...]) indexes")
-        if not (self.res.ensure_open() and other.res.ensure_open()):
-            raise KeyError("number_of_rows:int")
+        self._single_gpu("row folding", other)
         check(_lib.lib().bigsi_hip_fold_rows_into(self.handle, other.handle))
         self._after_column_move()
         return int(self.res.info().num_cols)
@@ -529,10 +525,7 @@ class HipHbmStorage(BaseStorage):
         """Give back the rows of the allocation behind num_rows (bigsi_hip_trim_rows): the counterpart of fold_rows, as
         shrink_to_fit is of compact_columns.  Needs room for the smaller copy while it runs (BigsiHipError with code ERR_NOMEM
         otherwise, the index unchanged)."""
-        if self.res.is_group:
-            raise BigsiHipError(_lib.ERR_STATE, "a multi-GPU index keeps the rows it was opened with")
-        if not self.res.ensure_open():
-            raise KeyError("number_of_rows:int")
+        self._single_gpu("trim_rows", why="a multi-GPU index keeps the rows it was opened with")
         check(_lib.lib().bigsi_hip_trim_rows(self.handle))
 
     def get_column(self, col):
@@ -546,9 +539,7 @@ class HipHbmStorage(BaseStorage):
         `mask`, the number of those among the rows the mask selects: |mask AND column| for every sample in one sweep of the matrix
         (bigsi_hip_column_popcounts / its group twin).  `mask`: a Bloom filter of this index as a BitRow / bitarray (num_rows
         bits), or its bytes / a uint8 array (ceil(num_rows / 8) bytes, the layout get_column returns)."""
-        res = self.res
-        if not res.ensure_open():
-            raise KeyError("number_of_rows:int")
+        res = self._opened()
         nb = (res.m + 7) // 8
         buf = None
         if mask is not None:
@@ -580,11 +571,8 @@ class HipHbmStorage(BaseStorage):
         (ceil(num_cols / 8) bytes as uint8 arrays or bytes; bits at columns >= num_cols are ignored).  Returns (pos_offsets
         np.uint64[n + 1], total np.uint32[positions], in_subset np.uint32[positions] or None): total counts the samples of the
         universe (all without one), in_subset those that are also in the subset."""
-        res = self.res
-        if res.is_group:
-            raise BigsiHipError(_lib.ERR_STATE, "k-mer prevalence is not available for multi-GPU (devices=[...]) indexes")
-        if not res.ensure_open():
-            raise KeyError("number_of_rows:int")
+        self._single_gpu("k-mer prevalence")
+        res = self._opened()
         seqs = list(seqs)
         if not seqs:
             return np.zeros(1, np.uint64), np.zeros(0, np.uint32), None
@@ -624,9 +612,7 @@ class HipHbmStorage(BaseStorage):
     # ---- fused query path
     @property
     def handle(self):
-        if not self.res.ensure_open():
-            raise KeyError("number_of_rows:int")
-        return self.res.ix
+        return self._opened().ix
 
     def lookup_kmers(self, kmers):
         """{kmer: row bytes} for a list of distinct k-mer strings (graph/index.py:42-49); any lengths."""

@@ -170,7 +170,9 @@ int bigsi_hip_insert_column(bigsi_hip_index *ix, uint64_t col, const uint8_t *bl
 int bigsi_hip_insert_columns(bigsi_hip_index *ix, uint64_t col0, uint64_t n, const uint8_t *blooms, uint64_t bloom_stride_bytes);
 /* KmerSignatureIndex.merge_indexes (bigsi/graph/index.py:54-60): append all columns of src after dst's, device to
  * device (same device, same num_rows); dst's capacity grows as needed.  Only columns [0, src num_cols) of src are read: bits
- * its rows hold behind them do not reach dst, whose rows are zero behind the appended columns; src is not changed. */
+ * its rows hold behind them do not reach dst, whose rows are zero behind the appended columns; src is not changed and may be a
+ * view or an ipc handle of another index (a view of dst itself: BIGSI_ERR_INVALID).  Both handles are held for the duration of the
+ * call (one thread per handle): BIGSI_ERR_STATE when another host thread is inside src. */
 int bigsi_hip_append_index(bigsi_hip_index *dst, const bigsi_hip_index *src);
 /* BitMatrix.get_column (bigsi/matrix/bitmatrix.py:50-61): out = ceil(num_rows/8) bytes, the bits of the last byte behind row
  * num_rows - 1 zero.  col < num_cols: a column the index does not have -- behind num_cols, inside the capacity or not -- is

@@ -26,7 +26,10 @@ extern "C" {
  *                    while views of it are open (their column count would go stale), as for bigsi_hip_reserve_cols.
  *   extract_columns  out of place: the kept columns of src become columns [0, K) of dst; src is only read and may be a view or
  *                    an ipc handle.  dst != src, same num_rows, same device (BIGSI_ERR_INVALID otherwise); dst must be writable
- *                    and hold no columns (num_cols == 0; BIGSI_ERR_STATE otherwise); its capacity grows as needed.
+ *                    and hold no columns (num_cols == 0; BIGSI_ERR_STATE otherwise); its capacity grows as needed.  While views
+ *                    of dst are open the call is refused as well (BIGSI_ERR_STATE: their column count would go stale).  Both
+ *                    handles are held for the duration of the call (one thread per handle): BIGSI_ERR_STATE when another
+ *                    host thread is inside src.
  *   shrink_to_fit    re-stride DOWN to the stride of max(num_cols, 1) columns: the counterpart of bigsi_hip_reserve_cols, which
  *                    only grows.  A no-op when the stride is already minimal; otherwise a writer that moves the matrix:
  *                    BIGSI_ERR_STATE for ipc / view handles and while views are open.  Needs room for the smaller copy beside

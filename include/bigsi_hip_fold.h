@@ -30,6 +30,9 @@ extern "C" {
  *                   plain copy of the rows).  dst != src, same device, same num_hashes (BIGSI_ERR_INVALID otherwise); dst must be
  *                   writable and hold no columns (BIGSI_ERR_STATE otherwise); its capacity grows to src's num_cols
  *                   (bigsi_hip_reserve_cols) and it ends with src's num_cols.  src is only read and may be a view or an ipc handle.
+ *                   While views of dst are open the call is refused as well (BIGSI_ERR_STATE: their column count would go
+ *                   stale).  Both handles are held for the duration of the call (one thread per handle): BIGSI_ERR_STATE when
+ *                   another host thread is inside src.
  *   trim_rows       the row counterpart of bigsi_hip_shrink_to_fit: when the allocation holds more rows than num_rows (after a
  *                   fold_rows), move the matrix into an allocation of num_rows x stride and free the old one.  ipc / view handles
  *                   get BIGSI_ERR_STATE (they do not know the owner's allocation); for the owner a no-op when nothing is to be

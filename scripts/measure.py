@@ -72,6 +72,24 @@ def run_steps(st, batches, threshold, reps, warm=3, prof=2, **kw):
     return wall, s
 
 
+def stride_for(cols):
+    """The row stride in bytes the library gives an index of `cols` columns (whole 128-byte lines)."""
+    return max(16, -(-(-(-cols // 64)) // 16) * 16) * 8
+
+
+def timed(fn):
+    """Wall-clock ms of one C call that must succeed."""
+    t0 = time.perf_counter()
+    check(fn())
+    return (time.perf_counter() - t0) * 1e3
+
+
+def get_rows(handle, ids, rb):
+    out = np.zeros((ids.size, rb), np.uint8)
+    check(_lib.lib().bigsi_hip_get_rows(handle, _lib.ptr(ids), ids.size, _lib.ptr(out), rb))
+    return out
+
+
 def emit(name, **kw):
     kw = dict(workload=name, **kw)
     print(json.dumps(kw), flush=True)
@@ -297,14 +315,6 @@ def compact():
     L, C = _lib.lib(), _lib.C
     shapes = ((10_000_000, 100_000), (25_000_000, 62_500))
 
-    def stride_for(cols):
-        return max(16, -(-(-(-cols // 64)) // 16) * 16) * 8
-
-    def timed(fn):
-        t0 = time.perf_counter()
-        check(fn())
-        return (time.perf_counter() - t0) * 1e3
-
     for m, n in shapes:
         st, fill = open_index("compact", m, n, 3)
         stride = int(st.res.info().row_stride_bytes)
@@ -384,16 +394,6 @@ def fold():
     shapes = ((10_000_000, 100_000), (25_000_000, 62_500))
     if os.environ.get("BIGSI_FOLD_SHAPES"):
         shapes = tuple(tuple(int(x) for x in sh.split("x")) for sh in os.environ["BIGSI_FOLD_SHAPES"].split(","))
-
-    def timed(fn):
-        t0 = time.perf_counter()
-        check(fn())
-        return (time.perf_counter() - t0) * 1e3
-
-    def get_rows(handle, ids, rb):
-        out = np.zeros((ids.size, rb), np.uint8)
-        check(L.bigsi_hip_get_rows(handle, _lib.ptr(ids), ids.size, _lib.ptr(out), rb))
-        return out
 
     def expectation(handle, m, n, d, seed):
         """(64 seeded destination rows -- the first, the last and one either side of 2^32 words among them --, the OR of their sources)"""
@@ -580,19 +580,6 @@ def collapse():
     m, n = 10_000_000, 100_000
     DROPPED = 0xFFFFFFFF
 
-    def stride_for(cols):
-        return max(16, -(-(-(-cols // 64)) // 16) * 16) * 8
-
-    def timed(fn):
-        t0 = time.perf_counter()
-        check(fn())
-        return (time.perf_counter() - t0) * 1e3
-
-    def rows_of(handle, ids, rb):
-        out = np.zeros((ids.size, rb), np.uint8)
-        check(L.bigsi_hip_get_rows(handle, _lib.ptr(ids), ids.size, _lib.ptr(out), rb))
-        return out
-
     st, fill = open_index("collapse", m, n, 3)
     stride = int(st.res.info().row_stride_bytes)
     src_bytes = m * (-(-n // 64)) * 8
@@ -603,7 +590,7 @@ def collapse():
     rng = np.random.default_rng(10)
     edge = (1 << 32) // (stride // 8)          # the first row whose offset in words is >= 2^32
     ids = np.unique(np.concatenate([rng.integers(0, m, 61).astype(np.uint64), np.array([edge - 1, edge, edge + 1], np.uint64)]))
-    before = np.unpackbits(rows_of(st.handle, ids, (n + 7) // 8), axis=1)[:, :n]
+    before = np.unpackbits(get_rows(st.handle, ids, (n + 7) // 8), axis=1)[:, :n]
     common = dict(m=m, cols=n, stride_bytes=stride, box_sorted_GBps=g_.value, fill_density=float(counts.sum()) / (m * n), edge_row=int(edge))
     # the yardstick of the same run: the copy of every column through k_compact_columns
     copy_ms = None
@@ -637,14 +624,14 @@ def collapse():
         want = np.zeros((groups, ids.size), np.uint8)
         cols = np.flatnonzero(group_of != DROPPED)
         np.maximum.at(want, group_of[cols].astype(np.int64), before[:, cols].T)
-        got = rows_of(dst, ids, need // m)
+        got = get_rows(dst, ids, need // m)
         exp = np.zeros_like(got)
         packed = np.packbits(want.T, axis=1)
         exp[:, :packed.shape[1]] = packed
         bits = int(counts[cols].sum())
         emit("collapse_" + name, groups=groups, call_ms=ms, bytes=src_bytes + need, GBps=(src_bytes + need) / ms / 1e6, bits_moved=bits,
              Gbits_per_s=bits / ms / 1e6, over_copy_all_kept=(ms / copy_ms) if copy_ms else None, rows_checked=int(ids.size),
-             rows_equal=bool(np.array_equal(got, exp)), source_unchanged=bool(np.array_equal(np.unpackbits(rows_of(st.handle, ids, (n + 7) // 8), axis=1)[:, :n], before)),
+             rows_equal=bool(np.array_equal(got, exp)), source_unchanged=bool(np.array_equal(np.unpackbits(get_rows(st.handle, ids, (n + 7) // 8), axis=1)[:, :n], before)),
              **common)
         check(L.bigsi_hip_close(dst))
     st.delete_all()

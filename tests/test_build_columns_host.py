@@ -7,8 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_compact_columns_host import ptr
-from test_fold_rows_host import cpu, junk_rows, twin_info, twin_open, twin_rows, twin_write          # noqa: F401  (cpu is a fixture)
+from raw_index import junk_rows, ptr
+from test_fold_rows_host import cpu, twin_info, twin_open, twin_rows, twin_write          # noqa: F401  (cpu is a fixture)
 
 ERR_RANGE = -4
 ROW_BLOCK = 1024

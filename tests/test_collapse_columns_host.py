@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_compact_columns_host import WIDTHS, Info, pack_keep, ptr, ragged_bits
+from raw_index import ptr, ragged_bits
+from test_compact_columns_host import WIDTHS, Info, pack_keep
 
 LIB = os.path.join(ROOT, "bigsi_amd", "libbigsi_cpu.so")
 ERR_INVALID, ERR_STATE = -1, -6

@@ -11,23 +11,12 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from raw_index import ptr, ragged_bits
 
 LIB = os.path.join(ROOT, "bigsi_amd", "libbigsi_cpu.so")
 ERR_INVALID, ERR_STATE = -1, -6
 WIDTHS = (1, 8, 63, 64, 65, 127, 128, 129, 1023, 1025, 8191, 8193)
 DELETED = "D3L3T3D"
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def ragged_bits(m, n):
-    """Every column distinct: column c set in exactly the rows r < (c * 37) % (m + 1), and the row r = c % m flipped, so that two
-    columns with the same height still differ."""
-    bits = (np.arange(m)[:, None] < ((np.arange(n) * 37) % (m + 1))[None, :]).astype(np.uint8)
-    bits[np.arange(n) % m, np.arange(n)] ^= 1
-    return bits
 
 
 def pack_keep(flags, junk=False):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, load_golden
+from raw_index import ptr
 
 LIB = os.path.join(ROOT, "bigsi_amd", "libbigsi_cpu.so")
 WORD_PARALLEL = 1 << 16
@@ -24,10 +25,6 @@ def cpu():
     L = C.CDLL(LIB)
     L.bigsi_cpu_last_error.restype = C.c_char_p
     return L
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def pack(seqs):

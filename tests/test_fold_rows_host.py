@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_compact_columns_host import Info, ptr
+from raw_index import junk_rows, ptr, rand_seq
+from test_compact_columns_host import Info
 from test_cpu_twin import Index
 
 LIB = os.path.join(ROOT, "bigsi_amd", "libbigsi_cpu.so")
@@ -137,12 +138,6 @@ def twin_info(L, ix):
     return inf
 
 
-def junk_rows(rng, m, n, stride):
-    """Random rows at the full stride: bits beyond column n - 1 (the rest of the last byte and the padding) are set too, and a fold
-    must drop them."""
-    return rng.integers(0, 256, size=(m, stride), dtype=np.uint8)
-
-
 def expected_fold(packed, d, n, out_bytes):
     """numpy on the very bytes written: the OR over the d row groups, cut to n columns, zero up to out_bytes."""
     m = packed.shape[0]
@@ -225,10 +220,6 @@ def test_twin_error_paths_and_trim(cpu):
 
 
 K, H = 11, 3
-
-
-def rand_seq(rng, n):
-    return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, size=n)].tobytes().decode("ascii")
 
 
 @pytest.mark.parametrize("m", [2 * 3 * 5 * 7, 1024])

@@ -25,65 +25,25 @@ import time
 import numpy as np
 import pytest
 
+from raw_index import Raw, junk_rows, ptr
 from test_build_columns_host import clean_rows, expected_append, expected_column, expected_insert, junk_filters
-from test_fold_rows_host import junk_rows, ptr
 
 pytestmark = pytest.mark.gpu
 ERR_RANGE, ERR_CAPACITY = -4, -5
 
 
-class Raw(object):
-    """One index straight on the C ABI."""
+def insert(a, col0, filters):
+    filters = np.ascontiguousarray(filters, dtype=np.uint8)
+    return a.L.bigsi_hip_insert_columns(a.ix, col0, filters.shape[0], ptr(filters), filters.shape[1])
 
-    def __init__(self, m, n=0, cap=None, packed=None):
-        from bigsi_amd import _lib
-        self.L, self.lib, self.m = _lib.lib(), _lib, m
-        self.ix = C.c_void_p()
-        _lib.check(self.L.bigsi_hip_open(m, n, cap or max(n, 1), 3, 0, C.byref(self.ix)))
-        if packed is not None:
-            self.write(packed)
 
-    def write(self, packed):
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        ids = np.arange(packed.shape[0], dtype=np.uint64)
-        self.lib.check(self.L.bigsi_hip_set_rows(self.ix, ptr(ids), ids.size, ptr(packed), packed.shape[1]))
+def insert_column(a, col, bloom):
+    return a.L.bigsi_hip_insert_column(a.ix, col, ptr(np.ascontiguousarray(bloom, dtype=np.uint8)))
 
-    def info(self):
-        inf = self.lib.Info()
-        self.lib.check(self.L.bigsi_hip_get_info(self.ix, C.byref(inf)))
-        return inf
 
-    @property
-    def stride(self):
-        return int(self.info().row_stride_bytes)
-
-    @property
-    def num_cols(self):
-        return int(self.info().num_cols)
-
-    def rows(self, ids=None):
-        """The rows `ids` (all by default) at the whole stride, over a buffer preset to a pattern."""
-        ids = np.arange(self.m, dtype=np.uint64) if ids is None else np.ascontiguousarray(ids, dtype=np.uint64)
-        out = np.full((ids.size, self.stride), 0xAB, np.uint8)
-        self.lib.check(self.L.bigsi_hip_get_rows(self.ix, ptr(ids), ids.size, ptr(out), out.shape[1]))
-        return out
-
-    def insert(self, col0, filters):
-        filters = np.ascontiguousarray(filters, dtype=np.uint8)
-        return self.L.bigsi_hip_insert_columns(self.ix, col0, filters.shape[0], ptr(filters), filters.shape[1])
-
-    def insert_column(self, col, bloom):
-        return self.L.bigsi_hip_insert_column(self.ix, col, ptr(np.ascontiguousarray(bloom, dtype=np.uint8)))
-
-    def column(self, col):
-        out = np.full((self.m + 7) // 8, 0xAB, np.uint8)
-        return self.L.bigsi_hip_get_column(self.ix, col, ptr(out)), out
-
-    def err(self):
-        return self.L.bigsi_hip_last_error()
-
-    def close(self):
-        self.lib.check(self.L.bigsi_hip_close(self.ix))
+def column(a, col):
+    out = np.full((int(a.info().num_rows) + 7) // 8, 0xAB, np.uint8)
+    return a.L.bigsi_hip_get_column(a.ix, col, ptr(out)), out
 
 
 def check_append(m, n0, n, cap, seed, pitch_extra=0):
@@ -95,7 +55,7 @@ def check_append(m, n0, n, cap, seed, pitch_extra=0):
         if n0:
             a.write(before)
         filters = junk_filters(rng, n, m, (m + 7) // 8 + pitch_extra)
-        assert a.insert(n0, filters) == 0, a.err()
+        assert insert(a, n0, filters) == 0, a.err()
         assert a.num_cols == n0 + n and a.stride == before.shape[1]
         assert np.array_equal(a.rows(), expected_insert(before, n0, n0, filters, m)), (m, n0, n)
     finally:
@@ -149,7 +109,7 @@ def test_d_overwrite_strictly_inside(col0, n):
         before = junk_rows(rng, M_D, 3000, a.stride)
         a.write(before)
         filters = junk_filters(rng, n, M_D, 144)
-        assert a.insert(col0, filters) == 0, a.err()
+        assert insert(a, col0, filters) == 0, a.err()
         assert a.num_cols == 3000
         assert np.array_equal(a.rows(), expected_insert(before, 3000, col0, filters, M_D)), (col0, n)
     finally:
@@ -167,12 +127,12 @@ def test_d_up_to_num_cols_and_capacity(n0, cap, col0, n):
         before = clean_rows(rng, M_D, n0, a.stride)
         a.write(before)
         filters = junk_filters(rng, n, M_D, 256)
-        assert a.insert(col0, filters) == 0, a.err()
+        assert insert(a, col0, filters) == 0, a.err()
         assert a.num_cols == max(n0, col0 + n)
         want = expected_insert(before, n0, col0, filters, M_D)
         assert np.array_equal(a.rows(), want), (n0, cap, col0, n)
         if col0 + 1 + n > a.stride * 8:          # one column further is refused, and nothing written
-            assert a.insert(col0 + 1, filters) == ERR_CAPACITY and np.array_equal(a.rows(), want)
+            assert insert(a, col0 + 1, filters) == ERR_CAPACITY and np.array_equal(a.rows(), want)
     finally:
         a.close()
 
@@ -227,15 +187,15 @@ def test_f_three_slabs_at_two_million_rows():
         a.write(head)
         stride = a.stride
         assert stride == 384
-        assert a.insert(n0, filters) == 0, a.err()
+        assert insert(a, n0, filters) == 0, a.err()
         assert a.num_cols == n0 + n
         for r0 in (0, (1 << 20) - 512, m - 1024):
             before = np.zeros((1024, stride), np.uint8)
             before[:, :n0 // 8] = head[r0:r0 + 1024]
-            got = a.rows(np.arange(r0, r0 + 1024))
+            got = a.rows(ids=np.arange(r0, r0 + 1024))
             assert np.array_equal(got, expected_insert(before, n0, n0, filters, m, row0=r0)), r0
         for col in (0, 39, 40, 935, 936, 1023, 1024, 1831, 1832, 2139):
-            rc, got = a.column(col)
+            rc, got = column(a, col)
             want = filters[col - n0] if col >= n0 else np.packbits((head[:, col // 8] >> (7 - col % 8)) & 1)
             assert rc == 0 and np.array_equal(got, want), col
     finally:
@@ -293,17 +253,17 @@ def test_h_insert_column_and_get_column(m):
         a.write(rows)
         for col in (0, 7, 8, 63, 64, n0):
             bloom = junk_filters(rng, 1, m)          # (the bits of its last byte behind row m - 1 are random)
-            assert a.insert_column(col, bloom) == 0, a.err()
+            assert insert_column(a, col, bloom) == 0, a.err()
             rows = expected_insert(rows, n0, col, bloom, m)
             assert np.array_equal(a.rows(), rows), (m, col)
         assert a.num_cols == n0 + 1
         for col in range(n0 + 1):
-            rc, got = a.column(col)
+            rc, got = column(a, col)
             assert rc == 0 and np.array_equal(got, expected_column(rows, col, m)), (m, col)
         for col in (n0 + 1, n0 + 2, 1023, 1024, 1 << 40):
-            rc, got = a.column(col)
+            rc, got = column(a, col)
             assert rc == ERR_RANGE and (got == 0xAB).all(), (m, col)
-        assert a.insert_column(n0 + 2, junk_filters(rng, 1, m)) == ERR_RANGE          # a gap is refused
+        assert insert_column(a, n0 + 2, junk_filters(rng, 1, m)) == ERR_RANGE          # a gap is refused
         assert np.array_equal(a.rows(), rows)
     finally:
         a.close()

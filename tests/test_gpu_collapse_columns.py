@@ -16,9 +16,9 @@ import pytest
 import yaml
 
 from conftest import ROOT
+from raw_index import Raw, ptr, ragged_bits, rand_seq
 from test_collapse_columns_host import DROPPED, collapse_maps, constants, expected_rows, junk_rows, plan, plan_lib  # noqa: F401 (plan_lib: a fixture)
-from test_compact_columns_host import WIDTHS, pack_keep, ptr, ragged_bits
-from test_gpu_compact_columns import Raw
+from test_compact_columns_host import WIDTHS, pack_keep
 
 pytestmark = pytest.mark.gpu
 _counter = itertools.count()
@@ -48,13 +48,13 @@ def check_collapse(bits, group_of, groups, ctx, against_extract=False):
         full = dst.rows()
         assert np.array_equal(full, expected_rows(bits, group_of, groups, full.shape[1])), ctx
         rb = (groups + 7) // 8
-        assert np.array_equal(dst.rows(rb), full[:, :rb]), ctx
+        assert np.array_equal(dst.rows(row_bytes=rb), full[:, :rb]), ctx
         assert np.array_equal(src.rows(), before) and src.info().num_cols == n, ctx
         if against_extract:          # a monotone injective map = the extraction of the same columns
             ext = Raw(m=m, n=0, cap=1)
             try:
                 assert ext.L.bigsi_hip_extract_columns(ext.ix, src.ix, ptr(pack_keep(group_of != DROPPED))) == 0, ext.L.bigsi_hip_last_error()
-                assert np.array_equal(ext.rows(rb), full[:, :rb]) and ext.info().num_cols == groups, ctx
+                assert np.array_equal(ext.rows(row_bytes=rb), full[:, :rb]) and ext.info().num_cols == groups, ctx
             finally:
                 ext.close()
     finally:
@@ -113,7 +113,7 @@ def test_d_several_windows(plan_lib):
     try:
         assert collapse(dst, src.ix, injective, groups) == 0, dst.L.bigsi_hip_last_error()
         assert ext.L.bigsi_hip_extract_columns(ext.ix, src.ix, ptr(pack_keep(injective != DROPPED))) == 0, ext.L.bigsi_hip_last_error()
-        taken = np.unpackbits(ext.rows((groups + 7) // 8), axis=1)[:, :groups]
+        taken = np.unpackbits(ext.rows(row_bytes=(groups + 7) // 8), axis=1)[:, :groups]
         assert np.array_equal(taken, bits[:, :groups])
         reordered = np.zeros_like(taken)
         reordered[:, perm] = taken
@@ -129,7 +129,7 @@ def test_d_several_windows(plan_lib):
 def test_e_views_as_source_and_refusals():
     bits = ragged_bits(300, 200)
     label, group_of, groups = collapse_maps(200)[4]
-    a, dst, other_m, other_h, full = source(bits), Raw(m=300, n=0, cap=1), Raw(m=301, n=0, cap=1), Raw(m=300, n=0, cap=1), Raw(bits)
+    a, dst, other_m, other_h, full = source(bits), Raw(m=300, n=0, cap=1), Raw(m=301, n=0, cap=1), Raw(m=300, n=0, cap=1), Raw.from_bits(bits)
     L = a.L
     a.lib.check(L.bigsi_hip_set_num_hashes(other_h.ix, 2))
     view, dst_view = C.c_void_p(), C.c_void_p()
@@ -161,7 +161,7 @@ def test_e_views_as_source_and_refusals():
         assert rc == ERR_INVALID and "141" in msg and str(groups + 5) in msg
         for r in (dst, other_m, other_h):          # a refused call left the destination empty
             assert r.info().num_cols == 0 and not r.rows().any()
-        assert np.array_equal(full.rows(25), np.packbits(bits, axis=1)) and full.info().num_cols == 200
+        assert np.array_equal(full.rows(row_bytes=25), np.packbits(bits, axis=1)) and full.info().num_cols == 200
         assert np.array_equal(a.rows(), before) and a.info().num_cols == 200 == a.info(view).num_cols
         # a view AS THE SOURCE works
         assert collapse(dst, view, group_of, groups) == 0, L.bigsi_hip_last_error()
@@ -178,7 +178,7 @@ def test_e_views_as_source_and_refusals():
 def test_f_an_ipc_handle_is_a_source_and_no_destination():
     """An index attached over hipIpc in a child process: collapsed from there into an index of the child's own, refused as destination."""
     bits = ragged_bits(60, 100)
-    a = Raw(bits)
+    a = Raw.from_bits(bits)
     try:
         handle = np.zeros(64, np.uint8)
         a.lib.check(a.L.bigsi_hip_export_ipc(a.ix, ptr(handle)))
@@ -204,17 +204,13 @@ def test_f_an_ipc_handle_is_a_source_and_no_destination():
         g = (np.arange(100) % 7).astype(np.uint32)
         g[::9] = DROPPED
         assert np.array_equal(np.frombuffer(bytes.fromhex(rows), np.uint8).reshape(60, 128), expected_rows(bits, g, 7, 128))
-        assert np.array_equal(a.rows(13), np.packbits(bits, axis=1)) and a.info().num_cols == 100
+        assert np.array_equal(a.rows(row_bytes=13), np.packbits(bits, axis=1)) and a.info().num_cols == 100
     finally:
         a.close()
 
 
 # --------------------------------------------------------------------------------------------- BIGSI level
 K, M, H, N_SAMPLES = 11, 4099, 3, 70
-
-
-def rand_seq(rng, n):
-    return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, size=n)].tobytes().decode("ascii")
 
 
 def config(d, tag):

@@ -16,62 +16,30 @@ import pytest
 import yaml
 
 from conftest import ROOT
-from test_compact_columns_host import WIDTHS, expected_rows, keep_patterns, pack_keep, ptr, ragged_bits
+from raw_index import Raw, ptr, ragged_bits, rand_seq
+from test_compact_columns_host import WIDTHS, expected_rows, keep_patterns, pack_keep
 
 pytestmark = pytest.mark.gpu
 _counter = itertools.count()
 ERR_INVALID, ERR_STATE = -1, -6
 
 
-class Raw(object):
-    """One index straight on the C ABI, holding the bit matrix `bits` (uint8[m, n] of 0 / 1) written with bigsi_hip_set_rows."""
-
-    def __init__(self, bits=None, m=None, n=0, cap=None):
-        from bigsi_amd import _lib
-        self.L, self.lib = _lib.lib(), _lib
-        self.m, self.n = (m, n) if bits is None else bits.shape
-        self.ix = C.c_void_p()
-        _lib.check(self.L.bigsi_hip_open(self.m, self.n, cap or self.n, 3, 0, C.byref(self.ix)))
-        if bits is not None:
-            self.write(np.packbits(bits, axis=1))
-
-    def write(self, packed):
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        ids = np.arange(self.m, dtype=np.uint64)
-        self.lib.check(self.L.bigsi_hip_set_rows(self.ix, ptr(ids), self.m, ptr(packed), packed.shape[1]))
-
-    def info(self, handle=None):
-        inf = self.lib.Info()
-        self.lib.check(self.L.bigsi_hip_get_info(handle or self.ix, C.byref(inf)))
-        return inf
-
-    def rows(self, row_bytes=None):
-        """The rows at `row_bytes` bytes each (default: the whole stride), over a buffer preset to a pattern."""
-        rb = int(self.info().row_stride_bytes) if row_bytes is None else row_bytes
-        out = np.full((self.m, rb), 0xAB, np.uint8)
-        ids = np.arange(self.m, dtype=np.uint64)
-        self.lib.check(self.L.bigsi_hip_get_rows(self.ix, ptr(ids), self.m, ptr(out), rb))
-        return out
-
-    def compact(self, keep, handle=None):
-        kept = C.c_uint64(1 << 60)
-        return self.L.bigsi_hip_compact_columns(handle or self.ix, ptr(keep), C.byref(kept)), kept.value
-
-    def close(self):
-        self.lib.check(self.L.bigsi_hip_close(self.ix))
+def compact(a, keep, handle=None):
+    kept = C.c_uint64(1 << 60)
+    return a.L.bigsi_hip_compact_columns(handle or a.ix, ptr(keep), C.byref(kept)), kept.value
 
 
 def check_compact_and_extract(bits, flags, keep, ctx):
     """In place and out of place give numpy's rows, zero from column K to the end of the stride; the source of an extraction stays."""
     m, n = bits.shape
     k = int(flags.sum())
-    a, src, dst = Raw(bits), Raw(bits), Raw(m=m, n=0, cap=1)
+    a, src, dst = Raw.from_bits(bits), Raw.from_bits(bits), Raw(m=m, n=0, cap=1)
     try:
         before = src.rows()
-        rc, kept = a.compact(keep)
+        rc, kept = compact(a, keep)
         assert rc == 0 and kept == k == a.info().num_cols, ctx
         for rb in ((n + 7) // 8, None):
-            got = a.rows(rb)
+            got = a.rows(row_bytes=rb)
             assert np.array_equal(got, expected_rows(bits, flags, got.shape[1])), ctx
         assert a.L.bigsi_hip_extract_columns(dst.ix, src.ix, ptr(keep)) == 0, a.L.bigsi_hip_last_error()
         assert dst.info().num_cols == k and dst.info().col_capacity >= k, ctx
@@ -115,16 +83,24 @@ def test_d_views_and_refusals():
     bits = ragged_bits(300, 200)
     flags = rng.random(200) < 0.5
     keep = pack_keep(flags)
-    a, dst = Raw(bits), Raw(m=300, n=0, cap=1)
+    a, dst = Raw.from_bits(bits), Raw(m=300, n=0, cap=1)
     view = C.c_void_p()
     a.lib.check(a.L.bigsi_hip_open_view(a.ix, C.byref(view)))
     try:
         before = a.rows()
         # a view is read-only, and its owner does not compact under it
         for handle in (view, a.ix):
-            rc, _ = a.compact(keep, handle)
+            rc, _ = compact(a, keep, handle)
             assert rc == ERR_STATE and a.L.bigsi_hip_last_error()
         assert np.array_equal(a.rows(), before) and a.info().num_cols == 200 == a.info(view).num_cols
+        # an empty destination with a view of its own open is refused: the view's column count would go stale
+        dst_view = C.c_void_p()
+        a.lib.check(a.L.bigsi_hip_open_view(dst.ix, C.byref(dst_view)))
+        try:
+            assert a.L.bigsi_hip_extract_columns(dst.ix, a.ix, ptr(keep)) == ERR_STATE and b"view" in a.L.bigsi_hip_last_error()
+            assert dst.info().num_cols == 0 and not dst.rows().any()
+        finally:
+            a.lib.check(a.L.bigsi_hip_close(dst_view))
         # ... but a view is a fine source
         assert a.L.bigsi_hip_extract_columns(dst.ix, view, ptr(keep)) == 0, a.L.bigsi_hip_last_error()
         got = dst.rows()
@@ -133,7 +109,7 @@ def test_d_views_and_refusals():
     finally:
         a.lib.check(a.L.bigsi_hip_close(view))
     try:
-        rc, kept = a.compact(keep)                                                          # the view is closed: now it goes
+        rc, kept = compact(a, keep)                                                          # the view is closed: now it goes
         assert rc == 0 and kept == int(flags.sum())
         assert np.array_equal(a.rows(), dst.rows()[:, :a.rows().shape[1]])
     finally:
@@ -145,11 +121,11 @@ def test_e_capacity_with_slack():
     """Opened for 5000 columns, holding 1000: everything from column K to the end of the 640-byte stride is zero afterwards."""
     bits = ragged_bits(100, 1000)
     flags = np.random.default_rng(5).random(1000) < 0.7
-    a = Raw(bits, cap=5000)
+    a = Raw.from_bits(bits, cap=5000)
     try:
         stride = int(a.info().row_stride_bytes)
         assert stride == 640
-        rc, kept = a.compact(pack_keep(flags))
+        rc, kept = compact(a, pack_keep(flags))
         assert rc == 0 and kept == int(flags.sum())
         assert a.info().row_stride_bytes == stride and a.info().col_capacity == 5120          # stride and capacity unchanged
         assert np.array_equal(a.rows(), expected_rows(bits, flags, stride))
@@ -161,10 +137,10 @@ def test_f_shrink_to_fit():
     bits = ragged_bits(300, 3000)
     flags = np.zeros(3000, bool)
     flags[::7] = True
-    a = Raw(bits)
+    a = Raw.from_bits(bits)
     try:
         assert a.L.bigsi_hip_shrink_to_fit(a.ix) == 0 and a.info().row_stride_bytes == 384          # already minimal: a no-op
-        rc, kept = a.compact(pack_keep(flags))
+        rc, kept = compact(a, pack_keep(flags))
         assert rc == 0 and kept == 429
         old = a.info()
         view = C.c_void_p()
@@ -179,7 +155,7 @@ def test_f_shrink_to_fit():
         assert new.index_bytes == 300 * 128 < old.index_bytes
         assert np.array_equal(a.rows(), expected_rows(bits, flags, 128))
         assert a.L.bigsi_hip_shrink_to_fit(a.ix) == 0 and a.info().row_stride_bytes == 128          # a second call is a no-op
-        rc, kept = a.compact(pack_keep(np.zeros(429, bool)))                                         # nothing kept, then shrunk
+        rc, kept = compact(a, pack_keep(np.zeros(429, bool)))                                         # nothing kept, then shrunk
         assert rc == 0 and kept == 0 and a.L.bigsi_hip_shrink_to_fit(a.ix) == 0 and a.info().row_stride_bytes == 128
         assert not a.rows().any()
     finally:
@@ -189,7 +165,7 @@ def test_f_shrink_to_fit():
 def test_g_errors():
     bits = ragged_bits(64, 100)
     keep = pack_keep(np.ones(100, bool))
-    a, full, other, empty = Raw(bits), Raw(bits), Raw(m=65, n=0, cap=1), Raw(m=64, n=0, cap=1)
+    a, full, other, empty = Raw.from_bits(bits), Raw.from_bits(bits), Raw(m=65, n=0, cap=1), Raw(m=64, n=0, cap=1)
     L = a.L
     try:
         for rc, want in ((L.bigsi_hip_compact_columns(None, ptr(keep), None), ERR_INVALID),
@@ -204,7 +180,7 @@ def test_g_errors():
             assert rc == want and L.bigsi_hip_last_error()
         assert L.bigsi_hip_compact_columns(a.ix, ptr(keep), None) == 0                                  # new_num_cols may be NULL
         for r in (a, full):
-            assert np.array_equal(r.rows(13), np.packbits(bits, axis=1)) and r.info().num_cols == 100  # nothing changed anything
+            assert np.array_equal(r.rows(row_bytes=13), np.packbits(bits, axis=1)) and r.info().num_cols == 100  # nothing changed anything
         assert empty.info().num_cols == 0 and not empty.rows().any()
     finally:
         for r in (a, full, other, empty):
@@ -214,10 +190,6 @@ def test_g_errors():
 # --------------------------------------------------------------------------------------------- BIGSI level
 K, M, H, N_SAMPLES = 11, 4099, 3, 70
 DEAD = (0, 63, 64, 69, 30)
-
-
-def rand_seq(rng, n):
-    return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, size=n)].tobytes().decode("ascii")
 
 
 def config(d, tag):

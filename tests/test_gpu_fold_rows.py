@@ -16,52 +16,17 @@ import pytest
 import yaml
 
 from conftest import ROOT, assert_results_equal
-from test_fold_rows_host import expected_fold, junk_rows, ptr
+from raw_index import Raw, junk_rows, ptr, rand_seq
+from test_fold_rows_host import expected_fold
 
 pytestmark = pytest.mark.gpu
 _counter = itertools.count()
 ERR_INVALID, ERR_RANGE, ERR_STATE = -1, -4, -6
 
 
-class Raw(object):
-    """One index straight on the C ABI; write() stores rows at any width up to the stride with bigsi_hip_set_rows."""
-
-    def __init__(self, m, n=0, cap=None, h=3, packed=None):
-        from bigsi_amd import _lib
-        self.L, self.lib = _lib.lib(), _lib
-        self.ix = C.c_void_p()
-        _lib.check(self.L.bigsi_hip_open(m, n, cap or max(n, 1), h, 0, C.byref(self.ix)))
-        if packed is not None:
-            self.write(packed)
-
-    def write(self, packed):
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        ids = np.arange(packed.shape[0], dtype=np.uint64)
-        self.lib.check(self.L.bigsi_hip_set_rows(self.ix, ptr(ids), ids.size, ptr(packed), packed.shape[1]))
-
-    def info(self, handle=None):
-        inf = self.lib.Info()
-        self.lib.check(self.L.bigsi_hip_get_info(handle or self.ix, C.byref(inf)))
-        return inf
-
-    @property
-    def stride(self):
-        return int(self.info().row_stride_bytes)
-
-    def rows(self, handle=None):
-        """Every row the index says it has, at the whole stride, over a buffer preset to a pattern."""
-        inf = self.info(handle)
-        out = np.full((int(inf.num_rows), int(inf.row_stride_bytes)), 0xAB, np.uint8)
-        ids = np.arange(int(inf.num_rows), dtype=np.uint64)
-        self.lib.check(self.L.bigsi_hip_get_rows(handle or self.ix, ptr(ids), ids.size, ptr(out), out.shape[1]))
-        return out
-
-    def fold(self, factor, handle=None):
-        new = C.c_uint64(1 << 60)
-        return self.L.bigsi_hip_fold_rows(handle or self.ix, C.c_uint64(factor), C.byref(new)), new.value
-
-    def close(self):
-        self.lib.check(self.L.bigsi_hip_close(self.ix))
+def fold(a, factor, handle=None):
+    new = C.c_uint64(1 << 60)
+    return a.L.bigsi_hip_fold_rows(handle or a.ix, C.c_uint64(factor), C.byref(new)), new.value
 
 
 def filled(m, n, cap, seed):
@@ -91,7 +56,7 @@ def test_a_kernel_against_numpy_in_place_and_into(i):
     dst = Raw(new_m, 0, 1)
     try:
         assert (a.stride != src.stride) and dst.stride == 128
-        rc, got_m = a.fold(d)
+        rc, got_m = fold(a, d)
         assert rc == 0 and got_m == new_m == a.info().num_rows, a.L.bigsi_hip_last_error()
         assert a.info().num_cols == n and a.info().row_stride_bytes == pa.shape[1] and a.info().index_bytes == new_m * pa.shape[1]
         assert np.array_equal(a.rows(), expected_fold(pa, d, n, pa.shape[1])), COMBOS[i]
@@ -112,7 +77,7 @@ def test_b_factor_one_copies_through_the_kernel(new_m, n):
     src, ps = filled(new_m, n, n + 5000, 7)
     dst = Raw(new_m, 0, 1)
     try:
-        assert src.fold(1) == (0, new_m) and np.array_equal(src.rows(), ps)
+        assert fold(src, 1) == (0, new_m) and np.array_equal(src.rows(), ps)
         assert src.L.bigsi_hip_fold_rows(src.ix, C.c_uint64(1), None) == 0          # new_num_rows may be NULL
         assert src.L.bigsi_hip_fold_rows_into(dst.ix, src.ix) == 0, src.L.bigsi_hip_last_error()
         assert np.array_equal(dst.rows(), expected_fold(ps, 1, n, dst.stride)) and dst.info().num_cols == n
@@ -125,7 +90,7 @@ def test_c_two_folds_equal_one_fold_by_the_product():
     a, pa = filled(67 * 6, 1000, 1000, 11)
     b = Raw(67 * 6, 1000, 1000, packed=pa)
     try:
-        assert a.fold(2) == (0, 201) and a.fold(3) == (0, 67) and b.fold(6) == (0, 67)
+        assert fold(a, 2) == (0, 201) and fold(a, 3) == (0, 67) and fold(b, 6) == (0, 67)
         want = expected_fold(pa, 6, 1000, pa.shape[1])
         assert np.array_equal(a.rows(), want) and np.array_equal(b.rows(), want)
     finally:
@@ -154,7 +119,7 @@ def test_d_trim_rows_gives_the_memory_back():
         assert hip.hipFree(p) == 0
         assert 0 <= granule <= 64 << 20
         assert a.L.bigsi_hip_trim_rows(a.ix) == 0          # nothing to gain yet: a no-op
-        assert a.fold(4) == (0, 16384)
+        assert fold(a, 4) == (0, 16384)
         want = expected_fold(pa, 4, 8192, 1024)
         assert np.array_equal(a.rows(), want)
         before = free_bytes()
@@ -169,7 +134,7 @@ def test_d_trim_rows_gives_the_memory_back():
         assert a.L.bigsi_hip_trim_rows(a.ix) == 0 and free_bytes() - before == gained          # a second call is a no-op
         # the trimmed index is a whole index: it grows and folds again
         a.lib.check(a.L.bigsi_hip_reserve_cols(a.ix, 9000))
-        assert a.fold(2) == (0, 8192)
+        assert fold(a, 2) == (0, 8192)
         assert np.array_equal(a.rows()[:, :1024], expected_fold(pa, 8, 8192, 1024))
     finally:
         a.close()
@@ -201,13 +166,21 @@ def test_e_refusals():
             msg = L.bigsi_hip_last_error().decode()
             assert rc == want and msg and all(w in msg for w in words), (rc, want, msg)
         assert np.array_equal(a.rows(), pa) and a.info().num_rows == 60 == a.info(view).num_rows          # a refused call changed nothing
+        # an empty destination with a view of its own open is refused: the view's column count would go stale
+        dst_view = C.c_void_p()
+        a.lib.check(L.bigsi_hip_open_view(empty30.ix, C.byref(dst_view)))
+        try:
+            assert L.bigsi_hip_fold_rows_into(empty30.ix, a.ix) == ERR_STATE and b"view" in L.bigsi_hip_last_error()
+            assert empty30.info().num_cols == 0 and not empty30.rows().any()
+        finally:
+            a.lib.check(L.bigsi_hip_close(dst_view))
         # a view AS THE SOURCE works
         assert L.bigsi_hip_fold_rows_into(empty30.ix, view) == 0, L.bigsi_hip_last_error()
         assert np.array_equal(empty30.rows(), expected_fold(pa, 2, 100, empty30.stride)) and empty30.info().num_cols == 100
     finally:
         a.lib.check(L.bigsi_hip_close(view))
     try:
-        assert a.fold(2) == (0, 30)                                                                       # the view is closed: now it goes
+        assert fold(a, 2) == (0, 30)                                                                       # the view is closed: now it goes
         assert np.array_equal(a.rows(), empty30.rows())
     finally:
         for r in (a, empty7, empty30, full, other_h):
@@ -237,10 +210,6 @@ def test_f_ipc_handles_are_refused():
 
 # --------------------------------------------------------------------------------------------- BIGSI level
 K, M, H, N_SAMPLES = 11, 2 * 17 * 1201, 3, 40
-
-
-def rand_seq(rng, n):
-    return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, size=n)].tobytes().decode("ascii")
 
 
 def config(d, tag, m=M):

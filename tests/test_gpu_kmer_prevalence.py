@@ -16,6 +16,7 @@ import pytest
 import yaml
 
 from conftest import ROOT, load_golden
+from raw_index import ptr, rand_seq
 from oracle import coracle
 
 pytestmark = pytest.mark.gpu
@@ -26,19 +27,11 @@ K = 31
 POP = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint32)
 
 
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def pack(seqs):
     data = [s.encode("ascii") for s in seqs]
     off = np.zeros(len(data) + 1, np.uint64)
     off[1:] = np.cumsum([len(d) for d in data])
     return b"".join(data), off
-
-
-def rand_seq(rng, n):
-    return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, size=n)].tobytes().decode("ascii")
 
 
 def mask_bytes(flags):

@@ -17,15 +17,12 @@ import pytest
 import yaml
 
 from conftest import ROOT
+from raw_index import ptr, rand_seq
 
 pytestmark = pytest.mark.gpu
 _counter = itertools.count()
 ERR_INVALID, ERR_CAPACITY = -1, -5
 SENTINEL = 0xDEADBEEF
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 class Raw(object):
@@ -215,10 +212,6 @@ def test_h_view_handle():
 
 # --------------------------------------------------------------------------------------------- BIGSI level
 K, M, H = 11, 4099, 3
-
-
-def rand_seq(rng, n):
-    return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, size=n)].tobytes().decode("ascii")
 
 
 def bits_of(bf):

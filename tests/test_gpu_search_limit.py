@@ -15,6 +15,7 @@ import pytest
 import yaml
 
 from conftest import ROOT, assert_results_equal
+from raw_index import rand_seq
 
 pytestmark = pytest.mark.gpu
 _counter = itertools.count()
@@ -26,10 +27,6 @@ THRESHOLDS = (1.0, 0.0, 0.29, 0.4, 0.83)
 def cfg(m, h=3, **sc):
     sc.setdefault("name", "lim%d" % next(_counter))
     return {"storage-engine": "hip-hbm", "storage-config": sc, "k": K, "m": m, "h": h}
-
-
-def rand_seq(rng, n):
-    return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, size=n)].tobytes().decode("ascii")
 
 
 def topn_colours(colours, counts, n, exact):

@@ -14,15 +14,12 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden
+from raw_index import ptr, rand_seq
 from oracle import coracle
 
 LIB = os.path.join(ROOT, "bigsi_amd", "libbigsi_cpu.so")
 ERR_INVALID, ERR_CAPACITY, ERR_STATE = -1, -5, -6
 SENTINEL = 0xDEADBEEF
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def pack(seqs):
@@ -38,10 +35,6 @@ def cpu():
     L = C.CDLL(LIB)
     L.bigsi_cpu_last_error.restype = C.c_char_p
     return L
-
-
-def rand_seq(rng, n):
-    return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, size=n)].tobytes().decode("ascii")
 
 
 def expected(bits, seqs, k, h, universe=None, subset=None):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from raw_index import ptr
 
 LIB = os.path.join(ROOT, "bigsi_amd", "libbigsi_cpu.so")
 ERR_INVALID, ERR_CAPACITY = -1, -5
@@ -20,10 +21,6 @@ def cpu():
     L = C.CDLL(LIB)
     L.bigsi_cpu_last_error.restype = C.c_char_p
     return L
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def twin_index(L, bits):

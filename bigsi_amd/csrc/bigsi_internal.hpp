@@ -1,5 +1,6 @@
 // bigsi_internal.hpp -- host-side structures shared by the translation units of libbigsi_hip.so
-// (bigsi_hip.hip: single-shard C ABI; bigsi_shard.hip: RCCL exchange, device groups, one-call search).
+// (bigsi_hip.hip: single-shard C ABI, the file <-> HBM pipeline; bigsi_shard.hip: RCCL exchange, device groups, one-call search;
+// bigsi_text.cpp: FASTA / FASTQ text; bigsi_rowsfile.cpp: the file side of that pipeline -- host only, it does not include this header).
 #pragma once
 #include "bigsi_hip.h"
 #include "bigsi_hip_collapse.h"
@@ -17,6 +18,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <thread>
 #include <vector>
 
@@ -285,32 +287,19 @@ uint32_t bigsi_exact_launch_queries(const bigsi_hip_index *ix);
 int bigsi_batch_collect(bigsi_hip_batch *b, uint32_t *num_kmers, uint32_t *num_unique, uint32_t *min_kmers, uint64_t *hit_offsets,
                         uint32_t *colours, uint32_t *counts, uint64_t capacity);
 int bigsi_use_device(const bigsi_hip_index *ix);
-// pread / pwrite of [off, off + len) with up to `threads` host threads (bigsi_hip.hip); 0 or errno
-int bigsi_file_io(int fd, bool write, uint8_t *buf, uint64_t off, uint64_t len, unsigned threads);
-constexpr uint64_t kBigsiIoChunkBytes = 256ull << 20;      // one pinned buffer of the file <-> HBM pipelines
-// The file side of load_rows_file / save_rows_file (single index and group).  `path` is a FILE (rows back to back from file_offset
-// on) or, when it ends in '/', a DIRECTORY holding the same rows striped RAID-0 fashion over kParts part files: writes to one
-// file are serialised by its inode lock and its page-cache tree -- 16 threads put 3.6-5.3 GB/s into ONE fresh tmpfs file
-// (pwrite or mmap alike) and 63 GB/s into 16 files (scripts/probe/tmpfs_write_probe.py, mmap_write_probe.cpp) -- so a save that is
-// to run at the PCIe rate needs several inodes.  Stripe s (rows [s * S, (s + 1) * S) of the range) lives in part s % P at
-// row offset (s / P) * S; `layout` in the directory records P, S, row_bytes and the row count, and a load reads it back.
-#include "bigsi_bdb.hpp"      // BigsiBdb: BerkeleyDB hash files without libdb (shared with libbigsi_cpu.so)
-
-struct BigsiRowsFile {
-    bool striped = false;
-    bool bdb = false;                      // `path` is a BerkeleyDB hash file: rows are its "<row>:bitarray" records (loads only)
-    BigsiBdb db;
-    std::vector<BigsiBdb::Loc> loc;        // bdb: where row row0 + i lives
-    uint64_t bdb_row0 = 0;
-    int fd = -1;
-    std::vector<int> fds;
-    uint64_t parts = 0, stripe_rows = 0, row_bytes = 0, file_offset = 0;
-    int open_(const char *path, bool save, uint64_t file_offset_, uint64_t row_bytes_, uint64_t n_rows, uint64_t row0 = 0, unsigned threads = 1);     // BIGSI_OK or an error (message set)
-    uint64_t chunk_rows() const;                                           // rows per pinned buffer
-    int io(bool write, uint8_t *buf, uint64_t rel_row, uint64_t n, unsigned threads) const;      // rows [rel_row, +n) of the range; 0 or errno
-    int sync_all() const;
-    void close_();
+#include "bigsi_rowsfile.hpp"      // BigsiRowsFile, bigsi_io_threads: the file side of the pipeline below (host only)
+// The ONE file <-> HBM pipeline (bigsi_hip.hip) behind load_rows_file / save_rows_file of a single index and of a group: it owns the
+// BigsiRowsFile, the two pinned buffers (`pin_flags`: hipHostMalloc's), the chunk loop of both directions, the fsync, the clean-up
+// and `st`.  The device side is the caller's: four callables over its own state.
+struct BigsiRowsDevice {
+    std::function<int(uint64_t buf_bytes)> prepare;      // once: a completion event per slot (and stream); staging for buf_bytes if needed
+    // rows [r0, +cn) of the index between `pin` (slot's buffer) and the device(s), in the call's direction: queued, completion recorded
+    std::function<int(int slot, uint8_t *pin, uint64_t r0, uint64_t cn)> queue;
+    std::function<int(int slot)> wait;                   // until what `queue` last recorded for the slot is done; error-checked
+    std::function<void()> release;                       // drain every stream (an error has been reported already), free what prepare made
 };
+int bigsi_rows_pipeline(const BigsiRowsDevice &dev, unsigned pin_flags, const char *path, uint64_t file_offset, uint64_t row0, uint64_t n_rows,
+                        uint64_t row_bytes, uint32_t threads, bool save, bool direct, bigsi_hip_io_stats *st);
 // profiling events (bigsi_hip_set_profiling): a pair around a group of launches on `st` (null: the index stream), collected in `dst`
 int bigsi_ev_begin(bigsi_hip_index *ix, EventPair *p, hipStream_t st = nullptr, bool row_and = false);
 int bigsi_ev_end(bigsi_hip_index *ix, EventPair *p, std::vector<EventPair> &dst, hipStream_t st = nullptr, uint32_t launches = 1);

@@ -385,6 +385,59 @@ def test_rows_file_io_with_any_row_length(hip, tmp_path):
     a.delete_all()
 
 
+@pytest.mark.parametrize("row_bytes,direct", [(12504, 0), (12544, 1)])
+def test_rows_file_over_three_chunks(hip, tmp_path, row_bytes, direct):
+    """The chunk loop of bigsi_hip_save_rows_file / load_rows_file where it reuses its two buffers: 60 000 rows of a 100 000-column
+    index are 750 MB, three chunks with a ragged last one, at a row length that is not the device pitch (staging buffers, reused per
+    slot, and the gather / scatter kernels) and at the device pitch (direct).  The rows on either side of every chunk boundary and
+    200 random ones are compared in the file and, after a load into a second index, on the device."""
+    import shutil
+    import time
+    from bigsi_amd import _lib
+    from bigsi_amd.storage import get_storage
+    m, n_cols = 60_000, 100_000
+    per = (256 << 20) // row_bytes          # mirrors BigsiRowsFile::chunk_rows() for a flat file: rows per 256 MiB pinned buffer
+    assert 2 * per < m < 3 * per and m % per
+    _, a = synth_index(hip, m, n_cols, 3, 97)
+    assert int(a.res.info().row_stride_bytes) == 12544
+    sel = np.unique(np.concatenate([[0, per - 1, per, 2 * per - 1, 2 * per, m - 1], np.random.default_rng(97).integers(0, m, size=200)])).astype(np.uint64)
+    want = np.asarray(a.get_rows_packed(sel, row_bytes)).copy()
+    assert want.any(axis=1).all()
+    d = "/dev/shm" if os.path.isdir("/dev/shm") and shutil.disk_usage("/dev/shm").free > 2 * m * row_bytes else str(tmp_path)
+    fn = os.path.join(d, "bigsi_three_chunks_%d_%d.bin" % (os.getpid(), row_bytes))
+    t0 = time.perf_counter()
+    try:
+        st = _lib.IoStats()
+        _lib.check(_lib.lib().bigsi_hip_save_rows_file(a.handle, fn.encode(), 0, 0, m, row_bytes, 0, _lib.C.byref(st)))
+        assert st.direct == direct and st.bytes == m * row_bytes == os.path.getsize(fn)
+        on_file = np.memmap(fn, dtype=np.uint8, mode="r", shape=(m, row_bytes))
+        assert np.array_equal(on_file[sel.astype(np.int64)], want)
+        del on_file
+        b = get_storage(cfg(31, m, 3, max_cols=n_cols, name="threechunks%d" % row_bytes))
+        b.delete_all()
+        b.set_integer("number_of_rows", m)
+        b.set_integer("number_of_cols", n_cols)
+        assert not _raw_rows(b, sel, row_bytes).any()                                               # a cleared index
+        st = _lib.IoStats()
+        _lib.check(_lib.lib().bigsi_hip_load_rows_file(b.handle, fn.encode(), 0, 0, m, row_bytes, 0, _lib.C.byref(st)))
+        assert st.direct == direct and st.bytes == m * row_bytes
+        assert np.array_equal(_raw_rows(b, sel, row_bytes), want)
+        b.delete_all()
+    finally:
+        if os.path.exists(fn):
+            os.remove(fn)
+        a.delete_all()
+    print("rows file over three chunks, row_bytes %d: %.2f s after the fill" % (row_bytes, time.perf_counter() - t0))
+
+
+def _raw_rows(st, ids, row_bytes):
+    """Rows straight from bigsi_hip_get_rows (no written-rows bookkeeping in the way)."""
+    from bigsi_amd import _lib
+    out = np.full((ids.size, row_bytes), 0xAB, np.uint8)
+    _lib.check(st.res.fn("get_rows")(st.handle, _lib.ptr(ids), ids.size, _lib.ptr(out), row_bytes))
+    return out
+
+
 def test_rows_file_striped_over_part_files(hip, tmp_path):
     """A path that ends in '/' is a DIRECTORY of 16 part files over which the rows are striped (stripes of ~4 MB; one inode takes a
     few GB/s of writes, sixteen take the PCIe rate): both row lengths, a range that starts and ends inside stripes, written by one

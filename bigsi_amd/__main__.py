@@ -130,7 +130,19 @@ def build_parser():
     sp.add_argument("to_config")
     sp.add_argument("--groups", required=True, metavar="FILE", help="sample<TAB>group lines; a group's colour follows its first appearance")
     sp.add_argument("--keep-others", action="store_true", help="samples the file does not name stay, each as a group of its own, after the named groups")
-    for name in ("vacuum", "extract", "fold", "prevalence", "collapse"):          # (named so that the refusal says why)
+    sp = common(sub.add_parser("distances", help="how much every sample shares with every other: bits shared, Jaccard index and containment of every pair, "
+                                                 "in one pass on the device"))
+    sp.add_argument("--samples", "-s", action="append", default=[], metavar="NAME", help="only these samples (default: every sample)")
+    sp.add_argument("--samples-file", default=None, metavar="FILE", help="one sample name per line")
+    sp.add_argument("--against-file", default=None, metavar="FILE", help="compare with these samples instead of with the same list (one name per line)")
+    sp.add_argument("--format", choices=["json", "csv"], default="json")
+    sp = common(sub.add_parser("cluster", help="groups of near-duplicate samples (single linkage over the pairs with a Jaccard index of at least T): "
+                                               "what `collapse --groups` takes"))
+    sp.add_argument("--min-jaccard", type=float, required=True, metavar="T", help="in (0, 1]")
+    sp.add_argument("--samples", "-s", action="append", default=[], metavar="NAME", help="only these samples (default: every sample)")
+    sp.add_argument("--samples-file", default=None, metavar="FILE", help="one sample name per line")
+    sp.add_argument("--out", default=None, metavar="FILE", help="also write the groups as sample<TAB>group lines, the file `collapse --groups` reads")
+    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "distances", "cluster"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -147,6 +159,27 @@ def similar_text(index, sample, limit=None, fmt="json"):
     from .stats import SIMILAR_KEYS, to_csv
     rows = index.similar_samples(sample, limit=limit)
     return to_csv(rows, SIMILAR_KEYS) if fmt == "csv" else json.dumps(rows)
+
+
+def distances_text(index, samples=None, against=None, fmt="json"):
+    """`distances`: BIGSI.sample_distances as JSON (the matrices as lists of rows), or as CSV: the three matrices one after the
+    other, each under a line with its name, rows and columns under the sample names."""
+    from .distances import to_matrix_csv
+    d = index.sample_distances(samples, against)
+    keys = ("bits_shared", "jaccard", "containment")
+    if fmt == "csv":
+        return "\n".join("# %s\n%s" % (k, to_matrix_csv(d[k], d["samples"], d["against"])) for k in keys)
+    return json.dumps({"samples": d["samples"], "against": d["against"], **{k: d[k].tolist() for k in keys}})
+
+
+def cluster_text(index, min_jaccard, samples=None, out=None):
+    """`cluster`: BIGSI.cluster_samples as JSON (group -> members); --out FILE also gets it as the lines `collapse --groups` reads."""
+    from .distances import groups_to_tsv
+    groups = index.cluster_samples(min_jaccard, samples)
+    if out:
+        with open(out, "w") as f:
+            f.write(groups_to_tsv(groups))
+    return json.dumps(groups)
 
 
 def vacuum_text(index, shrink=True):
@@ -292,6 +325,8 @@ def main(argv=None):
         p.error("fold is not available with --sharded: folding column shards is not implemented (use a single index)")
     if getattr(a, "sharded", False) and a.cmd == "prevalence":
         p.error("prevalence is not available with --sharded: the per-shard sweep plus a host sum is not implemented (use a single index)")
+    if getattr(a, "sharded", False) and a.cmd in ("distances", "cluster"):
+        p.error("%s is not available with --sharded: pairs of samples on different shards are not implemented (use a single index)" % a.cmd)
     if a.cmd == "prevalence" and (a.seq is None) == (a.fasta is None):
         p.error("prevalence takes SEQ or --fasta FILE (one of them)")
     if a.cmd == "fold" and not a.dry_run and not a.to_config:
@@ -360,6 +395,14 @@ def main(argv=None):
         queries = [a.seq] if a.fasta is None else [s for _, s in read_fasta(a.fasta)]
         names = extract_names(a)
         print(prevalence_text(BIGSI(config), queries, names or None, a.format))
+    elif a.cmd == "distances":
+        against = None
+        if a.against_file:
+            with open(a.against_file) as f:
+                against = [line.strip() for line in f if line.strip()]
+        print(distances_text(BIGSI(config), extract_names(a) or None, against, a.format))
+    elif a.cmd == "cluster":
+        print(cluster_text(BIGSI(config), a.min_jaccard, extract_names(a) or None, a.out))
     elif a.cmd == "hold":
         hold(config, a.handle, a.seconds, a.until_eof)
     return 0

@@ -206,6 +206,12 @@ PREVALENCE_SIGNATURES = {
     "bigsi_hip_batch_kmer_prevalence": (_i32, [_P, _P, _P, _P, _P, _u64]),
 }
 
+# every symbol include/bigsi_hip_pairwise.h declares (pairwise popcounts: the shared-bit counts of every pair of two lists of columns)
+PAIRWISE_SIGNATURES = {
+    "bigsi_hip_pairwise_popcounts": (_i32, [_P, _P, _u64, _P, _u64, _P, _u64]),
+    "bigsi_hip_pairwise_phase_ms": (_i32, [_P, _P]),
+}
+
 _lib = None
 
 
@@ -226,7 +232,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

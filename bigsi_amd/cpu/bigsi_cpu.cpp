@@ -19,6 +19,7 @@
 #include "bigsi_cpu_collapse.h"
 #include "bigsi_cpu_compact.h"
 #include "bigsi_cpu_fold.h"
+#include "bigsi_cpu_pairwise.h"
 #include "bigsi_cpu_prevalence.h"
 
 #include <math.h>
@@ -632,6 +633,37 @@ int bigsi_cpu_column_popcounts(bigsi_cpu_index *ix, const uint8_t *row_mask, uin
         const uint8_t *row = ix->row(r);
         for (uint64_t c = 0; c < ix->n_cols; c++)
             if (row[c >> 3] & (0x80u >> (c & 7))) out[c]++;
+    }
+    return BIGSI_OK;
+}
+
+// Pairwise popcounts: per row, the selected A columns that are set, each against every selected B column -- the plain loop
+int bigsi_cpu_pairwise_popcounts(bigsi_cpu_index *ix, const uint32_t *cols_a, uint64_t na, const uint32_t *cols_b, uint64_t nb, uint64_t *out,
+                                 uint64_t capacity)
+{
+    if (!ix || !cols_a || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (na == 0 || (cols_b && nb == 0)) return fail(BIGSI_ERR_INVALID, "an empty list of columns");
+    const uint32_t *cb = cols_b ? cols_b : cols_a;
+    if (!cols_b) nb = na;
+    for (uint64_t i = 0; i < na; i++)
+        if (cols_a[i] >= ix->n_cols)
+            return fail(BIGSI_ERR_RANGE, "cols_a[%llu] = %u is not a column of the index [0,%llu)", (unsigned long long)i, cols_a[i], (unsigned long long)ix->n_cols);
+    for (uint64_t j = 0; cols_b && j < nb; j++)
+        if (cols_b[j] >= ix->n_cols)
+            return fail(BIGSI_ERR_RANGE, "cols_b[%llu] = %u is not a column of the index [0,%llu)", (unsigned long long)j, cols_b[j], (unsigned long long)ix->n_cols);
+    const unsigned __int128 pairs = (unsigned __int128)na * nb;
+    if (pairs > capacity) return fail(BIGSI_ERR_CAPACITY, "capacity %llu is below na x nb = %llu x %llu", (unsigned long long)capacity, (unsigned long long)na, (unsigned long long)nb);
+    if (pairs > BIGSI_PAIRWISE_MAX_PAIRS)
+        return fail(BIGSI_ERR_RANGE, "na x nb = %llu x %llu is above BIGSI_PAIRWISE_MAX_PAIRS (%llu)", (unsigned long long)na, (unsigned long long)nb, (unsigned long long)BIGSI_PAIRWISE_MAX_PAIRS);
+    TRY(read_only(ix));
+    for (uint64_t e = 0; e < na * nb; e++) out[e] = 0;
+    for (uint64_t r = 0; r < ix->m; r++) {
+        const uint8_t *row = ix->row(r);
+        for (uint64_t i = 0; i < na; i++) {
+            if (!(row[cols_a[i] >> 3] & (0x80u >> (cols_a[i] & 7)))) continue;
+            for (uint64_t j = 0; j < nb; j++)
+                if (row[cb[j] >> 3] & (0x80u >> (cb[j] & 7))) out[i * nb + j]++;
+        }
     }
     return BIGSI_OK;
 }

@@ -1025,6 +1025,125 @@ extern "C" int bigsi_hip_collapse_columns_into(bigsi_hip_index *dst, const bigsi
     return BIGSI_OK;
 }
 
+// Pairwise popcounts (k_columns_to_planes, k_pair_popcount, k_pair_popcount_sum; chunks, slices and scratch: plan_pairwise; tables:
+// pairwise_tables).  Two allocations that live for this call only: the scratch (tables | planes | partials) and the 64-bit device
+// result.  Either may not fit beside a large index: BIGSI_ERR_NOMEM then, with nothing leaked and the runtime's sticky last-error
+// slot clear, as in replace_matrix.
+namespace {
+struct PairScratch {
+    void *scratch = nullptr, *result = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~PairScratch()
+    {
+        hipError_t e;
+        for (hipEvent_t v : ev)
+            if (v) { e = hipEventDestroy(v); (void)e; }
+        if (scratch) { e = hipFree(scratch); (void)e; }
+        if (result) { e = hipFree(result); (void)e; }
+    }
+};
+}  // namespace
+
+static int pair_alloc(void **p, size_t bytes, const char *what)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return BIGSI_OK;
+    (void)hipGetLastError();
+    *p = nullptr;
+    return fail(e == hipErrorOutOfMemory ? BIGSI_ERR_NOMEM : BIGSI_ERR_HIP, "bigsi_hip_pairwise_popcounts: hipMalloc of %zu bytes for %s beside the matrix failed: %s", bytes,
+                what, hipGetErrorString(e));
+}
+
+// with profiling on: the time of what was queued on the stream since `ev[0]` was recorded, added to *ms
+static int pair_phase(bigsi_hip_index *ix, PairScratch &s, double *ms)
+{
+    HIP_TRY(hipGetLastError());
+    if (!ix->profiling) return BIGSI_OK;
+    float t = 0;
+    HIP_TRY(hipEventRecord(s.ev[1], ix->stream));
+    HIP_TRY(hipEventSynchronize(s.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&t, s.ev[0], s.ev[1]));
+    *ms += t;
+    HIP_TRY(hipEventRecord(s.ev[0], ix->stream));
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_pairwise_popcounts(bigsi_hip_index *ix, const uint32_t *cols_a, uint64_t na, const uint32_t *cols_b, uint64_t nb, uint64_t *out,
+                                            uint64_t capacity)
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !cols_a || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (na == 0 || (cols_b && nb == 0)) return fail(BIGSI_ERR_INVALID, "an empty list of columns");
+    const bool symmetric = cols_b == nullptr;
+    if (symmetric) nb = na;
+    uint64_t bad = pairwise_first_bad(cols_a, na, ix->n_cols);
+    if (bad < na)
+        return fail(BIGSI_ERR_RANGE, "cols_a[%llu] = %u is not a column of the index [0,%llu)", (unsigned long long)bad, cols_a[bad], (unsigned long long)ix->n_cols);
+    if (!symmetric && (bad = pairwise_first_bad(cols_b, nb, ix->n_cols)) < nb)
+        return fail(BIGSI_ERR_RANGE, "cols_b[%llu] = %u is not a column of the index [0,%llu)", (unsigned long long)bad, cols_b[bad], (unsigned long long)ix->n_cols);
+    const unsigned __int128 pairs = (unsigned __int128)na * nb;
+    if (pairs > capacity) return fail(BIGSI_ERR_CAPACITY, "capacity %llu is below na x nb = %llu x %llu", (unsigned long long)capacity, (unsigned long long)na, (unsigned long long)nb);
+    if (pairs > BIGSI_PAIRWISE_MAX_PAIRS)
+        return fail(BIGSI_ERR_RANGE, "na x nb = %llu x %llu is above BIGSI_PAIRWISE_MAX_PAIRS (%llu)", (unsigned long long)na, (unsigned long long)nb, (unsigned long long)BIGSI_PAIRWISE_MAX_PAIRS);
+    static_assert(kPairwiseMaxPairs == BIGSI_PAIRWISE_MAX_PAIRS, "the planner's bound is the header's");
+    if (ix->m == 0) { memset(out, 0, na * nb * 8); return BIGSI_OK; }
+    TRY(use_device(ix));
+
+    const PairwiseTables t = pairwise_tables(cols_a, na, cols_b, nb);
+    const uint64_t nua = t.plane_a.size(), nub = symmetric ? nua : t.plane_b.size(), distinct = t.bit.size(), nw = t.words.size();
+    const PairwisePlan p = plan_pairwise(nua, nub, symmetric, ix->m, ix->stride_words);
+    if (p.tiles > 0x7FFFFFFFull || p.slices > 65535 || distinct * p.chunk_words * 8 > p.plane_bytes || t.words.back() >= ix->stride_words)
+        return fail(BIGSI_ERR_STATE, "internal: a pairwise plan of %llu tiles x %llu slices over %llu distinct columns does not fit a launch or its planes",
+                    (unsigned long long)p.tiles, (unsigned long long)p.slices, (unsigned long long)distinct);
+    // scratch: words | first | bit | plane_a | plane_b | map_a | map_b | planes | partials, every part on a 256-byte boundary
+    const std::vector<uint32_t> *tabs[7] = {&t.words, &t.first, &t.bit, &t.plane_a, &t.plane_b, &t.map_a, &t.map_b};
+    uint64_t off[9], at = 0;
+    for (int k = 0; k < 7; k++) { off[k] = at; at += round_up(tabs[k]->size() * 4, 256); }
+    off[7] = at; at += round_up(p.plane_bytes, 256);
+    off[8] = at; at += round_up(p.partial_bytes, 256);
+    PairScratch s;
+    TRY(pair_alloc(&s.scratch, at, "the planes and partial counts"));
+    TRY(pair_alloc(&s.result, na * nb * 8, "the result"));
+    uint8_t *base = reinterpret_cast<uint8_t *>(s.scratch);
+    for (int k = 0; k < 7; k++)
+        if (!tabs[k]->empty()) HIP_TRY(hipMemcpyAsync(base + off[k], tabs[k]->data(), tabs[k]->size() * 4, hipMemcpyHostToDevice, ix->stream));
+    const auto tab = [&](int k) { return reinterpret_cast<const uint32_t *>(base + off[k]); };
+    const uint32_t *d_plane_b = symmetric ? tab(3) : tab(4), *d_map_b = symmetric ? tab(5) : tab(6);
+    uint64_t *planes = reinterpret_cast<uint64_t *>(base + off[7]);
+    uint32_t *partial = reinterpret_cast<uint32_t *>(base + off[8]);
+    double ms[4] = {0, 0, 0, (double)p.chunks};
+    if (ix->profiling) {
+        HIP_TRY(hipEventCreate(&s.ev[0]));
+        HIP_TRY(hipEventCreate(&s.ev[1]));
+        HIP_TRY(hipEventRecord(s.ev[0], ix->stream));
+    }
+    const unsigned sum_grid = (unsigned)std::min<uint64_t>(ceil_div(na * nb, kBlock), 256 * 8 * 4);
+    for (uint64_t c = 0; c < p.chunks; c++) {
+        const uint64_t words = pairwise_chunk_words(p, c), slices = pairwise_chunk_slices(p, words);
+        hipLaunchKernelGGL(k_columns_to_planes, dim3((unsigned)ceil_div(words, kBlock / 64)), dim3(kBlock), 0, ix->stream, ix->d_index, ix->stride_words, ix->m,
+                           c * p.chunk_words * 64, words, tab(0), tab(1), tab(2), (uint32_t)nw, planes, p.chunk_words);
+        TRY(pair_phase(ix, s, &ms[0]));
+        hipLaunchKernelGGL(k_pair_popcount, dim3((unsigned)p.tiles, (unsigned)slices), dim3(kBlock), 0, ix->stream, planes, p.chunk_words, words, p.slice_words, tab(3),
+                           (uint32_t)nua, d_plane_b, (uint32_t)nub, (uint32_t)p.tiles_j, symmetric ? 1u : 0u, partial);
+        TRY(pair_phase(ix, s, &ms[1]));
+        hipLaunchKernelGGL(k_pair_popcount_sum, dim3(sum_grid), dim3(kBlock), 0, ix->stream, partial, slices, (uint32_t)nua, (uint32_t)nub, tab(5), na, d_map_b, nb,
+                           symmetric ? 1u : 0u, c ? 1u : 0u, reinterpret_cast<uint64_t *>(s.result));
+        TRY(pair_phase(ix, s, &ms[2]));
+    }
+    HIP_TRY(hipMemcpyAsync(out, s.result, na * nb * 8, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));          // (the scratch goes out of scope)
+    if (ix->profiling) memcpy(ix->pair_ms, ms, sizeof ms);
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_pairwise_phase_ms(bigsi_hip_index *ix, double ms[4])
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !ms) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    memcpy(ms, ix->pair_ms, sizeof ix->pair_ms);
+    return BIGSI_OK;
+}
+
 // Row folding (k_fold_rows; launch shape: plan_fold_rows).  `dst` may be `src` (in place: see the kernel); factors below kFoldLoads
 // have a kernel of their own (the factor is a compile-time constant there), every other factor runs the generic one.
 template <int D>

@@ -7,6 +7,7 @@
 #include "bigsi_hip_compact.h"
 #include "bigsi_hip_fold.h"
 #include "bigsi_hip_group.h"
+#include "bigsi_hip_pairwise.h"
 #include "bigsi_hip_prevalence.h"
 #include "bigsi_hip_testing.h"
 #include "bigsi_hip_text.h"
@@ -122,6 +123,7 @@ struct bigsi_hip_index {
     uint64_t and_total = 0;       // row-AND launches since the last stats reset, timed or not
     std::vector<EventPair> ev_and, ev_km, ev_cp, ev_pr, ev_tr, ev_ex, ev_free;
     uint64_t presence_bytes = 0;   // algorithmic bytes of the timed presence_hits calls
+    double pair_ms[4] = {0, 0, 0, 0};   // bigsi_hip_pairwise_phase_ms: the last profiled pairwise call's kernel times and chunks
     uint64_t wv() const { return ceil_div(n_cols, 64); }
     uint64_t rb() const { return ceil_div(n_cols, 8); }
 };

@@ -3353,6 +3353,132 @@ __global__ __launch_bounds__(kBlock) void k_fill_synth(
     }
 }
 
+// ------------------------------------------------------------------------------ pairwise popcounts: |column i AND column j| for lists of columns
+// Three kernels per chunk of rows (plan_pairwise, bigsi_launch.hpp, says how the rows are cut and why).
+//
+// k_columns_to_planes: the selected columns of a chunk, transposed.  A wavefront owns the 64-row group g of the chunk (rows
+// row0 + 64 g ..), a lane one row of it; planes[u * plane_stride + g] gets bit k = the bit of plane u's column in row row0 + 64 g + k.
+// The planes are the distinct selected columns in ascending order, so the wavefront walks the distinct source words upwards
+// (words / first / bit: pairwise_tables), kPlaneLoads 8-byte loads in flight per lane, and every selected column of a loaded word is
+// one shift, one __ballot and one 8-byte store by lane 0.  The lanes of a load touch 64 rows, i.e. 64 lines, of which the next
+// words of the same rows use the rest while they are in the cache.  A lane whose row is at or beyond num_rows loads nothing and
+// contributes 0: rows an in-place fold left in the allocation are never counted, and a group wholly beyond num_rows is a zero word.
+__global__ __launch_bounds__(kBlock) void k_columns_to_planes(
+    const uint64_t *__restrict__ index, uint64_t stride_words, uint64_t num_rows, uint64_t row0, uint64_t groups,
+    const uint32_t *__restrict__ words, const uint32_t *__restrict__ first, const uint32_t *__restrict__ bit, uint32_t num_words,
+    uint64_t *__restrict__ planes, uint64_t plane_stride)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (g >= groups) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t r = row0 + g * 64 + lane;
+    const bool valid = r < num_rows;
+    const uint64_t *row = index + (valid ? r : 0) * stride_words;
+    for (uint32_t k0 = 0; k0 < num_words; k0 += kPlaneLoads) {
+        uint64_t v[kPlaneLoads];
+#pragma unroll
+        for (int j = 0; j < kPlaneLoads; j++) v[j] = (valid && k0 + j < num_words) ? row[words[k0 + j]] : 0ull;
+#pragma unroll
+        for (int j = 0; j < kPlaneLoads; j++) {
+            if (k0 + j >= num_words) break;
+            const uint32_t u1 = first[k0 + j + 1];
+            for (uint32_t u = first[k0 + j]; u < u1; u++) {
+                const uint64_t word = __ballot((int)((v[j] >> bit[u]) & 1ull));
+                if (lane == 0) planes[(uint64_t)u * plane_stride + g] = word;
+            }
+        }
+    }
+}
+
+// k_pair_popcount: the tiled popcount "GEMM".  Workgroup (tile, slice): tile = (ti, tj) of kPairTile x kPairTile (distinct A column,
+// distinct B column) pairs, slice = words [w_begin, w_end) of the chunk's planes.  Both plane tiles are staged kPairStageWords words
+// at a time: a thread loads one 8-byte word (32 lanes = 256 consecutive bytes of one plane) and stores it at lds[word][column];
+// columns beyond the list and words beyond the slice are staged as 0.  Thread (ty, tx) of 16 x 16 owns the pairs
+// (pair_col(ty, a), pair_col(tx, b)), a, b < 4 -- two neighbouring columns in each half of the tile: per word it reads them as two
+// 16-byte values per operand (ds_read_b128) and does, per pair, two 32-bit ANDs and two popcounts that add into the pair's 32-bit
+// counter (v_bcnt_u32_b32 accumulates): 4 VALU operations per 64 pair-bits.
+// LDS layout, stated for the reads of a wavefront (a ds_read_b128 is served in four groups of 16 lanes, banks = (address / 4) % 64):
+// the word w of an operand is a run of kPairTile consecutive 64-bit values (kPairLdsStride = kPairTile + 2 apart from word to word:
+// 16-byte aligned).  A group holds at most two values of ty and up to sixteen of tx: an A read is two addresses 16 bytes apart, each
+// broadcast; a B read is sixteen consecutive 16-byte values = the 64 banks once.  Both are conflict-free.  The pad only serves the
+// staging stores.  (The first version read eight 8-byte values per word at a stride of 16 columns; the compiler paired them into
+// ds_read2_b64, half the bytes per LDS clock: DESIGN.md section 3 has both measurements.)
+// A counter sees at most 64 (w_end - w_begin) <= 2^30 rows.  Symmetric calls: the workgroups of tiles tj < ti leave at once, the
+// sum reads the mirror.  partial[slice][ua][ub]: nua x nub 32-bit counts per slice, no padding (stores are guarded).
+// the k-th of the kPairReg tile columns thread coordinate t (0 .. 15) owns: 2 t, 2 t + 1, 32 + 2 t, 32 + 2 t + 1
+__device__ __forceinline__ uint32_t pair_col(uint32_t t, int k) { return 2u * t + (uint32_t)(k & 1) + 32u * (uint32_t)(k >> 1); }
+
+__global__ __launch_bounds__(kBlock) void k_pair_popcount(
+    const uint64_t *__restrict__ planes, uint64_t plane_stride, uint64_t chunk_words, uint64_t slice_words,
+    const uint32_t *__restrict__ plane_a, uint32_t nua, const uint32_t *__restrict__ plane_b, uint32_t nub, uint32_t tiles_j, uint32_t symmetric,
+    uint32_t *__restrict__ partial)
+{
+    __shared__ __attribute__((aligned(16))) uint64_t lds_a[kPairStageWords * kPairLdsStride], lds_b[kPairStageWords * kPairLdsStride];
+    const uint32_t ti = blockIdx.x / tiles_j, tj = blockIdx.x % tiles_j;
+    if (symmetric && tj < ti) return;
+    const uint64_t w_begin = (uint64_t)blockIdx.y * slice_words, w_end = min(w_begin + slice_words, chunk_words);
+    const uint32_t t = threadIdx.x, ty = t >> 4, tx = t & 15u;
+    const uint32_t sw = t % kPairStageWords, sc = t / kPairStageWords;          // staging: this thread's word and first column
+    constexpr uint32_t kPass = kBlock / kPairStageWords;                          // columns staged per pass
+    uint32_t acc[kPairReg][kPairReg] = {};
+    for (uint64_t w0 = w_begin; w0 < w_end; w0 += kPairStageWords) {
+        const uint32_t nw = (uint32_t)min<uint64_t>(kPairStageWords, w_end - w0);
+        __syncthreads();          // (the previous stage has been read)
+#pragma unroll
+        for (uint32_t c = sc; c < (uint32_t)kPairTile; c += kPass) {
+            const uint32_t ia = ti * kPairTile + c, ib = tj * kPairTile + c;
+            lds_a[sw * kPairLdsStride + c] = (sw < nw && ia < nua) ? planes[(uint64_t)plane_a[ia] * plane_stride + w0 + sw] : 0ull;
+            lds_b[sw * kPairLdsStride + c] = (sw < nw && ib < nub) ? planes[(uint64_t)plane_b[ib] * plane_stride + w0 + sw] : 0ull;
+        }
+        __syncthreads();
+        for (uint32_t w = 0; w < nw; w++) {
+            uint64_t a[kPairReg], b[kPairReg];
+#pragma unroll
+            for (int i = 0; i < kPairReg; i += 2) {
+                const u64x2 va = *reinterpret_cast<const u64x2 *>(&lds_a[w * kPairLdsStride + 2 * ty + 16 * i]);
+                const u64x2 vb = *reinterpret_cast<const u64x2 *>(&lds_b[w * kPairLdsStride + 2 * tx + 16 * i]);
+                a[i] = va.x; a[i + 1] = va.y;
+                b[i] = vb.x; b[i + 1] = vb.y;
+            }
+#pragma unroll
+            for (int i = 0; i < kPairReg; i++)
+#pragma unroll
+                for (int j = 0; j < kPairReg; j++) {
+                    const uint64_t x = a[i] & b[j];
+                    acc[i][j] = __popc((uint32_t)(x >> 32)) + (__popc((uint32_t)x) + acc[i][j]);
+                }
+        }
+    }
+    uint32_t *out = partial + (uint64_t)blockIdx.y * nua * nub;
+#pragma unroll
+    for (int i = 0; i < kPairReg; i++) {
+        const uint32_t ia = ti * kPairTile + pair_col(ty, i);
+#pragma unroll
+        for (int j = 0; j < kPairReg; j++) {
+            const uint32_t ib = tj * kPairTile + pair_col(tx, j);
+            if (ia < nua && ib < nub) out[(uint64_t)ia * nub + ib] = acc[i][j];
+        }
+    }
+}
+
+// k_pair_popcount_sum: out[i][j] (64-bit, na x nb) gets -- `add` == 0, the first chunk -- or is increased by the sum over the chunk's
+// slices of partial[slice][map_a[i]][map_b[j]]: list positions that repeat a column read the same count.  Symmetric calls
+// (map_b == map_a, nub == nua) take a pair whose tile lies below the diagonal from the mirror tile, which k_pair_popcount did run.
+__global__ __launch_bounds__(kBlock) void k_pair_popcount_sum(
+    const uint32_t *__restrict__ partial, uint64_t slices, uint32_t nua, uint32_t nub, const uint32_t *__restrict__ map_a, uint64_t na,
+    const uint32_t *__restrict__ map_b, uint64_t nb, uint32_t symmetric, uint32_t add, uint64_t *__restrict__ out)
+{
+    const uint64_t total = na * nb, per_slice = (uint64_t)nua * nub;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (uint64_t)gridDim.x * kBlock) {
+        uint32_t u = map_a[e / nb], v = map_b[e % nb];
+        if (symmetric && v / kPairTile < u / kPairTile) { const uint32_t s = u; u = v; v = s; }
+        const uint32_t *p = partial + (uint64_t)u * nub + v;
+        uint64_t s = 0;
+        for (uint64_t k = 0; k < slices; k++) s += p[k * per_slice];
+        out[e] = add ? out[e] + s : s;
+    }
+}
+
 // ------------------------------------------------------------------------------ calibration: what this box gives bare row streams
 // bigsi_hip_probe_rows (MEASUREMENT): a kernel with NO BIGSI code reads row lists of the index itself the way the row-AND
 // kernels do -- one wavefront per 1 KiB column segment of every row of a "query", lane = 16 bytes, eight non-temporal loads in

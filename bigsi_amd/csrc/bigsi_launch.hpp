@@ -1,12 +1,14 @@
 // bigsi_launch.hpp -- the launch rule of a batch run, host-only: how K1 goes out (k1_plan) and how the row-AND kernels
 // (k_and_exact, k_and_count, k_count_combine) are launched for a batch of queries (plan_row_and), the sweep of the column popcounts
 // (plan_col_popcount), the per-call tables of the column compaction (plan_compact_columns), the sweep of the row folding
-// (plan_fold_rows), the sweep of the k-mer prevalence (plan_kmer_prevalence) and the per-call tables, launch shape and destination
-// window of the column collapse (plan_collapse_columns).  Pure functions of a handful of integers (and, for the compaction and the
-// collapse, of the keep bitmap / the group map): no HIP, no batch, no index.  bigsi_hip.hip carries the plans out;
-// tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp, prevalence_host.cpp and collapse_host.cpp compile this header as
-// plain host C++ and tests/test_abi_and_host.py, test_sample_stats_host.py, test_compact_columns_host.py, test_fold_rows_host.py,
-// test_kmer_prevalence_host.py and test_collapse_columns_host.py pin the decisions on the CPU.
+// (plan_fold_rows), the sweep of the k-mer prevalence (plan_kmer_prevalence), the per-call tables, launch shape and destination
+// window of the column collapse (plan_collapse_columns) and the chunks, slices, scratch and per-call tables of the pairwise popcounts
+// (plan_pairwise, pairwise_tables).  Pure functions of a handful of integers (and, for the compaction, the collapse and the pairwise
+// popcounts, of the keep bitmap / the group map / the column lists): no HIP, no batch, no index.  bigsi_hip.hip carries the plans out;
+// tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp, prevalence_host.cpp, collapse_host.cpp and pairwise_host.cpp compile
+// this header as plain host C++ and tests/test_abi_and_host.py, test_sample_stats_host.py, test_compact_columns_host.py,
+// test_fold_rows_host.py, test_kmer_prevalence_host.py, test_collapse_columns_host.py and test_pairwise_host.py pin the decisions on
+// the CPU.
 //
 // Every constant below was measured on an MI355X; the notes beside them say against what.  A GPU test compares results, and a slip
 // here keeps results right and costs the 3 to 20 % those notes record: change a constant only with a new measurement, and the pinned
@@ -594,6 +596,137 @@ static inline CollapsePlan plan_collapse_columns(uint64_t num_cols, const uint32
     p.grid = std::min<uint64_t>(ceil_div(rows, waves_per_block), kCollapseWaves / (kBlock / 64));
     p.lds_bytes = p.image_words * 8 * waves_per_block;
     return p;
+}
+
+// ------------------------------------------------------------------------------ pairwise popcounts (k_columns_to_planes, k_pair_popcount, k_pair_popcount_sum)
+// out[i][j] = |column cols_a[i] AND column cols_b[j]| over the rows: the bit-matrix product B^T B of the selected columns, the first
+// compute-bound sweep here.  The rows are taken in CHUNKS; per chunk three launches on the index stream:
+//   1. k_columns_to_planes transposes the distinct selected columns of the chunk into planes[u][chunk_words]: one 64-bit word per
+//      column and 64-row group (a wavefront owns the group, a lane a row, a ballot makes the word).  Rows at or beyond num_rows come
+//      out as 0, so what an in-place fold left behind num_rows is never counted.
+//   2. k_pair_popcount: a workgroup owns a kPairTile x kPairTile tile of (distinct A column, distinct B column) pairs and one SLICE
+//      of the chunk's words, stages both plane tiles kPairStageWords words at a time in LDS, every thread keeps a 4 x 4 block of
+//      32-bit counters and writes them to partial[slice][ua][ub].  Symmetric calls (cols_b == NULL) run the tiles tj >= ti only.
+//   3. k_pair_popcount_sum adds the slices of the chunk into the 64-bit [na][nb] device matrix (the first chunk assigns), through the
+//      maps from list position to distinct column -- repeats are expanded here -- and, for symmetric calls, from the mirror tile.
+// No global atomics, no workgroup waits for another.
+// The host tables (PairwiseTables): the distinct columns of both lists in ascending order (= ascending source word, so a loaded word
+// serves all of its selected columns and a 128-byte line is fetched once per 64-row group), as `words` (distinct source words),
+// `first` (the planes of word k are first[k] .. first[k + 1]) and `bit` (the plane's bit in its word AS IT LIES IN MEMORY,
+// collapse_mem_bit); plane_a / plane_b: the plane of the u-th distinct column of a list; map_a / map_b: list position -> u.
+// The plan:
+//   - chunk_words (64-row words per chunk): what kPairPlaneBytes of planes hold for the distinct columns (at most na_unique +
+//     nb_unique of them; symmetric: na_unique), at least 2, at most kPairMaxChunkWords; and from kPairSplitWords words (2048 rows)
+//     on never more than a third of the rows, so that every index of a few thousand rows already adds up three chunks (six more
+//     launches on a large index that would have fitted one).
+//   - slices: enough that tiles x slices reaches kPairWantGroups workgroups (8 per CU: the LDS of a workgroup is 32.5 KiB, four
+//     fit a CU), at least two, no slice below kPairMinSliceWords words unless that leaves one slice, and no more than
+//     kPairPartialBytes of partials hold (a selection of more than 2^27 distinct pairs has ONE slice: its partials alone are
+//     over 512 MiB).  The last slice and the last chunk are ragged; no slice is empty.
+//   - overflow: a 32-bit counter sees at most 64 x slice_words <= 64 x kPairMaxChunkWords = 2^30 rows.
+// Scratch (PairwisePlan::plane_bytes + partial_bytes, independent of num_rows): plane_bytes <= max(kPairPlaneBytes, 16 x distinct
+// columns), partial_bytes <= max(kPairPartialBytes, 4 x na_unique x nb_unique) -- 1.5 GiB for anything up to 2^26 distinct columns
+// and 2^28 distinct pairs; the tables are 12 bytes per distinct column and 4 per list entry beside it.
+// UNMEASURED starting values: kPairTile, the 4 x 4 register block, kPairStageWords, kPairWantGroups, kPlaneLoads.
+constexpr uint64_t kPairwiseMaxPairs = 1ull << 28;          // na x nb of one call (2 GiB of uint64): BIGSI_PAIRWISE_MAX_PAIRS
+constexpr int kPairTile = 64;                                // distinct columns per tile side
+constexpr int kPairReg = 4;                                  // a thread's block is kPairReg x kPairReg pairs (16 x 16 threads)
+constexpr int kPairStageWords = 32;                          // 64-row words of both tiles staged in LDS at a time
+constexpr int kPairLdsStride = kPairTile + 2;                // 64-bit words per staged word (the pad spreads the staging stores over the banks; even: 16-byte reads)
+constexpr int kPlaneLoads = 4;                               // independent 8-byte row loads a lane has in flight in k_columns_to_planes
+constexpr uint64_t kPairPlaneBytes = 512ull << 20;
+constexpr uint64_t kPairPartialBytes = 1ull << 30;
+constexpr uint64_t kPairMaxChunkWords = 1ull << 24;
+constexpr uint64_t kPairSplitWords = 32;
+constexpr uint64_t kPairSplitChunks = 3;
+constexpr uint64_t kPairMinSliceWords = 4;
+constexpr uint64_t kPairWantGroups = 2048;
+static_assert(kPairTile == 16 * kPairReg && kBlock == 16 * 16, "16 x 16 threads of kPairReg x kPairReg pairs cover a tile");
+static_assert(kBlock % kPairStageWords == 0 && kPairTile % (kBlock / kPairStageWords) == 0, "the staging loop covers a tile in whole passes");
+struct PairwisePlan {
+    uint64_t total_words = 0;        // ceil(num_rows / 64)
+    uint64_t chunk_words = 0;        // words per chunk = the stride of a plane
+    uint64_t chunks = 0;
+    uint64_t slice_words = 0;        // words per slice
+    uint64_t slices = 0;             // of a full chunk
+    uint64_t tiles_i = 0, tiles_j = 0;
+    uint64_t tiles = 0;              // workgroups per slice: tiles_i x tiles_j (symmetric: those below the diagonal leave at once)
+    uint64_t plane_bytes = 0, partial_bytes = 0;
+};
+// words of chunk c / slices of a chunk of `words` words
+static inline uint64_t pairwise_chunk_words(const PairwisePlan &p, uint64_t c) { return std::min(p.chunk_words, p.total_words - std::min(p.total_words, c * p.chunk_words)); }
+static inline uint64_t pairwise_chunk_slices(const PairwisePlan &p, uint64_t words) { return ceil_div(words, p.slice_words); }
+// na_unique, nb_unique >= 1 distinct columns (symmetric: nb_unique == na_unique); num_rows >= 1; `stride_words` bounds the distinct columns
+static inline PairwisePlan plan_pairwise(uint64_t na_unique, uint64_t nb_unique, bool symmetric, uint64_t num_rows, uint64_t stride_words)
+{
+    PairwisePlan p;
+    const uint64_t distinct = std::min<uint64_t>(symmetric ? na_unique : na_unique + nb_unique, std::max<uint64_t>(stride_words, 1) * 64);
+    p.total_words = std::max<uint64_t>(ceil_div(num_rows, 64), 1);
+    const uint64_t budget_words = std::min(std::max<uint64_t>(kPairPlaneBytes / (8 * distinct), 2), kPairMaxChunkWords);
+    p.chunk_words = std::min(budget_words, p.total_words >= kPairSplitWords ? ceil_div(p.total_words, kPairSplitChunks) : p.total_words);
+    p.chunks = ceil_div(p.total_words, p.chunk_words);
+    p.tiles_i = ceil_div(na_unique, kPairTile);
+    p.tiles_j = ceil_div(nb_unique, kPairTile);
+    p.tiles = p.tiles_i * p.tiles_j;
+    const uint64_t active = symmetric ? p.tiles_i * (p.tiles_i + 1) / 2 : p.tiles;
+    const uint64_t per_slice = 4 * na_unique * nb_unique;
+    const uint64_t by_budget = std::max<uint64_t>(kPairPartialBytes / per_slice, 1);
+    const uint64_t want = std::min(std::min(std::max<uint64_t>(ceil_div(kPairWantGroups, active), 2), by_budget), p.chunk_words);
+    p.slice_words = std::max(ceil_div(p.chunk_words, want), std::min(kPairMinSliceWords, by_budget > 1 ? ceil_div(p.chunk_words, 2) : p.chunk_words));
+    p.slices = ceil_div(p.chunk_words, p.slice_words);
+    p.plane_bytes = distinct * p.chunk_words * 8;
+    p.partial_bytes = p.slices * per_slice;
+    return p;
+}
+
+struct PairwiseTables {
+    std::vector<uint32_t> words, first, bit;          // first has words.size() + 1 entries, bit one per plane
+    std::vector<uint32_t> plane_a, plane_b;           // distinct column of a list -> plane (symmetric: plane_b is empty)
+    std::vector<uint32_t> map_a, map_b;               // list position -> distinct column of the list (symmetric: map_b is empty)
+};
+// the first entry of a list that is no column of the index, or n
+static inline uint64_t pairwise_first_bad(const uint32_t *cols, uint64_t n, uint64_t num_cols)
+{
+    for (uint64_t i = 0; i < n; i++)
+        if (cols[i] >= num_cols) return i;
+    return n;
+}
+// cols_b == nullptr: symmetric
+static inline PairwiseTables pairwise_tables(const uint32_t *cols_a, uint64_t na, const uint32_t *cols_b, uint64_t nb)
+{
+    PairwiseTables t;
+    std::vector<uint32_t> ua(cols_a, cols_a + na), ub, all;
+    std::sort(ua.begin(), ua.end());
+    ua.erase(std::unique(ua.begin(), ua.end()), ua.end());
+    if (cols_b) {
+        ub.assign(cols_b, cols_b + nb);
+        std::sort(ub.begin(), ub.end());
+        ub.erase(std::unique(ub.begin(), ub.end()), ub.end());
+        all.resize(ua.size() + ub.size());
+        all.erase(std::set_union(ua.begin(), ua.end(), ub.begin(), ub.end(), all.begin()), all.end());
+    } else
+        all = ua;
+    t.bit.reserve(all.size());
+    for (uint32_t c : all) {
+        if (t.words.empty() || t.words.back() != c >> 6) {
+            t.words.push_back(c >> 6);
+            t.first.push_back((uint32_t)t.bit.size());
+        }
+        t.bit.push_back(((c >> 3) & 7u) * 8u + 7u - (c & 7u));
+    }
+    t.first.push_back((uint32_t)t.bit.size());
+    const auto rank = [](const std::vector<uint32_t> &in, uint32_t c) { return (uint32_t)(std::lower_bound(in.begin(), in.end(), c) - in.begin()); };
+    t.plane_a.resize(ua.size());
+    for (size_t u = 0; u < ua.size(); u++) t.plane_a[u] = rank(all, ua[u]);
+    t.map_a.resize(na);
+    for (uint64_t i = 0; i < na; i++) t.map_a[i] = rank(ua, cols_a[i]);
+    if (cols_b) {
+        t.plane_b.resize(ub.size());
+        for (size_t u = 0; u < ub.size(); u++) t.plane_b[u] = rank(all, ub[u]);
+        t.map_b.resize(nb);
+        for (uint64_t j = 0; j < nb; j++) t.map_b[j] = rank(ub, cols_b[j]);
+    }
+    return t;
 }
 
 }  // namespace bigsi

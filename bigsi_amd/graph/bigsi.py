@@ -711,6 +711,67 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         n = min(len(counts), self.num_samples)
         return derive_similar(counts, int(bits.sum()), masked, self._sample_names(n), leave_out, limit)
 
+    # ------------------------------------------------------------------ sample-to-sample distances, near-duplicate groups
+    def _selected_colours(self, samples, names):
+        """(names, colours) of a selection: None = every live sample in colour order; a list = those samples in the order given
+        (KeyError for a name that is unknown or deleted, ValueError for an empty list)."""
+        if samples is None:
+            picked = [(n, c) for c, n in enumerate(names) if n is not None]
+        else:
+            if isinstance(samples, (str, bytes)):
+                raise TypeError("samples must be a list of sample names, got %r" % type(samples))
+            colour_of = {n: c for c, n in enumerate(names) if n is not None}
+            picked = []
+            for s in samples:
+                if s not in colour_of:
+                    raise KeyError(s)
+                picked.append((s, colour_of[s]))
+        if not picked:
+            raise ValueError("no samples to compare")
+        return [n for n, _ in picked], [c for _, c in picked]
+
+    def sample_distances(self, samples=None, against=None):
+        """How much every sample of `samples` shares with every sample of `against`:
+            {"samples": [names], "against": [names], "bits_shared": uint64[na, nb], "jaccard": float64[na, nb], "containment": float64[na, nb]}
+        (bigsi_amd/distances.py: derive_distances; the arithmetic of similar_samples, so row i holds similar_samples(samples[i])'s
+        values).  samples=None: every sample that is not deleted, in colour order; against=None: the same list as `samples`, the
+        square symmetric matrix.  ONE pass over the selected columns on the device (bigsi_hip_pairwise_popcounts) instead of one
+        masked sweep per sample.  KeyError for a name that is unknown or deleted, ValueError for an empty list and for more than
+        distances.MAX_PAIRS pairs (before any device call); multi-GPU (devices=[...]) indexes are refused."""
+        from ..distances import MAX_PAIRS, derive_distances
+        self._refuse_group("sample distances")
+        names = self._sample_names(self.num_samples)
+        a_names, a_cols = self._selected_colours(samples, names)
+        b_names, b_cols = (a_names, None) if against is None else self._selected_colours(against, names)
+        nb = len(a_names) if b_cols is None else len(b_cols)
+        if len(a_cols) * nb > MAX_PAIRS:
+            raise ValueError("%d x %d samples are more pairs than one call takes (%d)" % (len(a_cols), nb, MAX_PAIRS))
+        with self._device_lock():
+            inter = self.storage.pairwise_popcounts(a_cols, b_cols)
+            if b_cols is None:
+                set_a = set_b = inter.diagonal().copy()
+            else:
+                counts = self.storage.column_popcounts()
+                set_a, set_b = counts[np.asarray(a_cols)], counts[np.asarray(b_cols)]
+        jaccard, containment = derive_distances(inter, set_a, set_b)
+        return {"samples": a_names, "against": list(b_names), "bits_shared": inter, "jaccard": jaccard, "containment": containment}
+
+    def cluster_samples(self, min_jaccard, samples=None):
+        """Groups of near-duplicates: single linkage over the pairs of sample_distances(samples) with jaccard >= min_jaccard, as an
+        ordered mapping group name -> [member names] that BIGSI.collapse takes (bigsi_amd/distances.py: cluster_single_linkage --
+        groups by lowest member colour under that member's name, singletons kept).  min_jaccard must be in (0, 1]: ValueError."""
+        from ..distances import cluster_single_linkage
+        if isinstance(min_jaccard, bool) or not isinstance(min_jaccard, (int, float)) or not 0.0 < float(min_jaccard) <= 1.0:
+            raise ValueError("min_jaccard must be in (0, 1], got %r" % (min_jaccard,))
+        if samples is not None:          # (groups are ordered by colour, whatever order the names came in)
+            names = self._sample_names(self.num_samples)
+            picked, colours = self._selected_colours(samples, names)
+            if len(set(picked)) != len(picked):
+                raise ValueError("a sample is named twice")
+            samples = [n for _, n in sorted(zip(colours, picked))]
+        d = self.sample_distances(samples)
+        return cluster_single_linkage(d["jaccard"], d["samples"], float(min_jaccard))
+
     # ------------------------------------------------------------------ k-mer prevalence
     def kmer_prevalence_many(self, seqs, samples=None):
         """For every k-mer position of every sequence, how many samples hold the k-mer -- the transposed question of a search --

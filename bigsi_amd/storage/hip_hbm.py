@@ -565,6 +565,30 @@ class HipHbmStorage(BaseStorage):
         check(res.fn("column_popcounts")(res.ix, None if buf is None else _lib.ptr(buf), _lib.ptr(out), n))
         return out
 
+    def pairwise_popcounts(self, cols_a, cols_b=None):
+        """np.uint64[na, nb]: entry (i, j) is the number of rows in which column cols_a[i] AND column cols_b[j] are both set -- the
+        bits two samples' Bloom filters share -- for every pair of the two lists in one pass (bigsi_hip_pairwise_popcounts).
+        cols_b=None: cols_a against itself, the full square matrix, whose diagonal is column_popcounts of those columns.  The lists
+        may be unsorted and may repeat a column.  ValueError for an empty list and for more than distances.MAX_PAIRS pairs, before
+        any device call."""
+        from ..distances import MAX_PAIRS
+        self._single_gpu("pairwise popcounts")
+        a = np.ascontiguousarray(np.asarray(cols_a, dtype=np.int64).reshape(-1))
+        b = a if cols_b is None else np.ascontiguousarray(np.asarray(cols_b, dtype=np.int64).reshape(-1))
+        if a.size == 0 or b.size == 0:
+            raise ValueError("an empty list of columns")
+        if a.size * b.size > MAX_PAIRS:
+            raise ValueError("%d x %d pairs are more than one call takes (%d)" % (a.size, b.size, MAX_PAIRS))
+        for x in (a, b):
+            if x.min() < 0 or x.max() > 0xFFFFFFFF:
+                raise ValueError("a column number is not an unsigned 32-bit integer")
+        self._opened()
+        a32 = a.astype(np.uint32)
+        b32 = None if cols_b is None else b.astype(np.uint32)
+        out = np.zeros((a.size, b.size), dtype=np.uint64)
+        check(_lib.lib().bigsi_hip_pairwise_popcounts(self.handle, _lib.ptr(a32), a.size, _lib.ptr(b32), 0 if b32 is None else b.size, _lib.ptr(out), out.size))
+        return out
+
     def kmer_prevalence(self, seqs, k, universe=None, subset=None):
         """For every k-mer position of every sequence, the number of samples that hold the k-mer (bigsi_hip_kmer_prevalence: ONE
         device call; a k-mer is swept once and only its popcount leaves the device).  universe / subset: masks in the row format

@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [pairwise] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -634,6 +634,87 @@ def collapse():
              rows_equal=bool(np.array_equal(got, exp)), source_unchanged=bool(np.array_equal(np.unpackbits(get_rows(st.handle, ids, (n + 7) // 8), axis=1)[:, :n], before)),
              **common)
         check(L.bigsi_hip_close(dst))
+    st.delete_all()
+
+
+# the VALU rate the pairwise bound is derived from: CUs x SIMDs x lanes per clock x clock of the MI355X data sheet, NOT measured here
+PAIR_VALU_LANES_PER_CLOCK = 256 * 4 * 32
+PAIR_CLOCK_HZ = 2.4e9
+
+
+def pairwise():
+    """Pairwise popcounts (k_columns_to_planes, k_pair_popcount, k_pair_popcount_sum) on the C3 index at the collapse workload's
+    density: symmetric S = 1024 and S = 4096 (columns spread evenly over the width) and one rectangular 64 x 16384, beside two
+    figures of the same run: one unmasked column_popcounts sweep (the time of reading the matrix once: phase 1's yardstick when
+    the selection touches every line) and the route that exists today, a masked column_popcounts per sample (get_column + the masked
+    sweep, timed for 8 of the columns and scaled to S).  Wall-clock time of the whole C call, and the kernel times of the three phases
+    from a second, profiled call (HIP events, the call waits after every launch; the per-kernel table: this command under
+    `rocprofv3 --kernel-trace --stats`).  Phase 2's rate in pair-words/s (a pair-word: 64 rows of one pair, 4 VALU operations)
+    stands beside the bound 4 operations per pair-word give at the data sheet's lane count and clock (not measured here).  A sample
+    of the counts is checked against rows fetched from the index."""
+    L, C = _lib.lib(), _lib.C
+    m, n = 10_000_000, 100_000
+    st, fill = open_index("pairwise", m, n, 3)
+    stride = int(st.res.info().row_stride_bytes)
+    counts = st.column_popcounts()          # warm
+    ts = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        counts = st.column_popcounts()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    sweep_ms = sorted(ts)[1]
+    common = dict(m=m, cols=n, stride_bytes=stride, fill_density=float(counts.sum()) / (m * n), unmasked_sweep_ms=sweep_ms,
+                  unmasked_sweep_GBps=m * stride / sweep_ms / 1e6)
+    emit("pairwise_unmasked_sweep_yardstick", call_ms=sweep_ms, bytes=m * stride, note="fill %.2f s; median of 3 calls, wall clock" % fill, **common)
+    # the route that exists today: per sample its column as a row mask, then the masked sweep of every column
+    rng = np.random.default_rng(11)
+    eight = rng.choice(n, 8, replace=False)
+    st.column_popcounts(np.frombuffer(st.get_column(int(eight[0])), np.uint8))          # warm
+    t0 = time.perf_counter()
+    for c in eight:
+        st.column_popcounts(np.frombuffer(st.get_column(int(c)), np.uint8))
+    per_sample_ms = (time.perf_counter() - t0) * 1e3 / 8
+    emit("pairwise_today_masked_sweep_per_sample", call_ms=per_sample_ms, samples_timed=8, **common)
+    bound = PAIR_VALU_LANES_PER_CLOCK * PAIR_CLOCK_HZ / 4
+    ids = np.unique(rng.integers(0, m, 4096).astype(np.uint64))
+    rows = np.unpackbits(get_rows(st.handle, ids, (n + 7) // 8), axis=1)[:, :n]
+    shapes = (("symmetric_1024", np.linspace(0, n - 1, 1024).astype(np.uint32), None),
+              ("symmetric_4096", np.linspace(0, n - 1, 4096).astype(np.uint32), None),
+              ("rect_64x16384", np.linspace(0, n - 1, 64).astype(np.uint32), np.linspace(3, n - 4, 16384).astype(np.uint32)))
+    for name, a, b in shapes:
+        na, nb = a.size, a.size if b is None else b.size
+        out = np.zeros((na, nb), np.uint64)
+        call = lambda: L.bigsi_hip_pairwise_popcounts(st.handle, _lib.ptr(a), na, _lib.ptr(b), 0 if b is None else nb, _lib.ptr(out), out.size)  # noqa: E731
+        check(call())          # warm
+        ms = min(timed(call), timed(call))
+        check(L.bigsi_hip_set_profiling(st.handle, 1))
+        check(call())
+        phase = (C.c_double * 4)()
+        check(L.bigsi_hip_pairwise_phase_ms(st.handle, phase))
+        check(L.bigsi_hip_set_profiling(st.handle, 0))
+        distinct = np.unique(a).size if b is None else np.unique(np.concatenate([a, b])).size
+        words = np.unique((a if b is None else np.concatenate([a, b])) // 64).size
+        tiles_a, tiles_b = -(-np.unique(a).size // 64), -(-(np.unique(a).size if b is None else np.unique(b).size) // 64)
+        tiles = tiles_a * (tiles_a + 1) // 2 if b is None else tiles_a * tiles_b
+        pair_words = tiles * 64 * 64 * (-(-m // 64))          # what the kernel computes: whole tiles, the upper triangle when symmetric
+        # checks: the diagonal against column_popcounts and the symmetry (exact); 64 pairs against 4096 fetched rows (a subset of
+        # the rows: a lower bound); one row against today's route, the masked sweep under that sample's column (exact)
+        ok = None
+        if b is None:
+            ok = bool(np.array_equal(out.diagonal(), counts[a]) and np.array_equal(out, out.T))
+        sample_ok = bool((rows[:, a[:8]].T.astype(np.uint64) @ rows[:, (a if b is None else b)[:8]].astype(np.uint64) <= out[:8, :8]).all())
+        masked_check = None
+        if b is None:          # one column of today's route against the same column here
+            c0 = int(a[5])
+            mk = st.column_popcounts(np.frombuffer(st.get_column(c0), np.uint8))
+            masked_check = bool(np.array_equal(mk[a], out[5]))
+        emit("pairwise_" + name, na=na, nb=nb, distinct_columns=int(distinct), source_words=int(words), call_ms=ms, chunks=int(phase[3]),
+             planes_ms=phase[0], pairs_ms=phase[1], sum_ms=phase[2], planes_over_unmasked_sweep=phase[0] / sweep_ms,
+             pair_words=int(pair_words), pair_words_per_s=pair_words / phase[1] * 1e3, derived_bound_pair_words_per_s=bound,
+             frac_of_derived_bound=pair_words / phase[1] * 1e3 / bound,
+             bound_note="4 VALU ops per pair-word at %d lanes/clock x %.1f GHz: data sheet, not measured here" % (PAIR_VALU_LANES_PER_CLOCK, PAIR_CLOCK_HZ / 1e9),
+             today_ms_scaled=per_sample_ms * na, today_over_this=per_sample_ms * na / ms, diagonal_and_symmetry_ok=ok, sampled_rows_lower_bound_ok=sample_ok,
+             equals_masked_sweep_of_one_column=masked_check, **common)
     st.delete_all()
 
 

@@ -130,6 +130,12 @@ def build_parser():
     sp.add_argument("to_config")
     sp.add_argument("--groups", required=True, metavar="FILE", help="sample<TAB>group lines; a group's colour follows its first appearance")
     sp.add_argument("--keep-others", action="store_true", help="samples the file does not name stay, each as a group of its own, after the named groups")
+    sp = common(sub.add_parser("consensus", help="a new index, described by TO_CONFIG, in which every group of samples of this one is one column that keeps "
+                                                 "a bit only where at least P %% of the members have it (the core of the group; collapse keeps the union)"))
+    sp.add_argument("to_config")
+    sp.add_argument("--groups", required=True, metavar="FILE", help="sample<TAB>group lines, as for collapse")
+    sp.add_argument("--percent", type=int, default=100, metavar="P", help="in [1, 100]: a group of n members needs ceil(P n / 100) of them (default 100: all)")
+    sp.add_argument("--keep-others", action="store_true", help="samples the file does not name stay, each as a group of its own, after the named groups")
     sp = common(sub.add_parser("distances", help="how much every sample shares with every other: bits shared, Jaccard index and containment of every pair, "
                                                  "in one pass on the device"))
     sp.add_argument("--samples", "-s", action="append", default=[], metavar="NAME", help="only these samples (default: every sample)")
@@ -142,7 +148,7 @@ def build_parser():
     sp.add_argument("--samples", "-s", action="append", default=[], metavar="NAME", help="only these samples (default: every sample)")
     sp.add_argument("--samples-file", default=None, metavar="FILE", help="one sample name per line")
     sp.add_argument("--out", default=None, metavar="FILE", help="also write the groups as sample<TAB>group lines, the file `collapse --groups` reads")
-    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "distances", "cluster"):          # (named so that the refusal says why)
+    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -237,6 +243,24 @@ def collapse_text(index, config_name, to_config_name, pairs, keep_others=False):
                        "members": dict(zip(group_names, members))})
 
 
+def consensus_text(index, config_name, to_config_name, pairs, percent=100, keep_others=False):
+    """`consensus`: BIGSI.consensus into the index TO_CONFIG describes (it syncs its own snapshot); collapse's report, plus the
+    percentage and the number of members every group's column asks for."""
+    from .collapse import DROPPED, collapse_plan
+    from .consensus import group_sizes, need_of
+    new = index.consensus(get_config_from_file(to_config_name), pairs, percent=percent, keep_others=keep_others)
+    names = [index.colour_to_sample(c) for c in range(index.num_samples)]
+    group_of, group_names, members = collapse_plan(names, pairs, keep_others)
+    need = need_of(group_sizes(group_of, len(group_names)), percent)
+    from .graph.metadata import DELETION_SPECIAL_SAMPLE_NAME
+    live = sum(1 for n in names if n != DELETION_SPECIAL_SAMPLE_NAME)          # (deleted samples are not counted as dropped: they were gone)
+    moved = int((group_of != DROPPED).sum())
+    return json.dumps({"result": "consensus of %d of %d samples from %s at %d %% into %d groups in %s." % (moved, live, config_name, percent, len(group_names),
+                                                                                                         to_config_name),
+                       "groups": len(group_names), "samples_in": live, "samples_dropped": live - moved, "num_samples": new.num_samples,
+                       "members": dict(zip(group_names, members)), "percent": percent, "min_members": dict(zip(group_names, (int(x) for x in need)))})
+
+
 # k-mer positions of one device call of `prevalence --fasta` (a few bounded batches instead of one of any size: the device keeps a
 # partial count and a result per position)
 PREVALENCE_BATCH_POSITIONS = 1 << 20
@@ -319,7 +343,7 @@ def main(argv=None):
         (search_parser if a.cmd == "search" else bulk_parser).error("--limit is not available with --sharded (use a single index or storage-config devices)")
     config = get_config_from_file(a.config)
 
-    if getattr(a, "sharded", False) and a.cmd in ("vacuum", "extract", "collapse"):
+    if getattr(a, "sharded", False) and a.cmd in ("vacuum", "extract", "collapse", "consensus"):
         p.error("%s is not available with --sharded: column shards have a fixed width (use a single index)" % a.cmd)
     if getattr(a, "sharded", False) and a.cmd == "fold":
         p.error("fold is not available with --sharded: folding column shards is not implemented (use a single index)")
@@ -386,6 +410,8 @@ def main(argv=None):
         print(extract_text(BIGSI(config), a.config, a.to_config, extract_names(a)))
     elif a.cmd == "collapse":
         print(collapse_text(BIGSI(config), a.config, a.to_config, collapse_groups(a.groups), a.keep_others))
+    elif a.cmd == "consensus":
+        print(consensus_text(BIGSI(config), a.config, a.to_config, collapse_groups(a.groups), a.percent, a.keep_others))
     elif a.cmd == "fold":
         if a.dry_run:
             print(fold_dry_run_text(BIGSI(config), a.factor, a.format))

@@ -200,6 +200,11 @@ COLLAPSE_SIGNATURES = {
     "bigsi_hip_collapse_columns_into": (_i32, [_P, _P, _P, _u64]),
 }
 
+# every symbol include/bigsi_hip_consensus.h declares (consensus collapse: a group's column keeps a bit that enough members have)
+CONSENSUS_SIGNATURES = {
+    "bigsi_hip_consensus_columns_into": (_i32, [_P, _P, _P, _u64, _P]),
+}
+
 # every symbol include/bigsi_hip_prevalence.h declares (k-mer prevalence: per-position sample counts of a query)
 PREVALENCE_SIGNATURES = {
     "bigsi_hip_kmer_prevalence": (_i32, [_P, C.c_char_p, _P, _u32, _u32, _P, _P, _P, _P, _P, _u64]),
@@ -232,7 +237,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

@@ -18,6 +18,7 @@
 #include "bigsi_cpu.h"
 #include "bigsi_cpu_collapse.h"
 #include "bigsi_cpu_compact.h"
+#include "bigsi_cpu_consensus.h"
 #include "bigsi_cpu_fold.h"
 #include "bigsi_cpu_pairwise.h"
 #include "bigsi_cpu_prevalence.h"
@@ -735,6 +736,42 @@ int bigsi_cpu_collapse_columns_into(bigsi_cpu_index *dst, const bigsi_cpu_index 
             const uint32_t g = group_of[c];
             if (g != BIGSI_COLLAPSE_DROPPED && (x[c >> 3] & (0x80u >> (c & 7)))) y[g >> 3] |= (uint8_t)(0x80u >> (g & 7));
         }
+    }
+    dst->n_cols = num_groups;
+    return bdb_read_failed(src);
+}
+
+// Consensus collapse: destination column g = 1 where at least min_members[g] source columns of group g are set, one row and one
+// column at a time, one counter per group
+int bigsi_cpu_consensus_columns_into(bigsi_cpu_index *dst, const bigsi_cpu_index *src, const uint32_t *group_of, uint64_t num_groups,
+                                     const uint32_t *min_members)
+{
+    if (!dst || !src || !group_of || !min_members) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (num_groups == 0 || num_groups >= 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "num_groups %llu is not in [1, 2^32 - 1)", (unsigned long long)num_groups);
+    TRY(check_derive({/*in_place*/ nullptr, /*rows_divide*/ false, /*same_hashes*/ true}, dst, src));
+    for (uint64_t c = 0; c < src->n_cols; c++)
+        if (group_of[c] != BIGSI_COLLAPSE_DROPPED && group_of[c] >= num_groups)
+            return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither a group id below %llu nor BIGSI_COLLAPSE_DROPPED", (unsigned long long)c, group_of[c],
+                        (unsigned long long)num_groups);
+    for (uint64_t g = 0; g < num_groups; g++)
+        if (min_members[g] == 0)
+            return fail(BIGSI_ERR_INVALID, "min_members[%llu] is 0: a group keeps a bit that at least one member has (0 would mean an all-ones column)",
+                        (unsigned long long)g);
+    TRY(bigsi_cpu_reserve_cols(dst, num_groups));
+    std::vector<uint8_t> tmp, page;
+    std::vector<uint64_t> count(num_groups);
+    const uint64_t rb = src->rb();
+    for (uint64_t r = 0; r < src->m; r++) {
+        const uint8_t *x = src->fetch(r, rb, tmp, page);
+        uint8_t *y = dst->row(r);
+        memset(y, 0, dst->stride);
+        std::fill(count.begin(), count.end(), 0ull);
+        for (uint64_t c = 0; c < src->n_cols; c++) {
+            const uint32_t g = group_of[c];
+            if (g != BIGSI_COLLAPSE_DROPPED && (x[c >> 3] & (0x80u >> (c & 7)))) count[g]++;
+        }
+        for (uint64_t g = 0; g < num_groups; g++)
+            if (count[g] >= min_members[g]) y[g >> 3] |= (uint8_t)(0x80u >> (g & 7));
     }
     dst->n_cols = num_groups;
     return bdb_read_failed(src);

@@ -1025,6 +1025,61 @@ extern "C" int bigsi_hip_collapse_columns_into(bigsi_hip_index *dst, const bigsi
     return BIGSI_OK;
 }
 
+// Consensus collapse (k_consensus_columns<field bits>; tables, field width, launch shape and destination window:
+// plan_consensus_columns).  The tables live for this call only: the collapse's two and 4 bytes per destination column of thresholds.
+template <int FIELD_BITS>
+static void consensus_launch(bigsi_hip_index *dst, const bigsi_hip_index *src, const ConsensusPlan &p, const uint32_t *d_col, const uint64_t *d_live,
+                             const uint32_t *d_need)
+{
+    hipLaunchKernelGGL(k_consensus_columns<FIELD_BITS>, dim3((unsigned)p.grid), dim3(p.block), (size_t)p.lds_bytes, dst->stream, src->d_index, src->stride_words,
+                       dst->d_index, dst->stride_words, dst->m, d_col, d_live, d_need, p.table_words, p.dst_words, p.window_words, (uint32_t)p.image_words);
+}
+
+extern "C" int bigsi_hip_consensus_columns_into(bigsi_hip_index *dst, const bigsi_hip_index *src, const uint32_t *group_of, uint64_t num_groups,
+                                                const uint32_t *min_members)
+{
+    BIGSI_ENTER_DERIVE(dst, src);
+    if (!dst || !src || !group_of || !min_members) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (num_groups == 0 || num_groups >= 0xFFFFFFFFull) return fail(BIGSI_ERR_INVALID, "num_groups %llu is not in [1, 2^32 - 1)", (unsigned long long)num_groups);
+    TRY(check_derive({"bigsi_hip_consensus_columns_into", /*in_place*/ nullptr, /*rows_divide*/ false, /*same_hashes*/ true, /*into_empty*/ true}, dst, src));
+    const uint64_t bad = collapse_first_bad(src->n_cols, group_of, num_groups);
+    if (bad < src->n_cols)
+        return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither a group id below %llu nor BIGSI_COLLAPSE_DROPPED", (unsigned long long)bad, group_of[bad],
+                    (unsigned long long)num_groups);
+    const uint64_t zero = consensus_first_zero(min_members, num_groups);
+    if (zero < num_groups)
+        return fail(BIGSI_ERR_INVALID, "min_members[%llu] is 0: a group keeps a bit that at least one member has (0 would mean an all-ones column)",
+                    (unsigned long long)zero);
+    const ConsensusPlan p = plan_consensus_columns(src->n_cols, group_of, num_groups, min_members, dst->m);
+    TRY(begin_derive(dst, src, num_groups));
+    const uint64_t field_max = p.field_bits == 32 ? 0xFFFFFFFFull : (1ull << p.field_bits) - 1;
+    if (p.table_words > src->stride_words || round_up(p.dst_words, 2) > dst->stride_words || src->stride_words % kVec || dst->stride_words % kVec ||
+        p.lds_bytes > kCollapseLdsBytes || p.window_words == 0 || p.window_words % 2 || p.image_words % (2 * p.field_bits) ||
+        p.image_words < std::min<uint64_t>(p.window_words, round_up(p.dst_words, 2)) * p.field_bits || p.largest > field_max ||
+        p.need.size() != round_up(p.dst_words, 2) * 64 || p.grid == 0 || p.grid > 0x7FFFFFFFull)
+        return fail(BIGSI_ERR_STATE, "internal: a consensus plan of %llu source and %llu destination words at %u-bit fields does not fit the row strides (%llu, %llu) or the LDS (%llu bytes)",
+                    (unsigned long long)p.table_words, (unsigned long long)p.dst_words, p.field_bits, (unsigned long long)src->stride_words,
+                    (unsigned long long)dst->stride_words, (unsigned long long)p.lds_bytes);
+    CallScratch tab;
+    const uint64_t col_bytes = std::max<uint64_t>(p.dst_col.size() * 4, 16), live_bytes = std::max<uint64_t>(p.live.size() * 8, 16), need_bytes = p.need.size() * 4;
+    TRY(tab.buf.reserve(col_bytes + live_bytes + need_bytes));          // (col_bytes and live_bytes are multiples of 16: live is read 16 bytes at a time)
+    if (!p.dst_col.empty()) {
+        HIP_TRY(hipMemcpyAsync(tab.buf.p, p.dst_col.data(), p.dst_col.size() * 4, hipMemcpyHostToDevice, dst->stream));
+        HIP_TRY(hipMemcpyAsync(tab.buf.as<uint8_t>() + col_bytes, p.live.data(), p.live.size() * 8, hipMemcpyHostToDevice, dst->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(tab.buf.as<uint8_t>() + col_bytes + live_bytes, p.need.data(), need_bytes, hipMemcpyHostToDevice, dst->stream));
+    const uint32_t *d_col = tab.buf.as<uint32_t>();
+    const uint64_t *d_live = reinterpret_cast<const uint64_t *>(tab.buf.as<uint8_t>() + col_bytes);
+    const uint32_t *d_need = reinterpret_cast<const uint32_t *>(tab.buf.as<uint8_t>() + col_bytes + live_bytes);
+    if (p.field_bits == 8) consensus_launch<8>(dst, src, p, d_col, d_live, d_need);
+    else if (p.field_bits == 16) consensus_launch<16>(dst, src, p, d_col, d_live, d_need);
+    else consensus_launch<32>(dst, src, p, d_col, d_live, d_need);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dst->stream));          // (the tables go out of scope)
+    dst->n_cols = num_groups;
+    return BIGSI_OK;
+}
+
 // Pairwise popcounts (k_columns_to_planes, k_pair_popcount, k_pair_popcount_sum; chunks, slices and scratch: plan_pairwise; tables:
 // pairwise_tables).  Two allocations that live for this call only: the scratch (tables | planes | partials) and the 64-bit device
 // result.  Either may not fit beside a large index: BIGSI_ERR_NOMEM then, with nothing leaked and the runtime's sticky last-error

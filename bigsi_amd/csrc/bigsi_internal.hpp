@@ -5,6 +5,7 @@
 #include "bigsi_hip.h"
 #include "bigsi_hip_collapse.h"
 #include "bigsi_hip_compact.h"
+#include "bigsi_hip_consensus.h"
 #include "bigsi_hip_fold.h"
 #include "bigsi_hip_group.h"
 #include "bigsi_hip_pairwise.h"

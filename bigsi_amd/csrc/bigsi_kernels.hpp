@@ -2839,6 +2839,125 @@ __global__ __launch_bounds__(kBlock) void k_collapse_columns(
     }
 }
 
+// ------------------------------------------------------------------------------ consensus collapse: group columns by member count
+// Destination column g of every row is 1 iff at least min_members[g] source columns of group g are set in the row; everything from
+// column G to the end of the destination stride is zero afterwards.  k_collapse_columns with COUNTERS in the image: the same
+// source-driven walk (a wavefront owns whole rows and its own LDS image of one destination window; 16-byte source loads ANDed with
+// live; the set bits walked 32 at a time; table gathers in batches of kCollapseGathers), the tables from plan_consensus_columns
+// (bigsi_launch.hpp): dst_col[a] = the destination COLUMN of source bit address a, need[] = the thresholds in read-out order.
+//   - a bit whose destination column c lies in the window [lo, lo + span) adds 1 to the field of c: FIELD_BITS bits wide, PER = 32 /
+//     FIELD_BITS fields per 32-bit LDS word, field (c - lo) % PER of word (c - lo) / PER (ds_add_u32 without return).  A field never
+//     holds more than its group's size and the planner chose FIELD_BITS so that the size fits: no add carries into a neighbour;
+//   - read-out, per destination word w of the window: lane l takes the field of column 64 w + (l ^ 7) -- the column whose bit lies
+//     at bit l of the word in memory (collapse_mem_bit(l) = l ^ 7 below 64) -- and compares it with need[64 w + l]; the ballot of
+//     that predicate IS the memory word: no by_column.  The padding of `need` (kConsensusNever) makes the columns from G on zero, up
+//     to the end of the last pair of words, without a bound test.  128 words at a time: lane l keeps the ballots of words 2 l and
+//     2 l + 1 and stores them as 16 bytes, so the stores are coalesced like the collapse's;
+//   - the part of the image that was used is cleared with 16-byte LDS stores; the stride padding is stored as zeros.
+// ORDER: as k_collapse_columns (one wavefront per image, LDS instructions in program order, add is commutative); the compiler's order
+// is kept by collapse_image_fence after the adds and after the clear, as there, and once more between the read-out and the clear,
+// which here are different lanes' accesses to the same words.  No global atomics, no workgroup waits for another, no __syncthreads.
+// 64-bit row addressing; column numbers are 32 bits wide.  Bounds: the collapse's for the source; the read-out loads need[] below
+// 64 x round_up(ceil(G / 64), 2) = its size, touches image words below round_up(win_n, 2) x 64 / PER <= image_words x 2 and stores
+// pairs that end at or before round_up(ceil(G / 64), 2) <= dst_stride (window_words is even; the launcher checks the rest).
+template <int FIELD_BITS>
+__device__ __forceinline__ void consensus_walk(uint32_t x, const uint32_t *__restrict__ tab, uint32_t *img, uint32_t lo, uint32_t span)
+{
+    constexpr int B = kCollapseGathers;
+    constexpr uint32_t PER = 32u / FIELD_BITS;
+    while (x) {
+        uint32_t d[B];
+        bool on[B];
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            on[k] = x != 0u;
+            const uint32_t b = on[k] ? (uint32_t)__builtin_ctz(x) : 0u;
+            x &= x - 1u;
+            d[k] = on[k] ? tab[b] : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            const uint32_t a = d[k] - lo;          // (wraps for a destination below the window: then a >= span)
+            if (on[k] && a < span) atomicAdd(&img[a / PER], 1u << ((a % PER) * FIELD_BITS));
+        }
+    }
+}
+
+template <int FIELD_BITS>
+__global__ __launch_bounds__(kBlock) void k_consensus_columns(
+    const uint64_t *__restrict__ src, uint64_t src_stride, uint64_t *__restrict__ dst, uint64_t dst_stride, uint64_t m,
+    const uint32_t *__restrict__ dst_col, const uint64_t *__restrict__ live, const uint32_t *__restrict__ need, uint64_t table_words,
+    uint64_t dst_words, uint64_t window_words, uint32_t image_words)
+{
+    static_assert(FIELD_BITS == 8 || FIELD_BITS == 16 || FIELD_BITS == 32, "fields of 8, 16 or 32 bits");
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr int U = kCollapseLoads;
+    constexpr uint32_t PER = 32u / FIELD_BITS;
+    constexpr uint32_t FIELD_MASK = FIELD_BITS == 32 ? 0xFFFFFFFFu : (1u << (FIELD_BITS & 31)) - 1u;
+    const uint32_t lane = threadIdx.x & 63u, wave_in_block = threadIdx.x >> 6, waves_per_block = blockDim.x >> 6;
+    const uint64_t wave = (uint64_t)blockIdx.x * waves_per_block + wave_in_block, n_waves = (uint64_t)gridDim.x * waves_per_block;
+    uint32_t *img = reinterpret_cast<uint32_t *>(smem) + (size_t)wave_in_block * image_words * 2u;
+    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+    for (uint32_t i = lane * 4u; i < image_words * 2u; i += 256u) *reinterpret_cast<uint4 *>(img + i) = zero;
+    collapse_image_fence();
+    const uint64_t pieces = table_words / 2;          // 16-byte pieces of a source row that carry columns
+    const uint4 *live4 = reinterpret_cast<const uint4 *>(live);
+    const uint32_t my_col = lane ^ 7u;                // the column (within its 64) whose bit is bit `lane` of the word in memory
+    for (uint64_t row = wave; row < m; row += n_waves) {
+        const uint4 *srow = reinterpret_cast<const uint4 *>(src + row * src_stride);
+        uint64_t *drow = dst + row * dst_stride;
+        for (uint64_t win0 = 0; win0 < dst_words; win0 += window_words) {          // (wave-uniform)
+            const uint64_t win_n = dst_words - win0 < window_words ? dst_words - win0 : window_words;
+            const uint32_t lo = (uint32_t)(win0 * 64), span = (uint32_t)(win_n * 64);
+            for (uint64_t p0 = 0; p0 < pieces; p0 += 64 * U) {
+                // (a lane past the row's last piece loads that last piece again and walks nothing, as in k_collapse_columns)
+                uint4 v[U], lv[U];
+                uint64_t p[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint64_t q = p0 + (uint64_t)u * 64 + lane;
+                    p[u] = q < pieces ? q : pieces - 1;
+                    v[u] = srow[p[u]];
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) lv[u] = live4[p[u]];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const bool mine = p0 + (uint64_t)u * 64 + lane < pieces;
+                    const uint32_t *tab = dst_col + p[u] * 128;
+                    consensus_walk<FIELD_BITS>(mine ? v[u].x & lv[u].x : 0u, tab, img, lo, span);
+                    consensus_walk<FIELD_BITS>(mine ? v[u].y & lv[u].y : 0u, tab + 32, img, lo, span);
+                    consensus_walk<FIELD_BITS>(mine ? v[u].z & lv[u].z : 0u, tab + 64, img, lo, span);
+                    consensus_walk<FIELD_BITS>(mine ? v[u].w & lv[u].w : 0u, tab + 96, img, lo, span);
+                }
+            }
+            collapse_image_fence();          // every lane's adds of this window are in the image
+            const uint32_t pair_n = ((uint32_t)win_n + 1u) & ~1u;          // the words read out: whole pairs (<= 2 x window, 32 bits do)
+            const uint32_t *nrow = need + win0 * 64 + lane;
+            for (uint32_t b0 = 0; b0 < pair_n; b0 += 128u) {               // (wave-uniform)
+                const uint32_t cnt = pair_n - b0 < 128u ? pair_n - b0 : 128u;
+                uint64_t w0 = 0ull, w1 = 0ull;
+                for (uint32_t i = 0; i < cnt; i++) {          // (not unrolled: the compiler declines to, around the ballot)
+                    const uint32_t c = (b0 + i) * 64u + my_col;
+                    const uint32_t have = (img[c / PER] >> ((c % PER) * FIELD_BITS)) & FIELD_MASK;
+                    const uint64_t word = __ballot(have >= nrow[(uint64_t)(b0 + i) * 64]);
+                    if ((i >> 1) == lane) {
+                        if (i & 1u) w1 = word;
+                        else w0 = word;
+                    }
+                }
+                if (lane * 2u < cnt)
+                    *reinterpret_cast<uint4 *>(drow + win0 + b0 + lane * 2u) =
+                        make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32));
+            }
+            collapse_image_fence();          // every lane has read its fields before anybody clears them
+            for (uint32_t i = lane * 4u; i < pair_n * (2u * FIELD_BITS); i += 256u) *reinterpret_cast<uint4 *>(img + i) = zero;
+            collapse_image_fence();          // the image is clear before anybody's next add
+        }
+        for (uint64_t w = (dst_words + 1) / 2 * 2 + lane * 2u; w < dst_stride; w += 128) *reinterpret_cast<uint4 *>(drow + w) = zero;
+    }
+}
+
 // ------------------------------------------------------------------------------ row folding: the matrix under a smaller Bloom filter
 // dst row r = src row r | src row r + m' | ... | src row r + (factor - 1) m' for r in [0, m'), m' = m_dst: because a row id is
 // floor_mod(hash, m) (row_of_hash) and floor_mod(x, m) mod m' == floor_mod(x, m') for every divisor m' of m, this is bit for bit the

@@ -2,13 +2,14 @@
 // (k_and_exact, k_and_count, k_count_combine) are launched for a batch of queries (plan_row_and), the sweep of the column popcounts
 // (plan_col_popcount), the per-call tables of the column compaction (plan_compact_columns), the sweep of the row folding
 // (plan_fold_rows), the sweep of the k-mer prevalence (plan_kmer_prevalence), the per-call tables, launch shape and destination
-// window of the column collapse (plan_collapse_columns) and the chunks, slices, scratch and per-call tables of the pairwise popcounts
-// (plan_pairwise, pairwise_tables).  Pure functions of a handful of integers (and, for the compaction, the collapse and the pairwise
-// popcounts, of the keep bitmap / the group map / the column lists): no HIP, no batch, no index.  bigsi_hip.hip carries the plans out;
-// tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp, prevalence_host.cpp, collapse_host.cpp and pairwise_host.cpp compile
-// this header as plain host C++ and tests/test_abi_and_host.py, test_sample_stats_host.py, test_compact_columns_host.py,
-// test_fold_rows_host.py, test_kmer_prevalence_host.py, test_collapse_columns_host.py and test_pairwise_host.py pin the decisions on
-// the CPU.
+// window of the column collapse (plan_collapse_columns) and of the consensus collapse (plan_consensus_columns) and the chunks, slices,
+// scratch and per-call tables of the pairwise popcounts (plan_pairwise, pairwise_tables).  Pure functions of a handful of integers
+// (and, for the compaction, the collapses and the pairwise popcounts, of the keep bitmap / the group map / the column lists): no HIP,
+// no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp,
+// prevalence_host.cpp, collapse_host.cpp, consensus_host.cpp and pairwise_host.cpp compile this header as plain host C++ and
+// tests/test_abi_and_host.py, test_sample_stats_host.py, test_compact_columns_host.py, test_fold_rows_host.py,
+// test_kmer_prevalence_host.py, test_collapse_columns_host.py, test_consensus_columns_host.py and test_pairwise_host.py pin the
+// decisions on the CPU.
 //
 // Every constant below was measured on an MI355X; the notes beside them say against what.  A GPU test compares results, and a slip
 // here keeps results right and costs the 3 to 20 % those notes record: change a constant only with a new measurement, and the pinned
@@ -589,6 +590,100 @@ static inline CollapsePlan plan_collapse_columns(uint64_t num_cols, const uint32
         p.dst_bit[(c & ~63ull) + b] = (g & ~63u) + collapse_mem_bit(g & 63u);
         p.live[c >> 6] |= 1ull << b;
         p.moved++;
+    }
+    const uint64_t rows = std::max<uint64_t>(num_rows, 1);
+    const uint64_t waves_per_block = std::min<uint64_t>(rows, kBlock / 64);
+    p.block = (uint32_t)waves_per_block * 64;
+    p.grid = std::min<uint64_t>(ceil_div(rows, waves_per_block), kCollapseWaves / (kBlock / 64));
+    p.lds_bytes = p.image_words * 8 * waves_per_block;
+    return p;
+}
+
+// ------------------------------------------------------------------------------ consensus collapse (k_consensus_columns<FIELD_BITS>)
+// "Keep a bit where at least need[g] members have it": the collapse's map (group_of, kCollapseDropped), and destination column g of a
+// row is 1 iff at least min_members[g] source columns of group g are set in it.  The LDS image of a wavefront holds COUNTERS instead
+// of bits: one field of field_bits bits per group, 32 / field_bits of them packed into a 32-bit word (group c of a window that starts
+// at group lo is field (c - lo) % per_word of word (c - lo) / per_word).
+//   - live[w]: as the collapse's.
+//   - dst_col[a]: the destination COLUMN NUMBER of source bit address a (bits as they lie in memory: collapse_mem_bit on the source
+//     side only), or kCollapseDropped; as dst_bit, never compared with the sentinel on the device.
+//   - sizes[g]: the members of group g.  field_bits = the smallest of 8, 16, 32 whose maximum (255, 65 535, 2^32 - 1) is at least
+//     the largest size.  INVARIANT: a field's count never exceeds its group's size (a source column is added once per row) and the
+//     size never exceeds the field maximum, so no add ever carries into a neighbouring field.
+//   - need[64 w + l] = min_members[64 w + collapse_mem_bit(l)] for the destination word w: the order in which the lanes of the
+//     read-out hold the word's bits, so lane l loads entry 64 w + l (coalesced) and the ballot of count >= need IS the memory word.
+//     Padded with kConsensusNever up to round_up(dst_words, 2) words -- everything the read-out touches --, so the kernel never tests
+//     a group bound: a count is at most 2^32 - 2 (fewer than 2^32 - 1 columns) and never reaches it.
+// Window: a wavefront's image is at most kCollapseWindowWords x 8 bytes, as the collapse's, so a window holds
+// kCollapseWindowWords / field_bits destination words = 16 384, 8192 or 4096 groups (1000 groups of at most 255 members: one window).
+// image_words counts 64-bit LDS words like the collapse's: destination words of the image x field_bits.  Launch shape as
+// plan_collapse_columns: kCollapseWaves is INHERITED there from the column popcounts' sweep and inherited again here, measured for
+// neither kernel; kCollapseWindowWords is the collapse's UNMEASURED starting value.  INVARIANTS
+// (tests/test_consensus_columns_host.py): window_words is even; image_words is a multiple of 2 x field_bits and
+// <= kCollapseWindowWords at the planner's window; lds_bytes = image_words x 8 x wavefronts per workgroup <= kCollapseLdsBytes; the
+// windows (collapse_window's rule) tile [0, dst_words) without gap or overlap.
+constexpr uint32_t kConsensusNever = 0xFFFFFFFFu;
+struct ConsensusPlan {
+    uint64_t src_words = 0;          // ceil(num_cols / 64)
+    uint64_t table_words = 0;        // src_words rounded up to even: live has that many entries, dst_col 64 times as many
+    uint64_t dst_words = 0;          // ceil(num_groups / 64)
+    uint32_t field_bits = 8;         // 8, 16 or 32
+    uint64_t largest = 0;            // members of the largest group
+    uint64_t window_words = 0;       // destination words per window (even)
+    uint64_t windows = 1;            // passes per row (at least 1)
+    uint64_t image_words = 0;        // 64-bit words of one wavefront's LDS image
+    uint32_t block = 64;             // threads per workgroup
+    uint64_t grid = 0;               // workgroups; the wavefronts stride over the rows
+    uint64_t lds_bytes = 0;          // dynamic LDS per workgroup
+    uint64_t moved = 0;              // source columns that have a destination
+    std::vector<uint32_t> dst_col;   // 64 x table_words
+    std::vector<uint64_t> live;      // table_words
+    std::vector<uint32_t> sizes;     // num_groups
+    std::vector<uint32_t> need;      // 64 x round_up(dst_words, 2)
+};
+static inline uint32_t consensus_field_bits(uint64_t largest) { return largest <= 0xFFull ? 8u : largest <= 0xFFFFull ? 16u : 32u; }
+// the first group whose min_members entry is 0, or num_groups
+static inline uint64_t consensus_first_zero(const uint32_t *min_members, uint64_t num_groups)
+{
+    for (uint64_t g = 0; g < num_groups; g++)
+        if (min_members[g] == 0) return g;
+    return num_groups;
+}
+// window j of a plan: destination words [first, first + count)
+static inline void consensus_window(const ConsensusPlan &p, uint64_t j, uint64_t *first, uint64_t *count)
+{
+    *first = j * p.window_words;
+    *count = std::min<uint64_t>(p.window_words, p.dst_words - std::min(p.dst_words, *first));
+}
+// `group_of` as for plan_collapse_columns; `min_members`: num_groups entries (NULL: the tables that need it stay empty);
+// window_words 0: the planner's own, otherwise an even number of destination words
+static inline ConsensusPlan plan_consensus_columns(uint64_t num_cols, const uint32_t *group_of, uint64_t num_groups, const uint32_t *min_members,
+                                                   uint64_t num_rows, uint64_t window_words = 0)
+{
+    ConsensusPlan p;
+    p.src_words = ceil_div(num_cols, 64);
+    p.table_words = round_up(p.src_words, 2);
+    p.dst_words = ceil_div(num_groups, 64);
+    p.dst_col.assign(p.table_words * 64, kCollapseDropped);
+    p.live.assign(p.table_words, 0ull);
+    p.sizes.assign(num_groups, 0u);
+    for (uint64_t c = 0; c < num_cols; c++) {
+        const uint32_t g = group_of[c];
+        if (g == kCollapseDropped) continue;
+        const uint32_t b = collapse_mem_bit((uint32_t)(c & 63));
+        p.dst_col[(c & ~63ull) + b] = g;
+        p.live[c >> 6] |= 1ull << b;
+        p.sizes[g]++;
+        p.moved++;
+    }
+    for (uint32_t s : p.sizes) p.largest = std::max<uint64_t>(p.largest, s);
+    p.field_bits = consensus_field_bits(p.largest);
+    p.window_words = window_words ? window_words : kCollapseWindowWords / p.field_bits;
+    p.windows = std::max<uint64_t>(ceil_div(p.dst_words, p.window_words), 1);
+    p.image_words = std::min<uint64_t>(p.window_words, round_up(std::max<uint64_t>(p.dst_words, 1), 2)) * p.field_bits;
+    if (min_members) {
+        p.need.assign(round_up(p.dst_words, 2) * 64, kConsensusNever);
+        for (uint64_t g = 0; g < num_groups; g++) p.need[(g & ~63ull) + collapse_mem_bit((uint32_t)(g & 63))] = min_members[g];
     }
     const uint64_t rows = std::max<uint64_t>(num_rows, 1);
     const uint64_t waves_per_block = std::min<uint64_t>(rows, kBlock / 64);

@@ -905,7 +905,35 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
                 SampleMetadata(storage).add_samples(group_names)
             return self._derive(config, self.bloomfilter_size, fill)
 
-    # ------------------------------------------------------------------ what extract, collapse and fold_into share
+    # ------------------------------------------------------------------ consensus collapse: the core of every group of samples
+    def consensus(self, config, groups, percent=100, keep_others=False):
+        """A new index under `config` (as for collapse: same m, h, k, same device, a storage-config name of its own, nothing stored
+        under it yet) in which every GROUP of samples of this one is one column that keeps a bit only where at least `percent` % of
+        the group's members have it (bigsi_hip_consensus_columns_into: device to device, this index is only read): the CORE of the
+        group where collapse keeps its union.  need = max(1, ceil(percent x size / 100)) members (consensus.need_of, integers only).
+        A k-mer that at least `need` members hold has every one of its h bits in at least `need` member columns, so it is still found
+        in the group's column -- no false negatives for the core --, and the column's fill, hence its false-positive rate, falls as
+        percent rises where an OR of many members saturates.  percent=100 is bit for bit the index BIGSI.build makes from the AND of
+        the members' filters under the group names; percent=1 is collapse() for groups of up to 100 members.  groups, keep_others,
+        the colour order and KeyError / ValueError as for collapse (collapse.collapse_plan); a sample that keep_others keeps on its
+        own is a group of one, needs 1 and is copied.  percent: an int in [1, 100] (TypeError for a bool or a float, ValueError out
+        of range).  Returns the new BIGSI."""
+        from ..collapse import check_groups, collapse_plan
+        from ..consensus import check_percent, group_sizes, need_of
+        check_groups(groups, keep_others)               # (whatever these two raise, they raise before anything is read)
+        percent = check_percent(percent)
+        self._refuse_group("consensus collapse")
+        with self._device_lock():
+            group_of, group_names, _ = collapse_plan(self._colour_names(), groups, keep_others)
+            need = need_of(group_sizes(group_of, len(group_names)), percent)
+
+            def fill(storage):
+                if self.storage.consensus_columns_into(storage, group_of, len(group_names), need) != len(group_names):
+                    raise RuntimeError("the device made another number of columns than there are groups")
+                SampleMetadata(storage).add_samples(group_names)
+            return self._derive(config, self.bloomfilter_size, fill)
+
+    # ------------------------------------------------------------------ what extract, collapse, consensus and fold_into share
     def _refuse_group(self, what):
         if self.storage.res.is_group:
             from .._lib import ERR_STATE, BigsiHipError

@@ -483,6 +483,21 @@ class HipHbmStorage(BaseStorage):
         dst._after_column_move()
         return int(dst.res.info().num_cols)
 
+    def consensus_columns_into(self, dst, group_of, num_groups, min_members):
+        """Column g of `dst` -- as for collapse_columns_into: another resident hip-hbm index on the same device with the same m and h
+        that holds no columns yet -- becomes 1 in the rows in which at least min_members[g] of this index's columns c with
+        group_of[c] == g are set (bigsi_hip_consensus_columns_into); this index is only read.  group_of: as for
+        collapse_columns_into; min_members: one unsigned 32-bit entry per group, none of them 0 (1: the OR of the group, its size: the
+        AND, more than its size: a zero column).  Returns the number of columns of dst (num_groups)."""
+        from ..collapse import group_ids
+        from ..consensus import member_counts
+        self._single_gpu("consensus collapse", dst)
+        buf = group_ids(group_of, int(self.res.info().num_cols) if self.res.ensure_open() else 0, num_groups)
+        need = member_counts(min_members, num_groups)
+        check(_lib.lib().bigsi_hip_consensus_columns_into(dst.handle, self.handle, _lib.ptr(buf), int(num_groups), _lib.ptr(need)))
+        dst._after_column_move()
+        return int(dst.res.info().num_cols)
+
     def shrink_to_fit(self):
         """Give back the row stride beyond the columns the index holds (bigsi_hip_shrink_to_fit): the counterpart of reserve_cols."""
         self._single_gpu("shrink_to_fit", why="a multi-GPU index keeps the shard width it was opened with")

@@ -26,6 +26,7 @@
  *       MAINTENANCE  removing or extracting samples physically (column compaction, the capacity trim): include/bigsi_hip_compact.h.
  *                  The same index under a smaller Bloom filter size (row folding, the row trim): include/bigsi_hip_fold.h.
  *                  Groups of samples ORed into one column each of a new index (column collapse): include/bigsi_hip_collapse.h.
+ *                  Groups of samples by member count -- the core of a group (consensus collapse): include/bigsi_hip_consensus.h.
  *       PAIRWISE   the shared-bit counts of every pair of two lists of samples (all-vs-all overlap): include/bigsi_hip_pairwise.h.
  *       PREVALENCE for every k-mer position of a query the number of samples that hold the k-mer: include/bigsi_hip_prevalence.h.
  *       SHARING    export_ipc / open_ipc (another process) and open_view (another thread): read-only handles onto ONE resident matrix.

@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [pairwise] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -634,6 +634,68 @@ def collapse():
              rows_equal=bool(np.array_equal(got, exp)), source_unchanged=bool(np.array_equal(np.unpackbits(get_rows(st.handle, ids, (n + 7) // 8), axis=1)[:, :n], before)),
              **common)
         check(L.bigsi_hip_close(dst))
+    st.delete_all()
+
+
+def consensus():
+    """Consensus collapse (k_consensus_columns) on the C3 index beside the OR collapse of the SAME RUN on the same map: the collapse's
+    workload (b), 100 000 -> 1000 groups at random, with every group asking for 1 member, 50 % and 100 % of its size, and its
+    workload (c), the dereplication map (pairs and singletons), at 100 %.  Wall-clock time of the whole C call (table upload
+    included) into a destination reserved beforehand, each as a ratio over bigsi_hip_collapse_columns_into.  64 seeded rows -- the
+    rows either side of the one where row x stride_words passes 2^32 among them -- are checked against numpy after each call.  What
+    does not fit beside the index in device memory is skipped and says so."""
+    import torch
+    from bigsi_amd.consensus import group_sizes, need_of
+    L, C = _lib.lib(), _lib.C
+    m, n = 10_000_000, 100_000
+
+    st, fill = open_index("consensus", m, n, 3)
+    stride = int(st.res.info().row_stride_bytes)
+    src_bytes = m * (-(-n // 64)) * 8
+    counts = np.zeros(n, np.uint64)
+    check(L.bigsi_hip_column_popcounts(st.handle, None, _lib.ptr(counts), n))
+    rng = np.random.default_rng(10)
+    edge = (1 << 32) // (stride // 8)          # the first row whose offset in words is >= 2^32
+    ids = np.unique(np.concatenate([rng.integers(0, m, 61).astype(np.uint64), np.array([edge - 1, edge, edge + 1], np.uint64)]))
+    before = np.unpackbits(get_rows(st.handle, ids, (n + 7) // 8), axis=1)[:, :n].astype(np.int64)
+    common = dict(m=m, cols=n, stride_bytes=stride, fill_density=float(counts.sum()) / (m * n), edge_row=int(edge))
+    thousand = rng.integers(0, 1000, n).astype(np.uint32)          # (the same draws as collapse(): the same two maps)
+    derep = np.zeros(n, np.uint32)
+    pairs = rng.choice(n, 1000, replace=False)
+    second = np.zeros(n, bool)
+    second[pairs[1::2]] = True
+    derep[~second] = np.arange(int((~second).sum()), dtype=np.uint32)
+    derep[pairs[1::2]] = derep[pairs[0::2]]
+    for name, group_of, groups, percents in (("random_1000", thousand, 1000, (1, 50, 100)), ("dereplicate_1pct", derep, int((~second).sum()), (100,))):
+        room = m * stride_for(groups)
+        free = torch.cuda.mem_get_info()[0]
+        if room + (2 << 30) > free:
+            emit("consensus_" + name, groups=groups, skipped="the destination (%d bytes) does not fit beside the index (%d free)" % (room, free), **common)
+            continue
+        sizes = group_sizes(group_of, groups)
+        order = np.argsort(group_of, kind="stable")          # (every column has a group in both maps) the sampled rows' member counts:
+        starts = np.flatnonzero(np.r_[True, np.diff(group_of[order].astype(np.int64)) != 0])
+        have = np.zeros((ids.size, groups), np.int64)
+        have[:, group_of[order][starts]] = np.add.reduceat(before[:, order], starts, axis=1)
+        dst = C.c_void_p()
+        check(L.bigsi_hip_open(m, 0, groups, 3, 0, C.byref(dst)))
+        or_ms = timed(lambda: L.bigsi_hip_collapse_columns_into(dst, st.handle, _lib.ptr(group_of), groups))
+        check(L.bigsi_hip_close(dst))
+        emit("consensus_%s_or_collapse_yardstick" % name, groups=groups, call_ms=or_ms, bytes=src_bytes + room, bits_moved=int(counts.sum()), **common)
+        for percent in percents:
+            need = need_of(sizes, percent) if percent > 1 else np.ones(groups, np.uint32)
+            dst = C.c_void_p()
+            check(L.bigsi_hip_open(m, 0, groups, 3, 0, C.byref(dst)))
+            ms = timed(lambda: L.bigsi_hip_consensus_columns_into(dst, st.handle, _lib.ptr(group_of), groups, _lib.ptr(need)))
+            got = get_rows(dst, ids, room // m)
+            exp = np.zeros_like(got)
+            packed = np.packbits(have >= need.astype(np.int64)[None, :], axis=1)
+            exp[:, :packed.shape[1]] = packed
+            emit("consensus_%s_need_%s" % (name, "1" if percent == 1 else "%dpct" % percent), groups=groups, largest_group=int(sizes.max()),
+                 field_bits=8 if sizes.max() <= 255 else 16 if sizes.max() <= 65535 else 32, call_ms=ms, or_collapse_ms=or_ms, over_or_collapse=ms / or_ms,
+                 bytes=src_bytes + room, bits_counted=int(counts.sum()), Gbits_per_s=float(counts.sum()) / ms / 1e6, fill_out_sampled=float(np.unpackbits(got, axis=1)[:, :groups].mean()),
+                 rows_checked=int(ids.size), rows_equal=bool(np.array_equal(got, exp)), **common)
+            check(L.bigsi_hip_close(dst))
     st.delete_all()
 
 

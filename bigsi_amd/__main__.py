@@ -148,7 +148,13 @@ def build_parser():
     sp.add_argument("--samples", "-s", action="append", default=[], metavar="NAME", help="only these samples (default: every sample)")
     sp.add_argument("--samples-file", default=None, metavar="FILE", help="one sample name per line")
     sp.add_argument("--out", default=None, metavar="FILE", help="also write the groups as sample<TAB>group lines, the file `collapse --groups` reads")
-    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster"):          # (named so that the refusal says why)
+    sp = limited(common(sub.add_parser("tally", help="over all records of a FASTA file: which samples they hit, how many records each, and how many k-mers "
+                                                     "(summed on the device; no per-record results)")),
+                 "only the N samples that most records hit (ties to the lowest colour)")
+    sp.add_argument("fasta")
+    sp.add_argument("--threshold", "-t", type=float, default=1.0)
+    sp.add_argument("--format", choices=["json", "csv"], default="json")
+    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -286,6 +292,13 @@ def prevalence_text(index, queries, samples=None, fmt="json"):
     return json.dumps([dict({"query": q}, **r) for q, r in zip(queries, records)])
 
 
+def tally_text(index, queries, threshold=1.0, limit=None, fmt="json"):
+    """`tally`: BIGSI.tally over the queries; JSON: the record; CSV: sample_name,colour,queries_hit,kmers_found, one line per sample."""
+    from .tally import to_csv, to_json
+    rec = index.tally(queries, threshold=threshold, limit=limit)
+    return to_csv(rec) if fmt == "csv" else to_json(rec)
+
+
 def fold_dry_run_text(index, factor, fmt="json"):
     """`fold --dry-run`: nothing is touched.  The valid factors whose folded size is nearest to the one asked for, and per sample the
     fill and k-mer false-positive rate the balls-in-bins model PREDICTS (fold.fold_estimate) -- estimates, labelled as such; the exact
@@ -351,6 +364,8 @@ def main(argv=None):
         p.error("prevalence is not available with --sharded: the per-shard sweep plus a host sum is not implemented (use a single index)")
     if getattr(a, "sharded", False) and a.cmd in ("distances", "cluster"):
         p.error("%s is not available with --sharded: pairs of samples on different shards are not implemented (use a single index)" % a.cmd)
+    if getattr(a, "sharded", False) and a.cmd == "tally":
+        p.error("tally is not available with --sharded: the per-shard sums plus a host merge are not implemented (use a single index)")
     if a.cmd == "prevalence" and (a.seq is None) == (a.fasta is None):
         p.error("prevalence takes SEQ or --fasta FILE (one of them)")
     if a.cmd == "fold" and not a.dry_run and not a.to_config:
@@ -421,6 +436,8 @@ def main(argv=None):
         queries = [a.seq] if a.fasta is None else [s for _, s in read_fasta(a.fasta)]
         names = extract_names(a)
         print(prevalence_text(BIGSI(config), queries, names or None, a.format))
+    elif a.cmd == "tally":
+        print(tally_text(BIGSI(config), [s for _, s in read_fasta(a.fasta)], a.threshold, a.limit, a.format))
     elif a.cmd == "distances":
         against = None
         if a.against_file:

@@ -217,6 +217,16 @@ PAIRWISE_SIGNATURES = {
     "bigsi_hip_pairwise_phase_ms": (_i32, [_P, _P]),
 }
 
+# every symbol include/bigsi_hip_tally.h declares (query-set tally: per-sample hit totals of a stream, summed on the device)
+TALLY_SIGNATURES = {
+    "bigsi_hip_tally_create": (_i32, [_P, C.POINTER(_P)]),
+    "bigsi_hip_tally_destroy": (_i32, [_P]),
+    "bigsi_hip_tally_reset": (_i32, [_P]),
+    "bigsi_hip_tally_add_batch": (_i32, [_P, _P]),
+    "bigsi_hip_tally_add_stream": (_i32, [_P, C.c_char_p, _P, _u64, _u32, _dbl]),
+    "bigsi_hip_tally_fetch": (_i32, [_P, _P, _P, _u64, _P]),
+}
+
 _lib = None
 
 
@@ -237,7 +247,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()) + list(TALLY_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

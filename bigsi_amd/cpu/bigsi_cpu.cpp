@@ -22,6 +22,7 @@
 #include "bigsi_cpu_fold.h"
 #include "bigsi_cpu_pairwise.h"
 #include "bigsi_cpu_prevalence.h"
+#include "bigsi_cpu_tally.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1026,6 +1027,43 @@ int bigsi_cpu_kmer_prevalence(bigsi_cpu_index *ix, const char *seqs, const uint6
         }
     }
     return bdb_read_failed(ix);
+}
+
+// the query-set tally: every sequence searched in the reference's shape (search_reference_shaped: its hits are the (sample, k-mers
+// found) pairs a search reports), a sequence without k-mers skipped, the hits summed per sample.  A threshold below 0 asks for what 0
+// asks for (min_kmers is clamped at 0: every sample passes).
+int bigsi_cpu_search_tally(bigsi_cpu_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
+                           uint64_t *queries_hit, uint64_t *kmers_found, uint64_t capacity, uint64_t totals[4])
+{
+    if (!ix || !queries_hit || !kmers_found || !totals) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_seqs(seqs, offsets, n_seqs, k));
+    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
+    if (capacity < ix->n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "tally buffers hold %llu entries, %llu needed", (unsigned long long)capacity, (unsigned long long)ix->n_cols);
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    const uint64_t n_cols = ix->n_cols;
+    std::vector<uint64_t> hit(n_cols, 0), found(n_cols, 0);
+    std::vector<uint32_t> col(n_cols), cnt(n_cols);
+    uint64_t tot[4] = {0, 0, 0, 0};
+    QueryKmers q;
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        uint32_t nk, nu, mk;
+        Hits hits{nullptr, col.data(), cnt.data(), n_cols};
+        search_reference_shaped(ix, seqs + offsets[i], offsets[i + 1] - offsets[i], k, threshold < 0.0 ? 0.0 : threshold, q, &nk, &nu, &mk, hits);
+        if (nu == 0) { tot[2]++; continue; }
+        tot[0]++;
+        tot[1] += nu;
+        if (hits.total) tot[3]++;
+        for (uint64_t j = 0; j < hits.total; j++) {
+            hit[col[j]]++;
+            found[col[j]] += cnt[j];
+        }
+    }
+    TRY(bdb_read_failed(ix));
+    memcpy(queries_hit, hit.data(), n_cols * 8);
+    memcpy(kmers_found, found.data(), n_cols * 8);
+    memcpy(totals, tot, sizeof tot);
+    return BIGSI_OK;
 }
 
 int bigsi_cpu_score_presence(int, const uint8_t *bits, const uint64_t *bit_offsets, const uint32_t *num_kmers, const uint32_t *found,

@@ -387,6 +387,11 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
         bigsi_hip_batch_destroy(ix->prevalence_ws);
         ix->prevalence_ws = nullptr;
     }
+    for (bigsi_hip_batch *&w : ix->tally_ws)
+        if (w) {
+            bigsi_hip_batch_destroy(w);
+            w = nullptr;
+        }
     hipError_t e = hipSetDevice(ix->device);
     e = hipStreamSynchronize(ix->stream);
     if (ix->pre_stream) e = hipStreamSynchronize(ix->pre_stream);
@@ -2867,6 +2872,225 @@ extern "C" int bigsi_hip_kmer_prevalence(bigsi_hip_index *ix, const char *seqs, 
         bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
     }
     return rc;
+}
+
+// Query-set tally (include/bigsi_hip_tally.h; k_tally_hits + k_tally_totals, launch shape: plan_tally): per-sample sums over the
+// result vectors of runs made with BIGSI_RUN_SKIP_COMPACT.  One device allocation: queries_hit | kmers_found (wv * 64 entries each:
+// a lane's column always has an entry, the ones behind num_cols stay zero) | totals[4].  `last` is recorded behind everything queued
+// on behalf of the tally, on whichever stream it went to: reset and fetch wait for it, so a tally is in order with itself even when
+// the index's stream is replaced between calls (bigsi_hip_set_stream).
+struct bigsi_hip_tally {
+    bigsi_hip_index *ix = nullptr;
+    uint64_t n_cols = 0, m = 0, wv = 0;
+    uint32_t h = 0;
+    DevBuf acc;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    uint64_t host_skipped = 0;      // sequences of tally_add_stream chunks without any k-mer position: they never go to the device
+    bool unusable = false;          // a tally_add_stream failed half way: until tally_reset
+    uint64_t entries() const { return wv * 64; }
+    unsigned long long *queries_hit() const { return acc.as<unsigned long long>(); }
+    unsigned long long *kmers_found() const { return acc.as<unsigned long long>() + entries(); }
+    unsigned long long *totals() const { return acc.as<unsigned long long>() + 2 * entries(); }
+    size_t bytes() const { return (size_t)(2 * entries() + 4) * 8; }
+};
+
+static int tally_check(const bigsi_hip_tally *t, bool usable = true)
+{
+    const bigsi_hip_index *ix = t->ix;
+    if (ix->n_cols != t->n_cols || ix->m != t->m || ix->h != t->h)
+        return fail(BIGSI_ERR_STATE, "the index has changed since bigsi_hip_tally_create (%llu columns, %llu rows, %u hashes then; %llu, %llu, %u now)",
+                    (unsigned long long)t->n_cols, (unsigned long long)t->m, t->h, (unsigned long long)ix->n_cols, (unsigned long long)ix->m, ix->h);
+    if (usable && t->unusable) return fail(BIGSI_ERR_STATE, "a bigsi_hip_tally_add_stream on this tally failed half way: bigsi_hip_tally_reset starts over");
+    return BIGSI_OK;
+}
+
+// what is queued on `st` next comes after everything queued on behalf of the tally so far
+static int tally_order(bigsi_hip_tally *t, hipStream_t st)
+{
+    if (t->last && t->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, t->last, 0));
+    return BIGSI_OK;
+}
+
+static int tally_mark(bigsi_hip_tally *t, hipStream_t st)
+{
+    if (!t->last) HIP_TRY(hipEventCreateWithFlags(&t->last, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(t->last, st));
+    t->last_stream = st;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_tally_create(bigsi_hip_index *ix, bigsi_hip_tally **out)
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    TRY(use_device(ix));
+    bigsi_hip_tally *t = new (std::nothrow) bigsi_hip_tally();
+    if (!t) return fail(BIGSI_ERR_NOMEM, "host allocation failed");
+    t->ix = ix;
+    t->n_cols = ix->n_cols; t->m = ix->m; t->h = ix->h; t->wv = ix->wv();
+    int rc = t->acc.reserve(t->bytes());
+    if (rc == BIGSI_OK) {
+        hipError_t e = hipMemsetAsync(t->acc.p, 0, t->bytes(), ix->stream);
+        if (e != hipSuccess) rc = fail(BIGSI_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    }
+    if (rc == BIGSI_OK) rc = tally_mark(t, ix->stream);
+    if (rc != BIGSI_OK) { bigsi_hip_tally_destroy(t); return rc; }
+    *out = t;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_tally_destroy(bigsi_hip_tally *t)
+{
+    BusyGuard busy_guard_(t ? t->ix : nullptr, /*wait=*/true);
+    if (!t) return BIGSI_OK;
+    hipError_t e = hipSetDevice(t->ix->device);
+    if (t->last) { e = hipEventSynchronize(t->last); e = hipEventDestroy(t->last); }
+    (void)e;
+    t->acc.release();
+    delete t;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_tally_reset(bigsi_hip_tally *t)
+{
+    BIGSI_ENTER(t ? t->ix : nullptr);
+    if (!t) return fail(BIGSI_ERR_INVALID, "NULL tally");
+    TRY(tally_check(t, false));
+    TRY(use_device(t->ix));
+    hipStream_t st = t->ix->stream;
+    TRY(tally_order(t, st));
+    HIP_TRY(hipMemsetAsync(t->acc.p, 0, t->bytes(), st));
+    TRY(tally_mark(t, st));
+    t->host_skipped = 0;
+    t->unusable = false;
+    return BIGSI_OK;
+}
+
+// the two kernels for a batch whose SKIP_COMPACT run is the last thing queued on its run stream, and the batch's completion event
+// again behind them (what waits for the run -- reload, destroy, a fetch -- then waits for the tally's reads of its arrays too)
+static int tally_launch(bigsi_hip_tally *t, bigsi_hip_batch *b)
+{
+    bigsi_hip_index *ix = b->ix;
+    hipStream_t st = b->run_stream ? b->run_stream : ix->stream;
+    if (b->wv != t->wv) return fail(BIGSI_ERR_STATE, "internal: the batch's result vectors are %llu words, the tally's %llu", (unsigned long long)b->wv, (unsigned long long)t->wv);
+    const TallyPlan p = plan_tally(b->n_seqs, b->wv);
+    if (p.too_large || p.totals_grid > 0x7FFFFFFFull)
+        return fail(BIGSI_ERR_INVALID, "batch too large for one tally launch (%llu workgroups)", (unsigned long long)std::max(p.too_large, p.totals_grid));
+    if (p.grid == 0) return BIGSI_OK;
+    TRY(tally_order(t, st));
+    const uint64_t *bm = static_cast<const uint64_t *>(b->bit_vectors());
+    const uint64_t cstride = b->wv_pad * 64;
+    EventPair ep{};
+    TRY(bigsi_ev_begin(ix, &ep, st));
+#define BIGSI_TALLY(CountT, EXACT, CNT)                                                                                                     \
+    hipLaunchKernelGGL((k_tally_hits<CountT, EXACT>), dim3((unsigned)p.grid), dim3(p.block), 0, st, bm, b->wv_pad, (uint32_t)b->wv, t->n_cols, \
+                       b->n_seqs, b->num_unique.as<uint32_t>(), CNT, cstride, (uint32_t)p.word_groups, p.tile, t->queries_hit(), t->kmers_found())
+    if (b->exact) BIGSI_TALLY(uint16_t, true, (const uint16_t *)nullptr);
+    else if (b->count_bytes == 2) BIGSI_TALLY(uint16_t, false, static_cast<const uint16_t *>(b->counters()));
+    else BIGSI_TALLY(uint32_t, false, static_cast<const uint32_t *>(b->counters()));
+#undef BIGSI_TALLY
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tally_totals, dim3((unsigned)p.totals_grid), dim3(kBlock), 0, st, bm, b->wv_pad, (uint32_t)b->wv, t->n_cols, b->n_seqs,
+                       b->num_unique.as<uint32_t>(), t->totals());
+    HIP_TRY(hipGetLastError());
+    TRY(bigsi_ev_end(ix, &ep, ix->ev_cp, st, 2));      // (timed with the compaction it stands in for: bigsi_hip_stats' compact_ms)
+    TRY(tally_mark(t, st));
+    if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(b->done, st));
+    b->done_stale = false;
+    b->run_stream = st;
+    b->idle = false;
+    if (st == ix->stream) TRY(mark_main(ix));
+    return BIGSI_OK;
+}
+
+static int tally_check_batch(const bigsi_hip_tally *t, const bigsi_hip_batch *b)
+{
+    if (b->ix != t->ix) return fail(BIGSI_ERR_STATE, "the batch belongs to another index than the tally");
+    if (!b->ran) return fail(BIGSI_ERR_STATE, "bigsi_hip_batch_run has not completed for this batch");
+    if (b->compacted || b->fused_run) return fail(BIGSI_ERR_STATE, "the batch's last run built hit lists: a tally takes a run made with BIGSI_RUN_SKIP_COMPACT");
+    if (b->limit) return fail(BIGSI_ERR_STATE, "the batch has a result limit (bigsi_hip_batch_set_limit): a tally counts every hit");
+    if (b->ext_bitmaps || b->result_cols || b->comm)
+        return fail(BIGSI_ERR_STATE, "the batch has caller-owned bit vectors, a result width or a communicator: a tally takes a batch of one whole index");
+    if (b->run_h != t->h) return fail(BIGSI_ERR_STATE, "num_hashes changed since this batch ran (%u then, %u now): run it again", b->run_h, t->h);
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_tally_add_batch(bigsi_hip_tally *t, bigsi_hip_batch *b)
+{
+    BIGSI_ENTER(t ? t->ix : nullptr);
+    if (!t || !b) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(tally_check(t));
+    TRY(tally_check_batch(t, b));
+    TRY(use_device(t->ix));
+    return tally_launch(t, b);
+}
+
+// Two workspaces of the index (tally_ws), never the search stream's: chunk i is staged into workspace i & 1 -- host work, which first
+// waits for that workspace's chunk i - 2 (its completion event, recorded behind its tally kernels) -- while chunk i - 1 runs.
+extern "C" int bigsi_hip_tally_add_stream(bigsi_hip_tally *t, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold)
+{
+    BIGSI_ENTER(t ? t->ix : nullptr);
+    if (!t || !offsets) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    bigsi_hip_index *ix = t->ix;
+    TRY(tally_check(t));
+    if (n_seqs == 0) return fail(BIGSI_ERR_INVALID, "a batch needs at least one sequence");
+    if (k == 0) return fail(BIGSI_ERR_INVALID, "k must be > 0");
+    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
+    for (uint64_t i = 0; i < n_seqs; i++)
+        if (offsets[i + 1] < offsets[i]) return fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing");
+    if (offsets[n_seqs] - offsets[0] && !seqs) return fail(BIGSI_ERR_INVALID, "seqs is NULL");
+    const bool exact = threshold == 1.0;
+    const uint64_t wv_pad = round_up(ix->wv(), 2);
+    int rc = BIGSI_OK;
+    uint64_t chunk = 0;
+    for (uint64_t s0 = 0; s0 < n_seqs && rc == BIGSI_OK; chunk++) {
+        const uint64_t s1 = tally_chunk_end(offsets, n_seqs, s0, k, wv_pad, exact ? 0u : 4u);
+        bool any_pos = false;
+        for (uint64_t s = s0; s < s1 && !any_pos; s++) any_pos = offsets[s + 1] - offsets[s] >= k;
+        if (!any_pos) t->host_skipped += s1 - s0;
+        else {
+            bigsi_hip_batch **ws = &ix->tally_ws[chunk & 1];
+            rc = bigsi_batch_stage(ix, ws, seqs, offsets + s0, (uint32_t)(s1 - s0), k);
+            // (hits-only counters below threshold 1: the tally reads a counter only under a set bit, and a word that holds one keeps all 64)
+            if (rc == BIGSI_OK) rc = bigsi_batch_run(*ws, threshold, BIGSI_RUN_SKIP_COMPACT | (exact ? 0u : (uint32_t)BIGSI_RUN_SPARSE_COUNTS), false);
+            if (rc == BIGSI_OK) rc = tally_check_batch(t, *ws);
+            if (rc == BIGSI_OK) rc = tally_launch(t, *ws);
+        }
+        s0 = s1;
+    }
+    if (rc != BIGSI_OK) {
+        t->unusable = true;
+        for (bigsi_hip_batch *&w : ix->tally_ws) {
+            bigsi_hip_batch *b = w;
+            w = nullptr;
+            if (b) bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
+        }
+    }
+    return rc;
+}
+
+extern "C" int bigsi_hip_tally_fetch(bigsi_hip_tally *t, uint64_t *queries_hit, uint64_t *kmers_found, uint64_t capacity, uint64_t totals[4])
+{
+    BIGSI_ENTER(t ? t->ix : nullptr);
+    if (!t || !queries_hit || !kmers_found || !totals) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(tally_check(t));
+    if (capacity < t->n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "tally buffers hold %llu entries, %llu needed", (unsigned long long)capacity, (unsigned long long)t->n_cols);
+    TRY(use_device(t->ix));
+    hipStream_t st = t->ix->stream;
+    TRY(tally_order(t, st));
+    uint64_t tot[4];
+    HIP_TRY(hipMemcpyAsync(queries_hit, t->queries_hit(), t->n_cols * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(kmers_found, t->kmers_found(), t->n_cols * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(tot, t->totals(), sizeof tot, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    tot[2] += t->host_skipped;
+    memcpy(totals, tot, sizeof tot);
+    return BIGSI_OK;
 }
 
 // K5 at scale: the presence strings of all hits of the batch (see k_presence_bits).  The host sorts each sequence's hits by

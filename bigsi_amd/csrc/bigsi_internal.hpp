@@ -10,6 +10,7 @@
 #include "bigsi_hip_group.h"
 #include "bigsi_hip_pairwise.h"
 #include "bigsi_hip_prevalence.h"
+#include "bigsi_hip_tally.h"
 #include "bigsi_hip_testing.h"
 #include "bigsi_hip_text.h"
 
@@ -98,6 +99,7 @@ struct bigsi_hip_index {
     struct bigsi_hip_batch *search_ws = nullptr;      // bigsi_hip_search_batch's workspace, created at its first call
     struct bigsi_hip_batch *stream_ws[4] = {};        // bigsi_hip_search_stream's workspaces
     struct bigsi_hip_batch *prevalence_ws = nullptr;  // bigsi_hip_kmer_prevalence's workspace, created at its first call
+    struct bigsi_hip_batch *tally_ws[2] = {};         // bigsi_hip_tally_add_stream's workspaces, created at its first call
     uint64_t m = 0, n_cols = 0, cap_cols = 0, stride_words = 0;
     uint64_t alloc_rows = 0;      // rows the allocation behind d_index holds: m, or more after bigsi_hip_fold_rows (until bigsi_hip_trim_rows); never reported
     uint32_t h = 0;

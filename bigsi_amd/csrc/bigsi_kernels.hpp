@@ -3643,4 +3643,91 @@ __global__ __launch_bounds__(kBlock) void k_probe_rows(const uint64_t *__restric
     out[((uint64_t)(q - q0) * segs + seg) * 64 + lane] = acc;
 }
 
+// ------------------------------------------------------------------------------ query-set tally: per-sample hit totals of a batch
+// The vertical sum over the result vectors a run made with BIGSI_RUN_SKIP_COMPACT left behind: queries_hit[s] += 1 and kmers_found[s]
+// += c_q[s] for every query q whose bit of sample s is set (the AND of an exact run; count >= min_kmers of a counting run).  No hit
+// list is built and nothing is compacted.
+//
+// k_tally_hits (launch shape: plan_tally).  A wavefront owns result word w -- 64 columns, lane l the column 64 w + l, whose bit in
+// the word is bit_of_col(l), as K4 reads it (k_hits_write) -- and the queries [q0, q1) of one tile; the wavefronts of a workgroup own
+// neighbouring words of the same tile.  Per query ONE wave-uniform 8-byte load of the word, kTallyLoads of them in flight, ANDed with
+// valid_mask: bits behind num_cols are never trusted, and only words < wv are read (never the pad word of wv_pad).  A zero word --
+// nearly all of them in a hit-sparse stream -- is skipped in a uniform branch before anything else of the query is touched.  Otherwise
+// the query's num_unique (uniform; 0: the query has no k-mers and counts nowhere, whatever its vector holds), and every lane whose bit
+// is set adds 1 and its k-mers: num_unique on the exact path (EXACT: counters is never read), its own counter on the counting path (a
+// predicated load: the word's 64 counters are contiguous, one or two 128-byte lines per wavefront; in sparse mode the counters of a
+// word that holds a hit are valid).  The sums stay in registers over the tile; then every lane with a non-zero sum issues one 64-bit
+// atomic per accumulator, contiguous over the wavefront: a pair per column and WORKGROUP, never per query.  Integer sums: the result
+// does not depend on the order the atomics arrive in.
+template <typename CountT, bool EXACT>
+__global__ __launch_bounds__(kBlock) void k_tally_hits(
+    const uint64_t *__restrict__ bitmaps, uint64_t bm_stride, uint32_t wv, uint64_t n_cols, uint32_t n_seqs,
+    const uint32_t *__restrict__ num_unique, const CountT *__restrict__ counters, uint64_t counter_stride, uint32_t word_groups, uint32_t tile,
+    unsigned long long *__restrict__ queries_hit, unsigned long long *__restrict__ kmers_found)
+{
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    const uint32_t t = blockIdx.x / word_groups, w = (blockIdx.x - t * word_groups) * (kBlock / 64) + wave;
+    if (w >= wv) return;
+    const uint64_t vm = valid_mask(w, n_cols);
+    const uint64_t q0 = (uint64_t)t * tile, q1 = q0 + tile < n_seqs ? q0 + tile : n_seqs;
+    const uint32_t bit = bit_of_col(lane);
+    uint32_t hits = 0;
+    unsigned long long found = 0;
+    for (uint64_t q = q0; q < q1; q += kTallyLoads) {
+        uint64_t x[kTallyLoads];
+#pragma unroll
+        for (uint32_t j = 0; j < kTallyLoads; j++) x[j] = q + j < q1 ? bitmaps[(q + j) * bm_stride + w] & vm : 0ull;
+#pragma unroll
+        for (uint32_t j = 0; j < kTallyLoads; j++) {
+            if (x[j] == 0) continue;
+            const uint32_t u = num_unique[q + j];
+            if (u == 0) continue;
+            const bool mine = (x[j] >> bit) & 1ull;
+            hits += mine ? 1u : 0u;
+            if (EXACT) found += mine ? u : 0u;
+            else if (mine) found += counters[(q + j) * counter_stride + (uint64_t)w * 64 + lane];
+        }
+    }
+    if (hits) atomicAdd(&queries_hit[(uint64_t)w * 64 + lane], (unsigned long long)hits);
+    if (found) atomicAdd(&kmers_found[(uint64_t)w * 64 + lane], found);
+}
+
+// k_tally_totals: totals[0] += queries with k-mers, [1] += their unique k-mers, [2] += queries without, [3] += queries with k-mers and
+// at least one hit.  A workgroup owns kTallyTotalsTile queries, a wavefront every fourth of them (one each at the committed tile: the
+// sweep of a query's words is a chain of load latencies, so the queries are spread over as many wavefronts as there are): the lanes OR the
+// query's wv words (under valid_mask, kTallyLoads loads in flight) and the wavefront votes; the four wavefronts' sums meet in LDS and four
+// threads issue one atomic each.
+__global__ __launch_bounds__(kBlock) void k_tally_totals(
+    const uint64_t *__restrict__ bitmaps, uint64_t bm_stride, uint32_t wv, uint64_t n_cols, uint32_t n_seqs,
+    const uint32_t *__restrict__ num_unique, unsigned long long *__restrict__ totals)
+{
+    __shared__ unsigned long long lds[kBlock / 64][4];
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    const uint64_t q0 = (uint64_t)blockIdx.x * kTallyTotalsTile, q1 = q0 + kTallyTotalsTile < n_seqs ? q0 + kTallyTotalsTile : n_seqs;
+    unsigned long long counted = 0, unique = 0, skipped = 0, with_hits = 0;
+    for (uint64_t q = q0 + wave; q < q1; q += kBlock / 64) {
+        const uint32_t u = num_unique[q];
+        if (u == 0) { skipped++; continue; }
+        counted++;
+        unique += u;
+        uint64_t any = 0;
+        for (uint32_t w0 = lane; w0 < wv; w0 += 64 * kTallyLoads) {          // kTallyLoads independent loads in flight per lane
+            uint64_t x[kTallyLoads];
+#pragma unroll
+            for (uint32_t j = 0; j < kTallyLoads; j++) x[j] = w0 + 64 * j < wv ? bitmaps[q * bm_stride + w0 + 64 * j] : 0ull;
+#pragma unroll
+            for (uint32_t j = 0; j < kTallyLoads; j++) any |= x[j] & valid_mask(w0 + 64 * j, n_cols);
+        }
+        if (__ballot((int)(any != 0))) with_hits++;
+    }
+    if (lane == 0) { lds[wave][0] = counted; lds[wave][1] = unique; lds[wave][2] = skipped; lds[wave][3] = with_hits; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        unsigned long long s = 0;
+#pragma unroll
+        for (int i = 0; i < kBlock / 64; i++) s += lds[i][threadIdx.x];
+        if (s) atomicAdd(&totals[threadIdx.x], s);
+    }
+}
+
 }   // namespace bigsi

@@ -3,7 +3,8 @@
 // (plan_col_popcount), the per-call tables of the column compaction (plan_compact_columns), the sweep of the row folding
 // (plan_fold_rows), the sweep of the k-mer prevalence (plan_kmer_prevalence), the per-call tables, launch shape and destination
 // window of the column collapse (plan_collapse_columns) and of the consensus collapse (plan_consensus_columns) and the chunks, slices,
-// scratch and per-call tables of the pairwise popcounts (plan_pairwise, pairwise_tables).  Pure functions of a handful of integers
+// scratch and per-call tables of the pairwise popcounts (plan_pairwise, pairwise_tables) and the launch shape and stream cuts of the query-set
+// tally (plan_tally, plan_tally_chunks; pinned by tests/c_host/tally_host.cpp and tests/test_tally_host.py).  Pure functions of a handful of integers
 // (and, for the compaction, the collapses and the pairwise popcounts, of the keep bitmap / the group map / the column lists): no HIP,
 // no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp,
 // prevalence_host.cpp, collapse_host.cpp, consensus_host.cpp and pairwise_host.cpp compile this header as plain host C++ and
@@ -822,6 +823,64 @@ static inline PairwiseTables pairwise_tables(const uint32_t *cols_a, uint64_t na
         for (uint64_t j = 0; j < nb; j++) t.map_b[j] = rank(ub, cols_b[j]);
     }
     return t;
+}
+
+// ------------------------------------------------------------------------------ query-set tally (k_tally_hits, k_tally_totals)
+// k_tally_hits: a wavefront owns ONE result word (64 columns, lane = column) and a tile of kTallyTile queries; the kBlock / 64
+// wavefronts of a workgroup own neighbouring words of the same tile.  Workgroup b: word group b % word_groups, tile b / word_groups
+// (neighbouring workgroups read neighbouring words of the same queries).  A tile costs every column of a hit word one pair of 64-bit
+// atomics, so it is as long as keeps those rare (at most ceil(n_seqs / 128) pairs per column and batch) and as short as still gives a
+// narrow index some workgroups.  k_tally_totals: a workgroup owns kTallyTotalsTile queries, a wavefront every fourth of them -- one each:
+// a wavefront sweeps a query's words one load latency after the other, and 8192 queries of 1563 words on 64-query workgroups were 512
+// wavefronts on a device that holds 8192 (measured, both kernels per 8192 queries: 1.55 ms at 64, 0.63 ms at 4).
+constexpr uint32_t kTallyTile = 128;
+constexpr uint32_t kTallyLoads = 8;               // result words a wavefront has in flight
+constexpr uint32_t kTallyTotalsTile = 4;
+struct TallyPlan {
+    uint32_t block = kBlock, tile = kTallyTile;
+    uint64_t word_groups = 0, tiles = 0, grid = 0;            // grid = word_groups * tiles
+    uint64_t totals_grid = 0;
+    uint64_t too_large = 0;                                   // != 0: the workgroups one launch would take (more than 2^31 - 1): refused
+};
+static inline TallyPlan plan_tally(uint64_t n_seqs, uint64_t wv)
+{
+    TallyPlan p;
+    p.word_groups = ceil_div(wv, kBlock / 64);
+    p.tiles = ceil_div(n_seqs, p.tile);
+    p.grid = p.word_groups * p.tiles;
+    p.totals_grid = ceil_div(n_seqs, kTallyTotalsTile);
+    if (p.tiles && p.word_groups > 0x7FFFFFFFull / p.tiles) p.too_large = p.word_groups * p.tiles;
+    return p;
+}
+
+// The device batches of bigsi_hip_tally_add_stream: sequences [cut[i], cut[i + 1]) of the input, greedily as long as a chunk holds at
+// most kTallyChunkSeqs sequences, kTallyChunkPositions k-mer positions and kTallyCounterBytes of dense counters
+// (n_seqs * wv_pad * 64 * count_bytes: what a counting run allocates; count_bytes 0 for an exact stream, which has none) -- and always
+// at least one sequence, so that a single sequence beyond a bound is a chunk of its own.  The planner takes the counter width it is
+// given: the stream passes 4, the wider of the two a run may pick, so the bound holds whichever it picks.
+constexpr uint64_t kTallyChunkSeqs = 4096;
+constexpr uint64_t kTallyChunkPositions = 1ull << 20;
+constexpr uint64_t kTallyCounterBytes = 2ull << 30;          // BIGSI_TALLY_COUNTER_BYTES (include/bigsi_hip_tally.h)
+// end of the chunk that starts at sequence s0 < n_seqs
+static inline uint64_t tally_chunk_end(const uint64_t *offsets, uint64_t n_seqs, uint64_t s0, uint32_t k, uint64_t wv_pad, uint32_t count_bytes)
+{
+    const uint64_t per_seq = wv_pad * 64 * count_bytes;
+    const uint64_t by_bytes = per_seq ? std::max<uint64_t>(kTallyCounterBytes / per_seq, 1) : kTallyChunkSeqs;
+    const uint64_t most = std::min(std::min(kTallyChunkSeqs, by_bytes), n_seqs - s0);
+    uint64_t pos = 0, s = s0;
+    while (s < s0 + most) {
+        const uint64_t len = offsets[s + 1] - offsets[s], n = len >= k ? len - k + 1 : 0;
+        if (s > s0 && pos + n > kTallyChunkPositions) break;
+        pos += n;
+        s++;
+    }
+    return s;
+}
+static inline std::vector<uint64_t> plan_tally_chunks(const uint64_t *offsets, uint64_t n_seqs, uint32_t k, uint64_t wv_pad, uint32_t count_bytes)
+{
+    std::vector<uint64_t> cut(1, 0);
+    while (cut.back() < n_seqs) cut.push_back(tally_chunk_end(offsets, n_seqs, cut.back(), k, wv_pad, count_bytes));
+    return cut;
 }
 
 }  // namespace bigsi

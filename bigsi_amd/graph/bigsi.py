@@ -810,6 +810,43 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         """kmer_prevalence_many for one sequence: its dict."""
         return self.kmer_prevalence_many([seq], samples)[0]
 
+    # ------------------------------------------------------------------ query-set tally
+    def tally(self, seqs, threshold=1.0, limit=None, batch_kmers=1 << 19):
+        """The question a read set poses: of these sequences, which samples do they hit, how many sequences each, and how many
+        k-mers -- answered on the device (bigsi_hip_tally_add_stream: the hits of every sequence are the ones search(seq, threshold)
+        reports, summed per sample behind the row-AND kernels; no hit list is built and two numbers per sample leave the device).
+            {"queries": sequences counted, "kmers": their unique k-mers, "skipped": sequences shorter than k,
+             "queries_with_hits": counted sequences with at least one hit (a deleted sample's included),
+             "samples": [{"sample_name", "colour", "queries_hit", "kmers_found"}, ...]}
+        `samples` leaves out deleted samples and samples no sequence hit; most sequences first, ties to the lowest colour; limit=N
+        keeps the first N (cut on the host).  `seqs` is any iterable of ASCII sequences, fed in slices of about 8 x `batch_kmers`
+        k-mers, as search_stream slices its input.  Multi-GPU (devices=[...]) indexes are refused."""
+        from ..tally import record
+        limit = check_limit(limit)
+        if isinstance(seqs, (str, bytes)):
+            raise TypeError("seqs must be an iterable of sequences, got %r" % type(seqs))
+        if not threshold <= 1:
+            raise ValueError("threshold must be <= 1, got %r" % (threshold,))
+        self._refuse_group("a query-set tally")
+        k = int(self.kmer_size)
+        with self._device_lock():
+            t = self.storage.new_tally()
+            try:
+                for chunk in self._slices(iter(seqs), 64, None, batch_kmers * 8, k):
+                    t.add(chunk, k, threshold)
+                hit, found, totals = t.fetch()
+            finally:
+                t.close()
+            excluded = self._excluded_colours()
+        n = self.num_samples
+
+        def name_of(c):          # (a column the metadata has no record of is reported by its colour alone)
+            try:
+                return self.colour_to_sample(c) if c < n else None
+            except KeyError:
+                return None
+        return record(hit, found, totals, name_of, excluded, limit)
+
     # ------------------------------------------------------------------ column compaction: vacuum / extract
     def _colour_names(self):
         """names[c] of every colour, DELETION_SPECIAL_SAMPLE_NAME for a deleted one; the matrix must be as wide as the metadata."""

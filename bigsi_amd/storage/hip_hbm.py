@@ -636,6 +636,22 @@ class HipHbmStorage(BaseStorage):
                                                    None if in_sub is None else _lib.ptr(in_sub), cap))
         return pos, total[:cap], None if in_sub is None else in_sub[:cap]
 
+    def new_tally(self):
+        """A Tally over this index: zeroed per-sample sums on the device (bigsi_hip_tally_create)."""
+        self._single_gpu("a query-set tally")
+        return Tally(self)
+
+    def search_tally(self, seqs, k, threshold=1.0):
+        """Per-sample hit totals of a set of sequences, summed on the device (bigsi_hip_tally_add_stream: no hit list is built, two
+        uint64 per sample leave the device).  Returns (queries_hit np.uint64[num_cols], kmers_found np.uint64[num_cols], totals
+        np.uint64[4]: queries counted, their unique k-mers, queries skipped, counted queries with a hit)."""
+        t = self.new_tally()
+        try:
+            t.add(seqs, k, threshold)
+            return t.fetch()
+        finally:
+            t.close()
+
     def fill_synthetic(self, seed, shard=0, and_draws=2):
         if self.res.is_group:       # shard i of the group is filled as (seed, shard i)
             check(_lib.lib().bigsi_hip_group_fill_synthetic(self.res.ix, int(seed), int(and_draws)))
@@ -844,6 +860,55 @@ class HipHbmStorage(BaseStorage):
         total = int(off[-1])
         return nk, nu, off, col[:total], cnt[:total], bits[:int(need[0])], boff[:total + 1], rec[:total]
 
+
+
+class Tally(object):
+    """Per-sample sums over any number of query sets (bigsi_hip_tally): add() sequences or add_batch() a QueryBatch whose last run was
+    made with skip_compact=True, fetch() the sums, reset() them, close().  Single index only."""
+
+    def __init__(self, storage):
+        self.storage = storage
+        out = _lib.C.c_void_p()
+        check(_lib.lib().bigsi_hip_tally_create(storage.handle, _lib.C.byref(out)))
+        self.b = out
+        self.num_cols = int(storage.res.info().num_cols)
+        storage.res.batches.add(self)          # (it holds the index handle and must die before it, as a batch)
+
+    def add(self, seqs, k, threshold=1.0):
+        """bigsi_hip_tally_add_stream over a list of sequences (an empty list adds nothing)."""
+        seqs = seqs if isinstance(seqs, (list, tuple)) else list(seqs)
+        if not seqs:
+            return self
+        blob, off = _lib.pack_seqs(seqs)
+        check(_lib.lib().bigsi_hip_tally_add_stream(self.b, blob, _lib.ptr(off), len(seqs), int(k), float(threshold)))
+        return self
+
+    def add_batch(self, batch):
+        if batch.group:
+            raise BigsiHipError(_lib.ERR_STATE, "a query-set tally is not available on a multi-GPU batch")
+        check(_lib.lib().bigsi_hip_tally_add_batch(self.b, batch.b))
+        return self
+
+    def reset(self):
+        check(_lib.lib().bigsi_hip_tally_reset(self.b))
+        return self
+
+    def fetch(self):
+        n = self.num_cols
+        hit, found, totals = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(4, np.uint64)
+        check(_lib.lib().bigsi_hip_tally_fetch(self.b, _lib.ptr(hit), _lib.ptr(found), n, _lib.ptr(totals)))
+        return hit, found, totals
+
+    def close(self):
+        if self.b is not None:
+            check(_lib.lib().bigsi_hip_tally_destroy(self.b))
+            self.b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
 
 
 class QueryBatch(object):

@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -777,6 +777,76 @@ def pairwise():
              bound_note="4 VALU ops per pair-word at %d lanes/clock x %.1f GHz: data sheet, not measured here" % (PAIR_VALU_LANES_PER_CLOCK, PAIR_CLOCK_HZ / 1e9),
              today_ms_scaled=per_sample_ms * na, today_over_this=per_sample_ms * na / ms, diagonal_and_symmetry_ok=ok, sampled_rows_lower_bound_ok=sample_ok,
              equals_masked_sweep_of_one_column=masked_check, **common)
+    st.delete_all()
+
+
+def tally():
+    """Query-set tally (bigsi_hip_tally_add_stream) beside bigsi_hip_search_stream on the same input in the same run: 8192 x 1 kbp on
+    the C3 index (10 M x 100 k, h = 4), hit-sparse as drawn and hit-dense (bench.py's c5_dense recipe: every 16th query held whole by
+    1 % of the samples), at threshold 1.0 and 0.4; 65 536 reads of 61 bp on BASELINE configs[1]'s index (1 M x 10 k, h = 3), where the
+    search stream takes the one-launch read kernel and the tally cannot.  Per line: wall ms of one call of each (best of 3 after a
+    warm call; the tally's includes its reset and fetch), the tally kernels' own time (HIP events around k_tally_hits +
+    k_tally_totals: compact_ms of bigsi_hip_stats under profiling level 1, a run of its own) beside that run's row-AND and K1 time,
+    the time numpy takes from the search stream's hit lists to the same two vectors (two bincounts), and whether the vectors agree."""
+    L = _lib.lib()
+
+    def line(name, st, n_cols, seqs, thr, note):
+        blob, off = _lib.pack_seqs(seqs)
+        t = st.new_tally()
+
+        def tally_call():
+            t.reset()
+            check(L.bigsi_hip_tally_add_stream(t.b, blob, _lib.ptr(off), len(seqs), 31, float(thr)))
+            return t.fetch()
+        tally_call()
+        walls = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            got = tally_call()
+            walls.append((time.perf_counter() - t0) * 1e3)
+        check(L.bigsi_hip_set_profiling(st.handle, 1))
+        stats(st)
+        tally_call()
+        s = stats(st)
+        check(L.bigsi_hip_set_profiling(st.handle, 0))
+        st.search_many_packed(blob, off, 31, thr)
+        search, counted = [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            nk, nu, hoff, col, cnt = st.search_many_packed(blob, off, 31, thr)
+            t1 = time.perf_counter()
+            qh = np.bincount(col, minlength=n_cols).astype(np.uint64)
+            kf = np.bincount(col, weights=cnt, minlength=n_cols).astype(np.uint64)          # (float64 sums of integers below 2^53: exact)
+            t2 = time.perf_counter()
+            search.append((t1 - t0) * 1e3)
+            counted.append((t2 - t1) * 1e3)
+        agree = bool(np.array_equal(qh, got[0]) and np.array_equal(kf, got[1]) and int(got[2][0]) == int((nu > 0).sum()) and int(got[2][1]) == int(nu.sum()))
+        step_prof = s.kmerize_ms + s.and_ms + s.compact_ms
+        emit(name, threshold=thr, n_seqs=len(seqs), cols=n_cols, hits=int(hoff[-1]), samples_hit=int((got[0] > 0).sum()), queries_with_hits=int(got[2][3]),
+             tally_stream_ms=min(walls), search_stream_ms=min(search), bincount_ms=min(counted), search_plus_bincount_ms=min(search) + min(counted),
+             tally_kernels_ms=s.compact_ms, row_and_ms=s.and_ms, k1_ms=s.kmerize_ms, tally_kernels_frac_of_device=s.compact_ms / step_prof if step_prof else None,
+             tally_kernels_frac_of_call=s.compact_ms / min(walls), agree_with_search=agree, note=note)
+        t.close()
+        assert agree, name
+
+    m, n, h = 10_000_000, 100_000, 4
+    st, _ = open_index("tally", m, n, h)
+    rng = np.random.default_rng(11)
+    seqs = rand_seqs(rng, 8192, 1000)
+    for thr in (1.0, 0.4):
+        line("tally_c3_sparse", st, n, seqs, thr, "8192 x 1 kbp as drawn")
+    held, cols = seqs[::16], np.sort(rng.choice(n, size=n // 100, replace=False))
+    t0 = time.time()
+    for c in cols:
+        st.insert_kmers(int(c), held, 31)
+    plant_s = time.time() - t0
+    for thr in (1.0, 0.4):
+        line("tally_c3_dense", st, n, seqs, thr, "every 16th query held by 1 %% of the samples (planted in %.1f s)" % plant_s)
+    st.delete_all()
+    st, _ = open_index("tally_reads", 1_000_000, 10_000, 3)
+    reads = rand_seqs(rng, 65536, 61)
+    for thr in (1.0, 0.4):
+        line("tally_c2_reads", st, 10_000, reads, thr, "65 536 reads of 61 bp: the search stream takes the one-launch read kernel, the tally the non-fused route")
     st.delete_all()
 
 

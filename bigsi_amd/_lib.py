@@ -174,6 +174,7 @@ SIGNATURES = {
     "bigsi_hip_stats": (_i32, [_P, C.POINTER(Stats), _i32]),
     "bigsi_hip_probe_rows": (_i32, [_P, _u32, _u32, _u32, _u32, _u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bigsi_hip_fasta_pack": (_i32, [_P, _u64, _P, _P, _u64, C.POINTER(_u64)]),
+    "bigsi_hip_fastq_pack": (_i32, [_P, _u64, _P, _P, _u64, C.POINTER(_u64)]),
     "bigsi_hip_format_results": (_i32, [_i32, _P, _P, _u64, C.c_char_p, C.c_char_p, _i32, _P, _P, _P, _P, _P, _P, _P, _u64, _u32,
                                          C.POINTER(_P), C.POINTER(_u64)]),
     "bigsi_hip_format_results_scored": (_i32, [_i32, _P, _P, _u64, C.c_char_p, C.c_char_p, _i32, _P, _P, _P, _P, _P, _P, _P, _u64, _P, _u32,
@@ -290,6 +291,16 @@ def fasta_pack(data):
     check(rc)
     blob, off = np.empty(max(len(data), 1), np.uint8), np.empty(n.value + 1, np.uint64)
     check(lib().bigsi_hip_fasta_pack(data, len(data), ptr(blob), ptr(off), n.value, C.byref(n)))
+    return blob[:int(off[n.value])], off
+
+
+def fastq_pack(data):
+    """bigsi_hip_fastq_pack over the bytes of a FASTQ text of four-line records: (uint8 blob, uint64 offsets[n+1]) of its sequences;
+    BigsiHipError(ERR_INVALID), naming the record, for anything else."""
+    n = C.c_uint64(0)
+    check(lib().bigsi_hip_fastq_pack(data, len(data), None, None, 0, C.byref(n)))          # the sizing call
+    blob, off = np.empty(max(len(data), 1), np.uint8), np.empty(n.value + 1, np.uint64)
+    check(lib().bigsi_hip_fastq_pack(data, len(data), ptr(blob), ptr(off), n.value, C.byref(n)))
     return blob[:int(off[n.value])], off
 
 

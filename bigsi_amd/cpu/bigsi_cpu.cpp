@@ -20,6 +20,7 @@
 #include "bigsi_cpu_compact.h"
 #include "bigsi_cpu_consensus.h"
 #include "bigsi_cpu_fold.h"
+#include "bigsi_cpu_kmercount.h"
 #include "bigsi_cpu_pairwise.h"
 #include "bigsi_cpu_prevalence.h"
 #include "bigsi_cpu_tally.h"
@@ -32,6 +33,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <map>
 #include <new>
 #include <string>
 #include <string_view>
@@ -1133,6 +1135,139 @@ int bigsi_cpu_search_stream_scored(bigsi_cpu_index *ix, const char *seqs, const 
     bit_offsets[hit_offsets[n_seqs]] = at;
     if (!fits) return fail(BIGSI_ERR_CAPACITY, "bit buffer holds %llu bytes, %llu needed", (unsigned long long)bits_capacity, (unsigned long long)need);
     return BIGSI_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- the exact k-mer counter
+// (include/bigsi_cpu_kmercount.h.)  Plainly: every window read base by base, the canonical key taken by comparing the two packed
+// words, a std::map from key to count; the filter is bigsi_cpu_bloom over the kept keys' strings, hashed as they are.
+
+struct bigsi_cpu_kmer_counter {
+    uint32_t k = 0;
+    std::map<uint64_t, uint32_t> counts;
+    uint64_t counted = 0, skipped = 0;
+};
+
+namespace {
+inline int base_code(char ch)
+{
+    switch (ch) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+    default: return -1;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int bigsi_cpu_kmer_counter_create(int, uint32_t k, uint64_t, bigsi_cpu_kmer_counter **out)
+{
+    if (!out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (k == 0 || k > BIGSI_KMERCOUNT_MAX_K) return fail(BIGSI_ERR_INVALID, "k must be in [1, %u], got %u", BIGSI_KMERCOUNT_MAX_K, k);
+    bigsi_cpu_kmer_counter *c = new (std::nothrow) bigsi_cpu_kmer_counter();
+    if (!c) return fail(BIGSI_ERR_NOMEM, "host allocation failed");
+    c->k = k;
+    *out = c;
+    return BIGSI_OK;
+}
+
+int bigsi_cpu_kmer_counter_destroy(bigsi_cpu_kmer_counter *c)
+{
+    delete c;
+    return BIGSI_OK;
+}
+
+int bigsi_cpu_kmer_counter_reset(bigsi_cpu_kmer_counter *c)
+{
+    if (!c) return fail(BIGSI_ERR_INVALID, "NULL counter");
+    c->counts.clear();
+    c->counted = c->skipped = 0;
+    return BIGSI_OK;
+}
+
+int bigsi_cpu_kmer_counter_add(bigsi_cpu_kmer_counter *c, const char *seqs, const uint64_t *offsets, uint64_t n_seqs)
+{
+    if (!c) return fail(BIGSI_ERR_INVALID, "NULL counter");
+    if (n_seqs == 0) return BIGSI_OK;
+    if (!offsets) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    const uint32_t k = c->k;
+    uint64_t positions = 0;
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        if (offsets[i + 1] < offsets[i]) return fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing");
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        positions += len >= k ? len - k + 1 : 0;
+    }
+    if (offsets[n_seqs] - offsets[0] && !seqs) return fail(BIGSI_ERR_INVALID, "seqs is NULL");
+    if (positions > 0xFFFFFFFFull - (c->counted + c->skipped))
+        return fail(BIGSI_ERR_RANGE, "%llu more positions behind %llu: a k-mer counter takes at most 2^32 - 1 in its lifetime",
+                    (unsigned long long)positions, (unsigned long long)(c->counted + c->skipped));
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        const char *s = seqs + offsets[i];
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        for (uint64_t p = 0; p + k <= len; p++) {
+            uint64_t fwd = 0, rc = 0;
+            bool ok = true;
+            for (uint32_t j = 0; j < k && ok; j++) {
+                const int f = base_code(s[p + j]), r = base_code(s[p + k - 1 - j]);
+                ok = f >= 0 && r >= 0;
+                fwd = (fwd << 2) | (uint64_t)(f & 3);
+                rc = (rc << 2) | (uint64_t)(3 - (r & 3));
+            }
+            if (!ok) { c->skipped++; continue; }
+            c->counted++;
+            c->counts[std::min(fwd, rc)]++;
+        }
+    }
+    return BIGSI_OK;
+}
+
+int bigsi_cpu_kmer_counter_info(bigsi_cpu_kmer_counter *c, uint64_t out[4])
+{
+    if (!c || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    out[0] = c->counted;
+    out[1] = c->skipped;
+    out[2] = c->counts.size();
+    out[3] = 0;
+    return BIGSI_OK;
+}
+
+int bigsi_cpu_kmer_counter_spectrum(bigsi_cpu_kmer_counter *c, uint64_t out[256])
+{
+    if (!c || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    memset(out, 0, 256 * sizeof(uint64_t));
+    for (const auto &kv : c->counts) out[std::min<uint32_t>(kv.second, 255)]++;
+    return BIGSI_OK;
+}
+
+int bigsi_cpu_kmer_counter_fetch(bigsi_cpu_kmer_counter *c, uint64_t *keys, uint32_t *counts, uint64_t capacity, uint64_t *n)
+{
+    if (!c || !n) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    *n = c->counts.size();
+    if (capacity < *n) return fail(BIGSI_ERR_CAPACITY, "the table holds %llu k-mers, the buffers %llu", (unsigned long long)*n, (unsigned long long)capacity);
+    if (*n == 0) return BIGSI_OK;
+    if (!keys || !counts) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    uint64_t i = 0;
+    for (const auto &kv : c->counts) { keys[i] = kv.first; counts[i] = kv.second; i++; }
+    return BIGSI_OK;
+}
+
+int bigsi_cpu_kmer_counter_bloom(bigsi_cpu_kmer_counter *c, uint64_t m, uint32_t h, uint32_t min_count, uint8_t *out)
+{
+    if (!c || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (m == 0 || h == 0) return fail(BIGSI_ERR_INVALID, "m and h must be > 0");
+    if (min_count == 0) return fail(BIGSI_ERR_INVALID, "min_count must be >= 1");
+    const uint32_t k = c->k;
+    std::string kept;
+    for (const auto &kv : c->counts) {
+        if (kv.second < min_count) continue;
+        for (uint32_t j = 0; j < k; j++) kept.push_back("ACGT"[(kv.first >> (2 * (k - 1 - j))) & 3]);
+    }
+    return bigsi_cpu_bloom(0, kept.data(), kept.size() / k, k, m, h, BIGSI_BLOOM_RAW, out);
 }
 
 }  // extern "C"

@@ -456,7 +456,66 @@ extern "C" int bigsi_hip_fasta_pack(const char *text, uint64_t n_bytes, char *ou
     return BIGSI_OK;
 }
 
-extern "C" int bigsi_hip_format_results(int format, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, const char *threshold_text,
+// bigsi_hip_text.h: the sequences of a FASTQ text of four-line records.  One pass over the lines (LF, CR LF or CR); `emit` gets
+// every record's sequence.  Returns 0, or the number (from 1) of the record that is not four-line FASTQ, with the reason in *why.
+namespace {
+template <typename Emit>
+uint64_t scan_fastq(const char *text, uint64_t n_bytes, uint64_t *n_records, const char **why, Emit emit)
+{
+    uint64_t pos = 0, rec = 0, seq_a = 0, seq_b = 0;
+    uint32_t line_no = 0;          // line of the current record, 0..3
+    while (pos < n_bytes) {
+        uint64_t e = pos;
+        while (e < n_bytes && text[e] != '\n' && text[e] != '\r') {
+            if ((unsigned char)text[e] & 0x80) { *why = "a byte >= 0x80"; return rec + 1; }
+            e++;
+        }
+        const uint64_t a = pos, b = e;
+        pos = e < n_bytes ? e + 1 + (uint64_t)(text[e] == '\r' && e + 1 < n_bytes && text[e + 1] == '\n') : e;
+        if (line_no == 0) {
+            if (a == b) continue;          // (an empty line between or behind records)
+            if (text[a] != '@') { *why = "its first line does not start with '@'"; return rec + 1; }
+        } else if (line_no == 1) {
+            seq_a = a;
+            seq_b = b;
+        } else if (line_no == 2) {
+            if (a == b || text[a] != '+') { *why = "its third line does not start with '+' (multi-line FASTQ is not supported)"; return rec + 1; }
+        } else {
+            if (b - a != seq_b - seq_a) { *why = "its quality line is not as long as its sequence"; return rec + 1; }
+            emit(rec, seq_a, seq_b);
+            rec++;
+        }
+        line_no = (line_no + 1) & 3u;
+    }
+    // a record without its quality line is complete only when its sequence is empty too ("@r\n\n+\n" and the end of the text)
+    if (line_no == 3 && seq_a == seq_b) { emit(rec, seq_a, seq_b); rec++; line_no = 0; }
+    if (line_no != 0) { *why = "the text ends inside it"; return rec + 1; }
+    *n_records = rec;
+    return 0;
+}
+}   // namespace
+
+extern "C" int bigsi_hip_fastq_pack(const char *text, uint64_t n_bytes, char *out_seqs, uint64_t *out_offsets, uint64_t max_records, uint64_t *n_records)
+{
+    if ((n_bytes && !text) || !n_records) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    const char *why = "";
+    uint64_t n = 0;
+    uint64_t bad = scan_fastq(text, n_bytes, &n, &why, [](uint64_t, uint64_t, uint64_t) {});
+    if (bad) return fail(BIGSI_ERR_INVALID, "FASTQ record %llu: %s", (unsigned long long)bad, why);
+    *n_records = n;
+    if (!out_offsets && !out_seqs) return BIGSI_OK;      // (the sizing call: n + 1 offsets, at most n_bytes sequence bytes)
+    if (out_offsets && n > max_records) return fail(BIGSI_ERR_CAPACITY, "%llu records, room for %llu", (unsigned long long)n, (unsigned long long)max_records);
+    uint64_t w = 0;
+    scan_fastq(text, n_bytes, &n, &why, [&](uint64_t r, uint64_t a, uint64_t b) {
+        if (out_offsets) out_offsets[r] = w;
+        if (out_seqs) memcpy(out_seqs + w, text + a, b - a);
+        w += b - a;
+    });
+    if (out_offsets) out_offsets[n] = w;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_format_results(int format,const char *seqs, const uint64_t *offsets, uint64_t n_seqs, const char *threshold_text,
                                         const char *citation_text, int exact, const uint32_t *num_unique, const uint64_t *hit_offsets,
                                         const uint32_t *colours, const uint32_t *counts, const char *names, const uint64_t *name_offsets,
                                         const uint8_t *name_deleted, uint64_t n_names, uint32_t threads, char **out_text, uint64_t *out_bytes)

@@ -33,6 +33,13 @@ extern "C" {
  * bytes (the body of a string object of the host language, say: no copy afterwards); BIGSI_ERR_CAPACITY with the size needed in
  * *out_bytes if it is too small -- a call with a zero-byte buffer is the sizing call.  threads = 0: up to 16 host threads. */
 int bigsi_hip_fasta_pack(const char *text, uint64_t n_bytes, char *out_seqs, uint64_t *out_offsets, uint64_t max_records, uint64_t *n_records);
+/* bigsi_hip_fastq_pack: the same for a FASTQ text of four-line records (@name, sequence, +, quality): the sequences of sequencing
+ * reads, packed as the entry points that take sequences take them.  Lines end in LF, CR LF or CR; the last line needs no line end;
+ * an empty sequence line (with an empty quality line) is a record without bases; empty lines behind the last record are ignored.
+ * The sizing call and the outputs are bigsi_hip_fasta_pack's; BIGSI_ERR_CAPACITY when max_records is too small.  BIGSI_ERR_INVALID,
+ * with the number of the record (from 1) in bigsi_hip_last_error: a first line without '@', a third without '+' (so: multi-line
+ * FASTQ), a quality line of another length than the sequence, a record cut short, a byte >= 0x80. */
+int bigsi_hip_fastq_pack(const char *text, uint64_t n_bytes, char *out_seqs, uint64_t *out_offsets, uint64_t max_records, uint64_t *n_records);
 int bigsi_hip_format_results(int format, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, const char *threshold_text,
                              const char *citation_text, int exact, const uint32_t *num_unique, const uint64_t *hit_offsets,
                              const uint32_t *colours, const uint32_t *counts, const char *names, const uint64_t *name_offsets,

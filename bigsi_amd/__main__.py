@@ -81,6 +81,9 @@ def build_parser():
     sp = common(sub.add_parser("bloom", help="Bloom filter of the k-mers of a Cortex .ctx graph, a FASTA file or a one-k-mer-per-line text file"))
     sp.add_argument("infile")
     sp.add_argument("outfile")
+    sp.add_argument("--min-count", type=int, default=None, metavar="C",
+                    help="FASTQ / FASTA reads: keep the k-mers seen at least C times, counted exactly on the device (k <= 32; default 1 for FASTQ)")
+    sp.add_argument("--spectrum", default=None, metavar="FILE", help="FASTQ / FASTA reads: also write the k-mer abundance spectrum, 256 lines of count<TAB>distinct")
     sp = shardable(common(sub.add_parser("build")))
     sp.add_argument("--bloomfilters", "-b", action="append", default=[])
     sp.add_argument("--samples", "-s", action="append", default=[])
@@ -381,16 +384,26 @@ def main(argv=None):
     elif a.cmd == "variant_search":
         print(variant_search(BIGSI(config), a.reference, a.ref, a.pos, a.alt, a.gene, a.genbank, a.format, a.probes))
     elif a.cmd == "bloom":
-        first = open(a.infile, "rb").read(6)
-        if first == b"CORTEX":                      # the reference's input: a Cortex graph (bigsi/__main__.py:120-131)
-            from .cortex import extract_kmers_from_ctx
-            kmers = list(extract_kmers_from_ctx(a.infile, config["k"]))
-        elif first[:1] == b">":
-            kmers = [km for _, s in read_fasta(a.infile) for km in seq_to_kmers(s, config["k"])]
+        first = bloom_input_head(a.infile, a.min_count is not None or a.spectrum is not None)
+        min_count = bloom_counter_route(p, first, a.min_count, a.spectrum, config["k"])          # (refusals come before any device work)
+        if min_count is not None:
+            from .kmercount import bloom_from_reads, spectrum_text
+            spectra = [] if a.spectrum else None
+            row = bloom_from_reads(config, [os.path.abspath(a.infile)], min_count, spectrum_out=spectra)
+            if a.spectrum:
+                with open(a.spectrum, "w") as f:
+                    f.write(spectrum_text(spectra[0]))
         else:
-            kmers = [l.strip() for l in open(a.infile) if l.strip()]
+            if first == b"CORTEX":                  # the reference's input: a Cortex graph (bigsi/__main__.py:120-131)
+                from .cortex import extract_kmers_from_ctx
+                kmers = list(extract_kmers_from_ctx(a.infile, config["k"]))
+            elif first[:1] == b">":
+                kmers = [km for _, s in read_fasta(a.infile) for km in seq_to_kmers(s, config["k"])]
+            else:
+                kmers = [l.strip() for l in open(a.infile) if l.strip()]
+            row = BIGSI.bloom(config, kmers)
         with open(a.outfile, "wb") as f:
-            f.write(BIGSI.bloom(config, kmers).tobytes())
+            f.write(row.tobytes())
     elif a.cmd == "build":
         paths, samples = build_inputs(a)
         build_in_slabs(config, paths, samples)
@@ -484,6 +497,43 @@ def hold(config, handle=None, seconds=None, until_eof=False):
         os.remove(path)
     except OSError:
         pass
+
+
+def bloom_input_head(path, counter_wanted=False):
+    """The first six bytes of a `bloom` input: what decides its route.  A gzip file is looked into only for the k-mer counter, which
+    reads .gz itself: its head is that of the text inside when that is FASTQ ('@'), or FASTA ('>') with --min-count / --spectrum given.
+    Every other input -- a gzip file of anything else included -- is judged by its own bytes and takes the route it took before."""
+    with open(path, "rb") as f:
+        head = f.read(6)
+    if head[:2] == b"\x1f\x8b":
+        import gzip
+        try:
+            with gzip.open(path, "rb") as f:
+                inner = f.read(6)
+        except (OSError, EOFError):
+            return head
+        if inner[:1] == b"@" or (inner[:1] == b">" and counter_wanted):
+            return inner
+    return head
+
+
+def bloom_counter_route(parser, first, min_count, spectrum, k):
+    """The min_count the k-mer counter runs `bloom` with, or None for the routes of before (Cortex graph, FASTA windowed on the host, k-mer
+    list).  FASTQ ('@') always goes to the counter; FASTA only when --min-count or --spectrum asks for it.  What cannot be done is
+    refused through parser.error, before any device work."""
+    wanted = min_count is not None or spectrum is not None
+    reads = first[:1] in (b"@", b">")
+    if min_count is not None and min_count < 1:
+        parser.error("--min-count must be at least 1 (got %d)" % min_count)
+    if wanted and not reads:
+        parser.error("--min-count and --spectrum count the k-mers of reads (FASTQ or FASTA): a %s holds k-mers already"
+                     % ("Cortex graph" if first == b"CORTEX" else "k-mer list"))
+    if first[:1] != b"@" and not wanted:
+        return None
+    from .kmercount import MAX_K
+    if not 1 <= int(k) <= MAX_K:
+        parser.error("the k-mer counter takes k <= %d (config k = %d): FASTQ input, --min-count and --spectrum need it" % (MAX_K, int(k)))
+    return 1 if min_count is None else min_count
 
 
 def build_inputs(a):

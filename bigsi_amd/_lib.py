@@ -180,6 +180,7 @@ SIGNATURES = {
     "bigsi_hip_format_results_scored": (_i32, [_i32, _P, _P, _u64, C.c_char_p, C.c_char_p, _i32, _P, _P, _P, _P, _P, _P, _P, _u64, _P, _u32,
                                                 C.POINTER(_P), C.POINTER(_u64)]),
     "bigsi_hip_free_text": (None, [_P]),
+    "bigsi_hip_kmer_counter_set_limits": (_i32, [_P, _u64, _u64]),          # (include/bigsi_hip_testing.h)
 }
 
 # every symbol include/bigsi_hip_compact.h declares (column compaction: the maintenance layer)
@@ -228,6 +229,19 @@ TALLY_SIGNATURES = {
     "bigsi_hip_tally_fetch": (_i32, [_P, _P, _P, _u64, _P]),
 }
 
+# every symbol include/bigsi_hip_kmercount.h declares (exact k-mer counter: Bloom filters from raw reads, min-count on the device); the
+# host twin's library has the same eight under its own prefix (bigsi_amd/kmercount.py binds either set from this table)
+KMERCOUNT_SIGNATURES = {
+    "bigsi_hip_kmer_counter_create": (_i32, [_i32, _u32, _u64, C.POINTER(_P)]),
+    "bigsi_hip_kmer_counter_destroy": (_i32, [_P]),
+    "bigsi_hip_kmer_counter_reset": (_i32, [_P]),
+    "bigsi_hip_kmer_counter_add": (_i32, [_P, C.c_char_p, _P, _u64]),
+    "bigsi_hip_kmer_counter_info": (_i32, [_P, _P]),
+    "bigsi_hip_kmer_counter_spectrum": (_i32, [_P, _P]),
+    "bigsi_hip_kmer_counter_fetch": (_i32, [_P, _P, _P, _u64, C.POINTER(_u64)]),
+    "bigsi_hip_kmer_counter_bloom": (_i32, [_P, _u64, _u32, _u32, _P]),
+}
+
 _lib = None
 
 
@@ -248,7 +262,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()) + list(TALLY_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()) + list(TALLY_SIGNATURES.items()) + list(KMERCOUNT_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

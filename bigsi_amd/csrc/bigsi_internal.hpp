@@ -1,5 +1,6 @@
 // bigsi_internal.hpp -- host-side structures shared by the translation units of libbigsi_hip.so
 // (bigsi_hip.hip: single-shard C ABI, the file <-> HBM pipeline; bigsi_shard.hip: RCCL exchange, device groups, one-call search;
+// bigsi_kmercount.hip: the exact k-mer counter and its kernels, a code object of its own;
 // bigsi_text.cpp: FASTA / FASTQ text; bigsi_rowsfile.cpp: the file side of that pipeline -- host only, it does not include this header).
 #pragma once
 #include "bigsi_hip.h"
@@ -8,6 +9,7 @@
 #include "bigsi_hip_consensus.h"
 #include "bigsi_hip_fold.h"
 #include "bigsi_hip_group.h"
+#include "bigsi_hip_kmercount.h"
 #include "bigsi_hip_pairwise.h"
 #include "bigsi_hip_prevalence.h"
 #include "bigsi_hip_tally.h"

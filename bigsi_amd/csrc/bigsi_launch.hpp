@@ -4,7 +4,9 @@
 // (plan_fold_rows), the sweep of the k-mer prevalence (plan_kmer_prevalence), the per-call tables, launch shape and destination
 // window of the column collapse (plan_collapse_columns) and of the consensus collapse (plan_consensus_columns) and the chunks, slices,
 // scratch and per-call tables of the pairwise popcounts (plan_pairwise, pairwise_tables) and the launch shape and stream cuts of the query-set
-// tally (plan_tally, plan_tally_chunks; pinned by tests/c_host/tally_host.cpp and tests/test_tally_host.py).  Pure functions of a handful of integers
+// tally (plan_tally, plan_tally_chunks; pinned by tests/c_host/tally_host.cpp and tests/test_tally_host.py) and what the exact k-mer
+// counter decides about a call and its table (plan_kmer_count_add, kmer_stage_chunk, plan_kmer_table; pinned by
+// tests/c_host/kmercount_plan_host.cpp and tests/test_kmercount_plan_host.py).  Pure functions of a handful of integers
 // (and, for the compaction, the collapses and the pairwise popcounts, of the keep bitmap / the group map / the column lists): no HIP,
 // no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp,
 // prevalence_host.cpp, collapse_host.cpp, consensus_host.cpp and pairwise_host.cpp compile this header as plain host C++ and
@@ -881,6 +883,109 @@ static inline std::vector<uint64_t> plan_tally_chunks(const uint64_t *offsets, u
     std::vector<uint64_t> cut(1, 0);
     while (cut.back() < n_seqs) cut.push_back(tally_chunk_end(offsets, n_seqs, cut.back(), k, wv_pad, count_bytes));
     return cut;
+}
+
+// ------------------------------------------------------------------------------ exact k-mer counter (k_count_kmers, k_kmer_table_*)
+// plan_kmer_count_add: everything bigsi_hip_kmer_counter_add decides from the offsets alone -- the call's positions, its refusal and the
+// staging chunks -- BEFORE any byte behind `seqs` is touched (a refused call may name bytes it does not own: include/bigsi_cpu_kmercount.h).
+// A chunk is a range [begin, end) of the call's bytes of at most `chunk_bytes`; the reads it meets are [seq0, seq1), the first and the
+// last of them possibly in part.  Chunks are cut at read boundaries (the last boundary the limit allows); a read that reaches beyond
+// begin + chunk_bytes is cut there and the next chunk begins k - 1 bytes earlier, so that every window lies whole in exactly one
+// chunk.  The ranges run from offsets[0] to offsets[n_seqs] without a gap: each begins where the one before ended, or k - 1 before it.
+// The device stages a chunk's pieces behind one another with one separator byte (no base) after every piece that is not empty.
+constexpr uint64_t kKmerCountLifetime = 0xFFFFFFFFull;       // positions a counter takes in its lifetime (no uint32 count wraps)
+constexpr uint64_t kKmerChunkBytes = 32ull << 20;            // staging chunk of bigsi_hip_kmer_counter_add (not measured: a few chunks per GB of reads)
+constexpr uint64_t kKmerMinChunkBytes = 64;                  // >= 2 * BIGSI_KMERCOUNT_MAX_K: a cut read advances by chunk - (k - 1) > 0
+constexpr uint64_t kKmerInitialSlots = 1ull << 16;
+constexpr uint64_t kKmerMinSlots = 64;
+constexpr uint32_t kKmerTile = 4096;                         // window starts of a workgroup of k_count_kmers: kKmerLane per thread
+constexpr uint32_t kKmerLane = 16;                           // ... one 16-byte load and one 32-bit code word each
+static_assert(kKmerTile == kBlock * kKmerLane, "a thread of k_count_kmers owns one code word of window starts");
+struct KmerChunk {
+    uint64_t begin = 0, end = 0;          // bytes [begin, end) behind seqs
+    uint64_t seq0 = 0, seq1 = 0;          // the reads those bytes belong to
+    uint64_t positions = 0;               // windows of the chunk's pieces
+    uint64_t staged = 0;                  // bytes on the device: end - begin + one separator per non-empty piece
+};
+struct KmerAddPlan {
+    enum Refusal { kNone = 0, kNotMonotone = 1, kLifetime = 2 } refusal = kNone;
+    uint64_t bad_seq = 0;                 // kNotMonotone: the first read whose end lies before its start
+    uint64_t positions = 0;               // of the whole call
+    std::vector<KmerChunk> chunks;        // empty when refused
+};
+static inline uint64_t kmer_positions(uint64_t len, uint32_t k) { return len >= k ? len - k + 1 : 0; }
+static inline KmerAddPlan plan_kmer_count_add(uint32_t k, const uint64_t *offsets, uint64_t n_seqs, uint64_t taken, uint64_t chunk_bytes)
+{
+    KmerAddPlan p;
+    if (n_seqs == 0) return p;
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        if (offsets[i + 1] < offsets[i]) { p.refusal = KmerAddPlan::kNotMonotone; p.bad_seq = i; p.positions = 0; return p; }
+        p.positions += kmer_positions(offsets[i + 1] - offsets[i], k);          // (at most offsets[n_seqs] - offsets[0]: no overflow)
+    }
+    if (taken > kKmerCountLifetime || p.positions > kKmerCountLifetime - taken) { p.refusal = KmerAddPlan::kLifetime; return p; }
+    chunk_bytes = std::max(chunk_bytes, kKmerMinChunkBytes);
+    const uint64_t last = offsets[n_seqs];
+    uint64_t cur = offsets[0], s = 0;          // read s holds byte cur (or starts there)
+    while (cur < last) {
+        KmerChunk c;
+        c.begin = cur;
+        while (offsets[s + 1] <= cur && s + 1 < n_seqs) s++;          // (empty reads at the cut, and the read a boundary cut ended)
+        c.seq0 = s;
+        const uint64_t reach = last - cur > chunk_bytes ? cur + chunk_bytes : last;
+        const uint64_t j = (uint64_t)(std::upper_bound(offsets + s, offsets + n_seqs + 1, reach) - offsets) - 1;      // the last boundary <= reach
+        uint64_t next;
+        if (offsets[j] > cur) { c.end = offsets[j]; c.seq1 = j; next = c.end; }
+        else { c.end = reach; c.seq1 = s + 1; next = reach - (k - 1); }          // inside read s, which reaches beyond `reach`
+        for (uint64_t i = c.seq0; i < c.seq1; i++) {
+            const uint64_t a = std::max(offsets[i], c.begin), b = std::min(offsets[i + 1], c.end);
+            c.positions += kmer_positions(b - a, k);
+            c.staged += b > a ? b - a + 1 : 0;
+        }
+        p.chunks.push_back(c);
+        cur = next;
+    }
+    return p;
+}
+
+// A chunk's pieces behind one another in dst[0 .. c.staged), a separator byte (0: no base) behind every piece that is not empty, so
+// that no window of the staged stream spans two pieces.  Reads seqs[c.begin .. c.end) and nothing else; returns the bytes written.
+static inline uint64_t kmer_stage_chunk(const char *seqs, const uint64_t *offsets, const KmerChunk &c, uint8_t *dst)
+{
+    uint64_t at = 0;
+    for (uint64_t i = c.seq0; i < c.seq1; i++) {
+        const uint64_t a = std::max(offsets[i], c.begin), b = std::min(offsets[i + 1], c.end);
+        if (b <= a) continue;
+        std::copy(seqs + a, seqs + b, reinterpret_cast<char *>(dst) + at);
+        at += b - a;
+        dst[at++] = 0;
+    }
+    return at;
+}
+
+// The table rule: the slot count is a power of two, and before a chunk is launched distinct + positions_of_chunk <= slots / 2 holds
+// -- every window of the chunk may be a new key, so k_count_kmers never meets a table more than half full and its probe sequences stay
+// short; the host grows the table (k_kmer_table_rehash) to `slots` first when that is more than it has.  grid: the chunk's tiles.
+struct KmerTablePlan {
+    uint64_t slots = 0;
+    bool grow = false;
+    uint64_t grid = 0;
+    uint32_t block = kBlock;
+};
+static inline KmerTablePlan plan_kmer_table(uint64_t slots_now, uint64_t distinct, uint64_t chunk_positions, uint64_t chunk_staged)
+{
+    KmerTablePlan p;
+    p.slots = std::max(slots_now, kKmerMinSlots);
+    while (p.slots & (p.slots - 1)) p.slots += p.slots & (~p.slots + 1);          // up to a power of two
+    while (distinct + chunk_positions > p.slots / 2) p.slots *= 2;               // (both at most 2^32 - 1: no overflow)
+    p.grow = p.slots != slots_now;
+    p.grid = ceil_div(chunk_staged, kKmerTile);
+    return p;
+}
+// the table a counter starts with: twice the hint, at least `floor_slots`
+static inline uint64_t kmer_initial_slots(uint64_t expected_distinct, uint64_t floor_slots)
+{
+    const uint64_t want = std::min<uint64_t>(expected_distinct, kKmerCountLifetime);
+    return plan_kmer_table(floor_slots, want, 0, 0).slots;
 }
 
 }  // namespace bigsi

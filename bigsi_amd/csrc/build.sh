@@ -11,5 +11,5 @@ FLAGS="${BIGSI_HIP_EXTRA_FLAGS:-}"
 "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared \
     -Wall -Wextra -Wno-unused-parameter \
     -I"$ROOT/include" -I/opt/rocm/include $FLAGS \
-    -o "$OUT" "$HERE/bigsi_hip.hip" "$HERE/bigsi_shard.hip" "$HERE/bigsi_text.cpp" "$HERE/bigsi_rowsfile.cpp" -ldl -lpthread
+    -o "$OUT" "$HERE/bigsi_hip.hip" "$HERE/bigsi_shard.hip" "$HERE/bigsi_kmercount.hip" "$HERE/bigsi_text.cpp" "$HERE/bigsi_rowsfile.cpp" -ldl -lpthread
 echo "built $OUT"

@@ -305,6 +305,18 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         return BitRow.frombytes(raw.tobytes(), int(config["m"]))
 
     @classmethod
+    def bloom_from_reads(cls, config, paths_or_seqs, min_count=1):
+        """Bloom filter (m bits) of the canonical k-mers that occur at least `min_count` times in raw reads, counted exactly on the
+        device (bigsi_amd/kmercount.py): `paths_or_seqs` holds FASTQ / FASTA files (.gz or not; a str entry that names an existing
+        file, or any os.PathLike) and sequences (every other str or bytes entry; pass sequences as bytes where a str could be mistaken
+        for the name of a file in the working directory).  Needs config k <= 32; windows with a byte other than
+        ACGTacgt are skipped.  With min_count=1 and ACGT-only input this is BIGSI.bloom of the reads' k-mers, bit for bit."""
+        from ..kmercount import bloom_from_reads
+        if isinstance(paths_or_seqs, (str, bytes)):
+            raise TypeError("bloom_from_reads takes a list of files and sequences, not one of them")
+        return bloom_from_reads(config, paths_or_seqs, min_count)
+
+    @classmethod
     def build(cls, config, bloomfilters, samples):
         storage = get_storage(config)
         validate_build_params(bloomfilters, samples)

@@ -3,8 +3,8 @@
  * abundance spectrum and the Bloom filter of the k-mers seen at least C times -- byte for byte the filter bigsi_cpu_bloom (and
  * bigsi_hip_bloom) makes from the same k-mer list, so that a sample's filter can be made from raw sequencing data with the k-mers of
  * sequencing errors (seen once) left out.  Implemented plainly (a map, bigsi_cpu_bloom's hashing) for hosts without a GPU and as
- * the definition a device counter is to be held against; libbigsi_hip.so has no counterpart yet.  Entry points in the conventions of
- * bigsi_cpu.h (return codes, bigsi_cpu_last_error).
+ * the definition the device counter of libbigsi_hip.so (include/bigsi_hip_kmercount.h: the same entry points, counted in a hash table
+ * in HBM) is held against.  Entry points in the conventions of bigsi_cpu.h (return codes, bigsi_cpu_last_error).
  *
  * SEMANTICS (tests/kmercount_ref.py restates them):
  *   k        1 <= k <= 32 (BIGSI_ERR_INVALID beyond: a key is one 64-bit word).
@@ -35,7 +35,7 @@ extern "C" {
 
 typedef struct bigsi_cpu_kmer_counter bigsi_cpu_kmer_counter;
 
-/* `device` and `expected_distinct` (a sizing hint) are there for a device counter of the same shape; the host ignores both. */
+/* `device` and `expected_distinct` (a sizing hint) are the device counter's, which has the same shape; the host ignores both. */
 int bigsi_cpu_kmer_counter_create(int device, uint32_t k, uint64_t expected_distinct, bigsi_cpu_kmer_counter **out);
 int bigsi_cpu_kmer_counter_destroy(bigsi_cpu_kmer_counter *c);
 int bigsi_cpu_kmer_counter_reset(bigsi_cpu_kmer_counter *c);

@@ -78,6 +78,13 @@ int bigsi_hip_insert_columns_device(bigsi_hip_index *ix, uint64_t col0, uint64_t
 int bigsi_hip_probe_rows(bigsi_hip_index *ix, uint32_t rows_per_query, uint32_t n_queries, uint32_t sorted, uint32_t wgs, uint32_t reps,
                          double *gbps, double *launch_ms);
 
+/* K-MER COUNTER (include/bigsi_hip_kmercount.h): the staging chunk of later adds, in bytes (at least 64), and the slot count a
+ * reset starts from (a power of two, at least 64); 0 keeps the library's own value.  With small values a test reaches a chunk cut
+ * and several table growths with a few kilobytes of input; results do not depend on either.  BIGSI_ERR_STATE on a counter that
+ * holds anything: call it right after create or reset (an empty counter takes the new slot count at once). */
+struct bigsi_hip_kmer_counter;
+int bigsi_hip_kmer_counter_set_limits(struct bigsi_hip_kmer_counter *c, uint64_t chunk_bytes, uint64_t initial_slots);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,7 +157,14 @@ def build_parser():
     sp.add_argument("fasta")
     sp.add_argument("--threshold", "-t", type=float, default=1.0)
     sp.add_argument("--format", choices=["json", "csv"], default="json")
-    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally"):          # (named so that the refusal says why)
+    sp = common(sub.add_parser("window_search", help="the samples that hold some stretch of W consecutive k-mer positions of SEQ (or of every record "
+                                                     "of a FASTA file), the best window per sample and where on the query the match lies"))
+    sp.add_argument("seq", nargs="?", default=None)
+    sp.add_argument("--fasta", default=None, metavar="FILE", help="the queries: every record of a FASTA file")
+    sp.add_argument("--window", "-w", type=int, required=True, metavar="W", help="window length in k-mer positions (1 .. 65535)")
+    sp.add_argument("--threshold", "-t", type=float, default=1.0)
+    sp.add_argument("--format", choices=["json", "csv"], default="json")
+    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally", "window_search"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -302,6 +309,16 @@ def tally_text(index, queries, threshold=1.0, limit=None, fmt="json"):
     return to_csv(rec) if fmt == "csv" else to_json(rec)
 
 
+def window_search_text(index, queries, window, threshold=1.0, fmt="json"):
+    """`window_search`: BIGSI.search_windows_many over the queries, one device call per query (a long query is a call's worth of work,
+    and the device keeps counters per sequence).  JSON: the dicts, each with its "query" first; CSV: record,<result fields>, one line
+    per reported sample."""
+    from .window import to_csv, to_json
+    queries = list(queries)
+    recs = [index.search_windows(q, window, threshold) for q in queries]
+    return to_csv(recs) if fmt == "csv" else to_json(recs, queries)
+
+
 def fold_dry_run_text(index, factor, fmt="json"):
     """`fold --dry-run`: nothing is touched.  The valid factors whose folded size is nearest to the one asked for, and per sample the
     fill and k-mer false-positive rate the balls-in-bins model PREDICTS (fold.fold_estimate) -- estimates, labelled as such; the exact
@@ -369,6 +386,16 @@ def main(argv=None):
         p.error("%s is not available with --sharded: pairs of samples on different shards are not implemented (use a single index)" % a.cmd)
     if getattr(a, "sharded", False) and a.cmd == "tally":
         p.error("tally is not available with --sharded: the per-shard sums plus a host merge are not implemented (use a single index)")
+    if getattr(a, "sharded", False) and a.cmd == "window_search":
+        p.error("window_search is not available with --sharded: the per-shard sweep is not implemented (use a single index)")
+    if a.cmd == "window_search" and (a.seq is None) == (a.fasta is None):
+        p.error("window_search takes SEQ or --fasta FILE (one of them)")
+    if a.cmd == "window_search":
+        from .window import check_args
+        try:
+            check_args(a.window, a.threshold)
+        except ValueError as e:
+            p.error(str(e))
     if a.cmd == "prevalence" and (a.seq is None) == (a.fasta is None):
         p.error("prevalence takes SEQ or --fasta FILE (one of them)")
     if a.cmd == "fold" and not a.dry_run and not a.to_config:
@@ -449,6 +476,9 @@ def main(argv=None):
         queries = [a.seq] if a.fasta is None else [s for _, s in read_fasta(a.fasta)]
         names = extract_names(a)
         print(prevalence_text(BIGSI(config), queries, names or None, a.format))
+    elif a.cmd == "window_search":
+        queries = [a.seq] if a.fasta is None else [s for _, s in read_fasta(a.fasta)]
+        print(window_search_text(BIGSI(config), queries, a.window, a.threshold, a.format))
     elif a.cmd == "tally":
         print(tally_text(BIGSI(config), [s for _, s in read_fasta(a.fasta)], a.threshold, a.limit, a.format))
     elif a.cmd == "distances":

@@ -181,6 +181,7 @@ SIGNATURES = {
                                                 C.POINTER(_P), C.POINTER(_u64)]),
     "bigsi_hip_free_text": (None, [_P]),
     "bigsi_hip_kmer_counter_set_limits": (_i32, [_P, _u64, _u64]),          # (include/bigsi_hip_testing.h)
+    "bigsi_hip_window_set_limits": (_i32, [_P, _u64, _u64]),                # (include/bigsi_hip_testing.h)
 }
 
 # every symbol include/bigsi_hip_compact.h declares (column compaction: the maintenance layer)
@@ -211,6 +212,12 @@ CONSENSUS_SIGNATURES = {
 PREVALENCE_SIGNATURES = {
     "bigsi_hip_kmer_prevalence": (_i32, [_P, C.c_char_p, _P, _u32, _u32, _P, _P, _P, _P, _P, _u64]),
     "bigsi_hip_batch_kmer_prevalence": (_i32, [_P, _P, _P, _P, _P, _u64]),
+}
+
+# every symbol include/bigsi_hip_window.h declares (windowed search: the best window per sample and where the passing windows lie)
+WINDOW_SIGNATURES = {
+    "bigsi_hip_window_search": (_i32, [_P, C.c_char_p, _P, _u32, _u32, _u32, C.c_double, _P, _P, _P, _P, _P, _u64]),
+    "bigsi_hip_batch_window_search": (_i32, [_P, _u32, C.c_double, _P, _P, _P, _P, _P, _u64]),
 }
 
 # every symbol include/bigsi_hip_pairwise.h declares (pairwise popcounts: the shared-bit counts of every pair of two lists of columns)
@@ -262,7 +269,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()) + list(TALLY_SIGNATURES.items()) + list(KMERCOUNT_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()) + list(TALLY_SIGNATURES.items()) + list(KMERCOUNT_SIGNATURES.items()) + list(WINDOW_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

@@ -23,6 +23,7 @@
 #include "bigsi_cpu_kmercount.h"
 #include "bigsi_cpu_pairwise.h"
 #include "bigsi_cpu_prevalence.h"
+#include "bigsi_cpu_window.h"
 #include "bigsi_cpu_tally.h"
 
 #include <math.h>
@@ -1029,6 +1030,75 @@ int bigsi_cpu_kmer_prevalence(bigsi_cpu_index *ix, const char *seqs, const uint6
         }
     }
     return bdb_read_failed(ix);
+}
+
+// the windowed search (include/bigsi_cpu_window.h): per sequence a plain loop over the positions -- the AND of the position's h rows,
+// the bits behind the last column cut off -- that keeps, per column, the prefix sum of its presence; then per column the window
+// differences pre[s + We] - pre[s] over the starts: the maximum and its lowest start, the first and last start that reach `need`
+// and their number.  Columns in ascending order, so the hits are.
+int bigsi_cpu_window_search(bigsi_cpu_index *ix, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k, uint32_t window,
+                            double threshold, uint32_t *window_used, uint32_t *need, uint64_t *hit_offsets, uint32_t *colours,
+                            bigsi_hip_window_hit *records, uint64_t capacity)
+{
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_seqs(seqs, offsets, n_seqs, k));
+    if (window == 0 || window > BIGSI_WINDOW_MAX) return fail(BIGSI_ERR_INVALID, "window must be 1 .. %u k-mer positions (got %u)", BIGSI_WINDOW_MAX, window);
+    if (!(threshold > 0.0 && threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be in (0, 1] (got %g)", threshold);
+    if (!window_used || !need || !hit_offsets) return fail(BIGSI_ERR_INVALID, "window_used, need or hit_offsets is NULL");
+    if (capacity && (!colours || !records)) return fail(BIGSI_ERR_INVALID, "colours or records is NULL");
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    const uint64_t rb = ix->rb(), n_cols = ix->n_cols;
+    std::string canon;
+    std::vector<uint64_t> r(ix->h);
+    std::vector<uint8_t> acc(rb), tmp, page;
+    std::vector<uint32_t> pre;                      // pre[p * n_cols + c]: positions < p that hold column c
+    std::vector<uint32_t> out_col;
+    std::vector<bigsi_hip_window_hit> out_rec;
+    hit_offsets[0] = 0;
+    for (uint32_t i = 0; i < n_seqs; i++) {
+        const char *s = seqs + offsets[i];
+        const uint64_t len = offsets[i + 1] - offsets[i], n = len >= k ? len - k + 1 : 0;
+        const uint32_t we = (uint32_t)std::min<uint64_t>(n, window), thr = (uint32_t)ceil((double)we * threshold);
+        window_used[i] = we;
+        need[i] = thr;
+        if (n) {
+            pre.assign((n + 1) * n_cols, 0);
+            for (uint64_t p = 0; p < n; p++) {
+                canonical(s + p, k, canon);
+                rows_of(canon, ix->h, ix->m, r.data());
+                std::fill(acc.begin(), acc.end(), 0xFF);
+                for (uint32_t t = 0; t < ix->h; t++) {
+                    const uint8_t *x = ix->fetch(r[t], rb, tmp, page);
+                    for (uint64_t b = 0; b < rb; b++) acc[b] &= x[b];
+                }
+                for (uint64_t c = 0; c < n_cols; c++)
+                    pre[(p + 1) * n_cols + c] = pre[p * n_cols + c] + ((acc[c >> 3] & (0x80u >> (c & 7))) ? 1u : 0u);
+            }
+            const uint64_t starts = n - we + 1;
+            for (uint64_t c = 0; c < n_cols; c++) {
+                bigsi_hip_window_hit h{0, 0, 0, 0, 0, 0};
+                for (uint64_t st = 0; st < starts; st++) {
+                    const uint32_t found = pre[(st + we) * n_cols + c] - pre[st * n_cols + c];
+                    if (st == 0 || found > h.best_found) { h.best_found = found; h.best_start = (uint32_t)st; }
+                    if (found >= thr) {
+                        if (!h.windows_passing) h.first_start = (uint32_t)st;
+                        h.last_start = (uint32_t)st;
+                        h.windows_passing++;
+                    }
+                }
+                if (h.windows_passing) { out_col.push_back((uint32_t)c); out_rec.push_back(h); }
+            }
+        }
+        hit_offsets[i + 1] = out_col.size();
+    }
+    TRY(bdb_read_failed(ix));
+    if (out_col.size() > capacity)
+        return fail(BIGSI_ERR_CAPACITY, "hit buffers hold %llu entries, %llu needed", (unsigned long long)capacity, (unsigned long long)out_col.size());
+    if (!out_col.empty()) {
+        memcpy(colours, out_col.data(), out_col.size() * 4);
+        memcpy(records, out_rec.data(), out_rec.size() * sizeof(bigsi_hip_window_hit));
+    }
+    return BIGSI_OK;
 }
 
 // the query-set tally: every sequence searched in the reference's shape (search_reference_shaped: its hits are the (sample, k-mers

@@ -392,6 +392,10 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
             bigsi_hip_batch_destroy(w);
             w = nullptr;
         }
+    if (ix->window_ws) {
+        bigsi_hip_batch_destroy(ix->window_ws);
+        ix->window_ws = nullptr;
+    }
     hipError_t e = hipSetDevice(ix->device);
     e = hipStreamSynchronize(ix->stream);
     if (ix->pre_stream) e = hipStreamSynchronize(ix->pre_stream);
@@ -1760,7 +1764,7 @@ extern "C" int bigsi_hip_batch_destroy(bigsi_hip_batch *b)
     (void)e;
     b->planes.release();
     for (DevBuf *d : {&b->uniq, &b->upload, &b->pres_desc, &b->elem_seq_off, &b->pres_in, &b->pres_bits, &b->pres_out, &b->rows_sorted, &b->pos_query, &b->hsh, &b->rep, &b->seqs, &b->d_seq_off, &b->d_pos_off, &b->d_tab_off, &b->tab, &b->first_pos, &b->pos_unique, &b->tmp, &b->rows,
-                      &b->num_kmers, &b->num_unique, &b->min_kmers, &b->bitmaps, &b->counts, &b->scratch, &b->excl_bits, &b->ranked})
+                      &b->num_kmers, &b->num_unique, &b->min_kmers, &b->bitmaps, &b->counts, &b->scratch, &b->excl_bits, &b->ranked, &b->win_col, &b->win_cnt, &b->win_loc})
         d->release();
     b->hits.release();
     b->ghits.release();
@@ -2872,6 +2876,245 @@ extern "C" int bigsi_hip_kmer_prevalence(bigsi_hip_index *ix, const char *seqs, 
         bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
     }
     return rc;
+}
+
+// Windowed search (include/bigsi_hip_window.h; k_window_max + k_window_combine, launch shape: plan_window_search; K4's k_hits_totals /
+// k_hits_write on buffers of its own; k_window_bits + k_window_locate): per sample the best window of a batch that has run.  The
+// batch's scratch holds, for this call only: segments | segment offsets | need | the segments' maxima | hit bitmap | uint16 counters |
+// hit offsets | K4's group totals.  The hit lists go to win_col / win_cnt (the batch's own hit lists stay as its run left them), the
+// locate pass's word offsets, presence words and records to win_loc.  Everything goes to the index stream and is timed with the
+// presence kernels (bigsi_hip_set_profiling / bigsi_hip_stats: presence_ms).
+template <int P, int H>
+static void window_max_launch(const WindowPlan &p, bigsi_hip_batch *b, const WindowSeg *segs, uint64_t *partial)
+{
+    bigsi_hip_index *ix = b->ix;
+    hipLaunchKernelGGL((k_window_max<P, H>), dim3((unsigned)p.grid), dim3(kBlock), 0, ix->stream, ix->d_index, ix->stride_words, (uint32_t)ix->wv(),
+                       b->rows.as<uint64_t>(), b->d_pos_off.as<uint64_t>(), b->pos_unique.as<uint32_t>(), ix->h, segs, p.n_segs, p.tiles, partial, p.wvp);
+}
+template <int P>
+static void window_max_launch_h(const WindowPlan &p, bigsi_hip_batch *b, const WindowSeg *segs, uint64_t *partial)
+{
+    switch (b->ix->h) {
+    case 1: window_max_launch<P, 1>(p, b, segs, partial); break;
+    case 2: window_max_launch<P, 2>(p, b, segs, partial); break;
+    case 3: window_max_launch<P, 3>(p, b, segs, partial); break;
+    case 4: window_max_launch<P, 4>(p, b, segs, partial); break;
+    case 5: window_max_launch<P, 5>(p, b, segs, partial); break;
+    case 6: window_max_launch<P, 6>(p, b, segs, partial); break;
+    case 7: window_max_launch<P, 7>(p, b, segs, partial); break;
+    default: window_max_launch<P, 0>(p, b, segs, partial); break;
+    }
+}
+
+static int check_window_args(uint32_t window, double threshold, const uint32_t *window_used, const uint32_t *need, const uint64_t *hit_offsets,
+                             const uint32_t *colours, const bigsi_hip_window_hit *records, uint64_t capacity)
+{
+    if (window == 0 || window > BIGSI_WINDOW_MAX) return fail(BIGSI_ERR_INVALID, "window must be 1 .. %u k-mer positions (got %u)", BIGSI_WINDOW_MAX, window);
+    if (!(threshold > 0.0 && threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be in (0, 1] (got %g)", threshold);
+    if (!window_used || !need || !hit_offsets) return fail(BIGSI_ERR_INVALID, "window_used, need or hit_offsets is NULL");
+    if (capacity && (!colours || !records)) return fail(BIGSI_ERR_INVALID, "colours or records is NULL");
+    return BIGSI_OK;
+}
+
+// We and need of every sequence: ceil in IEEE double as min_kmers is derived (one multiply, as Python's math.ceil(We * t))
+static void window_needs(const uint32_t *n, uint32_t n_seqs, uint32_t window, double threshold, uint32_t *window_used, uint32_t *need)
+{
+    for (uint32_t q = 0; q < n_seqs; q++) {
+        const uint32_t we = std::min(n[q], window);
+        window_used[q] = we;
+        need[q] = (uint32_t)ceil((double)we * threshold);
+    }
+}
+
+static int window_launch(bigsi_hip_batch *b, uint32_t window, double threshold, uint32_t *window_used, uint32_t *need, uint64_t *hit_offsets,
+                         uint32_t *colours, bigsi_hip_window_hit *records, uint64_t capacity)
+{
+    static_assert(sizeof(bigsi_hip_window_hit) == sizeof(WindowRecord) && sizeof(WindowRecord) == 24, "the kernel's record is the header's");
+    bigsi_hip_index *ix = b->ix;
+    const uint32_t n_seqs = b->n_seqs;
+    if (b->run_h != ix->h) return fail(BIGSI_ERR_STATE, "num_hashes changed since this batch ran (%u then, %u now): run it again", b->run_h, ix->h);
+    if (ix->wv() > ix->stride_words || ix->stride_words % kVec)
+        return fail(BIGSI_ERR_STATE, "internal: %llu column words do not fit the row stride %llu", (unsigned long long)ix->wv(), (unsigned long long)ix->stride_words);
+    TRY(host_counts(b));
+    window_needs(b->h_num_kmers.data(), n_seqs, window, threshold, window_used, need);
+    memset(hit_offsets, 0, (n_seqs + 1) * 8ull);
+    if (b->total_pos == 0 || ix->n_cols == 0) return BIGSI_OK;
+    const uint64_t wv = ix->wv();
+    const WindowPlan p = plan_window_search(b->h_num_kmers.data(), n_seqs, window, wv, ix->h, ix->window_starts, ix->window_cap);
+    if (p.n_segs == 0) return BIGSI_OK;
+    if (p.grid_too_large)
+        return fail(BIGSI_ERR_INVALID, "window search too large for one launch: %llu segments x %u tiles = %llu workgroups (at most %llu)",
+                    (unsigned long long)p.n_segs, p.tiles, (unsigned long long)p.grid, 0x7FFFFFFFull);
+    if (p.partial_too_large)
+        return fail(BIGSI_ERR_INVALID, "window search too large: %llu segments x %u planes x %llu words = %llu bytes of per-segment maxima (cap %llu)",
+                    (unsigned long long)p.n_segs, p.planes, (unsigned long long)p.wvp, (unsigned long long)p.partial_bytes,
+                    (unsigned long long)(ix->window_cap ? ix->window_cap : kWindowPartialBytes));
+    const uint64_t bm_stride = p.wvp, out_stride = bm_stride * 64, counter_bytes = (uint64_t)n_seqs * out_stride * 2;
+    if (counter_bytes > kWindowPartialBytes)
+        return fail(BIGSI_ERR_INVALID, "window search too large: %u sequences x %llu columns = %llu bytes of counters (cap %llu): send fewer sequences per call",
+                    n_seqs, (unsigned long long)out_stride, (unsigned long long)counter_bytes, (unsigned long long)kWindowPartialBytes);
+    const uint32_t blocks_per_seq = (uint32_t)ceil_div(wv, kBlock);
+    const uint64_t combine_grid = (uint64_t)blocks_per_seq * n_seqs;
+    const uint32_t chunks = blocks_per_seq;
+    const uint64_t nchunks = (uint64_t)chunks * n_seqs;
+    if (combine_grid > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "window search too large for one launch: %llu result words", (unsigned long long)combine_grid);
+
+    // the call's tables, one upload: segments | segment offsets | need
+    const size_t o_segoff = round_up(p.n_segs * sizeof(WindowSeg), 256), o_need = round_up(o_segoff + (n_seqs + 1) * 8ull, 256);
+    const size_t o_partial = round_up(o_need + n_seqs * 4ull, 256), o_bm = round_up(o_partial + p.partial_bytes, 256);
+    const size_t o_cnt = round_up(o_bm + (uint64_t)n_seqs * bm_stride * 8, 256), o_hoff = round_up(o_cnt + counter_bytes, 256);
+    const size_t o_tot = round_up(o_hoff + (n_seqs + 1) * 8ull, 256), bytes = o_tot + kHitsMaxGroups * 4;
+    std::vector<uint8_t> tables(o_partial, 0);
+    memcpy(tables.data(), p.segs.data(), p.n_segs * sizeof(WindowSeg));
+    memcpy(tables.data() + o_segoff, p.seg_off.data(), (n_seqs + 1) * 8ull);
+    memcpy(tables.data() + o_need, need, n_seqs * 4ull);
+    TRY(b->scratch.reserve(bytes));
+    uint8_t *d = b->scratch.as<uint8_t>();
+    HIP_TRY(hipMemcpy(d, tables.data(), tables.size(), hipMemcpyHostToDevice));
+    const WindowSeg *d_segs = reinterpret_cast<const WindowSeg *>(d);
+    const uint64_t *d_segoff = reinterpret_cast<const uint64_t *>(d + o_segoff);
+    const uint32_t *d_need = reinterpret_cast<const uint32_t *>(d + o_need);
+    uint64_t *d_partial = reinterpret_cast<uint64_t *>(d + o_partial), *d_bm = reinterpret_cast<uint64_t *>(d + o_bm);
+    uint16_t *d_cnt = reinterpret_cast<uint16_t *>(d + o_cnt);
+    uint64_t *d_hoff = reinterpret_cast<uint64_t *>(d + o_hoff);
+    uint32_t *d_tot = reinterpret_cast<uint32_t *>(d + o_tot);
+    if (b->win_cap == 0) {
+        const uint64_t want = 1u << 16;
+        TRY(b->win_col.reserve(want * 4));
+        TRY(b->win_cnt.reserve(want * 4));
+        b->win_cap = want;
+    }
+
+    EventPair ep{};
+    TRY(bigsi_ev_begin(ix, &ep));
+    switch (p.planes) {
+    case 4: window_max_launch_h<4>(p, b, d_segs, d_partial); break;
+    case 8: window_max_launch_h<8>(p, b, d_segs, d_partial); break;
+    case 12: window_max_launch_h<12>(p, b, d_segs, d_partial); break;
+    default: window_max_launch_h<16>(p, b, d_segs, d_partial); break;
+    }
+    HIP_TRY(hipGetLastError());
+#define BIGSI_WINDOW_COMBINE(PL)                                                                                                       \
+    hipLaunchKernelGGL((k_window_combine<PL>), dim3((unsigned)combine_grid), dim3(kBlock), 0, ix->stream, d_partial, p.wvp, d_segoff, n_seqs, \
+                       (uint32_t)wv, blocks_per_seq, d_need, ix->n_cols, d_bm, bm_stride, d_cnt, out_stride)
+    switch (p.planes) {
+    case 4: BIGSI_WINDOW_COMBINE(4); break;
+    case 8: BIGSI_WINDOW_COMBINE(8); break;
+    case 12: BIGSI_WINDOW_COMBINE(12); break;
+    default: BIGSI_WINDOW_COMBINE(16); break;
+    }
+#undef BIGSI_WINDOW_COMBINE
+    HIP_TRY(hipGetLastError());
+    // K4 as compact_bits launches it, on this call's bitmap and counters
+    const uint32_t ipb = nchunks <= 16 ? (uint32_t)nchunks : (uint32_t)ceil_div(nchunks, (uint64_t)kHitsMaxGroups);
+    const uint64_t ngroups = ceil_div(nchunks, ipb);
+    auto hits_write = [&]() {
+        hipLaunchKernelGGL(k_hits_write, dim3((unsigned)ngroups), dim3(kBlock), 0, ix->stream, (const uint64_t *)d_bm, bm_stride, (uint32_t)wv, n_seqs, 1u,
+                           chunks, ix->n_cols, b->num_unique.as<uint32_t>(), ipb, d_tot, d_hoff, b->win_col.as<uint32_t>(), b->win_cnt.as<uint32_t>(),
+                           b->win_cap, (const void *)d_cnt, 2u, out_stride, kAllShards, (uint64_t *)nullptr, 0u, (const uint32_t *)nullptr,
+                           (volatile uint64_t *)nullptr, (uint64_t)0);
+    };
+    if (ngroups > 1)
+        hipLaunchKernelGGL(k_hits_totals, dim3((unsigned)ngroups), dim3(kBlock), 0, ix->stream, (const uint64_t *)d_bm, bm_stride, (uint32_t)wv, n_seqs, 1u,
+                           chunks, ipb, d_tot);
+    hits_write();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hit_offsets, d_hoff, (n_seqs + 1) * 8ull, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    const uint64_t total = hit_offsets[n_seqs];
+    if (total > capacity) {
+        TRY(bigsi_ev_end(ix, &ep, ix->ev_pr, nullptr, 4));
+        return fail(BIGSI_ERR_CAPACITY, "hit buffers hold %llu entries, %llu needed", (unsigned long long)capacity, (unsigned long long)total);
+    }
+    if (total == 0) return bigsi_ev_end(ix, &ep, ix->ev_pr, nullptr, 4);
+    if (total > b->win_cap) {          // the write pass overflowed: grow the lists and run it again (the totals are still there)
+        TRY(b->win_col.reserve(total * 4));
+        TRY(b->win_cnt.reserve(total * 4));
+        b->win_cap = total;
+        hits_write();
+        HIP_TRY(hipGetLastError());
+    }
+    // the locate pass: every hit's presence words, then its record
+    std::vector<uint64_t> word_off(n_seqs + 1, 0);
+    for (uint32_t q = 0; q < n_seqs; q++)
+        word_off[q + 1] = word_off[q] + (hit_offsets[q + 1] - hit_offsets[q]) * ceil_div(b->h_num_kmers[q], 64);
+    const uint64_t n_words = word_off[n_seqs], cap_bytes = ix->window_cap ? ix->window_cap : kWindowPartialBytes;
+    if (n_words * 8 > cap_bytes || ceil_div(n_words, kBlock / 64) > 0x7FFFFFFFull) {
+        TRY(bigsi_ev_end(ix, &ep, ix->ev_pr, nullptr, 4));
+        return fail(BIGSI_ERR_INVALID, "window search too large: %llu hits need %llu bytes of presence bits (cap %llu): send fewer sequences per call or raise the threshold",
+                    (unsigned long long)total, (unsigned long long)(n_words * 8), (unsigned long long)cap_bytes);
+    }
+    const size_t o_bits = round_up((n_seqs + 1) * 8ull, 256), o_rec = round_up(o_bits + n_words * 8, 256);
+    TRY(b->win_loc.reserve(o_rec + total * sizeof(WindowRecord)));
+    uint8_t *dl = b->win_loc.as<uint8_t>();
+    HIP_TRY(hipMemcpy(dl, word_off.data(), (n_seqs + 1) * 8ull, hipMemcpyHostToDevice));
+    const uint64_t *d_woff = reinterpret_cast<const uint64_t *>(dl);
+    uint64_t *d_bits = reinterpret_cast<uint64_t *>(dl + o_bits);
+    WindowRecord *d_rec = reinterpret_cast<WindowRecord *>(dl + o_rec);
+    hipLaunchKernelGGL(k_window_bits, dim3((unsigned)ceil_div(n_words, kBlock / 64)), dim3(kBlock), 0, ix->stream, ix->d_index, ix->stride_words,
+                       b->rows.as<uint64_t>(), b->d_pos_off.as<uint64_t>(), b->pos_unique.as<uint32_t>(), b->num_kmers.as<uint32_t>(), ix->h, n_seqs,
+                       d_woff, (const uint64_t *)d_hoff, b->win_col.as<uint32_t>(), d_bits);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_window_locate, dim3((unsigned)ceil_div(total, kBlock / 64)), dim3(kBlock), 0, ix->stream, (const uint64_t *)d_bits, d_woff,
+                       (const uint64_t *)d_hoff, n_seqs, b->num_kmers.as<uint32_t>(), d_need, window, d_rec);
+    HIP_TRY(hipGetLastError());
+    TRY(bigsi_ev_end(ix, &ep, ix->ev_pr, nullptr, 6));
+    std::vector<uint32_t> h_col(total), h_cnt(total);
+    std::vector<WindowRecord> h_rec(total);
+    HIP_TRY(hipMemcpyAsync(h_col.data(), b->win_col.p, total * 4, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(h_cnt.data(), b->win_cnt.p, total * 4, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(h_rec.data(), d_rec, total * sizeof(WindowRecord), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    // the two device routes must agree before anything is handed out
+    for (uint32_t q = 0; q < n_seqs; q++)
+        for (uint64_t i = hit_offsets[q]; i < hit_offsets[q + 1]; i++)
+            if (h_rec[i].best_found != h_cnt[i] || h_rec[i].best_found < need[q] || h_rec[i].windows_passing == 0)
+                return fail(BIGSI_ERR_STATE, "internal: the two window kernels disagree on hit %llu (sequence %u, colour %u): sliding maximum %u, located %u in %u passing windows, need %u",
+                            (unsigned long long)i, q, h_col[i], h_cnt[i], h_rec[i].best_found, h_rec[i].windows_passing, need[q]);
+    memcpy(colours, h_col.data(), total * 4);
+    memcpy(records, h_rec.data(), total * sizeof(WindowRecord));
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_batch_window_search(bigsi_hip_batch *b, uint32_t window, double threshold, uint32_t *window_used, uint32_t *need,
+                                             uint64_t *hit_offsets, uint32_t *colours, bigsi_hip_window_hit *records, uint64_t capacity)
+{
+    BIGSI_ENTER(b ? b->ix : nullptr);
+    TRY(need_run(b));
+    TRY(check_window_args(window, threshold, window_used, need, hit_offsets, colours, records, capacity));
+    if (b->elements) return fail(BIGSI_ERR_STATE, "a window search is not available for a batch of explicit k-mers");
+    return window_launch(b, window, threshold, window_used, need, hit_offsets, colours, records, capacity);
+}
+
+// The sequences are staged into a workspace of the index and run as an exact search, as bigsi_hip_kmer_prevalence does: the exact
+// row-AND is the cheapest run that leaves K1's arrays behind on every K1 route (a K1-only run is the follow-up: DESIGN.md).
+extern "C" int bigsi_hip_window_search(bigsi_hip_index *ix, const char *seqs, const uint64_t *offsets, uint32_t n_seqs, uint32_t k, uint32_t window,
+                                       double threshold, uint32_t *window_used, uint32_t *need, uint64_t *hit_offsets, uint32_t *colours,
+                                       bigsi_hip_window_hit *records, uint64_t capacity)
+{
+    BIGSI_ENTER(ix);
+    TRY(check_batch_args(ix, seqs, offsets, n_seqs, k));
+    TRY(check_window_args(window, threshold, window_used, need, hit_offsets, colours, records, capacity));
+    TRY(bigsi_batch_stage(ix, &ix->window_ws, seqs, offsets, n_seqs, k));
+    bigsi_hip_batch *b = ix->window_ws;
+    int rc = bigsi_batch_run(b, 1.0, 0, false);
+    if (rc == BIGSI_OK) rc = need_run(b);
+    if (rc == BIGSI_OK) rc = window_launch(b, window, threshold, window_used, need, hit_offsets, colours, records, capacity);
+    if (rc != BIGSI_OK && rc != BIGSI_ERR_CAPACITY && rc != BIGSI_ERR_INVALID) {
+        ix->window_ws = nullptr;
+        bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
+    }
+    return rc;
+}
+
+extern "C" int bigsi_hip_window_set_limits(bigsi_hip_index *ix, uint64_t starts_per_segment, uint64_t partial_bytes_cap)
+{
+    BIGSI_ENTER(ix);
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
+    if (starts_per_segment >= (1ull << 31)) return fail(BIGSI_ERR_INVALID, "starts_per_segment must be below 2^31 (got %llu)", (unsigned long long)starts_per_segment);
+    ix->window_starts = starts_per_segment;
+    ix->window_cap = partial_bytes_cap;
+    return BIGSI_OK;
 }
 
 // Query-set tally (include/bigsi_hip_tally.h; k_tally_hits + k_tally_totals, launch shape: plan_tally): per-sample sums over the

@@ -15,6 +15,7 @@
 #include "bigsi_hip_tally.h"
 #include "bigsi_hip_testing.h"
 #include "bigsi_hip_text.h"
+#include "bigsi_hip_window.h"
 
 #include <hip/hip_runtime.h>
 
@@ -102,6 +103,8 @@ struct bigsi_hip_index {
     struct bigsi_hip_batch *stream_ws[4] = {};        // bigsi_hip_search_stream's workspaces
     struct bigsi_hip_batch *prevalence_ws = nullptr;  // bigsi_hip_kmer_prevalence's workspace, created at its first call
     struct bigsi_hip_batch *tally_ws[2] = {};         // bigsi_hip_tally_add_stream's workspaces, created at its first call
+    struct bigsi_hip_batch *window_ws = nullptr;      // bigsi_hip_window_search's workspace, created at its first call
+    uint64_t window_starts = 0, window_cap = 0;       // bigsi_hip_window_set_limits: starts per segment, partial bytes cap (0: the planner's)
     uint64_t m = 0, n_cols = 0, cap_cols = 0, stride_words = 0;
     uint64_t alloc_rows = 0;      // rows the allocation behind d_index holds: m, or more after bigsi_hip_fold_rows (until bigsi_hip_trim_rows); never reported
     uint32_t h = 0;
@@ -236,6 +239,8 @@ struct bigsi_hip_batch {
     DevBuf exp_count;                                // the export kernel's finished-workgroups counter
     uint32_t exp_spec = 0;                           // hits the export carried along speculatively
     PresJob job;                                     // the K5 / K6 request in flight, its host vectors and pinned staging
+    DevBuf win_col, win_cnt, win_loc;                // windowed search: its own hit lists (the batch's stay) | word offsets, presence words, records
+    uint64_t win_cap = 0;                            // hits win_col / win_cnt can hold
     DevBuf pres_in, pres_bits, pres_out, pres_desc;   // K5 at scale (presence_hits): host-built pair lists, presence bits, strings, piece marks
     void *ext_bitmaps = nullptr;      // caller-owned bit vectors (bigsi_hip_batch_set_outputs: a shard's slot of a gather buffer)
     // the result vectors of a run: one bit per sample (the AND, or count >= min_kmers), and the counting path's counters

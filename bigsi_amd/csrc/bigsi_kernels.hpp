@@ -3128,6 +3128,341 @@ __global__ __launch_bounds__(kBlock) void k_kmer_prevalence_sum(
     if (out_sub) out_sub[p] = sub;
 }
 
+// ------------------------------------------------------------------------------ windowed search: the best window per sample
+// found(c, s) = number of positions p in [s, s + We) whose k-mer's h rows all have bit c; per column the maximum over the window
+// starts s (include/bigsi_hip_window.h).  K1 of any route has left rows[(pos_off[q] + u) * h .. +h) for the unique k-mers u of
+// sequence q and pos_unique[pos_off[q] + p] = the unique k-mer of position p: a position's A_p is the AND of the h rows of ITS
+// unique k-mer, so a repeated k-mer reuses a slot.
+// k_window_max (launch shape: plan_window_search, bigsi_launch.hpp): a wavefront owns one segment [a, b) of window starts of one
+// sequence and one tile of 64 x kVec column words; a lane owns kVec words, loaded 16 bytes at a time.  Per word it keeps two
+// bit-sliced counters of P planes (P >= bit_width(We)): `cur` = found(., s) of all 64 columns at once, `best` = the running maximum.
+//   warm-up  cur = sum of A_p over [a, a + We): k_and_count's ripple-carry add, 8 to 12 independent row loads in flight.
+//   step     s -> s + 1: A_enter of position s + We, A_leave of position s; in = A_enter & ~A_leave is added (ripple carry), out =
+//            A_leave & ~A_enter subtracted (ripple borrow).  No column has both, so cur never leaves [0, We].  A count grows only
+//            where `in` has a bit: the compare-and-select from the top plane down (gt |= eq & cur & ~best; eq &= ~(cur ^ best);
+//            best = gt ? cur : best) runs only when some lane of the wavefront has one (__ballot).  KM steps' 2 x KM x H loads are
+//            issued together (8 to 14 in flight), then applied in order.
+// Every plane array is indexed by compile-time constants in fully unrolled loops (registers, no scratch).  At the end the wavefront
+// stores its P planes of `best`, bit-sliced as they are, as 16-byte stores to partial[(seg * P + plane) * wvp + w0]: nobody else
+// writes that entry.  No atomics, no LDS, no scratch, and no workgroup waits for another.
+// Bounds: positions touched are a .. b - 2 + We <= n - 1 (b <= n - We + 1), each mapped through pos_unique to a slot u < num_unique[q]
+// <= n, so every slot index pos_off[q] + u is below total_pos and every row id below num_rows; the leaving position is s >= a.  A
+// loaded word pair starts at w0 < wv <= stride_words, w0 even and the stride a multiple of kVec words, so it ends inside the row;
+// words from wv to the stride are not loaded (the lane returns).  A stored pair ends at or before wvp = round_up(wv, kVec).
+template <int P, int H>
+__global__ __launch_bounds__(kBlock) void k_window_max(
+    const uint64_t *__restrict__ index, uint64_t stride_words, uint32_t wv, const uint64_t *__restrict__ rows,
+    const uint64_t *__restrict__ pos_off, const uint32_t *__restrict__ pos_unique, uint32_t h_rt, const WindowSeg *__restrict__ segs,
+    uint64_t n_segs, uint32_t tiles, uint64_t *__restrict__ partial, uint64_t wvp)
+{
+    constexpr int HH = H > 0 ? H : 1;
+    constexpr int KMW = H == 1 ? 8 : H <= 3 ? 4 : 2;          // warm-up positions per iteration
+    constexpr int KM = H == 1 ? 4 : H <= 3 ? 2 : 1;           // window steps per iteration (window_steps_per_iter)
+    const uint32_t h = H > 0 ? (uint32_t)H : h_rt;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wave >= n_segs * tiles) return;
+    const uint64_t seg = wave / tiles;
+    const uint32_t tile = (uint32_t)(wave - seg * tiles);
+    const uint32_t w0 = (tile * 64u + lane) * kVec;
+    if (w0 >= wv) return;
+    const uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)segs[seg].q);
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)segs[seg].a);
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)segs[seg].b);
+    const uint32_t we = (uint32_t)__builtin_amdgcn_readfirstlane((int)segs[seg].we);
+    const uint64_t p0 = pos_off[q];
+    const uint64_t *__restrict__ qrows = rows + p0 * h;
+    const uint32_t *__restrict__ pu = pos_unique + p0;
+
+    uint64_t cur[kVec][P], best[kVec][P];
+#pragma unroll
+    for (int e = 0; e < kVec; e++)
+#pragma unroll
+        for (int p = 0; p < P; p++) cur[e][p] = 0;
+
+    auto add = [&](const RowWords<kVec> &x) {
+        uint64_t c[kVec];
+#pragma unroll
+        for (int e = 0; e < kVec; e++) c[e] = x.word(e);
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+#pragma unroll
+            for (int e = 0; e < kVec; e++) {
+                const uint64_t t = cur[e][p] & c[e];
+                cur[e][p] ^= c[e];
+                c[e] = t;
+            }
+        }
+    };
+    auto step = [&](const RowWords<kVec> &enter, const RowWords<kVec> &leave) {
+        uint64_t in[kVec], c[kVec], bw[kVec];
+#pragma unroll
+        for (int e = 0; e < kVec; e++) {
+            in[e] = enter.word(e) & ~leave.word(e);
+            c[e] = in[e];
+            bw[e] = leave.word(e) & ~enter.word(e);
+        }
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+#pragma unroll
+            for (int e = 0; e < kVec; e++) {
+                const uint64_t t = cur[e][p] & c[e];
+                cur[e][p] ^= c[e];
+                c[e] = t;
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+#pragma unroll
+            for (int e = 0; e < kVec; e++) {
+                const uint64_t t = ~cur[e][p] & bw[e];
+                cur[e][p] ^= bw[e];
+                bw[e] = t;
+            }
+        }
+        uint64_t any = 0;
+#pragma unroll
+        for (int e = 0; e < kVec; e++) any |= in[e];
+        if (__ballot(any != 0) == 0ull) return;
+#pragma unroll
+        for (int e = 0; e < kVec; e++) {
+            uint64_t gt = 0, eq = ~0ull;
+#pragma unroll
+            for (int p = P - 1; p >= 0; p--) {
+                gt |= eq & cur[e][p] & ~best[e][p];
+                eq &= ~(cur[e][p] ^ best[e][p]);
+            }
+#pragma unroll
+            for (int p = 0; p < P; p++) best[e][p] = (cur[e][p] & gt) | (best[e][p] & ~gt);
+        }
+    };
+    // A_p of one position, its rows in groups of four loads (tails, and every position when h is a run-time value)
+    auto and_rows = [&](uint32_t p) {
+        const uint64_t *kr = qrows + (uint64_t)pu[p] * h;
+        RowWords<kVec> x = RowWords<kVec>::fill(~0ull);
+        uint32_t s = 0;
+        for (; s + 4 <= h; s += 4) {
+            RowWords<kVec> l0 = RowWords<kVec>::load(index, kr[s], stride_words, w0), l1 = RowWords<kVec>::load(index, kr[s + 1], stride_words, w0);
+            const RowWords<kVec> l2 = RowWords<kVec>::load(index, kr[s + 2], stride_words, w0), l3 = RowWords<kVec>::load(index, kr[s + 3], stride_words, w0);
+            l0 &= l2; l1 &= l3; l0 &= l1;
+            x &= l0;
+        }
+        for (; s < h; s++) x &= RowWords<kVec>::load(index, kr[s], stride_words, w0);
+        return x;
+    };
+
+    // warm-up: the window at start a
+    uint32_t p = a;
+    const uint32_t pe = a + we;
+    if (H > 0) {
+        for (; p + KMW <= pe; p += KMW) {
+            RowWords<kVec> v[KMW * HH];
+#pragma unroll
+            for (int g = 0; g < KMW; g++) {
+                const uint64_t *kr = qrows + (uint64_t)pu[p + g] * HH;
+#pragma unroll
+                for (int s = 0; s < HH; s++) v[g * HH + s] = RowWords<kVec>::load(index, kr[s], stride_words, w0);
+            }
+#pragma unroll
+            for (int g = 0; g < KMW; g++) {
+                RowWords<kVec> x = v[g * HH];
+#pragma unroll
+                for (int s = 1; s < HH; s++) x &= v[g * HH + s];
+                add(x);
+            }
+        }
+    }
+    for (; p < pe; p++) add(and_rows(p));
+#pragma unroll
+    for (int e = 0; e < kVec; e++)
+#pragma unroll
+        for (int pp = 0; pp < P; pp++) best[e][pp] = cur[e][pp];
+
+    // the steps a -> a + 1 -> ... -> b - 1
+    uint32_t s = a;
+    if (H > 0) {
+        for (; s + KM < b; s += KM) {
+            RowWords<kVec> ve[KM * HH], vl[KM * HH];
+#pragma unroll
+            for (int g = 0; g < KM; g++) {
+                const uint64_t *ke = qrows + (uint64_t)pu[s + g + we] * HH, *kl = qrows + (uint64_t)pu[s + g] * HH;
+#pragma unroll
+                for (int t = 0; t < HH; t++) {
+                    ve[g * HH + t] = RowWords<kVec>::load(index, ke[t], stride_words, w0);
+                    vl[g * HH + t] = RowWords<kVec>::load(index, kl[t], stride_words, w0);
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < KM; g++) {
+                RowWords<kVec> xe = ve[g * HH], xl = vl[g * HH];
+#pragma unroll
+                for (int t = 1; t < HH; t++) { xe &= ve[g * HH + t]; xl &= vl[g * HH + t]; }
+                step(xe, xl);
+            }
+        }
+    }
+    for (; s + 1 < b; s++) {
+        const RowWords<kVec> xe = and_rows(s + we), xl = and_rows(s);
+        step(xe, xl);
+    }
+
+    uint64_t *o = partial + seg * (uint64_t)P * wvp + w0;
+#pragma unroll
+    for (int pp = 0; pp < P; pp++) *reinterpret_cast<u64x2 *>(o + (uint64_t)pp * wvp) = u64x2{best[0][pp], best[kVec - 1][pp]};
+}
+
+// k_window_combine: a thread per (sequence, 64-column word): the per-column maximum over the sequence's segments (the same
+// compare-and-select over the stored planes), thresholded against need[q] into the hit bitmap K4 compacts -- columns >= num_cols
+// masked off, a sequence without segments (no k-mer position) all zero -- and, for words that hold a hit, expanded to uint16 counters
+// in the layout k_and_count leaves (out[q * out_stride + column]): k_hits_totals / k_hits_write then build the hit lists unchanged.
+template <int P>
+__global__ __launch_bounds__(kBlock) void k_window_combine(
+    const uint64_t *__restrict__ partial, uint64_t wvp, const uint64_t *__restrict__ seg_off, uint32_t n_seqs, uint32_t wv,
+    uint32_t blocks_per_seq, const uint32_t *__restrict__ need, uint64_t n_cols, uint64_t *__restrict__ hit_bitmap, uint64_t bm_stride,
+    uint16_t *__restrict__ out, uint64_t out_stride)
+{
+    const uint32_t q = blockIdx.x / blocks_per_seq, w = (blockIdx.x - q * blocks_per_seq) * kBlock + threadIdx.x;
+    if (q >= n_seqs || w >= wv) return;
+    const uint64_t s0 = seg_off[q], s1 = seg_off[q + 1];
+    uint64_t best[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) best[p] = 0;
+    for (uint64_t s = s0; s < s1; s++) {
+        uint64_t cur[P];
+#pragma unroll
+        for (int p = 0; p < P; p++) cur[p] = partial[(s * P + p) * wvp + w];
+        uint64_t gt = 0, eq = ~0ull;
+#pragma unroll
+        for (int p = P - 1; p >= 0; p--) {
+            gt |= eq & cur[p] & ~best[p];
+            eq &= ~(cur[p] ^ best[p]);
+        }
+#pragma unroll
+        for (int p = 0; p < P; p++) best[p] = (cur[p] & gt) | (best[p] & ~gt);
+    }
+    const uint32_t thr = need[q];
+    uint64_t gt = 0, eq = ~0ull;
+    if ((thr >> P) != 0) eq = 0;
+#pragma unroll
+    for (int p = P - 1; p >= 0; p--) {
+        if ((thr >> p) & 1u) eq &= best[p];
+        else { gt |= eq & best[p]; eq &= ~best[p]; }
+    }
+    const uint64_t ge = s0 < s1 ? (gt | eq) & valid_mask(w, n_cols) : 0ull;
+    hit_bitmap[(uint64_t)q * bm_stride + w] = ge;
+    if (ge == 0) return;
+    // column 8b + jj of the word sits at bit 8b + 7 - jj; 8 consecutive counters per store
+    uint16_t *o = out + (uint64_t)q * out_stride + (uint64_t)w * 64;
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        uint32_t c[8];
+#pragma unroll
+        for (int jj = 0; jj < 8; jj++) {
+            const int bit = 8 * b + 7 - jj;
+            uint32_t x = 0;
+#pragma unroll
+            for (int p = 0; p < P; p++) x |= (uint32_t)((best[p] >> bit) & 1ull) << p;
+            c[jj] = x;
+        }
+        *reinterpret_cast<uint4 *>(o + 8 * b) = uint4{c[0] | (c[1] << 16), c[2] | (c[3] << 16), c[4] | (c[5] << 16), c[6] | (c[7] << 16)};
+    }
+}
+
+// The second, independent route to a hit's record: its presence bits by position, then a walk over the window starts.
+// k_window_bits: a wavefront per (hit, 64 positions): lane l tests position 64 blk + l of the hit's sequence -- bit c of the AND of
+// the h words of the position's unique k-mer, 8-byte loads as k_presence makes them -- and the ballot is the word bits[g] (bit l =
+// position 64 blk + l, zero behind the last position).  The words of the hits of sequence q start at word_off[q]; hit i of q (i from
+// hit_off[q]) owns ceil(n / 64) of them.  Bounds: g < word_off[n_seqs] = the size of `bits`; positions p < n only.
+__global__ __launch_bounds__(kBlock) void k_window_bits(
+    const uint64_t *__restrict__ index, uint64_t stride_words, const uint64_t *__restrict__ rows, const uint64_t *__restrict__ pos_off,
+    const uint32_t *__restrict__ pos_unique, const uint32_t *__restrict__ num_kmers, uint32_t h, uint32_t n_seqs,
+    const uint64_t *__restrict__ word_off, const uint64_t *__restrict__ hit_off, const uint32_t *__restrict__ hit_col,
+    uint64_t *__restrict__ bits)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t g = (uint64_t)blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (g >= word_off[n_seqs]) return;
+    const uint32_t q = prevalence_owner(word_off, n_seqs, g);
+    const uint32_t n = num_kmers[q], words = (n + 63u) / 64u;
+    const uint64_t r = g - word_off[q];
+    const uint64_t hit = hit_off[q] + r / words;
+    const uint32_t blk = (uint32_t)(r % words);
+    const uint32_t c = hit_col[hit], p = blk * 64u + lane;
+    bool present = false;
+    if (p < n) {
+        const uint64_t p0 = pos_off[q];
+        const uint64_t *kr = rows + (p0 + pos_unique[p0 + p]) * h;
+        uint64_t x = ~0ull;
+        for (uint32_t s = 0; s < h; s++) x &= index[kr[s] * stride_words + (c >> 6)];
+        present = ((x >> bit_of_col(c & 63u)) & 1ull) != 0;
+    }
+    const uint64_t word = __ballot(present);
+    if (lane == 0) bits[g] = word;
+}
+
+struct WindowRecord {          // bigsi_hip_window_hit (include/bigsi_hip_window.h)
+    uint32_t best_found, best_start, first_start, last_start, windows_passing, reserved;
+};
+
+// k_window_locate: a wavefront per hit over the hit's presence words.  Lane l takes the window starts [l C, (l + 1) C) of the
+// sequence's n - We + 1, C = ceil(starts / 64) rounded up to a multiple of 64 (so that all lanes cross a word boundary in the same step): the first window's count from word popcounts, every further one from the running
+// difference found += bit(s + We - 1) - bit(s - 1); it keeps the best count and its lowest start, the first and last start that
+// reach need[q] and their number, and the wavefront reduces them over its lanes (shuffles; no LDS).  Its best_found shares no
+// arithmetic with k_window_max's: the library compares the two on the host.
+__global__ __launch_bounds__(kBlock) void k_window_locate(
+    const uint64_t *__restrict__ bits, const uint64_t *__restrict__ word_off, const uint64_t *__restrict__ hit_off, uint32_t n_seqs,
+    const uint32_t *__restrict__ num_kmers, const uint32_t *__restrict__ need, uint32_t window, WindowRecord *__restrict__ records)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t hit = (uint64_t)blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (hit >= hit_off[n_seqs]) return;
+    const uint32_t q = prevalence_owner(hit_off, n_seqs, hit);
+    const uint32_t n = num_kmers[q], words = (n + 63u) / 64u, we = n < window ? n : window, thr = need[q];
+    const uint64_t *__restrict__ B = bits + word_off[q] + (hit - hit_off[q]) * words;
+    const uint32_t starts = n - we + 1u, per = ((starts + 63u) / 64u + 63u) & ~63u;          // a multiple of 64: every lane reloads its words in the same step
+    const uint32_t lo = lane * per < starts ? lane * per : starts, hi = lo + per < starts ? lo + per : starts;
+    uint32_t best = 0, best_s = 0xFFFFFFFFu, first = 0xFFFFFFFFu, last = 0, count = 0;
+    if (lo < hi) {
+        // found(lo): the bits [lo, lo + we) -- whole words, the two ends masked
+        uint32_t found = 0;
+        const uint32_t e = lo + we;                             // (exclusive; e <= n)
+        for (uint32_t w = lo >> 6; w <= (e - 1u) >> 6; w++) {
+            uint64_t x = B[w];
+            if (w == lo >> 6) x &= ~0ull << (lo & 63u);
+            if (w == (e - 1u) >> 6 && (e & 63u)) x &= ~0ull >> (64u - (e & 63u));
+            found += (uint32_t)__popcll(x);
+        }
+        best = found;
+        best_s = lo;
+        if (found >= thr) { first = lo; last = lo; count = 1; }
+        uint64_t win = 0, wout = 0;                             // the words of the entering and the leaving bit: one load per 64 steps
+        for (uint32_t s = lo + 1u; s < hi; s++) {
+            const uint32_t in = s + we - 1u, out = s - 1u;      // (in <= n - 1: s <= starts - 1)
+            if ((in & 63u) == 0 || s == lo + 1u) win = B[in >> 6];
+            if ((out & 63u) == 0 || s == lo + 1u) wout = B[out >> 6];
+            found += (uint32_t)((win >> (in & 63u)) & 1ull);
+            found -= (uint32_t)((wout >> (out & 63u)) & 1ull);
+            if (found > best) { best = found; best_s = s; }
+            if (found >= thr) {
+                if (first == 0xFFFFFFFFu) first = s;
+                last = s;
+                count++;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t ob = (uint32_t)__shfl_xor((int)best, d, 64), os = (uint32_t)__shfl_xor((int)best_s, d, 64);
+        const uint32_t of = (uint32_t)__shfl_xor((int)first, d, 64), ol = (uint32_t)__shfl_xor((int)last, d, 64);
+        const uint32_t oc = (uint32_t)__shfl_xor((int)count, d, 64);
+        if (ob > best || (ob == best && os < best_s)) { best = ob; best_s = os; }
+        first = of < first ? of : first;
+        last = ol > last ? ol : last;
+        count += oc;
+    }
+    if (lane == 0) records[hit] = WindowRecord{best, best_s, first, last, count, 0u};
+}
+
 // transpose (bigsi/matrix/transpose.py:33-43) on the device: n Bloom filters (bloom c at blooms + c*bloom_stride, m bits,
 // row byte format) become columns [col0, col0+n) of the matrix.  One thread per (row, 64-column word); the 8 threads of
 // 8 consecutive rows read the same Bloom byte (one L1 line per wave), the word is read-modified-written once.

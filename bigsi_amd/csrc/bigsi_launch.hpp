@@ -6,7 +6,8 @@
 // scratch and per-call tables of the pairwise popcounts (plan_pairwise, pairwise_tables) and the launch shape and stream cuts of the query-set
 // tally (plan_tally, plan_tally_chunks; pinned by tests/c_host/tally_host.cpp and tests/test_tally_host.py) and what the exact k-mer
 // counter decides about a call and its table (plan_kmer_count_add, kmer_stage_chunk, plan_kmer_table; pinned by
-// tests/c_host/kmercount_plan_host.cpp and tests/test_kmercount_plan_host.py).  Pure functions of a handful of integers
+// tests/c_host/kmercount_plan_host.cpp and tests/test_kmercount_plan_host.py) and the segments, plane bucket, grid and refusals of the
+// windowed search's sweep (plan_window_search; pinned by tests/c_host/window_host.cpp and tests/test_window_host.py).  Pure functions of a handful of integers
 // (and, for the compaction, the collapses and the pairwise popcounts, of the keep bitmap / the group map / the column lists): no HIP,
 // no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp,
 // prevalence_host.cpp, collapse_host.cpp, consensus_host.cpp and pairwise_host.cpp compile this header as plain host C++ and
@@ -883,6 +884,89 @@ static inline std::vector<uint64_t> plan_tally_chunks(const uint64_t *offsets, u
     std::vector<uint64_t> cut(1, 0);
     while (cut.back() < n_seqs) cut.push_back(tally_chunk_end(offsets, n_seqs, cut.back(), k, wv_pad, count_bytes));
     return cut;
+}
+
+// ------------------------------------------------------------------------------ windowed search (k_window_max, k_window_combine)
+// plan_window_search: sequence q of a batch has n[q] k-mer positions, a window of We = min(W, n[q]) of them and the window starts
+// [0, n[q] - We]; the sweep cuts every sequence's starts into segments of at most S and a wavefront of k_window_max owns one
+// (segment, tile of 64 x kVec column words).  A segment [a, b) costs We positions of warm-up plus 2 (b - a - 1) positions of steps.
+//   - S: 4 x the largest We (at least 64) -- the warm-up is then a ninth of the traffic -- and shorter only while that leaves fewer
+//     than kWindowWaves wavefronts, never below the largest We (at least 64: there the warm-up is a third).  kWindowWaves is INHERITED
+//     from the column popcounts' sweep (kColPopWaves), not measured for this kernel.  `forced_starts` > 0 (bigsi_hip_window_set_limits)
+//     is taken as it is.
+//   - planes: the counters of a segment are `planes` bit planes, planes >= bit_width(largest We), in the buckets the kernel is
+//     instantiated for (4, 8, 12, 16).
+//   - partial: every (segment, plane) leaves wvp = round_up(wv, kVec) words: partial_bytes = n_segs x planes x wvp x 8, exactly.
+//   - refusals: a grid above 2^31 - 1 workgroups (grid_too_large), partial_bytes above the cap (partial_too_large; cap 0 = 2 GiB, the
+//     bound of the tally's dense counters).  The caller reports them with the numbers.
+//   - steps_per_iter: window steps whose 2 h row loads a lane issues together: 4 / 2 / 1 for h = 1 / 2-3 / more -- 8 to 14 independent
+//     16-byte loads in flight, as k_and_count keeps (h >= 8, the generic instantiation: one step, its rows one after the other).
+constexpr uint64_t kWindowWaves = kColPopWaves;
+constexpr uint64_t kWindowPartialBytes = 2ull << 30;
+constexpr uint32_t kWindowMax = 65535;                       // BIGSI_WINDOW_MAX (include/bigsi_hip_window.h)
+constexpr uint64_t kWindowMinSegment = 64;
+struct WindowSeg {
+    uint32_t q, a, b, we;      // window starts [a, b) of sequence q, whose window is `we` positions
+};
+struct WindowPlan {
+    uint32_t max_we = 0;             // the largest window of the batch (0: no sequence has a position)
+    uint32_t planes = 4;
+    uint64_t seg_starts = 0;         // S
+    uint32_t tiles = 1;              // wavefronts per segment: 64 x kVec words each
+    uint64_t n_segs = 0, waves = 0, grid = 0;
+    uint64_t wvp = 0;                // words per plane of a segment's entry
+    uint64_t partial_bytes = 0;
+    uint32_t steps_per_iter = 1;
+    bool grid_too_large = false, partial_too_large = false;
+    std::vector<WindowSeg> segs;
+    std::vector<uint64_t> seg_off;   // n_seqs + 1: sequence q owns segs[seg_off[q], seg_off[q + 1])
+};
+static inline uint32_t window_bit_width(uint32_t x)
+{
+    uint32_t w = 0;
+    while (x) { w++; x >>= 1; }
+    return w;
+}
+static inline uint32_t window_plane_bucket(uint32_t we) { return std::max<uint32_t>((uint32_t)round_up(window_bit_width(we), 4), 4); }
+static inline uint32_t window_steps_per_iter(uint32_t h) { return h <= 1 ? 4u : h <= 3 ? 2u : 1u; }
+static inline WindowPlan plan_window_search(const uint32_t *n, uint32_t n_seqs, uint32_t window, uint64_t wv, uint32_t h,
+                                            uint64_t forced_starts = 0, uint64_t partial_cap = 0)
+{
+    WindowPlan p;
+    uint64_t starts = 0;
+    for (uint32_t q = 0; q < n_seqs; q++) {
+        const uint32_t we = std::min(n[q], window);
+        if (!we) continue;
+        p.max_we = std::max(p.max_we, we);
+        starts += n[q] - we + 1;
+    }
+    p.planes = window_plane_bucket(p.max_we);
+    p.tiles = (uint32_t)std::max<uint64_t>(ceil_div(wv, 64 * kVec), 1);
+    p.wvp = round_up(wv, kVec);
+    p.steps_per_iter = window_steps_per_iter(h);
+    p.seg_off.assign((size_t)n_seqs + 1, 0);
+    if (!p.max_we) return p;
+    const uint64_t floor_s = std::max<uint64_t>(p.max_we, kWindowMinSegment), top_s = std::max<uint64_t>(4ull * p.max_we, kWindowMinSegment);
+    if (forced_starts) p.seg_starts = forced_starts;
+    else {
+        const uint64_t want_segs = std::max<uint64_t>(ceil_div(kWindowWaves, p.tiles), 1);
+        p.seg_starts = std::min(std::max(ceil_div(starts, want_segs), floor_s), top_s);
+    }
+    for (uint32_t q = 0; q < n_seqs; q++) {
+        p.seg_off[q] = p.segs.size();
+        const uint32_t we = std::min(n[q], window);
+        if (!we) continue;
+        const uint64_t nst = (uint64_t)n[q] - we + 1;
+        for (uint64_t a = 0; a < nst; a += p.seg_starts) p.segs.push_back(WindowSeg{q, (uint32_t)a, (uint32_t)std::min(a + p.seg_starts, nst), we});
+    }
+    p.seg_off[n_seqs] = p.segs.size();
+    p.n_segs = p.segs.size();
+    p.waves = p.n_segs * p.tiles;
+    p.grid = ceil_div(p.waves, kBlock / 64);
+    p.partial_bytes = p.n_segs * p.planes * p.wvp * 8;
+    p.grid_too_large = p.grid > 0x7FFFFFFFull;
+    p.partial_too_large = p.partial_bytes > (partial_cap ? partial_cap : kWindowPartialBytes);
+    return p;
 }
 
 // ------------------------------------------------------------------------------ exact k-mer counter (k_count_kmers, k_kmer_table_*)

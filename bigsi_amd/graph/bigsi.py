@@ -822,6 +822,46 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         """kmer_prevalence_many for one sequence: its dict."""
         return self.kmer_prevalence_many([seq], samples)[0]
 
+    # ------------------------------------------------------------------ windowed search
+    def search_windows_many(self, seqs, window, threshold=1.0):
+        """The local question a search cannot ask: which samples hold at least `threshold` of SOME stretch of `window` consecutive k-mer
+        positions of the query, and where on the query.  One dict per sequence,
+            {"num_kmers": n, "window": We = min(window, n), "min_found": ceil(We * threshold), "results": [...]}
+        and per reported sample {"sample_name", "colour", "best_found", "percent_found", "best_start", "match_start", "match_end",
+        "windows_passing"}: the best window's count (by POSITION: a repeated k-mer counts at each of its positions) and its lowest start,
+        the bases [match_start, match_end) of the query that the passing windows span (0-based) and how many windows pass.  Results by
+        best_found descending, ties to the lowest colour; deleted samples dropped.  ONE device call for all sequences
+        (bigsi_hip_window_search); records are bigsi_amd/window.py's.  A sequence shorter than k has no window and no result.
+        ValueError for a window outside 1 .. 65535, a threshold outside (0, 1] and sequences with non-ASCII characters; multi-GPU
+        (devices=[...]) indexes are refused."""
+        from ..window import assemble, check_args
+        if isinstance(seqs, (str, bytes)):
+            raise TypeError("seqs must be a list of sequences, got %r" % type(seqs))
+        seqs = list(seqs)
+        self._refuse_group("a window search")
+        window, threshold = check_args(window, threshold)
+        for s in seqs:
+            if not s.isascii():
+                raise ValueError("a window search takes ASCII sequences (queries with other characters are out of scope)")
+        if not seqs:
+            return []
+        k = int(self.kmer_size)
+        with self._device_lock():
+            used, need, off, colours, records = self.storage.window_search(seqs, k, window, threshold)
+            excluded = self._excluded_colours()
+        n = self.num_samples
+
+        def name_of(c):          # (a column the metadata has no record of is reported by its colour alone)
+            try:
+                return self.colour_to_sample(c) if c < n else None
+            except KeyError:
+                return None
+        return assemble(seqs, k, window, threshold, used, need, off, colours, records, name_of, excluded)
+
+    def search_windows(self, seq, window, threshold=1.0):
+        """search_windows_many for one sequence: its dict."""
+        return self.search_windows_many([seq], window, threshold)[0]
+
     # ------------------------------------------------------------------ query-set tally
     def tally(self, seqs, threshold=1.0, limit=None, batch_kmers=1 << 19):
         """The question a read set poses: of these sequences, which samples do they hit, how many sequences each, and how many

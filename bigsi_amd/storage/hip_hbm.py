@@ -636,6 +636,33 @@ class HipHbmStorage(BaseStorage):
                                                    None if in_sub is None else _lib.ptr(in_sub), cap))
         return pos, total[:cap], None if in_sub is None else in_sub[:cap]
 
+    def window_search(self, seqs, k, window, threshold=1.0):
+        """Per sequence the samples that hold some window of `window` k-mer positions at `threshold`, with the best window and the
+        extent of the passing ones (bigsi_hip_window_search: ONE device call; include/bigsi_hip_window.h).  Returns (window_used
+        np.uint32[n], need np.uint32[n], hit_offsets np.uint64[n + 1], colours np.uint32[hits], records: a structured array of
+        bigsi_amd.window.RECORD_DTYPE[hits])."""
+        from ..window import RECORD_DTYPE, check_args
+        self._single_gpu("a window search")
+        window, threshold = check_args(window, threshold)
+        res = self._opened()
+        seqs = list(seqs)
+        n = len(seqs)
+        used, need, off = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(n + 1, np.uint64)
+        if not seqs:
+            return used[:0], need[:0], off, np.zeros(0, np.uint32), np.zeros(0, RECORD_DTYPE)
+        blob, soff = _lib.pack_seqs(seqs)
+        cap = 1 << 12
+        while True:          # bigsi_hip_batch_fetch_hits' protocol: a refused call leaves the number of hits in hit_offsets
+            colours, records = np.zeros(cap, np.uint32), np.zeros(cap, RECORD_DTYPE)
+            rc = _lib.lib().bigsi_hip_window_search(self.handle, blob, _lib.ptr(soff), n, int(k), window, threshold, _lib.ptr(used), _lib.ptr(need),
+                                                    _lib.ptr(off), _lib.ptr(colours), _lib.ptr(records), cap)
+            if rc == _lib.ERR_CAPACITY and int(off[n]) > cap:
+                cap = int(off[n])
+                continue
+            check(rc)
+            total = int(off[n])
+            return used, need, off, colours[:total], records[:total]
+
     def new_tally(self):
         """A Tally over this index: zeroed per-sample sums on the device (bigsi_hip_tally_create)."""
         self._single_gpu("a query-set tally")

@@ -85,6 +85,12 @@ int bigsi_hip_probe_rows(bigsi_hip_index *ix, uint32_t rows_per_query, uint32_t 
 struct bigsi_hip_kmer_counter;
 int bigsi_hip_kmer_counter_set_limits(struct bigsi_hip_kmer_counter *c, uint64_t chunk_bytes, uint64_t initial_slots);
 
+/* WINDOWED SEARCH (include/bigsi_hip_window.h): window starts per segment of later sweeps of this index (0: the planner's own
+ * choice) and the cap, in bytes, on the per-segment maxima a sweep may leave (0: the library's 2 GiB).  With 64 starts per segment
+ * a test reaches segment boundaries with a few hundred positions, and with a small cap the refusal; results do not depend on the
+ * first.  BIGSI_ERR_INVALID for a NULL index or starts_per_segment >= 2^31. */
+int bigsi_hip_window_set_limits(bigsi_hip_index *ix, uint64_t starts_per_segment, uint64_t partial_bytes_cap);
+
 #ifdef __cplusplus
 }
 #endif

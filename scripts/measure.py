@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] [window] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -847,6 +847,66 @@ def tally():
     reads = rand_seqs(rng, 65536, 61)
     for thr in (1.0, 0.4):
         line("tally_c2_reads", st, 10_000, reads, thr, "65 536 reads of 61 bp: the search stream takes the one-launch read kernel, the tally the non-fused route")
+    st.delete_all()
+
+
+def window():
+    """Windowed search (bigsi_hip_window_search): one 100 kbp query, W = 1000, t = 0.9 on the C3 index (10 M x 100 k, h = 4); a 1.5 kbp
+    stretch of the query is planted in eight samples so that the call has hits to locate.  Per call: the wall clock, the window kernels by
+    the library's HIP events on the index stream (k_window_max + k_window_combine + K4 + k_window_bits + k_window_locate: presence_ms of
+    bigsi_hip_stats; the split per kernel is this command under `rocprofv3 --kernel-trace --stats`) and the exact run in front of them.
+    Algorithmic bytes of the sweep: 2 h rows per window start plus We h rows of warm-up per segment, times the row bytes.  Beside it, in
+    the same session and alternating with it: the row-AND kernel's rate on the same query (an exact batch run) and the only route to the
+    same answer without the feature -- the windows as separate queries through bigsi_hip_search_stream at the same threshold (the
+    counting path), every BIGSI_WINDOW_EVERY-th start (default 64) timed and scaled to all of them, labelled as a scaling.
+    BIGSI_WINDOW_SHAPE="MxNxHxQLENxW" replaces the shape."""
+    L, C = _lib.lib(), _lib.C
+    m, n, h, qlen, w = 10_000_000, 100_000, 4, 100_000, 1000
+    if os.environ.get("BIGSI_WINDOW_SHAPE"):
+        m, n, h, qlen, w = (int(x) for x in os.environ["BIGSI_WINDOW_SHAPE"].split("x"))
+    every, t, k = int(os.environ.get("BIGSI_WINDOW_EVERY", "64")), 0.9, 31
+    st, fill = open_index("window", m, n, h)
+    wv = -(-n // 64)
+    rng = np.random.default_rng(23)
+    query = rand_seqs(rng, 1, qlen)[0]
+    for c in range(8):
+        st.insert_kmers(1000 + 12_000 * c, [query[qlen // 5:qlen // 5 + 1500]], k)
+    npos = qlen - k + 1
+    starts = npos - w + 1
+    tiles = -(-wv // 128)
+    seg = min(max(-(-starts // max(-(-4096 // tiles), 1)), max(w, 64)), max(4 * w, 64))          # plan_window_search
+    n_segs = -(-starts // seg)
+    ab = (2 * h * (starts - n_segs) + w * h * n_segs) * wv * 8
+    unique = len({query[i:i + k] for i in range(npos)})
+    ab_and = unique * h * wv * 8
+    batch = st.new_batch([query], k)
+    subs = [query[s:s + w + k - 1] for s in range(0, starts, every)]
+    st.window_search([query], k, w, t)                  # warm: the workspace's allocations
+    batch.run(1.0)
+    st.search_many(subs[:8], k, t)
+    for rep in range(3):                                # the three legs alternate in one session
+        check(L.bigsi_hip_set_profiling(st.handle, 1))
+        stats(st)
+        t0 = time.perf_counter()
+        used, need, off, cols, recs = st.window_search([query], k, w, t)
+        call = (time.perf_counter() - t0) * 1e3
+        s_ = stats(st)
+        batch.run(1.0)
+        check(L.bigsi_hip_synchronize(st.handle))
+        sa = stats(st)
+        check(L.bigsi_hip_set_profiling(st.handle, 0))
+        t0 = time.perf_counter()
+        _, _, hoff, hcol, _ = st.search_many(subs, k, t)
+        sub_ms = (time.perf_counter() - t0) * 1e3
+        win_ms = s_.presence_ms
+        emit("window_search", rep=rep, m=m, cols=n, h=h, query_bp=qlen, window=w, threshold=t, positions=npos, starts=starts, segment_starts=seg,
+             segments=n_segs, hits=int(off[-1]), best_found_max=int(recs["best_found"].max()) if len(recs) else 0, call_ms=call,
+             window_kernels_ms=win_ms, exact_run_ms=s_.and_ms + s_.kmerize_ms + s_.compact_ms, alg_bytes=ab,
+             window_kernels_GBps=ab / win_ms / 1e6 if win_ms else None, row_and_ms=sa.and_ms, row_and_alg_bytes=ab_and,
+             row_and_GBps=ab_and / sa.and_ms / 1e6 if sa.and_ms else None, windows_as_queries=len(subs), windows_as_queries_ms=sub_ms,
+             windows_as_queries_hits=int(hoff[-1]), all_windows_scaled_ms=sub_ms * starts / len(subs), scaled_over_call=sub_ms * starts / len(subs) / call,
+             note="fill %.2f s; every %d-th window start timed through search_stream and SCALED to all %d starts" % (fill, every, starts))
+    batch.close()
     st.delete_all()
 
 

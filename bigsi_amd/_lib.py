@@ -22,6 +22,7 @@ RUN_NO_SORT = 16
 RUN_EARLY_EXIT = 32
 RUN_WEAK_FINGERPRINT = 64
 RUN_ONE_STREAM = 256
+RUN_BAND_SWEEP = 512
 BLOOM_RAW = 1
 SCORE_ORDERED = 1
 
@@ -182,6 +183,7 @@ SIGNATURES = {
     "bigsi_hip_free_text": (None, [_P]),
     "bigsi_hip_kmer_counter_set_limits": (_i32, [_P, _u64, _u64]),          # (include/bigsi_hip_testing.h)
     "bigsi_hip_window_set_limits": (_i32, [_P, _u64, _u64]),                # (include/bigsi_hip_testing.h)
+    "bigsi_hip_band_set_limits": (_i32, [_P, _u32, _u32]),                  # (include/bigsi_hip_testing.h)
 }
 
 # every symbol include/bigsi_hip_compact.h declares (column compaction: the maintenance layer)

@@ -1889,7 +1889,7 @@ static bool reads_fusable(const bigsi_hip_batch *b, uint32_t flags)
     const bool exact = b->exact;
     return b->k == 31 && b->total_pos > 0 && b->max_pos <= 63 && b->n_seqs <= kReadsMaxSeqs && b->wv <= (uint64_t)kBlock * kVec &&
            ix->h >= 2 && ix->h <= 4 && !b->ext_bitmaps && b->result_cols == 0 && b->limit == 0 &&
-           !(flags & (BIGSI_RUN_SKIP_COMPACT | BIGSI_RUN_K1_GLOBAL | BIGSI_RUN_EARLY_EXIT | BIGSI_RUN_NO_SORT)) &&
+           !(flags & (BIGSI_RUN_SKIP_COMPACT | BIGSI_RUN_K1_GLOBAL | BIGSI_RUN_EARLY_EXIT | BIGSI_RUN_NO_SORT | BIGSI_RUN_BAND_SWEEP)) &&
            (exact || (flags & BIGSI_RUN_SPARSE_COUNTS));     // the fused kernel keeps counters in registers: hits only
 }
 
@@ -2000,6 +2000,19 @@ static int launch_reads_fused(bigsi_hip_batch *b, hipStream_t st = nullptr, bool
 
 // see bigsi_internal.hpp: the launch rule (bigsi_launch.hpp) for 256-thread workgroups
 uint32_t bigsi_exact_launch_queries(const bigsi_hip_index *ix) { return exact_launch_queries(ceil_div(ix->n_cols, 64)); }
+
+// the band sweep's plan for a run of n_seqs queries of at most max_pos positions on results of wv words (bigsi_batch_run; the stream
+// sizes its exact chunks by it)
+static BandSweepPlan band_plan(const bigsi_hip_index *ix, uint32_t n_seqs, uint64_t wv, uint64_t max_pos, bool exact, uint32_t flags)
+{
+    return plan_band_sweep(RowAndInput{n_seqs, wv, max_pos, ix->h, exact, (flags & BIGSI_RUN_NO_SORT) != 0, (flags & BIGSI_RUN_EARLY_EXIT) != 0,
+                                       (flags & BIGSI_RUN_SPARSE_COUNTS) != 0},
+                           ix->m, (flags & BIGSI_RUN_BAND_SWEEP) != 0, ix->band_windows, ix->band_segs);
+}
+bool bigsi_band_sweep_taken(const bigsi_hip_index *ix, uint32_t n_seqs, uint64_t max_pos, uint32_t flags)
+{
+    return !(flags & BIGSI_RUN_FORCE_COUNTS) && band_plan(ix, n_seqs, ceil_div(ix->n_cols, 64), max_pos, true, flags).taken;
+}
 
 static K1Plan k1_plan(const bigsi_hip_batch *b, bool force_global) { return k1_plan(b->n_seqs, b->max_pos, b->max_len, b->elements, force_global); }
 
@@ -2245,6 +2258,10 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     const K1Plan k1 = k1_plan(b, (flags & BIGSI_RUN_K1_GLOBAL) != 0);
     const RowAndPlan plan = plan_row_and(RowAndInput{b->n_seqs, b->wv, b->max_pos, ix->h, b->exact, (flags & BIGSI_RUN_NO_SORT) != 0,
                                                      (flags & BIGSI_RUN_EARLY_EXIT) != 0, (flags & BIGSI_RUN_SPARSE_COUNTS) != 0});
+    // a large exact batch whose queries share rows: one band of every query per launch instead (plan_band_sweep)
+    const BandSweepPlan band = band_plan(ix, b->n_seqs, b->wv, b->max_pos, b->exact, flags);
+    // (several windows: the bounds are cut at k_sort_rows' buckets, the same for every query; K1's own sort has a shift per query)
+    const bool band_sorts = band.taken && band.windows > 1;
     // the sliced launches combine into preset result words (all ones for the AND, zero counters): K1 sets them on its way
     Preset preset;
     if (plan.preset) {
@@ -2255,13 +2272,12 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     EventPair ep{};
     bool sorted_by_k1 = false;
     TRY(flush_upload(b, ix->stream, k1.route == K1_WAVE || k1.route == K1_LDS));
-    TRY(run_kmerize(b, threshold, k1, plan.want_sorted, &sorted_by_k1, &preset));
+    TRY(run_kmerize(b, threshold, k1, (plan.want_sorted || band.taken) && !band_sorts, &sorted_by_k1, &preset));
     b->dirty = true;        // until finish_run
     const uint64_t *k2_rows = sorted_by_k1 ? b->rows_sorted.as<uint64_t>() : b->rows.as<uint64_t>();
-    if (plan.want_sorted && !sorted_by_k1) {
+    const uint32_t shift = sort_shift(ix->m, kSortBuckets);
+    if ((plan.want_sorted || band.taken) && !sorted_by_k1) {
         TRY(b->rows_sorted.reserve(std::max<uint64_t>(b->total_pos, 1) * ix->h * 8));
-        uint32_t shift = 0;
-        while (((ix->m - 1) >> shift) >= (uint64_t)kSortBuckets) shift++;
         TRY(ev_begin(ix, &ep));
         // 1024 threads per query for long row lists (a 1 kbp query at h=4 has 3880 rows), 256 otherwise
         if (b->max_pos * ix->h >= 2048)
@@ -2281,7 +2297,14 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         uint64_t *out = (uint64_t *)b->bit_vectors();
         if (plan.preset && !preset.done) HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)b->n_seqs * b->wv_pad * 8, ix->stream));
         TRY(ev_begin(ix, &ep, nullptr, true));
-        for (uint32_t i = 0; i < plan.n_launches; i++) {
+        for (uint32_t i = 0; i < band.n_launches; i++) {
+            const BandLaunch l = band.launch(i);
+            const BandWindow w = band_window(ix->m, l.window, band.windows, shift);
+            hipLaunchKernelGGL((k_and_exact_band<kBandUnroll, false>), dim3((unsigned)l.grid), dim3(kBlock), 0, ix->stream, ix->d_index, ix->stride_words,
+                               (uint32_t)b->wv, ix->n_cols, k2_rows, b->d_pos_off.as<uint64_t>(), b->num_unique.as<uint32_t>(), ix->h, b->n_seqs, l.seg0,
+                               l.nseg, w.lo, w.hi, l.window == 0 ? 1u : 0u, l.window + 1 == band.windows ? 1u : 0u, out, b->wv_pad);
+        }
+        for (uint32_t i = 0; i < (band.taken ? 0u : plan.n_launches); i++) {
             const RowAndLaunch l = plan.launch(i);
             // (a sliced last launch of an unsliced batch: its words alone)
             if (l.needs_preset && !plan.preset)
@@ -2295,7 +2318,7 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
 #undef BIGSI_LAUNCH_EXACT
         }
         HIP_TRY(hipGetLastError());
-        TRY(ev_end(ix, &ep, ix->ev_and, nullptr, plan.n_launches));
+        TRY(ev_end(ix, &ep, ix->ev_and, nullptr, band.taken ? band.n_launches : plan.n_launches));
     } else {
         b->count_bytes = plan.count_bytes;
         const uint64_t cstride = b->wv_pad * 64;
@@ -3114,6 +3137,17 @@ extern "C" int bigsi_hip_window_set_limits(bigsi_hip_index *ix, uint64_t starts_
     if (starts_per_segment >= (1ull << 31)) return fail(BIGSI_ERR_INVALID, "starts_per_segment must be below 2^31 (got %llu)", (unsigned long long)starts_per_segment);
     ix->window_starts = starts_per_segment;
     ix->window_cap = partial_bytes_cap;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_band_set_limits(bigsi_hip_index *ix, uint32_t windows, uint32_t segments_per_launch)
+{
+    BIGSI_ENTER(ix);
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
+    if (windows > kBandMaxWindows || segments_per_launch > 2)
+        return fail(BIGSI_ERR_INVALID, "at most %u windows and 2 segments per launch (got %u, %u)", kBandMaxWindows, windows, segments_per_launch);
+    ix->band_windows = windows;
+    ix->band_segs = segments_per_launch;
     return BIGSI_OK;
 }
 

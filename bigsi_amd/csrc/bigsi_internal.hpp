@@ -105,6 +105,7 @@ struct bigsi_hip_index {
     struct bigsi_hip_batch *tally_ws[2] = {};         // bigsi_hip_tally_add_stream's workspaces, created at its first call
     struct bigsi_hip_batch *window_ws = nullptr;      // bigsi_hip_window_search's workspace, created at its first call
     uint64_t window_starts = 0, window_cap = 0;       // bigsi_hip_window_set_limits: starts per segment, partial bytes cap (0: the planner's)
+    uint32_t band_windows = 0, band_segs = 0;         // bigsi_hip_band_set_limits: windows per band, segments per launch (0: the planner's)
     uint64_t m = 0, n_cols = 0, cap_cols = 0, stride_words = 0;
     uint64_t alloc_rows = 0;      // rows the allocation behind d_index holds: m, or more after bigsi_hip_fold_rows (until bigsi_hip_trim_rows); never reported
     uint32_t h = 0;
@@ -296,6 +297,7 @@ int bigsi_batch_export(bigsi_hip_batch *b);
 // queries a row-AND launch of a large exact batch takes on this index (bigsi_batch_run's launch rule: a whole number of workgroups per
 // CU, ~1600 live wavefronts): bigsi_hip_search_stream cuts its device batches at multiples of it, so that none ends in a part launch
 uint32_t bigsi_exact_launch_queries(const bigsi_hip_index *ix);
+bool bigsi_band_sweep_taken(const bigsi_hip_index *ix, uint32_t n_seqs, uint64_t max_pos, uint32_t flags);
 int bigsi_batch_collect(bigsi_hip_batch *b, uint32_t *num_kmers, uint32_t *num_unique, uint32_t *min_kmers, uint64_t *hit_offsets,
                         uint32_t *colours, uint32_t *counts, uint64_t capacity);
 int bigsi_use_device(const bigsi_hip_index *ix);

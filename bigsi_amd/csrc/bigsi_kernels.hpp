@@ -868,6 +868,62 @@ __global__ __launch_bounds__(1024) void k_and_exact(
     }
 }
 
+// The same AND as a band sweep (plan_band_sweep, bigsi_launch.hpp): a launch is the 1 KiB column segments [seg0, seg0 + nseg) of EVERY
+// query of the batch and the rows [r_lo, r_hi) of their address-ordered lists -- one wavefront per (query, segment), which finds its
+// part of the list by binary search (the wavefront's number goes through readfirstlane: the search and the row ids are scalar loads)
+// and streams it UNROLL rows at a time.  The first window of a band starts from all ones, a later one from the words the window
+// before it left in `out`: each word has one owner and the launches are stream-ordered, so plain load and store are enough.  The last
+// window applies valid_mask and the "no k-mers -> all zero" rule.  Plain loads (NT = false) are what lets a row that several queries
+// hold be served from cache the second time; non-temporal ones measured no gain from the repeats (profiles/band_sweep_probe.txt).
+template <int UNROLL, bool NT>
+__global__ __launch_bounds__(kBlock) void k_and_exact_band(
+    const uint64_t *__restrict__ index, uint64_t stride_words, uint32_t wv, uint64_t n_cols,
+    const uint64_t *__restrict__ rows, const uint64_t *__restrict__ pos_off, const uint32_t *__restrict__ num_unique,
+    uint32_t h, uint32_t n_seqs, uint32_t seg0, uint32_t nseg, uint64_t r_lo, uint64_t r_hi, uint32_t first, uint32_t last,
+    uint64_t *__restrict__ out, uint64_t out_stride_words)
+{
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6))), lane = threadIdx.x & 63u;
+    const uint32_t q = wave / nseg;
+    if (q >= n_seqs) return;
+    const uint32_t w0 = ((seg0 + wave % nseg) * 64u + lane) * kVec;
+    if (w0 >= wv) return;
+    const uint64_t Rall = (uint64_t)num_unique[q] * h;
+    const uint64_t *qrows = rows + pos_off[q] * h;
+    uint64_t r = 0, R = Rall;
+    for (uint64_t hi = Rall; r < hi;) {          // first row id >= r_lo
+        const uint64_t mid = r + ((hi - r) >> 1);
+        if (qrows[mid] < r_lo) r = mid + 1;
+        else hi = mid;
+    }
+    for (uint64_t lo = r; lo < R;) {             // first row id >= r_hi
+        const uint64_t mid = lo + ((R - lo) >> 1);
+        if (qrows[mid] < r_hi) lo = mid + 1;
+        else R = mid;
+    }
+    uint64_t *o = out + (uint64_t)q * out_stride_words + w0;
+    const bool two = w0 + 1 < out_stride_words;
+    u64x2 acc = {~0ull, ~0ull};
+    if (!first) {
+        acc.x = o[0];
+        if (two) acc.y = o[1];
+    }
+    for (; r + UNROLL <= R; r += UNROLL) {
+        u64x2 v[UNROLL];
+#pragma unroll
+        for (int j = 0; j < UNROLL; j++) v[j] = load_row_seg<NT>(index, qrows[r + j], stride_words, w0);
+#pragma unroll
+        for (int j = 0; j < UNROLL; j++) acc &= v[j];
+    }
+    for (; r < R; r++) acc &= load_row_seg<NT>(index, qrows[r], stride_words, w0);
+    if (last) {
+        if (Rall == 0) acc = u64x2{0ull, 0ull};
+        acc.x &= valid_mask(w0, n_cols);
+        acc.y &= valid_mask(w0 + 1, n_cols);
+    }
+    o[0] = acc.x;
+    if (two) o[1] = acc.y;
+}
+
 // ------------------------------------------------------------------------------ K2 + K3b: per-sample counts
 // For every unique k-mer: AND of its h rows (graph/index.py:75-80), then +1 into the counters of the samples whose
 // bit survived (unpack_and_sum, graph/bigsi.py:35-44).  Counters are bit-sliced: P planes of uint64 per word, a

@@ -7,7 +7,9 @@
 // tally (plan_tally, plan_tally_chunks; pinned by tests/c_host/tally_host.cpp and tests/test_tally_host.py) and what the exact k-mer
 // counter decides about a call and its table (plan_kmer_count_add, kmer_stage_chunk, plan_kmer_table; pinned by
 // tests/c_host/kmercount_plan_host.cpp and tests/test_kmercount_plan_host.py) and the segments, plane bucket, grid and refusals of the
-// windowed search's sweep (plan_window_search; pinned by tests/c_host/window_host.cpp and tests/test_window_host.py).  Pure functions of a handful of integers
+// windowed search's sweep (plan_window_search; pinned by tests/c_host/window_host.cpp and tests/test_window_host.py) and the band sweep
+// of a large exact batch (plan_band_sweep, band_window, band_lower_bound; pinned by tests/c_host/band_plan_host.cpp and
+// tests/test_band_plan_host.py).  Pure functions of a handful of integers
 // (and, for the compaction, the collapses and the pairwise popcounts, of the keep bitmap / the group map / the column lists): no HIP,
 // no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp,
 // prevalence_host.cpp, collapse_host.cpp, consensus_host.cpp and pairwise_host.cpp compile this header as plain host C++ and
@@ -263,6 +265,130 @@ inline RowAndLaunch RowAndPlan::launch(uint32_t i) const
     const uint64_t in_flight_at_8 = (uint64_t)n * in.wv * 8 * 8;
     l.unroll = (in.exact && in_flight_at_8 > (29ull << 19) /* 14.5 MB */ && l.slices == 1) ? 4 : 8;
     return l;
+}
+
+// ------------------------------------------------------------------------------ band sweep (k_and_exact_band)
+// A large exact batch references its index's rows several times over (rho = n_seqs x max_pos x h / m references per row: 4096 queries
+// of 1 kbp at h = 4 on 10 M rows 1.59, half of the references repeats of a row some other query holds too).  plan_row_and's launches
+// hold ~128 queries x all segments, and two queries that share a row meet it a launch apart, from HBM both times.  The band sweep turns
+// the loops round: a launch is ONE 1 KiB column segment (a band) of EVERY query of the batch, a wavefront per query, all of them
+// sweeping their address-ordered lists low -> high together, so that the second reference to a row comes while its lines are still in
+// the caches behind the CUs.  Optionally a band is cut into address windows, a launch each: the wavefront finds its part of the list
+// by binary search and carries its accumulator from window to window through the result words (one owner per word, launches
+// stream-ordered: plain load and store).
+//
+// Measured with the bare probe (scripts/probe/row_probe.hip, mode shared; profiles/band_sweep_probe.txt; 125 GB matrix of 12.5 KB rows,
+// lists of 3880 rows, GB/s = references x 1 KiB / time; `sorted` in the same job 6494-6501, with scalar row-id loads 6618-6664):
+//   - plain loads see the repeats, non-temporal loads do not: 4096 wavefronts, rho 1.59, one window, 2 loads: plain 7467, NT 6756
+//     (NT with NO repeats: 6753).  Without repeats plain loads are the slower ones (6113): the route pays only where rows repeat.
+//   - loads in flight per lane 2 / 4 / 8 (4096 wavefronts, rho 1.59, one window): 7467 / 7214 / 6638          -> kBandUnroll = 2
+//   - windows 1 / 4 / 16 / 64, 4096 wavefronts: 7467 / 7297 / 6857 / 5593; 8192 wavefronts (repeated share 0.70):
+//     6814 / 7192 / 7128 / 6428                                  -> one window up to 4096 queries, kBandWindowsLarge = 4 beyond
+//   - two segments per launch (8192 wavefronts for 4096 queries): 6539 at one window, 6929 at 16            -> kBandSegs = 1
+//   - repeated share 0 / 0.50 / 0.70 (rho 0 / 1.59 / 3.18, 4096 wavefronts): 6113 / 7467 / 7753.  Between the first two the rate
+//     crosses k_and_exact's 6.8 TB/s near a share of 0.26 (rho 0.63) -- interpolated, not measured -- and the route is taken from
+//     kBandMinRho = 1.0 on (share 0.37), where the interpolated rate is 4 % above it.
+//   - wavefronts per launch (one window, 2 loads, rho 1.59 / 3.18): 512: 1831 / 1917, 1024: 3527 / 3758, 2048: 6113 / 6591,
+//     3072: 7563 / 7907, 4096: 7467 / 7753 -- with two loads in flight a launch needs some 3000 wavefronts to fill the memory system,
+//     and below that plan_row_and's launches (13 segments x 8 loads of 128 queries) are the faster ones     -> kBandMinQueries = 3072
+//   - bytes in flight: the largest launch measured is 8192 wavefronts x 2 loads x 1 KiB = 16 MiB = kBandInFlightCap; larger batches
+//     keep plan_row_and's launches.
+//   - a last segment that holds few columns costs a launch nearly as long as a full one (its wavefronts wait for as many rows): the
+//     27 words of C3's 13th segment (1563 result words) as a launch of their own against riding in the 12th segment's launch (8192
+//     wavefronts, 14 lanes of every second one live), bench.py's step, interleaved on one box: 56.72 / 57.33 / 57.38 ms against
+//     55.33 / 55.91 / 56.01.  Taken up to kBandTailWords = 32 words (a quarter segment; only 27 was measured).
+// The blockIdx -> XCD map of k_and_exact is not kept: a wavefront is a (query, segment) and the probe ran without it.
+constexpr uint32_t kBandUnroll = 2;
+constexpr uint32_t kBandSegs = 1;
+constexpr uint32_t kBandWindowsLarge = 4;
+constexpr uint32_t kBandOneWindowQueries = 4096;
+constexpr double kBandMinRho = 1.0;
+constexpr uint32_t kBandMinQueries = 3072;
+constexpr uint64_t kBandInFlightCap = 16ull << 20;
+constexpr uint32_t kBandMaxWindows = 1u << 16;
+constexpr uint64_t kBandTailWords = 32;
+
+// The address-ordered lists are bucket-sorted, not fully sorted: ascending in (row id >> shift), any order inside a bucket, with the
+// smallest shift that leaves at most `buckets` buckets over [0, m) (k_sort_rows: kSortBuckets; K1's LDS route: its table's slots).
+static inline uint32_t sort_shift(uint64_t m, uint64_t buckets)
+{
+    uint32_t shift = 0;
+    while (m && ((m - 1) >> shift) >= buckets) shift++;
+    return shift;
+}
+
+// rows [lo, hi) of window w of W over m rows, cut at whole sort buckets (so that a window is a contiguous piece of every list): the
+// windows partition [0, m) for every W >= 1 (W above the number of buckets: most are empty)
+struct BandWindow {
+    uint64_t lo, hi;
+};
+static inline BandWindow band_window(uint64_t m, uint32_t w, uint32_t W, uint32_t shift)
+{
+    const uint64_t nb = m ? ((m - 1) >> shift) + 1 : 0;
+    const uint64_t lo = (uint64_t)((unsigned __int128)nb * w / W) << shift, hi = (uint64_t)((unsigned __int128)nb * (w + 1) / W) << shift;
+    return {std::min(lo, m), std::min(hi, m)};
+}
+
+// first index in the list r[0, n) whose row id is >= key, for a list ascending in (row id >> shift) and a key that is a multiple of
+// 2^shift or the number of rows (a window bound).  The kernel runs the same loop on scalar loads: at most 17 steps for 2^17 rows
+static inline uint64_t band_lower_bound(const uint64_t *r, uint64_t n, uint64_t key)
+{
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (r[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+struct BandLaunch {
+    uint32_t seg0, nseg;        // the launch's segments [seg0, seg0 + nseg) (the last group may reach past the result's last segment)
+    uint32_t window;            // of BandSweepPlan::windows
+    uint64_t grid;              // workgroups of kBlock threads: a wavefront per (query, segment)
+    uint32_t unroll;
+};
+struct BandSweepPlan {
+    bool taken = false;
+    uint32_t windows = 0, segs_per_launch = 0, seg_groups = 0, unroll = kBandUnroll;
+    uint64_t grid = 0, in_flight = 0;      // of a launch: workgroups, bytes in flight (wavefronts x unroll x 1 KiB)
+    uint32_t n_launches = 0;               // seg_groups x windows: group by group, a group's windows in ascending order
+    bool merge_tail = false;               // the last group is the last TWO segments (kBandTailWords)
+    BandLaunch launch(uint32_t i) const
+    {
+        const uint32_t g = i / windows;
+        const bool tail = merge_tail && g + 1 == seg_groups;
+        return {g * segs_per_launch, tail ? 2u : segs_per_launch, i % windows, tail ? 2 * grid : grid, unroll};
+    }
+};
+
+// `forced` (BIGSI_RUN_BAND_SWEEP): whatever rho and the batch's size; forced_windows / forced_segs (bigsi_hip_band_set_limits): 0
+// keeps the rule's value
+static inline BandSweepPlan plan_band_sweep(const RowAndInput &in, uint64_t m, bool forced = false, uint32_t forced_windows = 0,
+                                            uint32_t forced_segs = 0)
+{
+    BandSweepPlan p;
+    if (!in.exact || in.early_exit || in.no_sort || in.n_seqs == 0 || in.wv == 0 || m == 0) return p;
+    p.windows = forced_windows ? std::min(forced_windows, kBandMaxWindows) : in.n_seqs <= kBandOneWindowQueries ? 1 : kBandWindowsLarge;
+    p.segs_per_launch = forced_segs ? std::min(forced_segs, 2u) : kBandSegs;
+    const uint64_t segs = ceil_div(in.wv, 64 * kVec), waves = (uint64_t)in.n_seqs * p.segs_per_launch;
+    p.seg_groups = (uint32_t)ceil_div(segs, p.segs_per_launch);
+    p.grid = ceil_div(waves, kBlock / 64);
+    p.in_flight = waves * p.unroll * 1024;
+    if (p.grid > 0x7FFFFFFFull || (uint64_t)p.seg_groups * p.windows > 0x7FFFFFFFull) return p;
+    if (!forced) {
+        const RowAndPlan rp = plan_row_and(in);
+        const double rho = (double)in.n_seqs * (double)in.max_pos * in.h / (double)m;
+        if (rp.slices != 1 || !rp.want_sorted || rho < kBandMinRho || in.n_seqs < kBandMinQueries || p.in_flight > kBandInFlightCap) return p;
+    }
+    // a nearly empty last segment rides with its neighbour (one-window plans with the rule's own segments only)
+    if (!forced_segs && p.windows == 1 && segs >= 2 && in.wv - (segs - 1) * 64 * kVec <= kBandTailWords && 2 * p.in_flight <= kBandInFlightCap) {
+        p.merge_tail = true;
+        p.seg_groups--;
+    }
+    p.n_launches = p.seg_groups * p.windows;
+    p.taken = true;
+    return p;
 }
 
 // ------------------------------------------------------------------------------ column popcounts (k_col_popcount, k_col_popcount_sum)

@@ -150,17 +150,24 @@ int search_stream_impl(bigsi_hip_index *ix, const char *seqs, const uint64_t *of
     // lookups/s; gene-length and scored streams +-0)
     constexpr int kSlots = 4;
     static_assert(kSlots <= sizeof(ix->stream_ws) / sizeof(ix->stream_ws[0]), "a workspace per slot");
-    // a batch = at most 2^20 k-mer positions (gene-length queries: ~1000 of 1 kbp) and at most kChunkSeqs sequences (reads), whichever
-    // limit a chunk reaches first.  With the read kernel that ordered its hit lists inside the launch (rounds 2-3) 2^14 reads per launch
+    // a batch = at most kChunkPositions k-mer positions and at most kChunkSeqs sequences (reads), whichever limit a chunk reaches first.
+    // With the read kernel that ordered its hit lists inside the launch (rounds 2-3) 2^14 reads per launch
     // measured best; the wait-free kernel of round 4 prefers smaller launches, more of them in flight: host-visible over 1 M reads of
     // 61 bp 1.04 / 1.41 / 1.51 / 1.45 G lookups/s at 1024 / 2048 / 4096 / 16384 reads per batch, over 64 k reads 1.01 / 1.36 / 1.39 /
     // 1.27 G (interleaved, twice each)
-    // thresholded searches of gene-length queries take four times the positions: the counting kernel is ONE launch per chunk (chunked it
+    // Positions: exact and scored searches 2^20 (gene-length queries: ~1080 of 1 kbp; scored: K5 + K6 of a chunk run beside the next
+    // chunk's row-AND -- more, smaller chunks), thresholded ones 2^22: the counting kernel is ONE launch per chunk (chunked it
     // measured -4 ... 0 %, bigsi_batch_run), and every launch pays its tail -- 8192 x 1 kbp at 0.4 on 10 M x 100 k: 8 launches of ~1080
     // queries 0.774 of peak by the kernel's clock, one launch of 8192 0.80 (round 6).  The sequence cap still comes first for them: 4096
-    // queries of 1 kbp are ~4.0 M positions, under 2^22, so 8192 of them go out as two chunks (two launches) of 4096.  The counters of a
-    // chunk are 2 bytes x samples per query
-    const uint64_t kChunkPositions = (threshold == 1.0 || so) ? 1ull << 20 : 1ull << 22;      // (scored: K5 + K6 of a chunk run beside the next chunk's row-AND -- more, smaller chunks)
+    // queries of 1 kbp are ~4.0 M positions, under 2^22, so 8192 of them go out as two chunks of 4096.  The counters of a
+    // chunk are 2 bytes x samples per query.
+    // An exact chunk takes 2^22 positions too where that makes it large enough for the band sweep (plan_band_sweep: the queries of a
+    // chunk share rows only when there are thousands of them -- 1024 queries of 1 kbp on 10 M rows repeat 18 % of their row
+    // references, 4096 half): see `cut` below.  Its row lists are 2 x 8 bytes per row reference (4096 x 1 kbp at h = 4: 254 MB a slot), so the large chunk
+    // is taken only while four times that is free on the device
+    const bool small_chunks = threshold == 1.0 || so;
+    const uint64_t kChunkPositions = small_chunks ? 1ull << 20 : 1ull << 22;
+    const bool band_chunks = threshold == 1.0 && !so && !(flags & BIGSI_RUN_FORCE_COUNTS);
     constexpr uint64_t kChunkSeqs = 4096;
     const uint32_t launch_q = bigsi_exact_launch_queries(ix);
     struct Chunk { uint64_t first; uint32_t n; uint64_t hit0, bit0; bool scoring; };
@@ -225,20 +232,37 @@ int search_stream_impl(bigsi_hip_index *ix, const char *seqs, const uint64_t *of
     uint64_t next = 0;
     int slot = 0;
     while (next < n_seqs && rc == BIGSI_OK) {
-        // the next chunk: up to kChunkPositions k-mer positions, at least one sequence
-        uint64_t end = next, pos = 0;
-        while (end < n_seqs && end - next < kChunkSeqs) {
-            if (offsets[end + 1] < offsets[end]) { rc = fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing"); break; }
-            const uint64_t len = offsets[end + 1] - offsets[end], n = len >= k ? len - k + 1 : 0;
-            if (end > next && pos + n > kChunkPositions) break;
-            pos += std::max<uint64_t>(n, 1);
-            end++;
+        // the next chunk: up to `limit_pos` k-mer positions, at least one sequence
+        uint64_t end = next, max_pos = 0;
+        uint64_t pos = 0;
+        auto cut = [&](uint64_t limit_pos) -> int {
+            pos = 0;
+            end = next;
+            max_pos = 0;
+            while (end < n_seqs && end - next < kChunkSeqs) {
+                if (offsets[end + 1] < offsets[end]) return fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing");
+                const uint64_t len = offsets[end + 1] - offsets[end], n = len >= k ? len - k + 1 : 0;
+                if (end > next && pos + n > limit_pos) break;
+                pos += std::max<uint64_t>(n, 1);
+                max_pos = std::max(max_pos, n);
+                end++;
+            }
+            return BIGSI_OK;
+        };
+        // (exact: the large chunk if the band sweep takes it, else the small one)
+        bool band = false;
+        if (band_chunks) {
+            rc = cut(1ull << 22);
+            band = rc == BIGSI_OK && bigsi_band_sweep_taken(ix, (uint32_t)(end - next), max_pos, flags);
+            size_t free_b = 0, total_b = 0;
+            if (band && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b / 64 < pos * ix->h)) band = false;      // 4 x 16 bytes per reference
         }
+        if (rc == BIGSI_OK && !band) rc = cut(kChunkPositions);
         if (rc != BIGSI_OK) break;
         // an exact chunk of gene-length queries goes out as several row-AND launches of launch_q queries each: end it on a multiple of
         // that, so that no chunk closes with a part launch (10 M x 100 k, 8192 x 1 kbp per call: 8 chunks x 8 launches of 128 queries
         // instead of 8 x (8 + a launch of 57); round 6)
-        if (threshold == 1.0 && end < n_seqs && end - next >= 2ull * launch_q) end = next + (end - next) / launch_q * launch_q;
+        if (threshold == 1.0 && !band && end < n_seqs && end - next >= 2ull * launch_q) end = next + (end - next) / launch_q * launch_q;
         if (busy[slot]) rc = collect(slot);                    // this workspace's previous chunk (three chunks ago)
         if (rc == BIGSI_OK && so) rc = finish_score(slot);
         if (rc != BIGSI_OK) break;

@@ -992,8 +992,8 @@ class QueryBatch(object):
             pass
 
     def run(self, threshold, force_counts=False, skip_compact=False, k1_global=False, sparse_counts=False, early_exit=False,
-            weak_fingerprint=False, one_stream=False):
-        flags = ((_lib.RUN_ONE_STREAM if one_stream else 0) | (_lib.RUN_FORCE_COUNTS if force_counts else 0) | (_lib.RUN_SKIP_COMPACT if skip_compact else 0) |
+            weak_fingerprint=False, one_stream=False, band_sweep=False):
+        flags = ((_lib.RUN_ONE_STREAM if one_stream else 0) | (_lib.RUN_BAND_SWEEP if band_sweep else 0) | (_lib.RUN_FORCE_COUNTS if force_counts else 0) | (_lib.RUN_SKIP_COMPACT if skip_compact else 0) |
                  (_lib.RUN_K1_GLOBAL if k1_global else 0) | (_lib.RUN_SPARSE_COUNTS if sparse_counts else 0) |
                  (_lib.RUN_EARLY_EXIT if early_exit else 0) | (_lib.RUN_WEAK_FINGERPRINT if weak_fingerprint else 0))
         if self.group:

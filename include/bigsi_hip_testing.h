@@ -27,6 +27,10 @@ extern "C" {
 #define BIGSI_RUN_WEAK_FINGERPRINT 64u /* one-launch read path: 1-bit k-mer fingerprints, so that the dedupe takes its exact
                                           pairwise route (otherwise reached only on a 2^-32 fingerprint collision) */
 
+#define BIGSI_RUN_BAND_SWEEP 512u /* exact runs: take the band sweep (one column segment of every query per launch, plan_band_sweep)
+                                     whatever the batch's size and the share of repeated rows; declined with BIGSI_RUN_EARLY_EXIT,
+                                     BIGSI_RUN_NO_SORT and on the counting path */
+
 /* Run this index's kernels and copies on a caller-owned hipStream_t (e.g. torch's current stream, so
  * that RCCL collectives issued by the caller are ordered after them).  NULL restores the private stream.
  * With a caller-owned stream set, every kernel of the index goes to that one stream (see STREAMS in bigsi_hip.h). */
@@ -90,6 +94,12 @@ int bigsi_hip_kmer_counter_set_limits(struct bigsi_hip_kmer_counter *c, uint64_t
  * a test reaches segment boundaries with a few hundred positions, and with a small cap the refusal; results do not depend on the
  * first.  BIGSI_ERR_INVALID for a NULL index or starts_per_segment >= 2^31. */
 int bigsi_hip_window_set_limits(bigsi_hip_index *ix, uint64_t starts_per_segment, uint64_t partial_bytes_cap);
+
+/* BAND SWEEP (plan_band_sweep): address windows per band and column segments per launch (1 or 2) of later exact runs of this index
+ * that take the route; 0 keeps the planner's own value.  With many windows a test reaches empty windows and the hand-over of the
+ * accumulator between launches on a few hundred rows; results do not depend on either.  BIGSI_ERR_INVALID for a NULL index, more
+ * than 65536 windows or more than 2 segments. */
+int bigsi_hip_band_set_limits(bigsi_hip_index *ix, uint32_t windows, uint32_t segments_per_launch);
 
 #ifdef __cplusplus
 }

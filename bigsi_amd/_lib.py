@@ -184,6 +184,8 @@ SIGNATURES = {
     "bigsi_hip_kmer_counter_set_limits": (_i32, [_P, _u64, _u64]),          # (include/bigsi_hip_testing.h)
     "bigsi_hip_window_set_limits": (_i32, [_P, _u64, _u64]),                # (include/bigsi_hip_testing.h)
     "bigsi_hip_band_set_limits": (_i32, [_P, _u32, _u32]),                  # (include/bigsi_hip_testing.h)
+    "bigsi_hip_stream_set_limits": (_i32, [_P, _u64, _u64, _u64]),          # (include/bigsi_hip_testing.h)
+    "bigsi_hip_stream_last_chunks": (_i32, [_P, _P, _P, _u64, C.POINTER(_u64)]),          # (include/bigsi_hip_testing.h)
 }
 
 # every symbol include/bigsi_hip_compact.h declares (column compaction: the maintenance layer)

@@ -106,6 +106,9 @@ struct bigsi_hip_index {
     struct bigsi_hip_batch *window_ws = nullptr;      // bigsi_hip_window_search's workspace, created at its first call
     uint64_t window_starts = 0, window_cap = 0;       // bigsi_hip_window_set_limits: starts per segment, partial bytes cap (0: the planner's)
     uint32_t band_windows = 0, band_segs = 0;         // bigsi_hip_band_set_limits: windows per band, segments per launch (0: the planner's)
+    bigsi::StreamOverrides stream_limits;             // bigsi_hip_stream_set_limits: positions of a small / large chunk, sequences per chunk (0: the planner's)
+    std::vector<uint64_t> stream_chunk_first;         // bigsi_hip_stream_last_chunks: first sequence of every chunk the last stream call launched ...
+    std::vector<uint8_t> stream_chunk_band;           // ... and whether the loop gave it to the band sweep
     uint64_t m = 0, n_cols = 0, cap_cols = 0, stride_words = 0;
     uint64_t alloc_rows = 0;      // rows the allocation behind d_index holds: m, or more after bigsi_hip_fold_rows (until bigsi_hip_trim_rows); never reported
     uint32_t h = 0;

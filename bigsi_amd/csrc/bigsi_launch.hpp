@@ -9,7 +9,8 @@
 // tests/c_host/kmercount_plan_host.cpp and tests/test_kmercount_plan_host.py) and the segments, plane bucket, grid and refusals of the
 // windowed search's sweep (plan_window_search; pinned by tests/c_host/window_host.cpp and tests/test_window_host.py) and the band sweep
 // of a large exact batch (plan_band_sweep, band_window, band_lower_bound; pinned by tests/c_host/band_plan_host.cpp and
-// tests/test_band_plan_host.py).  Pure functions of a handful of integers
+// tests/test_band_plan_host.py) and the chunk cuts of the streamed search (stream_limits, stream_chunk_end, stream_round_to_launches;
+// pinned by tests/c_host/stream_plan_host.cpp and tests/test_stream_plan_host.py).  Pure functions of a handful of integers
 // (and, for the compaction, the collapses and the pairwise popcounts, of the keep bitmap / the group map / the column lists): no HIP,
 // no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp,
 // prevalence_host.cpp, collapse_host.cpp, consensus_host.cpp and pairwise_host.cpp compile this header as plain host C++ and
@@ -1196,6 +1197,81 @@ static inline uint64_t kmer_initial_slots(uint64_t expected_distinct, uint64_t f
 {
     const uint64_t want = std::min<uint64_t>(expected_distinct, kKmerCountLifetime);
     return plan_kmer_table(floor_slots, want, 0, 0).slots;
+}
+
+// ------------------------------------------------------------------------------ streamed search (search_stream_impl)
+// The cut rule of bigsi_hip_search_stream and its _ranked and _scored siblings: the input goes out as device batches ("chunks") of
+// consecutive sequences, kStreamSlots workspaces in flight.  A chunk holds at most `seqs` sequences and at most a position limit of
+// k-mer positions, whichever it reaches first, and always at least one sequence.
+//   - Position limit: exact (threshold 1.0) and scored streams take the small limit (2^20: gene-length queries ~1080 of 1 kbp; scored:
+//     K5 + K6 of a chunk run beside the next chunk's row-AND -- more, smaller chunks), thresholded ones the large limit (2^22: the
+//     counting kernel is ONE launch per chunk and every launch pays its tail -- 8192 x 1 kbp at 0.4 on 10 M x 100 k: 8 launches of
+//     ~1080 queries 0.774 of peak by the kernel's clock, one launch of 8192 0.80).  The sequence cap still comes first for them: 4096
+//     queries of 1 kbp are ~4.0 M positions, so 8192 of them go out as two chunks of 4096.
+//   - An exact, unscored stream without BIGSI_RUN_FORCE_COUNTS (band_chunks) first cuts at the large limit and keeps that chunk if the
+//     band sweep takes it (plan_band_sweep, and enough free device memory for its row lists: the loop's decision, not the planner's);
+//     otherwise it cuts again at the small limit.
+//   - An exact chunk that did not take the band sweep and has chunks behind it ends on a whole number of row-AND launches
+//     (exact_launch_queries) once it holds two launches' worth: no chunk closes with a part launch (10 M x 100 k, 8192 x 1 kbp per
+//     call: 8 chunks x 8 launches of 128 queries instead of 8 x (8 + a launch of 57)).
+//   - 4096 sequences per chunk: host-visible over 1 M reads of 61 bp 1.04 / 1.41 / 1.51 / 1.45 G lookups/s at 1024 / 2048 / 4096 /
+//     16384 reads per batch.  The workspaces are sized for that cap: an override may lower it, never raise it.
+// Pinned by tests/c_host/stream_plan_host.cpp and tests/test_stream_plan_host.py; tests/test_gpu_stream_cuts.py reaches the cuts with
+// small limits (bigsi_hip_stream_set_limits) and reads them back (bigsi_hip_stream_last_chunks).
+constexpr uint64_t kStreamChunkPositions = 1ull << 20;
+constexpr uint64_t kStreamLargeChunkPositions = 1ull << 22;
+constexpr uint64_t kStreamChunkSeqs = 4096;
+constexpr int kStreamSlots = 4;
+struct StreamOverrides {            // bigsi_hip_stream_set_limits: 0 keeps the rule's value
+    uint64_t chunk_positions = 0, large_chunk_positions = 0, chunk_seqs = 0;
+};
+struct StreamLimits {
+    uint64_t small_pos, large_pos;      // position limit of a small chunk, of a large chunk
+    uint64_t seqs;                      // sequences per chunk
+    bool small_chunks;                  // a chunk of this stream takes the small limit (else the large one)
+    bool band_chunks;                   // ... after the large one was tried for the band sweep
+    uint64_t chunk_pos() const { return small_chunks ? small_pos : large_pos; }
+};
+static inline StreamLimits stream_limits(double threshold, bool scored, bool force_counts, const StreamOverrides &o = StreamOverrides())
+{
+    StreamLimits l;
+    l.small_pos = o.chunk_positions ? o.chunk_positions : kStreamChunkPositions;
+    l.large_pos = o.large_chunk_positions ? o.large_chunk_positions : kStreamLargeChunkPositions;
+    l.seqs = o.chunk_seqs ? std::min(o.chunk_seqs, kStreamChunkSeqs) : kStreamChunkSeqs;
+    l.small_chunks = threshold == 1.0 || scored;
+    l.band_chunks = threshold == 1.0 && !scored && !force_counts;
+    return l;
+}
+
+// The chunk that starts at sequence `next` < n_seqs: sequences [next, end), greedily while it holds at most limit_seqs sequences and
+// limit_pos k-mer positions -- and at least one sequence, so that a sequence beyond the limit is a chunk of its own.  A sequence
+// without a k-mer (shorter than k, or empty) adds nothing to what is compared with the limit and one position to `pos`.
+struct StreamChunk {
+    uint64_t end = 0;
+    uint64_t pos = 0;          // sum of max(positions, 1) over the chunk
+    uint64_t max_pos = 0;      // positions of its longest sequence
+    bool bad_offsets = false;  // offsets[end + 1] < offsets[end]: the input is refused
+};
+static inline StreamChunk stream_chunk_end(const uint64_t *offsets, uint64_t n_seqs, uint64_t next, uint32_t k, uint64_t limit_pos, uint64_t limit_seqs)
+{
+    StreamChunk c;
+    c.end = next;
+    while (c.end < n_seqs && c.end - next < limit_seqs) {
+        if (offsets[c.end + 1] < offsets[c.end]) { c.bad_offsets = true; return c; }
+        const uint64_t len = offsets[c.end + 1] - offsets[c.end], n = len >= k ? len - k + 1 : 0;
+        if (c.end > next && c.pos + n > limit_pos) break;
+        c.pos += std::max<uint64_t>(n, 1);
+        c.max_pos = std::max(c.max_pos, n);
+        c.end++;
+    }
+    return c;
+}
+
+// sequences of a chunk cut at `n`, ended on whole row-AND launches of launch_q queries (see above)
+static inline uint64_t stream_round_to_launches(uint64_t n, uint32_t launch_q, bool more_follow, bool exact, bool band)
+{
+    if (exact && !band && more_follow && launch_q && n >= 2ull * launch_q) return n / launch_q * launch_q;
+    return n;
 }
 
 }  // namespace bigsi

@@ -118,7 +118,7 @@ extern "C" int bigsi_hip_search_batch(bigsi_hip_index *ix, const char *seqs, con
 }
 
 // BIGSI.search for ANY number of sequences in one call (bulk_search, bigsi/__main__.py:261-314, pays per query what this pays
-// per call): the library cuts the input into device batches of about 2^20 k-mer positions, keeps three workspaces in flight --
+// per call): the library cuts the input into device batches (bigsi_launch.hpp: stream_limits), keeps four workspaces in flight --
 // while one batch runs, the next is staged and uploaded and the results of the one before are exported and copied out -- and
 // writes every sequence's results at its place in the caller's arrays (hit_offsets are global: n_seqs + 1 entries).
 // BIGSI_ERR_CAPACITY (hit_offsets complete, colours / counts filled as far as they fit) when hit_capacity is too small.
@@ -140,6 +140,10 @@ int search_stream_impl(bigsi_hip_index *ix, const char *seqs, const uint64_t *of
                        uint32_t *colours, uint32_t *counts, uint64_t hit_capacity, const ScoredOut *so, uint32_t limit = 0,
                        const uint32_t *excluded = nullptr, uint64_t n_excluded = 0)
 {
+    if (ix) {      // bigsi_hip_stream_last_chunks: the chunks this call launches (none if it is refused right here)
+        ix->stream_chunk_first.clear();
+        ix->stream_chunk_band.clear();
+    }
     if (!ix || !offsets || !hit_offsets) return fail(BIGSI_ERR_INVALID, "NULL argument");
     if (k == 0) return fail(BIGSI_ERR_INVALID, "k must be > 0");
     if (so && (!so->bit_offsets || !so->bits_needed)) return fail(BIGSI_ERR_INVALID, "NULL argument");
@@ -148,27 +152,19 @@ int search_stream_impl(bigsi_hip_index *ix, const char *seqs, const uint64_t *of
     if (n_seqs == 0) return BIGSI_OK;
     // device batches in flight (1 M reads of 61 bp, host-visible, interleaved: 2 -> 1.14, 3 -> 1.47-1.50, 4 -> 1.51-1.53, 6 -> 1.49-1.51 G
     // lookups/s; gene-length and scored streams +-0)
-    constexpr int kSlots = 4;
+    constexpr int kSlots = bigsi::kStreamSlots;
     static_assert(kSlots <= sizeof(ix->stream_ws) / sizeof(ix->stream_ws[0]), "a workspace per slot");
-    // a batch = at most kChunkPositions k-mer positions and at most kChunkSeqs sequences (reads), whichever limit a chunk reaches first.
-    // With the read kernel that ordered its hit lists inside the launch (rounds 2-3) 2^14 reads per launch
-    // measured best; the wait-free kernel of round 4 prefers smaller launches, more of them in flight: host-visible over 1 M reads of
-    // 61 bp 1.04 / 1.41 / 1.51 / 1.45 G lookups/s at 1024 / 2048 / 4096 / 16384 reads per batch, over 64 k reads 1.01 / 1.36 / 1.39 /
-    // 1.27 G (interleaved, twice each)
-    // Positions: exact and scored searches 2^20 (gene-length queries: ~1080 of 1 kbp; scored: K5 + K6 of a chunk run beside the next
-    // chunk's row-AND -- more, smaller chunks), thresholded ones 2^22: the counting kernel is ONE launch per chunk (chunked it
-    // measured -4 ... 0 %, bigsi_batch_run), and every launch pays its tail -- 8192 x 1 kbp at 0.4 on 10 M x 100 k: 8 launches of ~1080
-    // queries 0.774 of peak by the kernel's clock, one launch of 8192 0.80 (round 6).  The sequence cap still comes first for them: 4096
-    // queries of 1 kbp are ~4.0 M positions, under 2^22, so 8192 of them go out as two chunks of 4096.  The counters of a
-    // chunk are 2 bytes x samples per query.
-    // An exact chunk takes 2^22 positions too where that makes it large enough for the band sweep (plan_band_sweep: the queries of a
+    // a batch = at most a position limit of k-mer positions and at most lim.seqs sequences (reads), whichever limit a chunk reaches
+    // first: the rule and what it was measured against are in bigsi_launch.hpp (stream_limits, stream_chunk_end,
+    // stream_round_to_launches).  With the read kernel that ordered its hit lists inside the launch (rounds 2-3) 2^14 reads per launch
+    // measured best; the wait-free kernel of round 4 prefers smaller launches, more of them in flight (over 64 k reads 1.01 / 1.36 /
+    // 1.39 / 1.27 G at 1024 / 2048 / 4096 / 16384 reads per batch, interleaved, twice each).  The counters of a chunk are 2 bytes x
+    // samples per query.
+    // An exact chunk takes the large limit too where that makes it large enough for the band sweep (plan_band_sweep: the queries of a
     // chunk share rows only when there are thousands of them -- 1024 queries of 1 kbp on 10 M rows repeat 18 % of their row
-    // references, 4096 half): see `cut` below.  Its row lists are 2 x 8 bytes per row reference (4096 x 1 kbp at h = 4: 254 MB a slot), so the large chunk
+    // references, 4096 half).  Its row lists are 2 x 8 bytes per row reference (4096 x 1 kbp at h = 4: 254 MB a slot), so the large chunk
     // is taken only while four times that is free on the device
-    const bool small_chunks = threshold == 1.0 || so;
-    const uint64_t kChunkPositions = small_chunks ? 1ull << 20 : 1ull << 22;
-    const bool band_chunks = threshold == 1.0 && !so && !(flags & BIGSI_RUN_FORCE_COUNTS);
-    constexpr uint64_t kChunkSeqs = 4096;
+    const bigsi::StreamLimits lim = bigsi::stream_limits(threshold, so != nullptr, (flags & BIGSI_RUN_FORCE_COUNTS) != 0, ix->stream_limits);
     const uint32_t launch_q = bigsi_exact_launch_queries(ix);
     struct Chunk { uint64_t first; uint32_t n; uint64_t hit0, bit0; bool scoring; };
     Chunk inflight[kSlots] = {};
@@ -236,33 +232,26 @@ int search_stream_impl(bigsi_hip_index *ix, const char *seqs, const uint64_t *of
         uint64_t end = next, max_pos = 0;
         uint64_t pos = 0;
         auto cut = [&](uint64_t limit_pos) -> int {
-            pos = 0;
-            end = next;
-            max_pos = 0;
-            while (end < n_seqs && end - next < kChunkSeqs) {
-                if (offsets[end + 1] < offsets[end]) return fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing");
-                const uint64_t len = offsets[end + 1] - offsets[end], n = len >= k ? len - k + 1 : 0;
-                if (end > next && pos + n > limit_pos) break;
-                pos += std::max<uint64_t>(n, 1);
-                max_pos = std::max(max_pos, n);
-                end++;
-            }
+            const bigsi::StreamChunk c = bigsi::stream_chunk_end(offsets, n_seqs, next, k, limit_pos, lim.seqs);
+            if (c.bad_offsets) return fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing");
+            end = c.end;
+            pos = c.pos;
+            max_pos = c.max_pos;
             return BIGSI_OK;
         };
         // (exact: the large chunk if the band sweep takes it, else the small one)
         bool band = false;
-        if (band_chunks) {
-            rc = cut(1ull << 22);
+        if (lim.band_chunks) {
+            rc = cut(lim.large_pos);
             band = rc == BIGSI_OK && bigsi_band_sweep_taken(ix, (uint32_t)(end - next), max_pos, flags);
             size_t free_b = 0, total_b = 0;
             if (band && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b / 64 < pos * ix->h)) band = false;      // 4 x 16 bytes per reference
         }
-        if (rc == BIGSI_OK && !band) rc = cut(kChunkPositions);
+        if (rc == BIGSI_OK && !band) rc = cut(lim.chunk_pos());
         if (rc != BIGSI_OK) break;
         // an exact chunk of gene-length queries goes out as several row-AND launches of launch_q queries each: end it on a multiple of
-        // that, so that no chunk closes with a part launch (10 M x 100 k, 8192 x 1 kbp per call: 8 chunks x 8 launches of 128 queries
-        // instead of 8 x (8 + a launch of 57); round 6)
-        if (threshold == 1.0 && !band && end < n_seqs && end - next >= 2ull * launch_q) end = next + (end - next) / launch_q * launch_q;
+        // that, so that no chunk closes with a part launch (round 6)
+        end = next + bigsi::stream_round_to_launches(end - next, launch_q, end < n_seqs, threshold == 1.0, band);
         if (busy[slot]) rc = collect(slot);                    // this workspace's previous chunk (three chunks ago)
         if (rc == BIGSI_OK && so) rc = finish_score(slot);
         if (rc != BIGSI_OK) break;
@@ -274,6 +263,8 @@ int search_stream_impl(bigsi_hip_index *ix, const char *seqs, const uint64_t *of
         if (rc != BIGSI_OK) break;
         inflight[slot] = Chunk{next, (uint32_t)(end - next), 0, 0, false};
         busy[slot] = true;
+        ix->stream_chunk_first.push_back(next);
+        ix->stream_chunk_band.push_back(band ? 1 : 0);
         next = end;
         if (so) {
             // the chunk before this one: hit lists out, scores requested (they run beside the chunk just launched)
@@ -316,6 +307,10 @@ extern "C" int bigsi_hip_search_stream_ranked(bigsi_hip_index *ix, const char *s
                                               const uint32_t *excluded, uint64_t n_excluded)
 {
     BIGSI_ENTER(ix);
+    if (ix) {      // (a call refused below has launched no chunk either)
+        ix->stream_chunk_first.clear();
+        ix->stream_chunk_band.clear();
+    }
     if (n_excluded && !limit) return fail(BIGSI_ERR_INVALID, "excluded colours are only valid with a limit (limit = 0 is off)");
     if (n_excluded && !excluded) return fail(BIGSI_ERR_INVALID, "excluded is NULL");
     return search_stream_impl(ix, seqs, offsets, n_seqs, k, threshold, flags, num_kmers, num_unique, min_kmers, hit_offsets, colours, counts,
@@ -331,11 +326,41 @@ extern "C" int bigsi_hip_search_stream_scored(bigsi_hip_index *ix, const char *s
                                               bigsi_hip_hit_score *scores, uint64_t *bits_needed)
 {
     BIGSI_ENTER(ix);
+    if (ix) {      // (a call refused below has launched no chunk either)
+        ix->stream_chunk_first.clear();
+        ix->stream_chunk_band.clear();
+    }
     if (hit_capacity && (!colours || !scores)) return fail(BIGSI_ERR_INVALID, "colours / scores is NULL");
     uint64_t needed = 0;
     const ScoredOut so{bits, bits_capacity, bit_offsets, scores, bits_needed ? bits_needed : &needed};
     return search_stream_impl(ix, seqs, offsets, n_seqs, k, threshold, flags, num_kmers, num_unique, min_kmers, hit_offsets, colours, counts,
                               hit_capacity, &so);
+}
+
+// include/bigsi_hip_testing.h: the stream's limits for later calls on this index, and the chunks of the last one
+extern "C" int bigsi_hip_stream_set_limits(bigsi_hip_index *ix, uint64_t chunk_positions, uint64_t large_chunk_positions, uint64_t chunk_seqs)
+{
+    BIGSI_ENTER(ix);
+    if (!ix) return fail(BIGSI_ERR_INVALID, "NULL index");
+    if (chunk_seqs > bigsi::kStreamChunkSeqs)
+        return fail(BIGSI_ERR_INVALID, "at most %llu sequences per chunk (got %llu)", (unsigned long long)bigsi::kStreamChunkSeqs, (unsigned long long)chunk_seqs);
+    ix->stream_limits.chunk_positions = chunk_positions;
+    ix->stream_limits.large_chunk_positions = large_chunk_positions;
+    ix->stream_limits.chunk_seqs = chunk_seqs;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_stream_last_chunks(bigsi_hip_index *ix, uint64_t *first, uint8_t *band, uint64_t capacity, uint64_t *n)
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !n) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    *n = ix->stream_chunk_first.size();
+    if (capacity < *n) return fail(BIGSI_ERR_CAPACITY, "the last stream call made %llu chunks, the buffers hold %llu", (unsigned long long)*n, (unsigned long long)capacity);
+    if (*n == 0) return BIGSI_OK;
+    if (!first || !band) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    std::copy(ix->stream_chunk_first.begin(), ix->stream_chunk_first.end(), first);
+    std::copy(ix->stream_chunk_band.begin(), ix->stream_chunk_band.end(), band);
+    return BIGSI_OK;
 }
 
 // ------------------------------------------------------------------------------ communicators

@@ -101,6 +101,18 @@ int bigsi_hip_window_set_limits(bigsi_hip_index *ix, uint64_t starts_per_segment
  * than 65536 windows or more than 2 segments. */
 int bigsi_hip_band_set_limits(bigsi_hip_index *ix, uint32_t windows, uint32_t segments_per_launch);
 
+/* STREAMED SEARCH (stream_limits, stream_chunk_end): the k-mer positions of a small chunk (the library's 2^20: exact and scored
+ * streams) and of a large chunk (2^22: thresholded streams, and the exact chunk that is tried for the band sweep), and the sequences per
+ * chunk (4096), of later bigsi_hip_search_stream / _ranked / _scored calls on this index; 0 keeps the library's value.  With small
+ * values a test reaches chunk cuts and the reuse of the four workspaces with a few hundred short queries; results do not depend on
+ * any of the three.  BIGSI_ERR_INVALID for a NULL index or chunk_seqs above 4096 (the workspaces are sized for that). */
+int bigsi_hip_stream_set_limits(bigsi_hip_index *ix, uint64_t chunk_positions, uint64_t large_chunk_positions, uint64_t chunk_seqs);
+/* The chunks the last streamed search on this index launched, in order: *n of them, first[i] the index of chunk i's first sequence,
+ * band[i] != 0 when the stream gave the chunk to the band sweep.  A stream of no sequences, and one refused before its first chunk
+ * (the argument checks of the three entry points included), report none; a stream that failed later the chunks launched until
+ * then.  capacity < *n is a sizing call: BIGSI_ERR_CAPACITY, *n set, nothing written (first and band may then be NULL). */
+int bigsi_hip_stream_last_chunks(bigsi_hip_index *ix, uint64_t *first, uint8_t *band, uint64_t capacity, uint64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2091,18 +2091,33 @@ def test_replace_and_drop_free_a_resident_index_of_another_shape(hip):
     assert HipHbmStorage.drop("same_name") is True and HipHbmStorage.drop("same_name") is False
 
 
+def assert_stream_cuts(st, seqs, thr, n_cols, h, m):
+    """the chunks of the last stream call on st (bigsi_hip_stream_last_chunks) are the cut rule's at the library's own limits, as
+    tests/stream_ref.py restates it; returns [(first, band)]"""
+    import stream_ref
+    from bigsi_amd import _lib
+    n = _lib.C.c_uint64(0)
+    assert _lib.lib().bigsi_hip_stream_last_chunks(st.handle, None, None, 0, _lib.C.byref(n)) == _lib.ERR_CAPACITY
+    first, band = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint8)
+    _lib.check(_lib.lib().bigsi_hip_stream_last_chunks(st.handle, _lib.ptr(first), _lib.ptr(band), n.value, _lib.C.byref(n)))
+    got = [(int(f), bool(b)) for f, b in zip(first, band)]
+    assert got == [(f, b) for f, b, _, _ in stream_ref.cuts([len(s_) for s_ in seqs], 31, thr, n_cols, h, m)]
+    return got
+
+
 def test_search_stream_entry_point_equals_batch_runs(hip):
-    """bigsi_hip_search_stream (any number of sequences in one call, three workspaces in flight, pinned staging + export kernel):
-    reads (the one-launch kernel, several chunks), gene-length queries (chunks cut by k-mer positions), a mix with sequences
-    shorter than k, and a hit buffer that is too small at first -- all equal to plain batch runs and to the oracle; the one-call
-    bigsi_hip_search_batch goes through the same staging and must agree too."""
+    """bigsi_hip_search_stream (any number of sequences in one call, four workspaces in flight, pinned staging + export kernel):
+    reads (the one-launch kernel, 18 chunks of 4096 sequences), gene-length queries (chunks cut by k-mer positions: 2^20 for an exact
+    stream, 2^22 for a thresholded one), a mix with sequences shorter than k, and a hit buffer that is too small at first -- all
+    equal to plain batch runs and to the oracle; the one-call bigsi_hip_search_batch goes through the same staging and must agree
+    too."""
     from oracle.ref_model import SynthOracle
     m, n_cols, h = 200_003, 9_000, 3
     c, st = synth_index(hip, m, n_cols, h, 44, draws=1)
     orc = SynthOracle(44, 0, m, n_cols, h, 31, 1)
     rng = np.random.default_rng(8)
-    reads = random_seqs(rng, 70_000, 61, 61)                  # > 2 chunks of 2^15 sequences
-    genes = random_seqs(rng, 1300, 900, 1100)                 # > 2 chunks of 2^19 positions
+    reads = random_seqs(rng, 70_000, 61, 61)                  # 18 chunks of 4096 sequences
+    genes = random_seqs(rng, 1300, 900, 1100)                 # exact: 2 chunks of 2^20 positions
     mixed = random_seqs(rng, 300, 10, 200) + ["ACGT", ""] + random_seqs(rng, 50, 1000, 3000)
     for col_, s_ in ((5, reads[3]), (8999, reads[40_000]), (77, genes[700]), (4000, mixed[320])):
         st.insert_kmers(col_, [s_], 31)
@@ -2111,6 +2126,8 @@ def test_search_stream_entry_point_equals_batch_runs(hip):
         st._search_cap = 4                                   # force the grow-and-retry protocol
         nk, nu, off, col, cnt = st.search_many(seqs, 31, thr)
         assert off[0] == 0 and int(off[-1]) == col.size == cnt.size
+        chunks = assert_stream_cuts(st, seqs, thr, n_cols, h, m)
+        assert len(chunks) == -(-len(seqs) // 4096) if seqs is not genes else len(chunks) == 2
         # against plain batches of 5000 sequences
         pos = 0
         for lo in range(0, len(seqs), 5000):
@@ -2159,9 +2176,13 @@ def test_search_stream_entry_point_equals_batch_runs(hip):
 def test_search_stream_chunks_cut_at_whole_row_and_launches(hip):
     """Round 6: bigsi_hip_search_stream ends an exact chunk of gene-length queries on a multiple of the row-AND launch size (no chunk closes
     with a part launch) and gives thresholded searches four times the positions per chunk.  On 20 000 samples a launch takes 768 queries
-    and 2^20 positions are 2093 queries of 531 bp: exact chunks of 1536.  Thresholded chunks would take 8371 such queries by positions,
-    but the cap of 4096 sequences per chunk comes first: chunks of 4096.  Several chunks of each kind here, hits planted on both sides of
-    every cut, against plain batches (hit lists whole) and the oracle (sampled)."""
+    and 2^20 positions are 2092 queries of 531 bp: exact chunks of 1536 -- where the band sweep does not take the chunk.  Since exact
+    chunks grow to 2^22 positions for the band sweep it does take it here (4096 queries on 200 003 rows: every row referenced 30 times):
+    the exact stream of 5000 is a band chunk of 4096, the cap on sequences, and a remainder of 904.  Thresholded chunks would take 8371
+    such queries by positions, but the cap of 4096 sequences per chunk comes first: chunks of 4096, cuts at 4096 and 8192.  The cuts
+    are asserted (bigsi_hip_stream_last_chunks against tests/stream_ref.py); the planted hits also stand where the rule of round 6 cut
+    (1535 | 1536, 3071 | 3072) and at 8370 | 8371, where no stream of this test cuts.  tests/test_gpu_stream_cuts.py reaches the
+    rounding (test_exact_chunks_end_on_whole_launches) and the other edges with small limits.  Against plain batches (hit lists whole) and the oracle (sampled)."""
     from oracle.ref_model import SynthOracle
     m, n_cols, h = 200_003, 20_000, 3
     c, st = synth_index(hip, m, n_cols, h, 45, draws=1)
@@ -2175,6 +2196,7 @@ def test_search_stream_chunks_cut_at_whole_row_and_launches(hip):
     for seqs, thr in ((genes[:5000], 1.0), (genes, 0.45)):
         nk, nu, off, col, cnt = st.search_many(seqs, 31, thr)
         assert off[0] == 0 and int(off[-1]) == col.size == cnt.size and int(off[-1]) >= 4
+        assert assert_stream_cuts(st, seqs, thr, n_cols, h, m) == ([(0, True), (4096, False)] if thr == 1.0 else [(0, False), (4096, False), (8192, False)])
         for lo in range(0, len(seqs), 3000):
             part = seqs[lo:lo + 3000]
             b = st.new_batch(part, 31)

@@ -53,6 +53,15 @@ class GroupInfo(C.Structure):
                 ("rccl", C.c_uint32)]
 
 
+class HitsPath(C.Structure):
+    """bigsi_hip_hits_path (include/bigsi_hip_testing.h): the path a batch's last run took through K4, the export and collect"""
+    _fields_ = [(name, C.c_uint32) for name in ("groups", "items_per_group", "single_workgroup", "inline_export", "rewrites", "exp_spec",
+                                                "collect_fetch", "one_launch")]
+
+
+HITS_PATH_OF_BATCH, HITS_PATH_OF_INDEX, HITS_PATH_OF_GROUP_BATCH = 0, 1, 2
+
+
 class IoStats(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("seconds", C.c_double), ("file_seconds", C.c_double), ("threads", C.c_uint32), ("direct", C.c_uint32)]
 
@@ -186,6 +195,7 @@ SIGNATURES = {
     "bigsi_hip_band_set_limits": (_i32, [_P, _u32, _u32]),                  # (include/bigsi_hip_testing.h)
     "bigsi_hip_stream_set_limits": (_i32, [_P, _u64, _u64, _u64]),          # (include/bigsi_hip_testing.h)
     "bigsi_hip_stream_last_chunks": (_i32, [_P, _P, _P, _u64, C.POINTER(_u64)]),          # (include/bigsi_hip_testing.h)
+    "bigsi_hip_hits_last_path": (_i32, [_P, _u32, C.POINTER(HitsPath)]),                  # (include/bigsi_hip_testing.h)
 }
 
 # every symbol include/bigsi_hip_compact.h declares (column compaction: the maintenance layer)

@@ -1936,7 +1936,7 @@ static int launch_reads_fused(bigsi_hip_batch *b, hipStream_t st = nullptr, bool
     TRY(b->bitmaps.reserve((size_t)b->n_seqs * b->wv_pad * 8));
     TRY(hb.hit_off.reserve((b->n_seqs + 2) * 8ull));          // (query-ordered offsets: filled by whoever orders the lists)
     if (hb.cap == 0 && !hb.xcol) {
-        const uint64_t want = 1u << 16;
+        const uint64_t want = kHitsInitialCapacity;
         TRY(hb.hit_col.reserve(want * 4));
         TRY(hb.hit_cnt.reserve(want * 4));
         hb.cap = want;
@@ -2223,6 +2223,7 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
 
     b->fused_run = false;
     b->exported_inline = false;
+    b->path = bigsi_hip_hits_path{};
     if (reads_fusable(b, flags)) {
         // (K1 rewrites arrays the previous run of this batch may still be reading, on a read stream or the gather stream)
         TRY(b->rows.reserve(std::max<uint64_t>(b->total_pos, 1) * ix->h * 8));
@@ -2241,6 +2242,8 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
         TRY(ev_end(ix, &fe, ix->ev_and, st));
         b->run_h = ix->h;
         b->fused_run = true;
+        b->path.one_launch = 1;
+        b->path.inline_export = b->exported_inline ? 1 : 0;
         b->count_bytes = 2;
         b->sparse_counts = !b->exact;
         b->compacted = true;
@@ -2415,25 +2418,31 @@ static int compact_bits(bigsi_hip_batch *b, HitBufs &hb, const void *src, const 
     if (nchunks > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "too many compaction chunks");
     TRY(hb.hit_off.reserve((b->n_seqs + 1) * 8ull));
     if (hb.cap == 0 && !hb.xcol) {
-        const uint64_t want = 1u << 16;
+        const uint64_t want = kHitsInitialCapacity;
         TRY(hb.hit_col.reserve(want * 4));
         TRY(hb.hit_cnt.reserve(want * 4));
         hb.cap = want;
     }
-    const uint64_t max_groups = kHitsMaxGroups;
     // a handful of items (one or two gene-length queries: a latency-bound call) go to ONE workgroup, which needs nobody's totals
-    const uint32_t ipb = nchunks <= 16 ? (uint32_t)nchunks : (uint32_t)ceil_div(nchunks, max_groups);
-    const uint64_t ngroups = ceil_div(nchunks, ipb);
+    const HitsPlan hp = plan_hits(nchunks, n_shards);
+    const uint32_t ipb = hp.ipb;
+    const uint64_t ngroups = hp.groups;
     TRY(hb.chunk_hits.reserve(kHitsMaxGroups * 4));
     if (!write_only && ngroups > 1)
         hipLaunchKernelGGL(k_hits_totals, dim3((unsigned)ngroups), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv, b->n_seqs,
                            n_shards, chunks, ipb, hb.chunk_hits.as<uint32_t>());
     // a one-call search whose compaction is ONE workgroup (a gene-length query or two): that workgroup exports the results itself
-    const bool inline_export = b->one_call && &hb == &b->hits && !write_only && ngroups == 1 && n_shards == 1 && chunks <= 16 && st == b->ix->stream;
+    const bool inline_export = b->one_call && &hb == &b->hits && !write_only && hp.single && st == b->ix->stream;
     if (inline_export) {
         TRY(export_prepare(b, st));
         b->exported_inline = true;
     }
+    // (bigsi_hip_hits_last_path)
+    b->path.groups = (uint32_t)ngroups;
+    b->path.items_per_group = ipb;
+    b->path.single_workgroup = hp.single ? 1 : 0;
+    if (write_only) b->path.rewrites++;
+    else b->path.inline_export = inline_export ? 1 : 0;
     hipLaunchKernelGGL(k_hits_write, dim3((unsigned)ngroups), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv, b->n_seqs,
                        n_shards, chunks, shard_cols, b->num_unique.as<uint32_t>(), ipb, hb.chunk_hits.as<uint32_t>(),
                        hb.hit_off.as<uint64_t>(), hb.col(), hb.cnt(), hb.capacity(), counters, b->count_bytes, b->wv_pad * 64, own_shard,
@@ -2486,6 +2495,7 @@ static int fetch_read_hits(bigsi_hip_batch *b, uint64_t *hit_offsets, uint32_t *
         TRY(hb.hit_col.reserve(total * 4));          // counters lived in registers: the whole pass again, on the stream it ran on
         TRY(hb.hit_cnt.reserve(total * 4));
         hb.cap = total;
+        b->path.rewrites++;
         TRY(launch_reads_fused(b, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -3029,8 +3039,9 @@ static int window_launch(bigsi_hip_batch *b, uint32_t window, double threshold, 
 #undef BIGSI_WINDOW_COMBINE
     HIP_TRY(hipGetLastError());
     // K4 as compact_bits launches it, on this call's bitmap and counters
-    const uint32_t ipb = nchunks <= 16 ? (uint32_t)nchunks : (uint32_t)ceil_div(nchunks, (uint64_t)kHitsMaxGroups);
-    const uint64_t ngroups = ceil_div(nchunks, ipb);
+    const HitsPlan hp = plan_hits(nchunks);
+    const uint32_t ipb = hp.ipb;
+    const uint64_t ngroups = hp.groups;
     auto hits_write = [&]() {
         hipLaunchKernelGGL(k_hits_write, dim3((unsigned)ngroups), dim3(kBlock), 0, ix->stream, (const uint64_t *)d_bm, bm_stride, (uint32_t)wv, n_seqs, 1u,
                            chunks, ix->n_cols, b->num_unique.as<uint32_t>(), ipb, d_tot, d_hoff, b->win_col.as<uint32_t>(), b->win_cnt.as<uint32_t>(),
@@ -3696,7 +3707,7 @@ static int export_prepare(bigsi_hip_batch *b, hipStream_t st)
     const uint32_t n = b->n_seqs;
     // (room in the pinned block for the hit lists the export carries along: 16 per sequence -- a read stream whose reads match a
     // handful of samples each then never takes the slower fetch route; the block is only written as far as there are hits)
-    const uint64_t spec = std::min<uint64_t>(std::max<uint64_t>(1024, 16ull * n), std::min<uint64_t>(hb.capacity(), 1u << 20));
+    const uint64_t spec = export_spec(n, hb.capacity());
     const size_t o_uniq = (n + 2ull) * 8, o_col = o_uniq + ((3ull * n + 1) & ~1ull) * 4, bytes = o_col + 8 * spec;
     TRY(pinned_reserve(&b->pin_out, &b->pin_out_cap, bytes));
     // completion: the kernel's last workgroup writes the export's serial into a pinned word the host spins on (no event record, no
@@ -3708,6 +3719,7 @@ static int export_prepare(bigsi_hip_batch *b, hipStream_t st)
         HIP_TRY(hipMemsetAsync(b->exp_count.p, 0, 256, st));
     }
     b->exp_spec = (uint32_t)spec;
+    b->path.exp_spec = (uint32_t)spec;
     b->exp_serial++;
     b->exp_stream = st;
     return BIGSI_OK;
@@ -3775,6 +3787,7 @@ int bigsi_batch_collect(bigsi_hip_batch *b, uint32_t *num_kmers, uint32_t *num_u
     if (total > hb.capacity() || (b->fused_run && total > b->exp_spec)) {
         // rare: hit lists that outgrew the device buffers (the general route regrows them and repeats the launch), or a read
         // run with more hits than its export carried along (their query order is made on the host)
+        b->path.collect_fetch = 1;
         TRY(bigsi_hip_batch_fetch_unique(b, num_kmers, num_unique, min_kmers));
         const int rc2 = bigsi_hip_batch_fetch_hits(b, hit_offsets, colours, counts, capacity);
         b->idle = !b->job.pending;

@@ -1431,7 +1431,7 @@ constexpr uint32_t kAllShards = 0xFFFFFFFFu;
 // about the dispatcher and about whatever else runs on the device (other streams, other processes) that nothing enforces.
 // The launch boundary costs ~5 us per batch (0.5 % of a 1 ms step at configs[3] / [4]; batches of reads do not come here, they
 // write their hits from k_reads_fused) and removes the only unbounded wait the library had.
-constexpr uint32_t kHitsMaxGroups = 1024;
+// (kHitsMaxGroups and the rule that picks ipb: plan_hits, bigsi_launch.hpp)
 
 // item ci of the (seq, shard, chunk) order; the host keeps the number of items below 2^31, so the divisions are 32-bit ones
 // (a 64-bit division is a ~100-instruction routine on this hardware: three of them per item were most of K4's time on a

@@ -10,7 +10,9 @@
 // windowed search's sweep (plan_window_search; pinned by tests/c_host/window_host.cpp and tests/test_window_host.py) and the band sweep
 // of a large exact batch (plan_band_sweep, band_window, band_lower_bound; pinned by tests/c_host/band_plan_host.cpp and
 // tests/test_band_plan_host.py) and the chunk cuts of the streamed search (stream_limits, stream_chunk_end, stream_round_to_launches;
-// pinned by tests/c_host/stream_plan_host.cpp and tests/test_stream_plan_host.py).  Pure functions of a handful of integers
+// pinned by tests/c_host/stream_plan_host.cpp and tests/test_stream_plan_host.py) and the launch shape of the hit-list compaction and
+// the size of the pinned export (plan_hits, export_spec; pinned by tests/c_host/hits_plan_host.cpp and tests/test_hits_plan_host.py).
+// Pure functions of a handful of integers
 // (and, for the compaction, the collapses and the pairwise popcounts, of the keep bitmap / the group map / the column lists): no HIP,
 // no batch, no index.  bigsi_hip.hip carries the plans out; tests/c_host/launch_host.cpp, compact_host.cpp, fold_host.cpp,
 // prevalence_host.cpp, collapse_host.cpp, consensus_host.cpp and pairwise_host.cpp compile this header as plain host C++ and
@@ -1272,6 +1274,45 @@ static inline uint64_t stream_round_to_launches(uint64_t n, uint32_t launch_q, b
 {
     if (exact && !band && more_follow && launch_q && n >= 2ull * launch_q) return n / launch_q * launch_q;
     return n;
+}
+
+// ------------------------------------------------------------------------------ K4 hit lists (k_hits_totals, k_hits_write) and the export
+// K4 works on items: an item is one 256-word chunk of one (sequence, shard) result vector, in (seq, shard, chunk) order, `nchunks`
+// of them in all (the host keeps that below 2^31).  Workgroup g owns the `ipb` consecutive items [g ipb, (g + 1) ipb).
+//   - At most kHitsOneGroupItems items (one or two gene-length queries: a latency-bound call) go to ONE workgroup, which needs
+//     nobody's totals; on an unsharded buffer that workgroup takes k_hits_write's single-workgroup body (every thread a run of
+//     consecutive words of a query) and, in a one-call search, writes the caller's pinned block itself.
+//   - More items are spread over at most kHitsMaxGroups workgroups: ipb = ceil(nchunks / kHitsMaxGroups), groups = ceil(nchunks / ipb),
+//     so that groups ipb >= nchunks > (groups - 1) ipb -- no workgroup is empty, the last one may be short.
+// No items: one workgroup that owns nothing (the library does not launch K4 for an empty batch).
+// The pinned block of an export carries the first export_spec hits along: kExportSpecPerSeq per sequence -- a read stream whose reads
+// match a handful of samples each then never takes the slower fetch route --, at least kExportSpecMin, never more than the device
+// lists hold, nor than kExportSpecMax.
+// Pinned by tests/c_host/hits_plan_host.cpp and tests/test_hits_plan_host.py; tests/test_gpu_hit_lists.py reads the path a run took
+// back through bigsi_hip_hits_last_path.
+constexpr uint32_t kHitsMaxGroups = 1024;
+constexpr uint32_t kHitsOneGroupItems = 16;
+constexpr uint64_t kHitsInitialCapacity = 1ull << 16;      // entries the hit lists start with
+constexpr uint64_t kExportSpecMin = 1024, kExportSpecPerSeq = 16, kExportSpecMax = 1ull << 20;
+struct HitsPlan {
+    uint32_t ipb = 1;           // items per workgroup
+    uint64_t groups = 1;        // workgroups
+    bool single = false;        // k_hits_write takes its single-workgroup body
+};
+static inline HitsPlan plan_hits(uint64_t nchunks, uint32_t n_shards = 1)
+{
+    HitsPlan p;
+    if (nchunks > 0) {
+        p.ipb = nchunks <= kHitsOneGroupItems ? (uint32_t)nchunks : (uint32_t)ceil_div(nchunks, (uint64_t)kHitsMaxGroups);
+        p.groups = ceil_div(nchunks, p.ipb);
+    }
+    // (one workgroup means at most kHitsOneGroupItems items, hence at most that many chunks per vector: the kernel's own test)
+    p.single = p.groups == 1 && n_shards == 1;
+    return p;
+}
+static inline uint64_t export_spec(uint64_t n_seqs, uint64_t capacity)
+{
+    return std::min<uint64_t>(std::max<uint64_t>(kExportSpecMin, kExportSpecPerSeq * n_seqs), std::min<uint64_t>(capacity, kExportSpecMax));
 }
 
 }  // namespace bigsi

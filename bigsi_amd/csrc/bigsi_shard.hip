@@ -585,6 +585,26 @@ struct bigsi_hip_group_batch {
     uint32_t limit = 0;                  // bigsi_hip_group_batch_set_limit: every member trims to its top N, fetch_hits cuts the union to N
 };
 
+// include/bigsi_hip_testing.h: the path the last run of a batch took through K4, the export and collect (reads host state only)
+extern "C" int bigsi_hip_hits_last_path(const void *owner, uint32_t kind, bigsi_hip_hits_path *out)
+{
+    if (!owner || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    const bigsi_hip_batch *b = nullptr;
+    switch (kind) {
+    case BIGSI_HITS_PATH_OF_BATCH: b = static_cast<const bigsi_hip_batch *>(owner); break;
+    case BIGSI_HITS_PATH_OF_INDEX: b = static_cast<const bigsi_hip_index *>(owner)->search_ws; break;
+    case BIGSI_HITS_PATH_OF_GROUP_BATCH: {
+        const bigsi_hip_group_batch *gb = static_cast<const bigsi_hip_group_batch *>(owner);
+        if (!gb->b.empty() && gb->ran) b = gb->b[0];
+        break;
+    }
+    default: return fail(BIGSI_ERR_INVALID, "unknown owner kind %u", kind);
+    }
+    if (!b || !b->ran) return fail(BIGSI_ERR_STATE, "no run to report: the batch has not run (or the index has no one-call workspace)");
+    *out = b->path;
+    return BIGSI_OK;
+}
+
 __global__ void k_add_counts(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) dst[i] += src[i];

@@ -113,6 +113,30 @@ int bigsi_hip_stream_set_limits(bigsi_hip_index *ix, uint64_t chunk_positions, u
  * then.  capacity < *n is a sizing call: BIGSI_ERR_CAPACITY, *n set, nothing written (first and band may then be NULL). */
 int bigsi_hip_stream_last_chunks(bigsi_hip_index *ix, uint64_t *first, uint8_t *band, uint64_t capacity, uint64_t *n);
 
+/* HIT LISTS AND THE EXPORT (plan_hits, export_spec): the path the LAST run of a batch took through the hit-list compaction
+ * (k_hits_totals / k_hits_write), the export into pinned memory and bigsi_batch_collect.  Results never depend on it; a test built
+ * for one path asserts it here first.  The call only reads what the run, its fetches and its collect left on the host: it queues
+ * nothing and waits for nothing.
+ *   groups, items_per_group  k_hits_write's grid and the items a workgroup owns (0, 0: K4 did not run -- a one-launch read run, or a
+ *                            run without hit lists)
+ *   single_workgroup         k_hits_write took its single-workgroup body
+ *   inline_export            the run's own kernel wrote the caller's pinned block (k_hits_write's single-workgroup body, or the read
+ *                            kernel of a one-read call) -- there was no export kernel
+ *   rewrites                 write passes repeated after the lists were grown (the read kernel: whole launches repeated)
+ *   exp_spec                 hits the export carried along (0: the run exported nothing)
+ *   collect_fetch            the one-call search took its results by the fetch route, not from the pinned block
+ *   one_launch               the run was the one-launch read kernel (k_reads_fused; a one-call search then exports with k_export_reads)
+ * `kind` says what `owner` is: a bigsi_hip_batch, a bigsi_hip_index (its one-call workspace: the last bigsi_hip_search_batch) or a
+ * bigsi_hip_group_batch (member 0, whose gathered lists the host reads).  BIGSI_ERR_INVALID for a NULL argument or an unknown kind,
+ * BIGSI_ERR_STATE when there is no such batch or it has not run. */
+typedef struct bigsi_hip_hits_path {
+    uint32_t groups, items_per_group, single_workgroup, inline_export, rewrites, exp_spec, collect_fetch, one_launch;
+} bigsi_hip_hits_path;
+#define BIGSI_HITS_PATH_OF_BATCH 0u
+#define BIGSI_HITS_PATH_OF_INDEX 1u
+#define BIGSI_HITS_PATH_OF_GROUP_BATCH 2u
+int bigsi_hip_hits_last_path(const void *owner, uint32_t kind, bigsi_hip_hits_path *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,17 @@ class HitsPath(C.Structure):
 HITS_PATH_OF_BATCH, HITS_PATH_OF_INDEX, HITS_PATH_OF_GROUP_BATCH = 0, 1, 2
 
 
+class RowAndPath(C.Structure):
+    """bigsi_hip_row_and_path (include/bigsi_hip_testing.h): the route a batch's last run took through K1, the row sort and the row-AND"""
+    _fields_ = [(name, C.c_uint32) for name in ("k1_route", "band_taken", "band_windows", "band_launches", "slices", "block", "tiles", "chunk_q",
+                                                "n_launches", "last_slices", "last_block", "last_unroll", "sorted_by", "early_exit", "preset_by",
+                                                "zero_copy")]
+
+
+K1_ELEMENTS, K1_WAVE, K1_LDS, K1_GLOBAL = 0, 1, 2, 3
+SORTED_BY_NONE, SORTED_BY_K1, SORTED_BY_SORT256, SORTED_BY_SORT1024 = 0, 1, 2, 3
+
+
 class IoStats(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("seconds", C.c_double), ("file_seconds", C.c_double), ("threads", C.c_uint32), ("direct", C.c_uint32)]
 
@@ -196,6 +207,8 @@ SIGNATURES = {
     "bigsi_hip_stream_set_limits": (_i32, [_P, _u64, _u64, _u64]),          # (include/bigsi_hip_testing.h)
     "bigsi_hip_stream_last_chunks": (_i32, [_P, _P, _P, _u64, C.POINTER(_u64)]),          # (include/bigsi_hip_testing.h)
     "bigsi_hip_hits_last_path": (_i32, [_P, _u32, C.POINTER(HitsPath)]),                  # (include/bigsi_hip_testing.h)
+    "bigsi_hip_batch_last_row_and": (_i32, [_P, _u32, C.POINTER(RowAndPath)]),            # (include/bigsi_hip_testing.h)
+    "bigsi_hip_batch_fetch_rows_sorted": (_i32, [_P, _u32, _P, _u64, C.POINTER(_u32)]),   # (include/bigsi_hip_testing.h)
 }
 
 # every symbol include/bigsi_hip_compact.h declares (column compaction: the maintenance layer)

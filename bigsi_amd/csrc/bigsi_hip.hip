@@ -2224,6 +2224,7 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     b->fused_run = false;
     b->exported_inline = false;
     b->path = bigsi_hip_hits_path{};
+    b->rpath = bigsi_hip_row_and_path{};
     if (reads_fusable(b, flags)) {
         // (K1 rewrites arrays the previous run of this batch may still be reading, on a read stream or the gather stream)
         TRY(b->rows.reserve(std::max<uint64_t>(b->total_pos, 1) * ix->h * 8));
@@ -2279,11 +2280,30 @@ int bigsi_batch_run(bigsi_hip_batch *b, double threshold, uint32_t flags, bool o
     b->dirty = true;        // until finish_run
     const uint64_t *k2_rows = sorted_by_k1 ? b->rows_sorted.as<uint64_t>() : b->rows.as<uint64_t>();
     const uint32_t shift = sort_shift(ix->m, kSortBuckets);
+    const uint32_t sort_block = sort_rows_block(b->max_pos, ix->h);
+    {   // (bigsi_hip_batch_last_row_and: a few host fields per run)
+        bigsi_hip_row_and_path &rp = b->rpath;
+        rp.k1_route = (uint32_t)k1.route;
+        rp.band_taken = band.taken ? 1u : 0u;
+        rp.band_windows = band.taken ? band.windows : 0u;
+        rp.band_launches = band.taken ? band.n_launches : 0u;
+        rp.slices = plan.slices; rp.block = plan.block; rp.tiles = plan.tiles; rp.chunk_q = plan.chunk_q; rp.n_launches = plan.n_launches;
+        if (plan.n_launches) {
+            const RowAndLaunch l = plan.launch(plan.n_launches - 1);
+            rp.last_slices = l.slices; rp.last_block = l.block; rp.last_unroll = l.unroll;
+        }
+        const bool sorts = (plan.want_sorted || band.taken) && !sorted_by_k1;
+        rp.sorted_by = sorted_by_k1 ? BIGSI_SORTED_BY_K1 : !sorts ? BIGSI_SORTED_BY_NONE : sort_block == 1024 ? BIGSI_SORTED_BY_SORT1024 : BIGSI_SORTED_BY_SORT256;
+        rp.early_exit = (b->exact && !band.taken && (flags & BIGSI_RUN_EARLY_EXIT)) ? 1u : (!b->exact && plan.early) ? 1u : 0u;
+        rp.preset_by = !plan.preset ? 0u : preset.done ? 1u : 2u;
+        rp.zero_copy = b->zero_copy ? 1u : 0u;
+        b->sorted_tab_mult = k1.tab_mult;
+    }
     if ((plan.want_sorted || band.taken) && !sorted_by_k1) {
         TRY(b->rows_sorted.reserve(std::max<uint64_t>(b->total_pos, 1) * ix->h * 8));
         TRY(ev_begin(ix, &ep));
         // 1024 threads per query for long row lists (a 1 kbp query at h=4 has 3880 rows), 256 otherwise
-        if (b->max_pos * ix->h >= 2048)
+        if (sort_block == 1024)
             hipLaunchKernelGGL((k_sort_rows<1024>), dim3(b->n_seqs), dim3(1024), 0, ix->stream, b->rows.as<uint64_t>(), b->rows_sorted.as<uint64_t>(),
                                b->d_pos_off.as<uint64_t>(), b->num_unique.as<uint32_t>(), ix->h, 1u, shift);
         else
@@ -2735,6 +2755,27 @@ extern "C" int bigsi_hip_batch_fetch_rows(bigsi_hip_batch *b, uint32_t seq, uint
     const uint64_t n = (uint64_t)b->h_num_unique[seq] * b->ix->h;
     if (n > capacity) return fail(BIGSI_ERR_CAPACITY, "rows buffer holds %llu, %llu needed", (unsigned long long)capacity, (unsigned long long)n);
     if (n) HIP_TRY(hipMemcpy(rows, b->rows.as<uint64_t>() + b->pos_off[seq] * b->ix->h, n * 8, hipMemcpyDeviceToHost));
+    return BIGSI_OK;
+}
+
+// include/bigsi_hip_testing.h: the list K2 streamed, as the last run's K1 or k_sort_rows left it (one copy, no kernel)
+extern "C" int bigsi_hip_batch_fetch_rows_sorted(bigsi_hip_batch *b, uint32_t seq, uint64_t *rows, uint64_t capacity, uint32_t *shift)
+{
+    BIGSI_ENTER(b ? b->ix : nullptr);
+    TRY(need_run(b));
+    if (!shift) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (seq >= b->n_seqs) return fail(BIGSI_ERR_RANGE, "sequence %u out of range", seq);
+    if (b->rpath.sorted_by == BIGSI_SORTED_BY_NONE) return fail(BIGSI_ERR_STATE, "the last run made no address-ordered row list");
+    TRY(host_counts(b));
+    const uint64_t n = (uint64_t)b->h_num_unique[seq] * b->ix->h;
+    if (n > capacity) return fail(BIGSI_ERR_CAPACITY, "rows buffer holds %llu, %llu needed", (unsigned long long)capacity, (unsigned long long)n);
+    if (b->rpath.sorted_by == BIGSI_SORTED_BY_K1) {       // (k_kmerize_lds: as many buckets as the query's dedupe table has slots)
+        const uint64_t pos = b->pos_off[seq + 1] - b->pos_off[seq];
+        uint64_t tsize = 2;
+        while (tsize < (uint64_t)b->sorted_tab_mult * pos) tsize <<= 1;
+        *shift = sort_shift(b->ix->m, tsize);
+    } else *shift = sort_shift(b->ix->m, kSortBuckets);
+    if (n) HIP_TRY(hipMemcpy(rows, b->rows_sorted.as<uint64_t>() + b->pos_off[seq] * b->ix->h, n * 8, hipMemcpyDeviceToHost));
     return BIGSI_OK;
 }
 

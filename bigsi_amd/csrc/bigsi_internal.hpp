@@ -263,6 +263,8 @@ struct bigsi_hip_batch {
     bool weak_fp = false;         // BIGSI_RUN_WEAK_FINGERPRINT of the last one-launch run (a re-launch after a regrow repeats it)
     bool fused_run = false;           // the last run was the one-launch read kernel (k_reads_fused)
     bigsi_hip_hits_path path{};       // bigsi_hip_hits_last_path: how the last run's hit lists were built and handed out
+    bigsi_hip_row_and_path rpath{};   // bigsi_hip_batch_last_row_and: the last run's route through K1, the row sort and the row-AND
+    uint32_t sorted_tab_mult = 0;     // rpath.sorted_by == K1: slots per position of the dedupe tables the lists were sorted in
     bool elements = false;            // k-mers were given explicitly (bigsi_hip_batch_create_elements): K1 = k_rows_raw
     DevBuf elem_seq_off;              // elements: first element of every sequence
     uint32_t count_bytes = 2;

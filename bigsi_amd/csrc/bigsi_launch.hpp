@@ -320,6 +320,10 @@ static inline uint32_t sort_shift(uint64_t m, uint64_t buckets)
     return shift;
 }
 
+// threads of k_sort_rows' workgroup (its two instances): 1024 per query for long row lists (a 1 kbp query at h = 4 has 3880 rows),
+// kBlock otherwise (pinned, with k1_plan's routes, by tests/c_host/launch_host.cpp and tests/test_knockout_host.py)
+static inline uint32_t sort_rows_block(uint64_t max_pos, uint32_t h) { return max_pos * h >= 2048 ? 1024u : (uint32_t)kBlock; }
+
 // rows [lo, hi) of window w of W over m rows, cut at whole sort buckets (so that a window is a contiguous piece of every list): the
 // windows partition [0, m) for every W >= 1 (W above the number of buckets: most are empty)
 struct BandWindow {

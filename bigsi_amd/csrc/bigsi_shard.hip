@@ -605,6 +605,26 @@ extern "C" int bigsi_hip_hits_last_path(const void *owner, uint32_t kind, bigsi_
     return BIGSI_OK;
 }
 
+// include/bigsi_hip_testing.h: the last run's route through K1, the row sort and the row-AND (reads host state only)
+extern "C" int bigsi_hip_batch_last_row_and(const void *owner, uint32_t kind, bigsi_hip_row_and_path *out)
+{
+    if (!owner || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    const bigsi_hip_batch *b = nullptr;
+    switch (kind) {
+    case BIGSI_HITS_PATH_OF_BATCH: b = static_cast<const bigsi_hip_batch *>(owner); break;
+    case BIGSI_HITS_PATH_OF_INDEX: b = static_cast<const bigsi_hip_index *>(owner)->search_ws; break;
+    case BIGSI_HITS_PATH_OF_GROUP_BATCH: {
+        const bigsi_hip_group_batch *gb = static_cast<const bigsi_hip_group_batch *>(owner);
+        if (!gb->b.empty() && gb->ran) b = gb->b[0];
+        break;
+    }
+    default: return fail(BIGSI_ERR_INVALID, "unknown owner kind %u", kind);
+    }
+    if (!b || !b->ran) return fail(BIGSI_ERR_STATE, "no run to report: the batch has not run (or the index has no one-call workspace)");
+    *out = b->rpath;
+    return BIGSI_OK;
+}
+
 __global__ void k_add_counts(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) dst[i] += src[i];
@@ -1139,6 +1159,22 @@ extern "C" int bigsi_hip_group_batch_run(bigsi_hip_group_batch *gb, double thres
         HIP_TRY(hipSetDevice(g->ix[0]->device));
         for (uint32_t i = 0; i < g->n(); i++)
             for (auto *o : gb->b) HIP_TRY(hipStreamWaitEvent(g->comm[i]->stream, o->done, 0));     // every slot written
+    }
+    // a thresholded run sums the members' count arrays entry by entry (group_reduce_counts): they must be of one size.  The fetch of
+    // an exact run grows member 0's lists alone (group_fetch_all), so after one that overflowed the other members catch up here
+    if (!gb->b[0]->exact) {
+        uint64_t cap = 0;
+        for (auto *b : gb->b)
+            if (!b->ghits.xcol) cap = std::max(cap, b->ghits.cap);
+        for (auto *b : gb->b) {
+            HitBufs &hb = b->ghits;
+            if (hb.xcol || hb.cap == 0 || hb.cap >= cap) continue;
+            TRY(bigsi_use_device(b->ix));
+            if (b->g_done) HIP_TRY(hipEventSynchronize(b->g_done));      // (its last compaction wrote the lists about to be replaced)
+            TRY(hb.hit_col.reserve(cap * 4));
+            TRY(hb.hit_cnt.reserve(cap * 4));
+            hb.cap = cap;
+        }
     }
     for (uint32_t i = 0; i < g->n(); i++) {
         TRY(bigsi_use_device(gb->b[i]->ix));

@@ -137,6 +137,34 @@ typedef struct bigsi_hip_hits_path {
 #define BIGSI_HITS_PATH_OF_GROUP_BATCH 2u
 int bigsi_hip_hits_last_path(const void *owner, uint32_t kind, bigsi_hip_hits_path *out);
 
+/* THE ROW-AND'S ROUTE (k1_plan, plan_row_and, plan_band_sweep, sort_rows_block): how the LAST run of a batch went through K1, the
+ * row sort and the row-AND launches.  Results never depend on it; a test built for one route asserts it here first
+ * (tests/knockout_cases.py).  bigsi_batch_run fills the record from the plans it holds anyway; the call only reads it: it queues
+ * nothing and waits for nothing.  `owner` and `kind` as for bigsi_hip_hits_last_path, and the same errors.
+ *   k1_route                 0 explicit k-mers, 1 one wavefront per query, 2 the LDS route (k_kmerize_lds), 3 the global route
+ *   band_taken, band_windows, band_launches   the band sweep (k_and_exact_band) and its launches; 0, 0, 0: plan_row_and's launches
+ *   slices, block, tiles, chunk_q, n_launches  plan_row_and's answer for the whole batch
+ *   last_slices, last_block, last_unroll       its last launch (a chunked batch's tail is planned again: RowAndPlan::launch)
+ *   sorted_by                who made the address-ordered row list K2 streamed: BIGSI_SORTED_BY_*
+ *   early_exit               BIGSI_RUN_EARLY_EXIT reached the kernel
+ *   preset_by                who set the result words a sliced exact run ANDs into: 0 nobody (not sliced), 1 K1, 2 a memset
+ *   zero_copy                K1 read the sequences in place from the caller's pinned staging (a one-call search)
+ * A one-launch read run (k_reads_fused) leaves the record zero. */
+typedef struct bigsi_hip_row_and_path {
+    uint32_t k1_route, band_taken, band_windows, band_launches, slices, block, tiles, chunk_q, n_launches, last_slices, last_block,
+        last_unroll, sorted_by, early_exit, preset_by, zero_copy;
+} bigsi_hip_row_and_path;
+#define BIGSI_SORTED_BY_NONE 0u
+#define BIGSI_SORTED_BY_K1 1u
+#define BIGSI_SORTED_BY_SORT256 2u
+#define BIGSI_SORTED_BY_SORT1024 3u
+int bigsi_hip_batch_last_row_and(const void *owner, uint32_t kind, bigsi_hip_row_and_path *out);
+/* The row list K2 streamed for sequence `seq` in the last run of `b` -- num_unique x num_hashes row ids, `capacity` entries at
+ * least -- and the shift it is bucket-ordered by (ascending in row >> shift): per query sort_shift(m, slots of the query's dedupe
+ * table) on K1's LDS route, sort_shift(m, 8192) for k_sort_rows.  One device-to-host copy, no kernel.  BIGSI_ERR_STATE when the
+ * last run made no sorted list, BIGSI_ERR_RANGE / BIGSI_ERR_CAPACITY as bigsi_hip_batch_fetch_rows. */
+int bigsi_hip_batch_fetch_rows_sorted(bigsi_hip_batch *b, uint32_t seq, uint64_t *rows, uint64_t capacity, uint32_t *shift);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,17 @@ uint64_t launch_host_plan(uint32_t n_seqs, uint64_t wv, uint64_t max_pos, uint32
     return p.n_launches;
 }
 
+// k1_plan: out[] = route, hs_cap, sq_bytes, tab_mult, tab_cap, lds
+void launch_host_k1_plan(uint32_t n_seqs, uint64_t max_pos, uint64_t max_len, int elements, int force_global, uint64_t *out)
+{
+    const bigsi::K1Plan p = bigsi::k1_plan(n_seqs, max_pos, max_len, elements != 0, force_global != 0);
+    const uint64_t rec[6] = {(uint64_t)p.route, p.hs_cap, p.sq_bytes, p.tab_mult, p.tab_cap, p.lds};
+    for (int i = 0; i < 6; i++) out[i] = rec[i];
+}
+
+// threads of k_sort_rows' workgroup: 256 or 1024
+uint32_t launch_host_sort_rows_block(uint64_t max_pos, uint32_t h) { return bigsi::sort_rows_block(max_pos, h); }
+
 // the one grid formula
 uint64_t launch_host_grid(uint64_t n, uint64_t tiles, uint64_t slices) { return bigsi::row_and_grid(n, tiles, slices); }
 

@@ -989,7 +989,8 @@ def test_k1_fused_lds_equals_global_path(hip, k, lens):
     """K1 has three routes -- one wavefront per query (all queries <= 64 positions), one fused launch with the dedupe table
     in LDS (all queries <= 4096 positions) and the four-kernel global-table route (longer queries, or forced by
     BIGSI_RUN_K1_GLOBAL).  Same row ids, unique counts,
-    position->unique maps (seen through presence strings) and hits from both, and both equal the oracle."""
+    position->unique maps (seen through presence strings) and hits from both, and both equal the oracle.  (The runs here are
+    thresholded, so the LDS route's fused row sort does not run: its list is held against rows() in tests/test_gpu_knockout.py.)"""
     from bigsi_amd.storage import get_storage
     from oracle import coracle
     m, n_cols, h = 2503, 128, 3

@@ -209,6 +209,7 @@ SIGNATURES = {
     "bigsi_hip_hits_last_path": (_i32, [_P, _u32, C.POINTER(HitsPath)]),                  # (include/bigsi_hip_testing.h)
     "bigsi_hip_batch_last_row_and": (_i32, [_P, _u32, C.POINTER(RowAndPath)]),            # (include/bigsi_hip_testing.h)
     "bigsi_hip_batch_fetch_rows_sorted": (_i32, [_P, _u32, _P, _u64, C.POINTER(_u32)]),   # (include/bigsi_hip_testing.h)
+    "bigsi_hip_rank_select_arrays": (_i32, [_i32, _P, _u64, _u32, _u32, _P, _u32, _P, _P, _P, _u32, _u32, _P]),   # (include/bigsi_hip_testing.h)
 }
 
 # every symbol include/bigsi_hip_compact.h declares (column compaction: the maintenance layer)

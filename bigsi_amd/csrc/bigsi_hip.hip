@@ -2396,6 +2396,21 @@ extern "C" int bigsi_hip_batch_run(bigsi_hip_batch *b, double threshold, uint32_
     return bigsi_batch_run(b, threshold, flags, false);
 }
 
+// The one launch of k_rank_select (rank_select below; bigsi_hip_rank_select_arrays): one workgroup per query over n_seqs x stride_words
+// hit words, of which the first wv are the result; counters n_seqs x 64 * stride_words of count_bytes each (2: uint16_t, 4: uint32_t),
+// null on an exact run, which takes the uint16_t instance and reads neither them nor num_unique / min_kmers.
+static void launch_rank_select(uint32_t n_seqs, const uint64_t *src, uint64_t stride_words, uint32_t wv, const void *counters, uint32_t count_bytes,
+                               const uint32_t *num_unique, const uint32_t *min_kmers, const uint64_t *excluded, uint32_t limit, uint64_t *dst,
+                               hipStream_t st)
+{
+    if (count_bytes == 4 && counters)
+        hipLaunchKernelGGL((k_rank_select<uint32_t>), dim3(n_seqs), dim3(kBlock), 0, st, src, stride_words, wv, (const uint32_t *)counters,
+                           stride_words * 64, num_unique, min_kmers, excluded, limit, dst);
+    else
+        hipLaunchKernelGGL((k_rank_select<uint16_t>), dim3(n_seqs), dim3(kBlock), 0, st, src, stride_words, wv, (const uint16_t *)counters,
+                           stride_words * 64, num_unique, min_kmers, excluded, limit, dst);
+}
+
 // k_rank_select over the batch's hit vectors `src` (counters: the counting run's, null on the exact path) into `dst` (may be `src`),
 // n_seqs x wv_pad words.  The excluded colours' bit vector is built on first use and again whenever the result width outgrew it.
 static int rank_select(bigsi_hip_batch *b, const void *src, const void *counters, void *dst, hipStream_t st)
@@ -2414,14 +2429,8 @@ static int rank_select(bigsi_hip_batch *b, const void *src, const void *counters
         ex = b->excl_bits.as<uint64_t>();
     }
     if (b->n_seqs == 0) return BIGSI_OK;
-    if (b->count_bytes == 4 && counters)
-        hipLaunchKernelGGL((k_rank_select<uint32_t>), dim3(b->n_seqs), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv,
-                           (const uint32_t *)counters, b->wv_pad * 64, b->num_unique.as<uint32_t>(), b->min_kmers.as<uint32_t>(), ex, b->limit,
-                           (uint64_t *)dst);
-    else
-        hipLaunchKernelGGL((k_rank_select<uint16_t>), dim3(b->n_seqs), dim3(kBlock), 0, st, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv,
-                           (const uint16_t *)counters, b->wv_pad * 64, b->num_unique.as<uint32_t>(), b->min_kmers.as<uint32_t>(), ex, b->limit,
-                           (uint64_t *)dst);
+    launch_rank_select(b->n_seqs, (const uint64_t *)src, b->wv_pad, (uint32_t)b->wv, counters, b->count_bytes, b->num_unique.as<uint32_t>(),
+                       b->min_kmers.as<uint32_t>(), ex, b->limit, (uint64_t *)dst, st);
     HIP_TRY(hipGetLastError());
     return BIGSI_OK;
 }
@@ -3719,6 +3728,44 @@ extern "C" int bigsi_hip_score_presence(int device, const uint8_t *bits, const u
     if (e == hipSuccess) e = hipMemcpy(scores, d + o_out, n * sizeof(bigsi_hip_hit_score), hipMemcpyDeviceToHost);
     hipError_t e2 = hipFree(d); (void)e2;
     if (e != hipSuccess) return fail(BIGSI_ERR_HIP, "bigsi_hip_score_presence: %s", hipGetErrorString(e));
+    return BIGSI_OK;
+}
+
+// k_rank_select on the caller's arrays (include/bigsi_hip_testing.h): no index and no batch -- one upload, the launch rank_select()
+// makes (launch_rank_select), one download of the whole output.
+extern "C" int bigsi_hip_rank_select_arrays(int device, const uint64_t *hits, uint64_t stride_words, uint32_t wv, uint32_t n_seqs,
+                                            const void *counters, uint32_t counter_bytes, const uint32_t *num_unique, const uint32_t *min_kmers,
+                                            const uint64_t *excluded, uint32_t limit, uint32_t in_place, uint64_t *out)
+{
+    if (!hits || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (limit == 0) return fail(BIGSI_ERR_INVALID, "limit is 0");
+    if (wv > stride_words) return fail(BIGSI_ERR_INVALID, "wv %u exceeds the stride of %llu words", wv, (unsigned long long)stride_words);
+    if (counters && counter_bytes != 2 && counter_bytes != 4) return fail(BIGSI_ERR_INVALID, "counter_bytes %u is neither 2 nor 4", counter_bytes);
+    if (counters && (!num_unique || !min_kmers)) return fail(BIGSI_ERR_INVALID, "counters without num_unique and min_kmers");
+    if (n_seqs > 0x7FFFFFFFu || stride_words > (1ull << 26)) return fail(BIGSI_ERR_INVALID, "too large for one call");
+    if (n_seqs == 0) return BIGSI_OK;
+    HIP_TRY(hipSetDevice(device));
+    const size_t words = (size_t)n_seqs * stride_words, n_count = counters ? words * 64 * counter_bytes : 0;
+    const size_t o_out = round_up(words * 8, 256), o_cnt = round_up(o_out + words * 8, 256), o_nu = round_up(o_cnt + n_count, 256);
+    const size_t o_mk = round_up(o_nu + n_seqs * 4ull, 256), o_ex = round_up(o_mk + n_seqs * 4ull, 256), total = o_ex + (size_t)wv * 8 + 8;
+    uint8_t *d = nullptr;
+    HIP_TRY(hipMalloc((void **)&d, total));
+    uint64_t *d_hits = reinterpret_cast<uint64_t *>(d), *d_out = in_place ? d_hits : reinterpret_cast<uint64_t *>(d + o_out);
+    hipError_t e = hipMemcpy(d_hits, hits, words * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !in_place) e = hipMemcpy(d_out, out, words * 8, hipMemcpyHostToDevice);      // (the caller's preset)
+    if (e == hipSuccess && counters) e = hipMemcpy(d + o_cnt, counters, n_count, hipMemcpyHostToDevice);
+    if (e == hipSuccess && counters) e = hipMemcpy(d + o_nu, num_unique, n_seqs * 4ull, hipMemcpyHostToDevice);
+    if (e == hipSuccess && counters) e = hipMemcpy(d + o_mk, min_kmers, n_seqs * 4ull, hipMemcpyHostToDevice);
+    if (e == hipSuccess && excluded && wv) e = hipMemcpy(d + o_ex, excluded, (size_t)wv * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_rank_select(n_seqs, d_hits, stride_words, wv, counters ? d + o_cnt : nullptr, counter_bytes, (const uint32_t *)(d + o_nu),
+                           (const uint32_t *)(d + o_mk), excluded ? (const uint64_t *)(d + o_ex) : nullptr, limit, d_out, 0);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, words * 8, hipMemcpyDeviceToHost);
+    hipError_t e2 = hipFree(d); (void)e2;
+    if (e != hipSuccess) return fail(BIGSI_ERR_HIP, "bigsi_hip_rank_select_arrays: %s", hipGetErrorString(e));
     return BIGSI_OK;
 }
 

@@ -165,6 +165,24 @@ int bigsi_hip_batch_last_row_and(const void *owner, uint32_t kind, bigsi_hip_row
  * last run made no sorted list, BIGSI_ERR_RANGE / BIGSI_ERR_CAPACITY as bigsi_hip_batch_fetch_rows. */
 int bigsi_hip_batch_fetch_rows_sorted(bigsi_hip_batch *b, uint32_t seq, uint64_t *rows, uint64_t capacity, uint32_t *shift);
 
+/* THE TOP-N SELECTION ON CALLER DATA (k_rank_select; its peer for K6 is bigsi_hip_score_presence): no index, no batch.  For n_seqs
+ * queries the call stages
+ *   hits        uint64[n_seqs][stride_words], row format (column 8b + j of a word at bit 8b + 7 - j), of which the first wv words of a
+ *               query are its result (wv <= stride_words);
+ *   counters    uint16 (counter_bytes 2) or uint32 (4) [n_seqs][64 * stride_words], one per column, or NULL for an exact run (then
+ *               num_unique and min_kmers are not read and may be NULL); the kernel reads a counter only where the column is a hit;
+ *   num_unique, min_kmers   uint32[n_seqs];
+ *   excluded    uint64[wv] in row format, shared by all queries, or NULL;
+ * launches the instance and the grid a limited search launches (one workgroup per query, the same argument meaning as rank_select()
+ * in bigsi_hip.hip), waits, and copies all of [n_seqs][stride_words] back into `out`.  in_place = 0: the kernel writes a second
+ * buffer, preset with what `out` holds on entry -- so a caller sees which words the kernel left alone; in_place != 0: the kernel
+ * trims the staged hits themselves (out == hits on the device: a group member's slot of the gather buffer).
+ * BIGSI_ERR_INVALID, before any device work, for hits or out NULL, wv > stride_words, counters with a counter_bytes other than 2 or 4
+ * or without num_unique / min_kmers, and limit == 0. */
+int bigsi_hip_rank_select_arrays(int device, const uint64_t *hits, uint64_t stride_words, uint32_t wv, uint32_t n_seqs, const void *counters,
+                                 uint32_t counter_bytes, const uint32_t *num_unique, const uint32_t *min_kmers, const uint64_t *excluded,
+                                 uint32_t limit, uint32_t in_place, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

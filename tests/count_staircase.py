@@ -103,10 +103,10 @@ def make_fillers(main, n, fmax, seed):
 
 class Staircase(object):
     """The staircase of one main sequence.  Attributes: u, thresholds, mks (min_kmers of the main per threshold), targets, columns
-    (list of (column, target, family)), edges (the named edge columns), row_ids (uint64, ascending) and packed (uint8[rows,
+    (list of (column, target, family); `columns=` gives them instead of the general staircase), edges (the named edge columns), row_ids (uint64, ascending) and packed (uint8[rows,
     ceil(n_cols / 8)]): the rows to write."""
 
-    def __init__(self, s, h, m, n_cols, thresholds, seed, tile_words=(), late_from=None):
+    def __init__(self, s, h, m, n_cols, thresholds, seed, tile_words=(), late_from=None, columns=None):
         self.main, self.h, self.m, self.n_cols, self.seed = s, h, m, n_cols, seed
         first, _ = coracle.unique_kmers(s, K)
         self.u = u = len(first)
@@ -121,6 +121,13 @@ class Staircase(object):
         rng = np.random.default_rng(seed)
         orders = {"early": np.arange(u), "late": np.arange(u)[::-1].copy(), "scattered": rng.permutation(u)}
         done = {f: self._completion(orders[f]) for f in FAMILIES}
+        if columns is not None:
+            # the caller's own columns instead of the general staircase (tests/rank_cases.py): placed by the same bisection
+            self.columns = [(int(c), int(t), f) for c, t, f in columns]
+            self.edges = sorted(c for c, _, _ in self.columns)
+            assert len(set(self.edges)) == len(self.edges) and 0 <= self.edges[0] and self.edges[-1] < n_cols and late_from is None
+            self._place(orders, done)
+            return
 
         # the general staircase lies in [0, hi); with late_from the columns from there on hold late-family columns at mk - 1 and mk only
         hi = n_cols if late_from is None else late_from
@@ -141,6 +148,9 @@ class Staircase(object):
             late_t = sorted({t for mk in self.mks for t in (mk - 1, mk)})
             self.columns += [(c, late_t[i % len(late_t)], "late") for i, c in enumerate(self.late_edges)]
             self.edges = self.edges + self.late_edges
+        self._place(orders, done)
+
+    def _place(self, orders, done):
         for c, t, f in self.columns:
             length = self._bisect(done[f], t)
             rows = np.unique(self.kidx[orders[f][:length]])

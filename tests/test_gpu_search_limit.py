@@ -156,7 +156,8 @@ def test_multi_digit_selection_gene_length_query(ranked):
 
 
 def test_uint32_counters():
-    """> 65 535 k-mers in one query: 32-bit counters, three digits."""
+    """> 65 535 k-mers in one query: 32-bit counters.  66 000 k-mers are 17 bits: TWO 12-bit digits (the third pass needs 2^24 unique
+    k-mers in one query and is reached through bigsi_hip_rank_select_arrays only: tests/test_gpu_rank_select.py)."""
     from bigsi_amd.storage import get_storage
     from oracle.ref_model import SynthOracle
     m, n_cols, h = 1009, 100, 2

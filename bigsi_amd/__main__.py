@@ -26,6 +26,17 @@ def positive_int(text):
     return n
 
 
+def non_negative_int(text):
+    """argparse type of --margin: an integer >= 0."""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("invalid int value: %r" % text)
+    if n < 0:
+        raise argparse.ArgumentTypeError("must be >= 0, got %d" % n)
+    return n
+
+
 def get_config_from_file(config_file):            # __main__.py:86-94
     config_file = config_file or os.environ.get("BIGSI_CONFIG")
     if not config_file:
@@ -164,7 +175,17 @@ def build_parser():
     sp.add_argument("--window", "-w", type=int, required=True, metavar="W", help="window length in k-mer positions (1 .. 65535)")
     sp.add_argument("--threshold", "-t", type=float, default=1.0)
     sp.add_argument("--format", choices=["json", "csv"], default="json")
-    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally", "window_search"):          # (named so that the refusal says why)
+    sp = common(sub.add_parser("classify", help="for every record of a FASTA file: which group of samples it belongs to (the hits of each group weighed "
+                                                "on the device; one line per record)"))
+    sp.add_argument("fasta")
+    sp.add_argument("--groups", required=True, metavar="FILE", help="sample<TAB>group lines, as for collapse; a group's id follows its first appearance")
+    sp.add_argument("--threshold", "-t", type=float, default=1.0)
+    sp.add_argument("--margin", type=non_negative_int, default=1, metavar="D",
+                    help="assign a record hit by several groups only when the best group found at least D k-mers more than the next (default 1)")
+    sp.add_argument("--others", default=None, metavar="NAME", help="samples the file does not name form one more group called NAME")
+    sp.add_argument("--format", choices=["tsv", "json"], default="tsv")
+    sp.add_argument("--summary-only", action="store_true", help="reads per group, ambiguous, unclassified and skipped only")
+    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally", "window_search", "classify"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -309,6 +330,16 @@ def tally_text(index, queries, threshold=1.0, limit=None, fmt="json"):
     return to_csv(rec) if fmt == "csv" else to_json(rec)
 
 
+def classify_text(index, records, pairs, threshold=1.0, margin=1, others=None, fmt="tsv", summary_only=False):
+    """`classify`: BIGSI.classify over the (name, sequence) records of a FASTA file.  TSV: name, verdict, group, best_found, num_kmers,
+    second group, second_found, best sample -- one line per record, the summary behind them as `# key<TAB>value` lines; JSON: the
+    result, each record with its "name" first."""
+    from .classify import to_json, to_tsv
+    names = [n for n, _ in records]
+    res = index.classify([s for _, s in records], pairs, threshold=threshold, margin=margin, others=others)
+    return to_json(res, names, summary_only) if fmt == "json" else to_tsv(res, names, summary_only)
+
+
 def window_search_text(index, queries, window, threshold=1.0, fmt="json"):
     """`window_search`: BIGSI.search_windows_many over the queries, one device call per query (a long query is a call's worth of work,
     and the device keeps counters per sequence).  JSON: the dicts, each with its "query" first; CSV: record,<result fields>, one line
@@ -386,6 +417,18 @@ def main(argv=None):
         p.error("%s is not available with --sharded: pairs of samples on different shards are not implemented (use a single index)" % a.cmd)
     if getattr(a, "sharded", False) and a.cmd == "tally":
         p.error("tally is not available with --sharded: the per-shard sums plus a host merge are not implemented (use a single index)")
+    if getattr(a, "sharded", False) and a.cmd == "classify":
+        p.error("classify is not available with --sharded: a group's samples may lie on several shards and the per-shard records plus a host merge "
+                "are not implemented (use a single index)")
+    if a.cmd == "classify":
+        from .collapse import check_groups
+        if not a.threshold <= 1:
+            p.error("classify: the threshold must be <= 1, got %r" % (a.threshold,))
+        try:
+            classify_pairs = collapse_groups(a.groups)
+            check_groups(classify_pairs)
+        except (OSError, ValueError) as e:
+            p.error("classify --groups: %s" % e)
     if getattr(a, "sharded", False) and a.cmd == "window_search":
         p.error("window_search is not available with --sharded: the per-shard sweep is not implemented (use a single index)")
     if a.cmd == "window_search" and (a.seq is None) == (a.fasta is None):
@@ -481,6 +524,8 @@ def main(argv=None):
         print(window_search_text(BIGSI(config), queries, a.window, a.threshold, a.format))
     elif a.cmd == "tally":
         print(tally_text(BIGSI(config), [s for _, s in read_fasta(a.fasta)], a.threshold, a.limit, a.format))
+    elif a.cmd == "classify":
+        print(classify_text(BIGSI(config), read_fasta(a.fasta), classify_pairs, a.threshold, a.margin, a.others, a.format, a.summary_only))
     elif a.cmd == "distances":
         against = None
         if a.against_file:

@@ -25,6 +25,7 @@
 #include "bigsi_cpu_prevalence.h"
 #include "bigsi_cpu_window.h"
 #include "bigsi_cpu_tally.h"
+#include "bigsi_cpu_classify.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1135,6 +1136,59 @@ int bigsi_cpu_search_tally(bigsi_cpu_index *ix, const char *seqs, const uint64_t
     memcpy(queries_hit, hit.data(), n_cols * 8);
     memcpy(kmers_found, found.data(), n_cols * 8);
     memcpy(totals, tot, sizeof tot);
+    return BIGSI_OK;
+}
+
+// read classification: every sequence searched in the reference's shape, its hits (ascending colours, each with the k-mers found)
+// weighed per group -- the number of hit columns, the largest count and the first colour that holds it --, then the two best hit
+// groups by (found descending, lower id).  A threshold below 0 asks for what 0 asks for.
+int bigsi_cpu_classify(bigsi_cpu_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
+                       const uint32_t *group_of, uint64_t n_entries, uint32_t n_groups, bigsi_hip_classify_record *records)
+{
+    if (!ix || !group_of || !records) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_seqs(seqs, offsets, n_seqs, k));
+    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    if (n_entries != ix->n_cols)
+        return fail(BIGSI_ERR_INVALID, "group_of has %llu entries, the index has %llu columns", (unsigned long long)n_entries, (unsigned long long)ix->n_cols);
+    if (n_groups == 0 || n_groups > BIGSI_CLASSIFY_MAX_GROUPS) return fail(BIGSI_ERR_INVALID, "n_groups must be 1 .. %u (got %u)", BIGSI_CLASSIFY_MAX_GROUPS, n_groups);
+    for (uint64_t c = 0; c < n_entries; c++)
+        if (group_of[c] != BIGSI_CLASSIFY_NONE && group_of[c] >= n_groups)
+            return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither below n_groups (%u) nor BIGSI_CLASSIFY_NONE", (unsigned long long)c, group_of[c], n_groups);
+    const uint64_t n_cols = ix->n_cols;
+    std::vector<uint32_t> col(n_cols), cnt(n_cols), samples(n_groups), found(n_groups), colour(n_groups);
+    std::vector<bigsi_hip_classify_record> out(n_seqs);
+    QueryKmers q;
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        uint32_t nk, nu, mk;
+        Hits hits{nullptr, col.data(), cnt.data(), n_cols};
+        search_reference_shaped(ix, seqs + offsets[i], offsets[i + 1] - offsets[i], k, threshold < 0.0 ? 0.0 : threshold, q, &nk, &nu, &mk, hits);
+        bigsi_hip_classify_record r = {0, 0, 0, 0, BIGSI_CLASSIFY_NONE, 0, BIGSI_CLASSIFY_NONE, 0, BIGSI_CLASSIFY_NONE, 0, BIGSI_CLASSIFY_NONE, 0};
+        if (nu) {
+            r.num_unique = nu;
+            r.min_kmers = mk;
+            std::fill(samples.begin(), samples.end(), 0u);
+            for (uint64_t j = 0; j < hits.total; j++) {
+                const uint32_t g = group_of[col[j]];
+                if (g == BIGSI_CLASSIFY_NONE) continue;
+                r.samples_hit++;
+                if (samples[g]++ == 0 || cnt[j] > found[g]) { found[g] = cnt[j]; colour[g] = col[j]; }
+            }
+            for (uint32_t g = 0; g < n_groups; g++) {
+                if (!samples[g]) continue;
+                r.groups_hit++;
+                if (r.best_group == BIGSI_CLASSIFY_NONE || found[g] > r.best_found) {
+                    r.second_group = r.best_group; r.second_found = r.best_found; r.second_colour = r.best_colour; r.second_samples_hit = r.best_samples_hit;
+                    r.best_group = g; r.best_found = found[g]; r.best_colour = colour[g]; r.best_samples_hit = samples[g];
+                } else if (r.second_group == BIGSI_CLASSIFY_NONE || found[g] > r.second_found) {
+                    r.second_group = g; r.second_found = found[g]; r.second_colour = colour[g]; r.second_samples_hit = samples[g];
+                }
+            }
+        }
+        out[i] = r;
+    }
+    TRY(bdb_read_failed(ix));
+    memcpy(records, out.data(), n_seqs * sizeof(bigsi_hip_classify_record));
     return BIGSI_OK;
 }
 

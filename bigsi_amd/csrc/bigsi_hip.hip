@@ -392,6 +392,11 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
             bigsi_hip_batch_destroy(w);
             w = nullptr;
         }
+    for (bigsi_hip_batch *&w : ix->classify_ws)
+        if (w) {
+            bigsi_hip_batch_destroy(w);
+            w = nullptr;
+        }
     if (ix->window_ws) {
         bigsi_hip_batch_destroy(ix->window_ws);
         ix->window_ws = nullptr;
@@ -412,7 +417,11 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
         if (ix->pin_ev[s_]) e = hipEventDestroy(ix->pin_ev[s_]);
         ix->dev_rows[s_].release();
         ix->dev_ids[s_].release();
+        if (ix->classify_pin[s_]) e = hipHostFree(ix->classify_pin[s_]);
+        if (ix->classify_ev[s_]) e = hipEventDestroy(ix->classify_ev[s_]);
+        ix->classify_rec[s_].release();
     }
+    ix->classify_groups.release();
     if (ix->view_of) ix->view_of->views--;
     if (ix->d_index && ix->attach == bigsi_hip_index::kOwner) e = hipFree(ix->d_index);
     else if (ix->d_index && ix->attach == bigsi_hip_index::kIpc) e = hipIpcCloseMemHandle(ix->d_index);
@@ -3429,6 +3438,163 @@ extern "C" int bigsi_hip_tally_fetch(bigsi_hip_tally *t, uint64_t *queries_hit, 
     tot[2] += t->host_skipped;
     memcpy(totals, tot, sizeof tot);
     return BIGSI_OK;
+}
+
+// Read classification (include/bigsi_hip_classify.h; k_classify_groups, launch shape: plan_classify): per query the two best groups of
+// samples over the result vectors of a run made with BIGSI_RUN_SKIP_COMPACT.  The index keeps the uploaded group_of, a device record
+// buffer per stream slot and, for the stream call, a pinned twin and an event per slot.
+static_assert(sizeof(bigsi_hip_classify_record) == 48, "record layout: three uint4 per query (k_classify_groups)");
+constexpr bigsi_hip_classify_record kClassifyEmpty = {0, 0, 0, 0, BIGSI_CLASSIFY_NONE, 0, BIGSI_CLASSIFY_NONE, 0, BIGSI_CLASSIFY_NONE, 0, BIGSI_CLASSIFY_NONE, 0};
+
+static int classify_check_groups(const bigsi_hip_index *ix, const uint32_t *group_of, uint64_t n_entries, uint32_t n_groups)
+{
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    if (n_entries != ix->n_cols)
+        return fail(BIGSI_ERR_INVALID, "group_of has %llu entries, the index has %llu columns", (unsigned long long)n_entries, (unsigned long long)ix->n_cols);
+    if (plan_classify(1, ix->wv(), n_groups).bad_groups) return fail(BIGSI_ERR_INVALID, "n_groups must be 1 .. %u (got %u)", kClassifyMaxGroups, n_groups);
+    const uint64_t bad = classify_bad_column(group_of, n_entries, n_groups);
+    if (bad != n_entries)
+        return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither below n_groups (%u) nor BIGSI_CLASSIFY_NONE", (unsigned long long)bad, group_of[bad], n_groups);
+    return BIGSI_OK;
+}
+
+// what tally_check_batch refuses, for a batch of its own index
+static int classify_check_batch(const bigsi_hip_batch *b)
+{
+    if (!b->ran) return fail(BIGSI_ERR_STATE, "bigsi_hip_batch_run has not completed for this batch");
+    if (b->compacted || b->fused_run)
+        return fail(BIGSI_ERR_STATE, "the batch's last run built hit lists: a classification takes a run made with BIGSI_RUN_SKIP_COMPACT");
+    if (b->limit) return fail(BIGSI_ERR_STATE, "the batch has a result limit (bigsi_hip_batch_set_limit): a classification weighs every hit");
+    if (b->ext_bitmaps || b->result_cols || b->comm)
+        return fail(BIGSI_ERR_STATE, "the batch has caller-owned bit vectors, a result width or a communicator: a classification takes a batch of one whole index");
+    if (b->run_h != b->ix->h) return fail(BIGSI_ERR_STATE, "num_hashes changed since this batch ran (%u then, %u now): run it again", b->run_h, b->ix->h);
+    if (b->wv != b->ix->wv()) return fail(BIGSI_ERR_STATE, "num_cols changed since this batch ran: run it again");
+    return BIGSI_OK;
+}
+
+// the kernel for a batch whose SKIP_COMPACT run is the last thing queued on its run stream (*pst), its records into `slot`'s device
+// buffer, and the batch's completion event again behind it (the tally's ordering rule: what waits for the run -- reload, destroy --
+// then waits for the kernel's reads of the batch's arrays too).  group_of is on the device already, ordered before the kernel.
+static int classify_launch(bigsi_hip_batch *b, uint32_t n_groups, int slot, hipStream_t *pst)
+{
+    bigsi_hip_index *ix = b->ix;
+    hipStream_t st = b->run_stream ? b->run_stream : ix->stream;
+    *pst = st;
+    const ClassifyPlan p = plan_classify(b->n_seqs, b->wv, n_groups);
+    if (p.too_large || p.bad_groups) return fail(BIGSI_ERR_INVALID, "batch too large for one classification launch (%llu workgroups)", (unsigned long long)p.too_large);
+    TRY(ix->classify_rec[slot].reserve((size_t)b->n_seqs * sizeof(bigsi_hip_classify_record)));
+    const uint64_t *bm = static_cast<const uint64_t *>(b->bit_vectors());
+    const uint64_t cstride = b->wv_pad * 64;
+    EventPair ep{};
+    TRY(bigsi_ev_begin(ix, &ep, st));
+#define BIGSI_CLASSIFY(CountT, EXACT, CNT)                                                                                                  \
+    hipLaunchKernelGGL((k_classify_groups<CountT, EXACT>), dim3((unsigned)p.grid), dim3(p.block), p.lds_bytes, st, bm, b->wv_pad, (uint32_t)b->wv, \
+                       ix->n_cols, b->num_unique.as<uint32_t>(), b->threshold, CNT, cstride, ix->classify_groups.as<uint32_t>(), n_groups,   \
+                       p.table_bytes, ix->classify_rec[slot].as<uint4>())
+    if (b->exact) BIGSI_CLASSIFY(uint16_t, true, (const uint16_t *)nullptr);
+    else if (b->count_bytes == 2) BIGSI_CLASSIFY(uint16_t, false, static_cast<const uint16_t *>(b->counters()));
+    else BIGSI_CLASSIFY(uint32_t, false, static_cast<const uint32_t *>(b->counters()));
+#undef BIGSI_CLASSIFY
+    HIP_TRY(hipGetLastError());
+    TRY(bigsi_ev_end(ix, &ep, ix->ev_cp, st, 1));      // (timed with the compaction it stands in for: bigsi_hip_stats' compact_ms)
+    if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(b->done, st));
+    b->done_stale = false;
+    b->run_stream = st;
+    b->idle = false;
+    if (st == ix->stream) TRY(mark_main(ix));
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_classify_batch(bigsi_hip_batch *b, const uint32_t *group_of, uint64_t n_entries, uint32_t n_groups,
+                                        bigsi_hip_classify_record *records, uint64_t capacity)
+{
+    BIGSI_ENTER(b ? b->ix : nullptr);
+    if (!b || !group_of || !records) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    bigsi_hip_index *ix = b->ix;
+    TRY(classify_check_groups(ix, group_of, n_entries, n_groups));
+    TRY(classify_check_batch(b));
+    if (capacity < b->n_seqs)
+        return fail(BIGSI_ERR_CAPACITY, "the record buffer holds %llu entries, %u needed", (unsigned long long)capacity, b->n_seqs);
+    TRY(use_device(ix));
+    hipStream_t st = b->run_stream ? b->run_stream : ix->stream;
+    TRY(ix->classify_groups.reserve((size_t)n_entries * 4));
+    HIP_TRY(hipMemcpyAsync(ix->classify_groups.p, group_of, (size_t)n_entries * 4, hipMemcpyHostToDevice, st));
+    TRY(classify_launch(b, n_groups, 0, &st));
+    HIP_TRY(hipMemcpyAsync(records, ix->classify_rec[0].p, (size_t)b->n_seqs * sizeof(bigsi_hip_classify_record), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return BIGSI_OK;
+}
+
+// Two workspaces of the index (classify_ws), never the search stream's or the tally's: chunk i is staged into workspace i & 1 -- host
+// work, which first waits for that workspace's chunk i - 2 -- while chunk i - 1 runs; the records of chunk i - 1 are collected (its
+// slot's event, then a host copy out of the pinned twin) once chunk i is queued.
+static int classify_collect(bigsi_hip_index *ix, int slot, bigsi_hip_classify_record *dst, uint64_t n)
+{
+    HIP_TRY(hipEventSynchronize(ix->classify_ev[slot]));
+    memcpy(dst, ix->classify_pin[slot], (size_t)n * sizeof(bigsi_hip_classify_record));
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_classify_stream(bigsi_hip_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
+                                         const uint32_t *group_of, uint64_t n_entries, uint32_t n_groups, bigsi_hip_classify_record *records)
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !offsets || !group_of || !records) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    if (n_seqs == 0) return fail(BIGSI_ERR_INVALID, "a batch needs at least one sequence");
+    if (k == 0) return fail(BIGSI_ERR_INVALID, "k must be > 0");
+    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
+    for (uint64_t i = 0; i < n_seqs; i++)
+        if (offsets[i + 1] < offsets[i]) return fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing");
+    if (offsets[n_seqs] - offsets[0] && !seqs) return fail(BIGSI_ERR_INVALID, "seqs is NULL");
+    TRY(classify_check_groups(ix, group_of, n_entries, n_groups));
+    TRY(use_device(ix));
+    const size_t slot_bytes = (size_t)kTallyChunkSeqs * sizeof(bigsi_hip_classify_record);
+    for (int s = 0; s < 2; s++) {
+        if (!ix->classify_pin[s]) HIP_TRY(hipHostMalloc(&ix->classify_pin[s], slot_bytes, hipHostMallocDefault));
+        if (!ix->classify_ev[s]) HIP_TRY(hipEventCreateWithFlags(&ix->classify_ev[s], hipEventDisableTiming));
+    }
+    TRY(ix->classify_groups.reserve((size_t)n_entries * 4));
+    HIP_TRY(hipMemcpyAsync(ix->classify_groups.p, group_of, (size_t)n_entries * 4, hipMemcpyHostToDevice, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));      // (a pageable source: the upload is over before the caller's array can change, whichever stream a chunk runs on)
+    const bool exact = threshold == 1.0;
+    const uint64_t wv_pad = round_up(ix->wv(), 2);
+    int rc = BIGSI_OK;
+    uint64_t chunk = 0, pend_s0 = 0, pend_n = 0;      // the chunk whose records are still on their way: slot pend_slot
+    int pend_slot = -1;
+    for (uint64_t s0 = 0; s0 < n_seqs && rc == BIGSI_OK;) {
+        const uint64_t s1 = tally_chunk_end(offsets, n_seqs, s0, k, wv_pad, exact ? 0u : 4u);
+        bool any_pos = false;
+        for (uint64_t s = s0; s < s1 && !any_pos; s++) any_pos = offsets[s + 1] - offsets[s] >= k;
+        if (!any_pos) std::fill(records + s0, records + s1, kClassifyEmpty);
+        else {
+            const int slot = (int)(chunk & 1);
+            bigsi_hip_batch **ws = &ix->classify_ws[slot];
+            hipStream_t st = nullptr;
+            rc = bigsi_batch_stage(ix, ws, seqs, offsets + s0, (uint32_t)(s1 - s0), k);
+            // (hits-only counters below threshold 1: the kernel reads a counter only under a set bit, and a word that holds one keeps all 64)
+            if (rc == BIGSI_OK) rc = bigsi_batch_run(*ws, threshold, BIGSI_RUN_SKIP_COMPACT | (exact ? 0u : (uint32_t)BIGSI_RUN_SPARSE_COUNTS), false);
+            if (rc == BIGSI_OK) rc = classify_check_batch(*ws);
+            if (rc == BIGSI_OK) rc = classify_launch(*ws, n_groups, slot, &st);
+            if (rc == BIGSI_OK) {
+                hipError_t e = hipMemcpyAsync(ix->classify_pin[slot], ix->classify_rec[slot].p, (size_t)(s1 - s0) * sizeof(bigsi_hip_classify_record), hipMemcpyDeviceToHost, st);
+                if (e == hipSuccess) e = hipEventRecord(ix->classify_ev[slot], st);
+                if (e != hipSuccess) rc = fail(BIGSI_ERR_HIP, "queueing the record download: %s", hipGetErrorString(e));
+            }
+            if (rc == BIGSI_OK && pend_slot >= 0) rc = classify_collect(ix, pend_slot, records + pend_s0, pend_n);
+            if (rc == BIGSI_OK) { pend_slot = slot; pend_s0 = s0; pend_n = s1 - s0; }
+            chunk++;
+        }
+        s0 = s1;
+    }
+    if (rc == BIGSI_OK && pend_slot >= 0) rc = classify_collect(ix, pend_slot, records + pend_s0, pend_n);
+    if (rc != BIGSI_OK)
+        for (bigsi_hip_batch *&w : ix->classify_ws) {
+            bigsi_hip_batch *b = w;
+            w = nullptr;
+            if (b) bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
+        }
+    return rc;
 }
 
 // K5 at scale: the presence strings of all hits of the batch (see k_presence_bits).  The host sorts each sequence's hits by

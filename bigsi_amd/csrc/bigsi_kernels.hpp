@@ -4018,4 +4018,131 @@ __global__ __launch_bounds__(kBlock) void k_tally_totals(
     }
 }
 
+// ------------------------------------------------------------------------------ read classification: per-query verdicts over sample groups
+// The horizontal sum over the result vectors a run made with BIGSI_RUN_SKIP_COMPACT left behind (include/bigsi_hip_classify.h has the
+// definition): per query and group of columns how many columns are hit, the largest count among them and the lowest colour that
+// holds it; out of the device go the two best groups, twelve uint32 per query.
+//
+// k_classify_groups (launch shape: plan_classify): ONE workgroup per query.
+//   pass 1  the threads OR the query's wv words (thread = word: coalesced, kTallyLoads loads in flight) under valid_mask -- bits behind
+//           num_cols are never trusted, the pad word of wv_pad is never read.  A query without k-mers, or without a set bit -- nearly
+//           all of a hit-sparse stream --, writes its empty record and leaves before any LDS table is touched.
+//   table   dynamic LDS, zeroed: best[n_groups] (uint64: found << 32 | 0xFFFFFFFF - colour, so that ONE integer max yields the largest
+//           count and, among its columns, the lowest colour) | hits[n_groups] (uint32) | the wavefronts' partial results.
+//   pass 2  a wavefront reads 64 words again (from L2), votes on the non-zero ones and takes them one after the other in the tally's
+//           layout: lane l = column 64 w + l, bit bit_of_col(l).  A lane whose bit is set loads its group_of entry and, on the
+//           counting path, its counter (both contiguous over the wavefront; in sparse mode all 64 counters of a word that holds a hit
+//           are valid; EXACT: counters is never read, a hit has found = num_unique), and in a group issues an LDS add on hits[g] and an
+//           LDS 64-bit max on best[g].
+//   reduce  after a barrier every thread scans groups g = t, t + kBlock, ... for its two best keys found << 32 | 0xFFFFFFFF - g (found
+//           descending, ties to the lower id; 0: none) and its number of hit groups; a butterfly over the wavefront, the wavefronts'
+//           results through LDS, and thread 0 writes the record.
+// Integer add and max only, no global atomic: the record does not depend on the order anything arrives in.
+constexpr uint32_t kClassifyNone = 0xFFFFFFFFu;       // BIGSI_CLASSIFY_NONE (include/bigsi_hip_classify.h)
+
+__device__ __forceinline__ void classify_merge(unsigned long long &a1, unsigned long long &a2, unsigned long long b1, unsigned long long b2)
+{
+    const unsigned long long lo = a1 < b1 ? a1 : b1, hi2 = a2 > b2 ? a2 : b2;
+    a1 = a1 > b1 ? a1 : b1;
+    a2 = lo > hi2 ? lo : hi2;
+}
+
+template <typename CountT, bool EXACT>
+__global__ __launch_bounds__(kBlock) void k_classify_groups(
+    const uint64_t *__restrict__ bitmaps, uint64_t bm_stride, uint32_t wv, uint64_t n_cols, const uint32_t *__restrict__ num_unique, double threshold,
+    const CountT *__restrict__ counters, uint64_t counter_stride, const uint32_t *__restrict__ group_of, uint32_t n_groups, uint32_t table_bytes,
+    uint4 *__restrict__ records)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    unsigned long long *best = reinterpret_cast<unsigned long long *>(smem);
+    uint32_t *hits = reinterpret_cast<uint32_t *>(smem + (size_t)n_groups * 8);
+    unsigned long long *part = reinterpret_cast<unsigned long long *>(smem + table_bytes);      // [kBlock / 64][3]: key1, key2, groups | samples
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    const uint64_t q = blockIdx.x;
+    const uint64_t *bm = bitmaps + q * bm_stride;
+    uint4 *rec = records + q * 3;
+    const uint32_t u = num_unique[q];
+    const double mkd = ceil((double)u * threshold);          // min_kmers as K1 computes it
+    const uint32_t mk = mkd > 0.0 ? (uint32_t)mkd : 0u;
+    uint64_t any = 0;
+    if (u)
+        for (uint32_t w0 = threadIdx.x; w0 < wv; w0 += kBlock * kTallyLoads) {
+            uint64_t x[kTallyLoads];
+#pragma unroll
+            for (uint32_t j = 0; j < kTallyLoads; j++) x[j] = w0 + kBlock * j < wv ? bm[w0 + kBlock * j] : 0ull;
+#pragma unroll
+            for (uint32_t j = 0; j < kTallyLoads; j++) any |= x[j] & valid_mask(w0 + kBlock * j, n_cols);
+        }
+    if (!__syncthreads_or((int)(any != 0))) {
+        if (threadIdx.x == 0) {
+            rec[0] = make_uint4(u, u ? mk : 0u, 0u, 0u);
+            rec[1] = make_uint4(kClassifyNone, 0u, kClassifyNone, 0u);
+            rec[2] = make_uint4(kClassifyNone, 0u, kClassifyNone, 0u);
+        }
+        return;
+    }
+    for (uint32_t g = threadIdx.x; g < n_groups; g += kBlock) { best[g] = 0ull; hits[g] = 0u; }
+    __syncthreads();
+    const uint32_t bit = bit_of_col(lane);
+    uint32_t samples = 0;                                    // hit columns in any group, counted once per wavefront (uniform)
+    for (uint32_t base = wave * 64; base < wv; base += kBlock) {
+        const uint32_t w0 = base + lane;
+        const uint64_t x = w0 < wv ? bm[w0] & valid_mask(w0, n_cols) : 0ull;
+        uint64_t todo = __ballot((int)(x != 0));
+        while (todo) {
+            const int src = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const uint64_t xw = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), src) << 32) |
+                                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, src);
+            const uint64_t col = (uint64_t)(base + (uint32_t)src) * 64 + lane;          // < n_cols wherever the bit is set (valid_mask)
+            const bool mine = (xw >> bit) & 1ull;
+            const uint32_t g = mine ? group_of[col] : kClassifyNone;
+            const bool grouped = g != kClassifyNone;
+            samples += (uint32_t)__popcll(__ballot((int)grouped));
+            if (grouped) {
+                const uint32_t found = EXACT ? u : (uint32_t)counters[q * counter_stride + col];
+                atomicAdd(&hits[g], 1u);
+                atomicMax(&best[g], ((unsigned long long)found << 32) | (0xFFFFFFFFu - (uint32_t)col));
+            }
+        }
+    }
+    __syncthreads();
+    unsigned long long k1 = 0, k2 = 0;
+    uint32_t groups = 0;
+    for (uint32_t g = threadIdx.x; g < n_groups; g += kBlock)
+        if (hits[g]) {
+            groups++;
+            classify_merge(k1, k2, (best[g] & 0xFFFFFFFF00000000ull) | (0xFFFFFFFFu - g), 0ull);
+        }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o1 = __shfl_xor(k1, d), o2 = __shfl_xor(k2, d);
+        classify_merge(k1, k2, o1, o2);
+        groups += __shfl_xor(groups, d);
+    }
+    if (lane == 0) { part[wave * 3] = k1; part[wave * 3 + 1] = k2; part[wave * 3 + 2] = ((unsigned long long)groups << 32) | samples; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t samples_all = 0;
+        groups = 0;
+        k1 = k2 = 0;
+        for (uint32_t i = 0; i < kBlock / 64; i++) {
+            classify_merge(k1, k2, part[i * 3], part[i * 3 + 1]);
+            groups += (uint32_t)(part[i * 3 + 2] >> 32);
+            samples_all += (uint32_t)part[i * 3 + 2];
+        }
+        uint4 place[2];
+        const unsigned long long key[2] = {k1, k2};
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const uint32_t g = 0xFFFFFFFFu - (uint32_t)key[i];
+            place[i] = key[i] ? make_uint4(g, (uint32_t)(best[g] >> 32), 0xFFFFFFFFu - (uint32_t)best[g], hits[g])
+                              : make_uint4(kClassifyNone, 0u, kClassifyNone, 0u);
+        }
+        rec[0] = make_uint4(u, mk, groups, samples_all);
+        rec[1] = place[0];
+        rec[2] = place[1];
+    }
+}
+
 }   // namespace bigsi

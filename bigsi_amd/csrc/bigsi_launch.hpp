@@ -1019,6 +1019,40 @@ static inline std::vector<uint64_t> plan_tally_chunks(const uint64_t *offsets, u
     return cut;
 }
 
+// ------------------------------------------------------------------------------ read classification (k_classify_groups)
+// One workgroup of kBlock threads per query.  Dynamic LDS: the per-group table best[n_groups] (uint64) | hits[n_groups] (uint32), rounded
+// up to 16 bytes, and behind it three uint64 per wavefront for the final reduction -- 48 KiB + 96 bytes at kClassifyMaxGroups, three
+// workgroups per CU; a table of a hundred groups does not bound the occupancy.  A query whose result vector is empty leaves before it
+// touches the table (pass 1 of the kernel), so the grid is the batch, whatever the hit density.  Refused: more than 2^31 - 1 workgroups,
+// n_groups outside 1 .. kClassifyMaxGroups.
+constexpr uint32_t kClassifyMaxGroups = 4096;               // BIGSI_CLASSIFY_MAX_GROUPS (include/bigsi_hip_classify.h)
+constexpr uint32_t kClassifyNoGroup = 0xFFFFFFFFu;          // BIGSI_CLASSIFY_NONE
+struct ClassifyPlan {
+    uint32_t block = kBlock;
+    uint64_t grid = 0;
+    uint32_t table_bytes = 0, lds_bytes = 0;                  // the table alone; with the wavefronts' partial results (the launch's dynamic LDS)
+    uint64_t too_large = 0;                                   // != 0: the workgroups one launch would take (more than 2^31 - 1): refused
+    bool bad_groups = false;                                  // n_groups is 0 or above kClassifyMaxGroups: refused
+};
+static inline ClassifyPlan plan_classify(uint64_t n_seqs, uint64_t wv, uint64_t n_groups)
+{
+    ClassifyPlan p;
+    (void)wv;                                                 // (a workgroup sweeps its query's words itself: the width changes no launch figure)
+    p.grid = n_seqs;
+    if (n_seqs > 0x7FFFFFFFull) p.too_large = n_seqs;
+    if (n_groups == 0 || n_groups > kClassifyMaxGroups) { p.bad_groups = true; return p; }
+    p.table_bytes = (uint32_t)round_up(n_groups * 12, 16);
+    p.lds_bytes = p.table_bytes + (kBlock / 64) * 3 * 8;
+    return p;
+}
+// the first column whose group_of entry is neither below n_groups nor kClassifyNoGroup; n_entries when every entry is fine
+static inline uint64_t classify_bad_column(const uint32_t *group_of, uint64_t n_entries, uint64_t n_groups)
+{
+    for (uint64_t c = 0; c < n_entries; c++)
+        if (group_of[c] != kClassifyNoGroup && group_of[c] >= n_groups) return c;
+    return n_entries;
+}
+
 // ------------------------------------------------------------------------------ windowed search (k_window_max, k_window_combine)
 // plan_window_search: sequence q of a batch has n[q] k-mer positions, a window of We = min(W, n[q]) of them and the window starts
 // [0, n[q] - We]; the sweep cuts every sequence's starts into segments of at most S and a wavefront of k_window_max owns one

@@ -899,6 +899,69 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
                 return None
         return record(hit, found, totals, name_of, excluded, limit)
 
+    # ------------------------------------------------------------------ read classification
+    def _classify_groups(self, groups, others):
+        """(group_of uint32[matrix columns], group names) of classify.classify_plan over this index's colours: a deleted sample, a
+        colour without a metadata record and a column behind the metadata are in no group."""
+        from ..classify import NONE, classify_plan
+        names = []
+        for c in range(self.num_samples):
+            try:
+                names.append(self.colour_to_sample(c))
+            except KeyError:
+                names.append(DELETION_SPECIAL_SAMPLE_NAME)
+        group_of, group_names = classify_plan(names, groups, others)
+        n_cols = int(self.storage.get_integer("number_of_cols"))
+        full = np.full(n_cols, NONE, dtype=np.uint32)
+        full[:min(n_cols, group_of.size)] = group_of[:n_cols]
+        return full, group_names
+
+    def classify_arrays(self, seqs, groups, threshold=1.0, others=None, batch_kmers=1 << 19):
+        """The per-record question of a read set: which GROUP of samples does each sequence belong to -- answered on the device
+        (bigsi_hip_classify_stream: per sequence and group the hits search(seq, threshold) reports are weighed behind the row-AND
+        kernels; no hit list is built and 48 bytes per sequence leave the device).  Yields (chunk, records) per slice of the input:
+        the slice's sequences and a structured array of classify.RECORD_DTYPE, one record each, whose group ids index the names
+        classify.classify_plan(names, groups, others) gives.  `groups` is what collapse takes (a mapping group -> [samples] or (sample,
+        group) pairs); `seqs` is any iterable of ASCII sequences, fed in slices of about 8 x `batch_kmers` k-mers, as tally slices its
+        input.  Multi-GPU (devices=[...]) indexes are refused."""
+        if isinstance(seqs, (str, bytes)):
+            raise TypeError("seqs must be an iterable of sequences, got %r" % type(seqs))
+        if not threshold <= 1:
+            raise ValueError("threshold must be <= 1, got %r" % (threshold,))
+        from ..collapse import check_groups
+        check_groups(groups)
+        self._refuse_group("read classification")
+        k = int(self.kmer_size)
+        with self._device_lock():
+            group_of, group_names = self._classify_groups(groups, others)
+            for chunk in self._slices(iter(seqs), 64, None, batch_kmers * 8, k):
+                for s in chunk:
+                    if not isinstance(s, str) or not s.isascii():
+                        raise ValueError("read classification takes ASCII sequences (queries with other characters are out of scope)")
+                yield chunk, self.storage.classify(chunk, k, threshold, group_of, len(group_names))
+
+    def classify(self, seqs, groups, threshold=1.0, margin=1, others=None):
+        """classify_arrays over all of `seqs`, as names: {"groups": [group names in id order], "records": [one dict per sequence:
+        "verdict" (assigned / ambiguous / unclassified / skipped), "group" (the assigned group), "best_sample" (the lowest sample of
+        the best group that found most k-mers), "num_kmers", "min_kmers", "groups_hit", "samples_hit" and best_* / second_* with group
+        names for ids], "summary": {"reads", "assigned": {group: reads}, "ambiguous", "unclassified", "skipped"}}.  The verdict rule is
+        classify.verdicts': assigned when one group is hit or the best group found at least `margin` k-mers more than the next.  A
+        colour the metadata has no record of is reported by its colour alone."""
+        from ..classify import RECORD_DTYPE, result, verdicts
+        verdicts(np.zeros(0, RECORD_DTYPE), [], margin)          # (the margin is checked before any device call)
+        parts = [rec for _, rec in self.classify_arrays(seqs, groups, threshold, others)]
+        records = np.concatenate(parts) if parts else np.zeros(0, RECORD_DTYPE)
+        with self._device_lock():
+            _, group_names = self._classify_groups(groups, others)
+        n = self.num_samples
+
+        def name_of(c):          # (a column the metadata has no record of is reported by its colour alone)
+            try:
+                return self.colour_to_sample(c) if c < n else None
+            except KeyError:
+                return None
+        return result(records, group_names, name_of, margin)
+
     # ------------------------------------------------------------------ column compaction: vacuum / extract
     def _colour_names(self):
         """names[c] of every colour, DELETION_SPECIAL_SAMPLE_NAME for a deleted one; the matrix must be as wide as the metadata."""

@@ -679,6 +679,23 @@ class HipHbmStorage(BaseStorage):
         finally:
             t.close()
 
+    def classify(self, seqs, k, threshold, group_of, n_groups):
+        """Per sequence the two best groups of samples (bigsi_hip_classify_stream: the hits of every group are weighed on the device, 48
+        bytes per sequence leave it; include/bigsi_hip_classify.h).  group_of: one uint32 per column, below n_groups or
+        bigsi_amd.classify.NONE.  Returns a structured array of bigsi_amd.classify.RECORD_DTYPE[len(seqs)]."""
+        from ..classify import RECORD_DTYPE
+        self._single_gpu("read classification")
+        res = self._opened()
+        seqs = list(seqs)
+        records = np.zeros(len(seqs), RECORD_DTYPE)
+        if not seqs:
+            return records
+        group_of = np.ascontiguousarray(group_of, dtype=np.uint32)
+        blob, off = _lib.pack_seqs(seqs)
+        check(_lib.lib().bigsi_hip_classify_stream(self.handle, blob, _lib.ptr(off), len(seqs), int(k), float(threshold), _lib.ptr(group_of), group_of.size,
+                                                   int(n_groups), _lib.ptr(records)))
+        return records
+
     def fill_synthetic(self, seed, shard=0, and_draws=2):
         if self.res.is_group:       # shard i of the group is filled as (seed, shard i)
             check(_lib.lib().bigsi_hip_group_fill_synthetic(self.res.ix, int(seed), int(and_draws)))

@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] [window] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] [classify] [window] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -847,6 +847,81 @@ def tally():
     reads = rand_seqs(rng, 65536, 61)
     for thr in (1.0, 0.4):
         line("tally_c2_reads", st, 10_000, reads, thr, "65 536 reads of 61 bp: the search stream takes the one-launch read kernel, the tally the non-fused route")
+    st.delete_all()
+
+
+def classify():
+    """Read classification (bigsi_hip_classify_stream) beside the query-set tally (bigsi_hip_tally_add_stream + fetch) on the same input
+    in the same run -- the tally's inputs: 8192 x 1 kbp on the C3 index (10 M x 100 k, h = 4), hit-sparse as drawn and hit-dense (every
+    16th query held whole by 1 % of the samples), at threshold 1.0 and 0.4; 65 536 reads of 61 bp on 1 M x 10 k, h = 3.  group_of: 100
+    groups of neighbouring colours.  Per line: wall ms of one call of each (best of 3 after a warm call, the two alternating; the
+    tally's includes its reset and fetch), their ratio, and from one profiled call of each (level 1, runs of their own) the kernel's own
+    time by HIP events (k_classify_groups, resp. k_tally_hits + k_tally_totals: compact_ms of bigsi_hip_stats) beside that call's
+    row-AND and K1 time."""
+    L = _lib.lib()
+    from bigsi_amd.classify import RECORD_DTYPE
+
+    def line(name, st, n_cols, seqs, thr, note):
+        blob, off = _lib.pack_seqs(seqs)
+        t = st.new_tally()
+        n_groups = 100
+        group_of = (np.arange(n_cols, dtype=np.uint64) * n_groups // n_cols).astype(np.uint32)
+        records = np.zeros(len(seqs), RECORD_DTYPE)
+
+        def tally_call():
+            t.reset()
+            check(L.bigsi_hip_tally_add_stream(t.b, blob, _lib.ptr(off), len(seqs), 31, float(thr)))
+            return t.fetch()
+
+        def classify_call():
+            check(L.bigsi_hip_classify_stream(st.handle, blob, _lib.ptr(off), len(seqs), 31, float(thr), _lib.ptr(group_of), n_cols, n_groups, _lib.ptr(records)))
+        tally_call()
+        classify_call()
+        walls_t, walls_c = [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            got = tally_call()
+            t1 = time.perf_counter()
+            classify_call()
+            t2 = time.perf_counter()
+            walls_t.append((t1 - t0) * 1e3)
+            walls_c.append((t2 - t1) * 1e3)
+        check(L.bigsi_hip_set_profiling(st.handle, 1))
+        stats(st)
+        classify_call()
+        sc = stats(st)
+        tally_call()
+        stl = stats(st)
+        check(L.bigsi_hip_set_profiling(st.handle, 0))
+        # the two calls saw the same hits: the records' grouped hit columns sum to the tally's queries_hit (every column is in a group)
+        agree = int(records["samples_hit"].astype(np.uint64).sum()) == int(got[0].sum()) and int((records["num_unique"] > 0).sum()) == int(got[2][0])
+        step_prof = sc.kmerize_ms + sc.and_ms + sc.compact_ms
+        emit(name, threshold=thr, n_seqs=len(seqs), cols=n_cols, n_groups=n_groups, queries_with_groups=int((records["groups_hit"] > 0).sum()),
+             hit_columns=int(records["samples_hit"].astype(np.uint64).sum()), classify_stream_ms=min(walls_c), tally_stream_ms=min(walls_t),
+             classify_over_tally=min(walls_c) / min(walls_t), classify_kernel_ms=sc.compact_ms, classify_row_and_ms=sc.and_ms, classify_k1_ms=sc.kmerize_ms,
+             classify_kernel_frac_of_device=sc.compact_ms / step_prof if step_prof else None, classify_kernel_frac_of_call=sc.compact_ms / min(walls_c),
+             tally_kernels_ms=stl.compact_ms, tally_row_and_ms=stl.and_ms, tally_k1_ms=stl.kmerize_ms, agree_with_tally=agree, note=note)
+        t.close()
+        assert agree, name
+
+    m, n, h = 10_000_000, 100_000, 4
+    st, _ = open_index("classify", m, n, h)
+    rng = np.random.default_rng(11)
+    seqs = rand_seqs(rng, 8192, 1000)
+    for thr in (1.0, 0.4):
+        line("classify_c3_sparse", st, n, seqs, thr, "8192 x 1 kbp as drawn")
+    held, cols = seqs[::16], np.sort(rng.choice(n, size=n // 100, replace=False))
+    t0 = time.time()
+    for c in cols:
+        st.insert_kmers(int(c), held, 31)
+    plant_s = time.time() - t0
+    for thr in (1.0, 0.4):
+        line("classify_c3_dense", st, n, seqs, thr, "every 16th query held by 1 %% of the samples (planted in %.1f s)" % plant_s)
+    st.delete_all()
+    st, _ = open_index("classify_reads", 1_000_000, 10_000, 3)
+    reads = rand_seqs(rng, 65536, 61)
+    for thr in (1.0, 0.4):
+        line("classify_c2_reads", st, 10_000, reads, thr, "65 536 reads of 61 bp")
     st.delete_all()
 
 

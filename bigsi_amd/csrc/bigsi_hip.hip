@@ -368,6 +368,15 @@ static void recycle_events(bigsi_hip_index *ix)
     }
 }
 
+// A workspace of the index is given up: the slot first, then the batch (which waits for its work).  Leaves the thread's error message
+// of a failed call in place.
+static void drop_workspace(bigsi_hip_batch *&w)
+{
+    bigsi_hip_batch *b = w;
+    w = nullptr;
+    if (b) bigsi_hip_batch_destroy(b);
+}
+
 extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
 {
     if (!ix) return BIGSI_OK;
@@ -377,30 +386,10 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
         g.release();      // (the guard must not outlive the handle; whoever closes a handle owns it)
     }
     if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_close: %d view(s) of this index are still open (close them first)", ix->views.load());
-    if (ix->search_ws) {
-        bigsi_hip_batch_destroy(ix->search_ws);
-        ix->search_ws = nullptr;
-    }
-    for (auto &w : ix->stream_ws)
-        if (w) { bigsi_hip_batch_destroy(w); w = nullptr; }
-    if (ix->prevalence_ws) {
-        bigsi_hip_batch_destroy(ix->prevalence_ws);
-        ix->prevalence_ws = nullptr;
-    }
-    for (bigsi_hip_batch *&w : ix->tally_ws)
-        if (w) {
-            bigsi_hip_batch_destroy(w);
-            w = nullptr;
-        }
-    for (bigsi_hip_batch *&w : ix->classify_ws)
-        if (w) {
-            bigsi_hip_batch_destroy(w);
-            w = nullptr;
-        }
-    if (ix->window_ws) {
-        bigsi_hip_batch_destroy(ix->window_ws);
-        ix->window_ws = nullptr;
-    }
+    const std::pair<bigsi_hip_batch **, int> workspaces[] = {{&ix->search_ws, 1},   {ix->stream_ws, 4},   {&ix->prevalence_ws, 1},
+                                                             {ix->tally_ws, 2},     {ix->classify_ws, 2}, {&ix->window_ws, 1}};
+    for (const auto &[ws, n] : workspaces)
+        for (int i = 0; i < n; i++) drop_workspace(ws[i]);
     hipError_t e = hipSetDevice(ix->device);
     e = hipStreamSynchronize(ix->stream);
     if (ix->pre_stream) e = hipStreamSynchronize(ix->pre_stream);
@@ -2963,10 +2952,7 @@ extern "C" int bigsi_hip_kmer_prevalence(bigsi_hip_index *ix, const char *seqs, 
     int rc = bigsi_batch_run(b, 1.0, 0, false);
     if (rc == BIGSI_OK) rc = need_run(b);
     if (rc == BIGSI_OK) rc = prevalence_launch(b, universe, subset, total, in_subset);
-    if (rc != BIGSI_OK) {
-        ix->prevalence_ws = nullptr;
-        bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
-    }
+    if (rc != BIGSI_OK) drop_workspace(ix->prevalence_ws);
     return rc;
 }
 
@@ -3193,10 +3179,7 @@ extern "C" int bigsi_hip_window_search(bigsi_hip_index *ix, const char *seqs, co
     int rc = bigsi_batch_run(b, 1.0, 0, false);
     if (rc == BIGSI_OK) rc = need_run(b);
     if (rc == BIGSI_OK) rc = window_launch(b, window, threshold, window_used, need, hit_offsets, colours, records, capacity);
-    if (rc != BIGSI_OK && rc != BIGSI_ERR_CAPACITY && rc != BIGSI_ERR_INVALID) {
-        ix->window_ws = nullptr;
-        bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
-    }
+    if (rc != BIGSI_OK && rc != BIGSI_ERR_CAPACITY && rc != BIGSI_ERR_INVALID) drop_workspace(ix->window_ws);
     return rc;
 }
 
@@ -3219,6 +3202,95 @@ extern "C" int bigsi_hip_band_set_limits(bigsi_hip_index *ix, uint32_t windows, 
     ix->band_windows = windows;
     ix->band_segs = segments_per_launch;
     return BIGSI_OK;
+}
+
+// Consumers of result vectors (the tally and the classification below): kernels that read what a run made with BIGSI_RUN_SKIP_COMPACT
+// leaves behind -- the per-query result vectors and, below threshold 1, the counters -- for one batch, or for a stream cut into chunks.
+struct VectorConsumer {
+    const char *noun, *every_hit;      // for the refusals: "a tally" "counts" every hit
+    bool host_chunks_take_a_slot;      // consume_stream: a chunk that never goes to the device still advances the workspace slot
+};
+constexpr VectorConsumer kTallyConsumer = {"a tally", "counts", true};
+constexpr VectorConsumer kClassifyConsumer = {"a classification", "weighs", false};
+
+// a batch a consumer may read: a finished SKIP_COMPACT run of one whole index, as the index is now
+static int check_consumer_batch(const bigsi_hip_batch *b, const VectorConsumer &who)
+{
+    if (!b->ran) return fail(BIGSI_ERR_STATE, "bigsi_hip_batch_run has not completed for this batch");
+    if (b->compacted || b->fused_run)
+        return fail(BIGSI_ERR_STATE, "the batch's last run built hit lists: %s takes a run made with BIGSI_RUN_SKIP_COMPACT", who.noun);
+    if (b->limit) return fail(BIGSI_ERR_STATE, "the batch has a result limit (bigsi_hip_batch_set_limit): %s %s every hit", who.noun, who.every_hit);
+    if (b->ext_bitmaps || b->result_cols || b->comm)
+        return fail(BIGSI_ERR_STATE, "the batch has caller-owned bit vectors, a result width or a communicator: %s takes a batch of one whole index", who.noun);
+    if (b->run_h != b->ix->h) return fail(BIGSI_ERR_STATE, "num_hashes changed since this batch ran (%u then, %u now): run it again", b->run_h, b->ix->h);
+    if (b->wv != b->ix->wv()) return fail(BIGSI_ERR_STATE, "num_cols changed since this batch ran: run it again");
+    return BIGSI_OK;
+}
+
+// the stream a consumer's kernels go to: behind the batch's run, the last thing queued on its run stream
+static hipStream_t consumer_stream(const bigsi_hip_batch *b) { return b->run_stream ? b->run_stream : b->ix->stream; }
+
+// The run's counters -> the template instance <CountT, EXACT> a consumer kernel is compiled for: f(EXACT tag, typed counter pointer)
+template <typename F>
+static void with_counters(const bigsi_hip_batch *b, F &&f)
+{
+    if (b->exact) f(std::true_type{}, (const uint16_t *)nullptr);
+    else if (b->count_bytes == 2) f(std::false_type{}, static_cast<const uint16_t *>(b->counters()));
+    else f(std::false_type{}, static_cast<const uint32_t *>(b->counters()));
+}
+
+// The ordering rule, behind a consumer's last kernel on `st`: the batch's completion event is recorded again there, so whatever waits
+// for the run -- reload, destroy, a fetch -- then waits for the consumer's reads of the batch's arrays too.  (finish_run's other
+// fields hold their values already: a batch that passed check_consumer_batch has ran set and dirty clear.)
+static int finish_consumer(bigsi_hip_batch *b, hipStream_t st)
+{
+    b->idle = false;
+    return finish_run(b, st, false, st == b->ix->stream);
+}
+
+// the arguments of a stream call, all offsets included, before any device work
+static int check_stream_args(const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold)
+{
+    if (n_seqs == 0) return fail(BIGSI_ERR_INVALID, "a batch needs at least one sequence");
+    if (k == 0) return fail(BIGSI_ERR_INVALID, "k must be > 0");
+    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
+    for (uint64_t i = 0; i < n_seqs; i++)
+        if (offsets[i + 1] < offsets[i]) return fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing");
+    if (offsets[n_seqs] - offsets[0] && !seqs) return fail(BIGSI_ERR_INVALID, "seqs is NULL");
+    return BIGSI_OK;
+}
+
+// A stream through two workspaces of the index (`ws`: the consumer's own, never the search stream's or another consumer's): chunk i is
+// staged into workspace i & 1 -- host work, which first waits for that workspace's chunk i - 2 (its completion event, recorded behind
+// its consumer kernels) -- while chunk i - 1 runs.  A chunk without any k-mer position never goes to the device: host_only(s0, s1).
+// Every other chunk is run and handed over: launch(batch, slot, s0, s1).  A failed call gives both workspaces up.
+template <typename HostOnly, typename Launch>
+static int consume_stream(bigsi_hip_index *ix, bigsi_hip_batch *(&ws)[2], const VectorConsumer &who, const char *seqs, const uint64_t *offsets,
+                          uint64_t n_seqs, uint32_t k, double threshold, HostOnly &&host_only, Launch &&launch)
+{
+    const bool exact = threshold == 1.0;
+    const uint64_t wv_pad = round_up(ix->wv(), 2);
+    int rc = BIGSI_OK;
+    uint64_t chunk = 0;
+    for (uint64_t s0 = 0; s0 < n_seqs && rc == BIGSI_OK;) {
+        const uint64_t s1 = tally_chunk_end(offsets, n_seqs, s0, k, wv_pad, exact ? 0u : 4u);
+        bool any_pos = false;
+        for (uint64_t s = s0; s < s1 && !any_pos; s++) any_pos = offsets[s + 1] - offsets[s] >= k;
+        if (!any_pos) host_only(s0, s1);
+        else {
+            const int slot = (int)(chunk & 1);
+            rc = bigsi_batch_stage(ix, &ws[slot], seqs, offsets + s0, (uint32_t)(s1 - s0), k);
+            // (hits-only counters below threshold 1: a consumer reads a counter only under a set bit, and a word that holds one keeps all 64)
+            if (rc == BIGSI_OK) rc = bigsi_batch_run(ws[slot], threshold, BIGSI_RUN_SKIP_COMPACT | (exact ? 0u : (uint32_t)BIGSI_RUN_SPARSE_COUNTS), false);
+            if (rc == BIGSI_OK) rc = check_consumer_batch(ws[slot], who);
+            if (rc == BIGSI_OK) rc = launch(ws[slot], slot, s0, s1);
+        }
+        if (any_pos || who.host_chunks_take_a_slot) chunk++;
+        s0 = s1;
+    }
+    if (rc != BIGSI_OK)
+        for (bigsi_hip_batch *&w : ws) drop_workspace(w);
+    return rc;
 }
 
 // Query-set tally (include/bigsi_hip_tally.h; k_tally_hits + k_tally_totals, launch shape: plan_tally): per-sample sums over the
@@ -3316,13 +3388,11 @@ extern "C" int bigsi_hip_tally_reset(bigsi_hip_tally *t)
     return BIGSI_OK;
 }
 
-// the two kernels for a batch whose SKIP_COMPACT run is the last thing queued on its run stream, and the batch's completion event
-// again behind them (what waits for the run -- reload, destroy, a fetch -- then waits for the tally's reads of its arrays too)
+// the two kernels for a batch that passed check_consumer_batch (its result vectors are then as wide as the tally's), and finish_consumer
 static int tally_launch(bigsi_hip_tally *t, bigsi_hip_batch *b)
 {
     bigsi_hip_index *ix = b->ix;
-    hipStream_t st = b->run_stream ? b->run_stream : ix->stream;
-    if (b->wv != t->wv) return fail(BIGSI_ERR_STATE, "internal: the batch's result vectors are %llu words, the tally's %llu", (unsigned long long)b->wv, (unsigned long long)t->wv);
+    hipStream_t st = consumer_stream(b);
     const TallyPlan p = plan_tally(b->n_seqs, b->wv);
     if (p.too_large || p.totals_grid > 0x7FFFFFFFull)
         return fail(BIGSI_ERR_INVALID, "batch too large for one tally launch (%llu workgroups)", (unsigned long long)std::max(p.too_large, p.totals_grid));
@@ -3332,38 +3402,19 @@ static int tally_launch(bigsi_hip_tally *t, bigsi_hip_batch *b)
     const uint64_t cstride = b->wv_pad * 64;
     EventPair ep{};
     TRY(bigsi_ev_begin(ix, &ep, st));
-#define BIGSI_TALLY(CountT, EXACT, CNT)                                                                                                     \
-    hipLaunchKernelGGL((k_tally_hits<CountT, EXACT>), dim3((unsigned)p.grid), dim3(p.block), 0, st, bm, b->wv_pad, (uint32_t)b->wv, t->n_cols, \
-                       b->n_seqs, b->num_unique.as<uint32_t>(), CNT, cstride, (uint32_t)p.word_groups, p.tile, t->queries_hit(), t->kmers_found())
-    if (b->exact) BIGSI_TALLY(uint16_t, true, (const uint16_t *)nullptr);
-    else if (b->count_bytes == 2) BIGSI_TALLY(uint16_t, false, static_cast<const uint16_t *>(b->counters()));
-    else BIGSI_TALLY(uint32_t, false, static_cast<const uint32_t *>(b->counters()));
-#undef BIGSI_TALLY
+    with_counters(b, [&](auto exact, const auto *cnt) {
+        using CountT = std::remove_const_t<std::remove_pointer_t<decltype(cnt)>>;
+        hipLaunchKernelGGL((k_tally_hits<CountT, decltype(exact)::value>), dim3((unsigned)p.grid), dim3(p.block), 0, st, bm, b->wv_pad, (uint32_t)b->wv,
+                           t->n_cols, b->n_seqs, b->num_unique.as<uint32_t>(), cnt, cstride, (uint32_t)p.word_groups, p.tile, t->queries_hit(),
+                           t->kmers_found());
+    });
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_tally_totals, dim3((unsigned)p.totals_grid), dim3(kBlock), 0, st, bm, b->wv_pad, (uint32_t)b->wv, t->n_cols, b->n_seqs,
                        b->num_unique.as<uint32_t>(), t->totals());
     HIP_TRY(hipGetLastError());
     TRY(bigsi_ev_end(ix, &ep, ix->ev_cp, st, 2));      // (timed with the compaction it stands in for: bigsi_hip_stats' compact_ms)
     TRY(tally_mark(t, st));
-    if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->done, st));
-    b->done_stale = false;
-    b->run_stream = st;
-    b->idle = false;
-    if (st == ix->stream) TRY(mark_main(ix));
-    return BIGSI_OK;
-}
-
-static int tally_check_batch(const bigsi_hip_tally *t, const bigsi_hip_batch *b)
-{
-    if (b->ix != t->ix) return fail(BIGSI_ERR_STATE, "the batch belongs to another index than the tally");
-    if (!b->ran) return fail(BIGSI_ERR_STATE, "bigsi_hip_batch_run has not completed for this batch");
-    if (b->compacted || b->fused_run) return fail(BIGSI_ERR_STATE, "the batch's last run built hit lists: a tally takes a run made with BIGSI_RUN_SKIP_COMPACT");
-    if (b->limit) return fail(BIGSI_ERR_STATE, "the batch has a result limit (bigsi_hip_batch_set_limit): a tally counts every hit");
-    if (b->ext_bitmaps || b->result_cols || b->comm)
-        return fail(BIGSI_ERR_STATE, "the batch has caller-owned bit vectors, a result width or a communicator: a tally takes a batch of one whole index");
-    if (b->run_h != t->h) return fail(BIGSI_ERR_STATE, "num_hashes changed since this batch ran (%u then, %u now): run it again", b->run_h, t->h);
-    return BIGSI_OK;
+    return finish_consumer(b, st);
 }
 
 extern "C" int bigsi_hip_tally_add_batch(bigsi_hip_tally *t, bigsi_hip_batch *b)
@@ -3371,52 +3422,23 @@ extern "C" int bigsi_hip_tally_add_batch(bigsi_hip_tally *t, bigsi_hip_batch *b)
     BIGSI_ENTER(t ? t->ix : nullptr);
     if (!t || !b) return fail(BIGSI_ERR_INVALID, "NULL argument");
     TRY(tally_check(t));
-    TRY(tally_check_batch(t, b));
+    if (b->ix != t->ix) return fail(BIGSI_ERR_STATE, "the batch belongs to another index than the tally");
+    TRY(check_consumer_batch(b, kTallyConsumer));
     TRY(use_device(t->ix));
     return tally_launch(t, b);
 }
 
-// Two workspaces of the index (tally_ws), never the search stream's: chunk i is staged into workspace i & 1 -- host work, which first
-// waits for that workspace's chunk i - 2 (its completion event, recorded behind its tally kernels) -- while chunk i - 1 runs.
+// consume_stream over the index's tally_ws
 extern "C" int bigsi_hip_tally_add_stream(bigsi_hip_tally *t, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold)
 {
     BIGSI_ENTER(t ? t->ix : nullptr);
     if (!t || !offsets) return fail(BIGSI_ERR_INVALID, "NULL argument");
-    bigsi_hip_index *ix = t->ix;
     TRY(tally_check(t));
-    if (n_seqs == 0) return fail(BIGSI_ERR_INVALID, "a batch needs at least one sequence");
-    if (k == 0) return fail(BIGSI_ERR_INVALID, "k must be > 0");
-    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
-    for (uint64_t i = 0; i < n_seqs; i++)
-        if (offsets[i + 1] < offsets[i]) return fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing");
-    if (offsets[n_seqs] - offsets[0] && !seqs) return fail(BIGSI_ERR_INVALID, "seqs is NULL");
-    const bool exact = threshold == 1.0;
-    const uint64_t wv_pad = round_up(ix->wv(), 2);
-    int rc = BIGSI_OK;
-    uint64_t chunk = 0;
-    for (uint64_t s0 = 0; s0 < n_seqs && rc == BIGSI_OK; chunk++) {
-        const uint64_t s1 = tally_chunk_end(offsets, n_seqs, s0, k, wv_pad, exact ? 0u : 4u);
-        bool any_pos = false;
-        for (uint64_t s = s0; s < s1 && !any_pos; s++) any_pos = offsets[s + 1] - offsets[s] >= k;
-        if (!any_pos) t->host_skipped += s1 - s0;
-        else {
-            bigsi_hip_batch **ws = &ix->tally_ws[chunk & 1];
-            rc = bigsi_batch_stage(ix, ws, seqs, offsets + s0, (uint32_t)(s1 - s0), k);
-            // (hits-only counters below threshold 1: the tally reads a counter only under a set bit, and a word that holds one keeps all 64)
-            if (rc == BIGSI_OK) rc = bigsi_batch_run(*ws, threshold, BIGSI_RUN_SKIP_COMPACT | (exact ? 0u : (uint32_t)BIGSI_RUN_SPARSE_COUNTS), false);
-            if (rc == BIGSI_OK) rc = tally_check_batch(t, *ws);
-            if (rc == BIGSI_OK) rc = tally_launch(t, *ws);
-        }
-        s0 = s1;
-    }
-    if (rc != BIGSI_OK) {
-        t->unusable = true;
-        for (bigsi_hip_batch *&w : ix->tally_ws) {
-            bigsi_hip_batch *b = w;
-            w = nullptr;
-            if (b) bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
-        }
-    }
+    TRY(check_stream_args(seqs, offsets, n_seqs, k, threshold));
+    const int rc = consume_stream(
+        t->ix, t->ix->tally_ws, kTallyConsumer, seqs, offsets, n_seqs, k, threshold, [&](uint64_t s0, uint64_t s1) { t->host_skipped += s1 - s0; },
+        [&](bigsi_hip_batch *b, int, uint64_t, uint64_t) { return tally_launch(t, b); });
+    if (rc != BIGSI_OK) t->unusable = true;
     return rc;
 }
 
@@ -3458,28 +3480,11 @@ static int classify_check_groups(const bigsi_hip_index *ix, const uint32_t *grou
     return BIGSI_OK;
 }
 
-// what tally_check_batch refuses, for a batch of its own index
-static int classify_check_batch(const bigsi_hip_batch *b)
-{
-    if (!b->ran) return fail(BIGSI_ERR_STATE, "bigsi_hip_batch_run has not completed for this batch");
-    if (b->compacted || b->fused_run)
-        return fail(BIGSI_ERR_STATE, "the batch's last run built hit lists: a classification takes a run made with BIGSI_RUN_SKIP_COMPACT");
-    if (b->limit) return fail(BIGSI_ERR_STATE, "the batch has a result limit (bigsi_hip_batch_set_limit): a classification weighs every hit");
-    if (b->ext_bitmaps || b->result_cols || b->comm)
-        return fail(BIGSI_ERR_STATE, "the batch has caller-owned bit vectors, a result width or a communicator: a classification takes a batch of one whole index");
-    if (b->run_h != b->ix->h) return fail(BIGSI_ERR_STATE, "num_hashes changed since this batch ran (%u then, %u now): run it again", b->run_h, b->ix->h);
-    if (b->wv != b->ix->wv()) return fail(BIGSI_ERR_STATE, "num_cols changed since this batch ran: run it again");
-    return BIGSI_OK;
-}
-
-// the kernel for a batch whose SKIP_COMPACT run is the last thing queued on its run stream (*pst), its records into `slot`'s device
-// buffer, and the batch's completion event again behind it (the tally's ordering rule: what waits for the run -- reload, destroy --
-// then waits for the kernel's reads of the batch's arrays too).  group_of is on the device already, ordered before the kernel.
-static int classify_launch(bigsi_hip_batch *b, uint32_t n_groups, int slot, hipStream_t *pst)
+// the kernel for a batch that passed check_consumer_batch, on its consumer_stream `st`, its records into `slot`'s device buffer, and
+// finish_consumer.  group_of is on the device already, ordered before the kernel.
+static int classify_launch(bigsi_hip_batch *b, uint32_t n_groups, int slot, hipStream_t st)
 {
     bigsi_hip_index *ix = b->ix;
-    hipStream_t st = b->run_stream ? b->run_stream : ix->stream;
-    *pst = st;
     const ClassifyPlan p = plan_classify(b->n_seqs, b->wv, n_groups);
     if (p.too_large || p.bad_groups) return fail(BIGSI_ERR_INVALID, "batch too large for one classification launch (%llu workgroups)", (unsigned long long)p.too_large);
     TRY(ix->classify_rec[slot].reserve((size_t)b->n_seqs * sizeof(bigsi_hip_classify_record)));
@@ -3487,23 +3492,15 @@ static int classify_launch(bigsi_hip_batch *b, uint32_t n_groups, int slot, hipS
     const uint64_t cstride = b->wv_pad * 64;
     EventPair ep{};
     TRY(bigsi_ev_begin(ix, &ep, st));
-#define BIGSI_CLASSIFY(CountT, EXACT, CNT)                                                                                                  \
-    hipLaunchKernelGGL((k_classify_groups<CountT, EXACT>), dim3((unsigned)p.grid), dim3(p.block), p.lds_bytes, st, bm, b->wv_pad, (uint32_t)b->wv, \
-                       ix->n_cols, b->num_unique.as<uint32_t>(), b->threshold, CNT, cstride, ix->classify_groups.as<uint32_t>(), n_groups,   \
-                       p.table_bytes, ix->classify_rec[slot].as<uint4>())
-    if (b->exact) BIGSI_CLASSIFY(uint16_t, true, (const uint16_t *)nullptr);
-    else if (b->count_bytes == 2) BIGSI_CLASSIFY(uint16_t, false, static_cast<const uint16_t *>(b->counters()));
-    else BIGSI_CLASSIFY(uint32_t, false, static_cast<const uint32_t *>(b->counters()));
-#undef BIGSI_CLASSIFY
+    with_counters(b, [&](auto exact, const auto *cnt) {
+        using CountT = std::remove_const_t<std::remove_pointer_t<decltype(cnt)>>;
+        hipLaunchKernelGGL((k_classify_groups<CountT, decltype(exact)::value>), dim3((unsigned)p.grid), dim3(p.block), p.lds_bytes, st, bm, b->wv_pad,
+                           (uint32_t)b->wv, ix->n_cols, b->num_unique.as<uint32_t>(), b->threshold, cnt, cstride, ix->classify_groups.as<uint32_t>(),
+                           n_groups, p.table_bytes, ix->classify_rec[slot].as<uint4>());
+    });
     HIP_TRY(hipGetLastError());
     TRY(bigsi_ev_end(ix, &ep, ix->ev_cp, st, 1));      // (timed with the compaction it stands in for: bigsi_hip_stats' compact_ms)
-    if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->done, st));
-    b->done_stale = false;
-    b->run_stream = st;
-    b->idle = false;
-    if (st == ix->stream) TRY(mark_main(ix));
-    return BIGSI_OK;
+    return finish_consumer(b, st);
 }
 
 extern "C" int bigsi_hip_classify_batch(bigsi_hip_batch *b, const uint32_t *group_of, uint64_t n_entries, uint32_t n_groups,
@@ -3513,22 +3510,21 @@ extern "C" int bigsi_hip_classify_batch(bigsi_hip_batch *b, const uint32_t *grou
     if (!b || !group_of || !records) return fail(BIGSI_ERR_INVALID, "NULL argument");
     bigsi_hip_index *ix = b->ix;
     TRY(classify_check_groups(ix, group_of, n_entries, n_groups));
-    TRY(classify_check_batch(b));
+    TRY(check_consumer_batch(b, kClassifyConsumer));
     if (capacity < b->n_seqs)
         return fail(BIGSI_ERR_CAPACITY, "the record buffer holds %llu entries, %u needed", (unsigned long long)capacity, b->n_seqs);
     TRY(use_device(ix));
-    hipStream_t st = b->run_stream ? b->run_stream : ix->stream;
+    hipStream_t st = consumer_stream(b);
     TRY(ix->classify_groups.reserve((size_t)n_entries * 4));
     HIP_TRY(hipMemcpyAsync(ix->classify_groups.p, group_of, (size_t)n_entries * 4, hipMemcpyHostToDevice, st));
-    TRY(classify_launch(b, n_groups, 0, &st));
+    TRY(classify_launch(b, n_groups, 0, st));
     HIP_TRY(hipMemcpyAsync(records, ix->classify_rec[0].p, (size_t)b->n_seqs * sizeof(bigsi_hip_classify_record), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return BIGSI_OK;
 }
 
-// Two workspaces of the index (classify_ws), never the search stream's or the tally's: chunk i is staged into workspace i & 1 -- host
-// work, which first waits for that workspace's chunk i - 2 -- while chunk i - 1 runs; the records of chunk i - 1 are collected (its
-// slot's event, then a host copy out of the pinned twin) once chunk i is queued.
+// consume_stream over the index's classify_ws: the records of chunk i - 1 are collected (its slot's event, then a host copy out of the
+// pinned twin) once chunk i is queued.
 static int classify_collect(bigsi_hip_index *ix, int slot, bigsi_hip_classify_record *dst, uint64_t n)
 {
     HIP_TRY(hipEventSynchronize(ix->classify_ev[slot]));
@@ -3541,12 +3537,7 @@ extern "C" int bigsi_hip_classify_stream(bigsi_hip_index *ix, const char *seqs, 
 {
     BIGSI_ENTER(ix);
     if (!ix || !offsets || !group_of || !records) return fail(BIGSI_ERR_INVALID, "NULL argument");
-    if (n_seqs == 0) return fail(BIGSI_ERR_INVALID, "a batch needs at least one sequence");
-    if (k == 0) return fail(BIGSI_ERR_INVALID, "k must be > 0");
-    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
-    for (uint64_t i = 0; i < n_seqs; i++)
-        if (offsets[i + 1] < offsets[i]) return fail(BIGSI_ERR_INVALID, "offsets must be non-decreasing");
-    if (offsets[n_seqs] - offsets[0] && !seqs) return fail(BIGSI_ERR_INVALID, "seqs is NULL");
+    TRY(check_stream_args(seqs, offsets, n_seqs, k, threshold));
     TRY(classify_check_groups(ix, group_of, n_entries, n_groups));
     TRY(use_device(ix));
     const size_t slot_bytes = (size_t)kTallyChunkSeqs * sizeof(bigsi_hip_classify_record);
@@ -3557,43 +3548,26 @@ extern "C" int bigsi_hip_classify_stream(bigsi_hip_index *ix, const char *seqs, 
     TRY(ix->classify_groups.reserve((size_t)n_entries * 4));
     HIP_TRY(hipMemcpyAsync(ix->classify_groups.p, group_of, (size_t)n_entries * 4, hipMemcpyHostToDevice, ix->stream));
     HIP_TRY(hipStreamSynchronize(ix->stream));      // (a pageable source: the upload is over before the caller's array can change, whichever stream a chunk runs on)
-    const bool exact = threshold == 1.0;
-    const uint64_t wv_pad = round_up(ix->wv(), 2);
-    int rc = BIGSI_OK;
-    uint64_t chunk = 0, pend_s0 = 0, pend_n = 0;      // the chunk whose records are still on their way: slot pend_slot
+    uint64_t pend_s0 = 0, pend_n = 0;      // the chunk whose records are still on their way: slot pend_slot
     int pend_slot = -1;
-    for (uint64_t s0 = 0; s0 < n_seqs && rc == BIGSI_OK;) {
-        const uint64_t s1 = tally_chunk_end(offsets, n_seqs, s0, k, wv_pad, exact ? 0u : 4u);
-        bool any_pos = false;
-        for (uint64_t s = s0; s < s1 && !any_pos; s++) any_pos = offsets[s + 1] - offsets[s] >= k;
-        if (!any_pos) std::fill(records + s0, records + s1, kClassifyEmpty);
-        else {
-            const int slot = (int)(chunk & 1);
-            bigsi_hip_batch **ws = &ix->classify_ws[slot];
-            hipStream_t st = nullptr;
-            rc = bigsi_batch_stage(ix, ws, seqs, offsets + s0, (uint32_t)(s1 - s0), k);
-            // (hits-only counters below threshold 1: the kernel reads a counter only under a set bit, and a word that holds one keeps all 64)
-            if (rc == BIGSI_OK) rc = bigsi_batch_run(*ws, threshold, BIGSI_RUN_SKIP_COMPACT | (exact ? 0u : (uint32_t)BIGSI_RUN_SPARSE_COUNTS), false);
-            if (rc == BIGSI_OK) rc = classify_check_batch(*ws);
-            if (rc == BIGSI_OK) rc = classify_launch(*ws, n_groups, slot, &st);
-            if (rc == BIGSI_OK) {
-                hipError_t e = hipMemcpyAsync(ix->classify_pin[slot], ix->classify_rec[slot].p, (size_t)(s1 - s0) * sizeof(bigsi_hip_classify_record), hipMemcpyDeviceToHost, st);
-                if (e == hipSuccess) e = hipEventRecord(ix->classify_ev[slot], st);
-                if (e != hipSuccess) rc = fail(BIGSI_ERR_HIP, "queueing the record download: %s", hipGetErrorString(e));
-            }
-            if (rc == BIGSI_OK && pend_slot >= 0) rc = classify_collect(ix, pend_slot, records + pend_s0, pend_n);
-            if (rc == BIGSI_OK) { pend_slot = slot; pend_s0 = s0; pend_n = s1 - s0; }
-            chunk++;
-        }
-        s0 = s1;
+    int rc = consume_stream(
+        ix, ix->classify_ws, kClassifyConsumer, seqs, offsets, n_seqs, k, threshold,
+        [&](uint64_t s0, uint64_t s1) { std::fill(records + s0, records + s1, kClassifyEmpty); },
+        [&](bigsi_hip_batch *b, int slot, uint64_t s0, uint64_t s1) -> int {
+            hipStream_t st = consumer_stream(b);
+            TRY(classify_launch(b, n_groups, slot, st));
+            hipError_t e = hipMemcpyAsync(ix->classify_pin[slot], ix->classify_rec[slot].p, (size_t)(s1 - s0) * sizeof(bigsi_hip_classify_record), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipEventRecord(ix->classify_ev[slot], st);
+            if (e != hipSuccess) return fail(BIGSI_ERR_HIP, "queueing the record download: %s", hipGetErrorString(e));
+            if (pend_slot >= 0) TRY(classify_collect(ix, pend_slot, records + pend_s0, pend_n));
+            pend_slot = slot; pend_s0 = s0; pend_n = s1 - s0;
+            return BIGSI_OK;
+        });
+    if (rc == BIGSI_OK && pend_slot >= 0) {
+        rc = classify_collect(ix, pend_slot, records + pend_s0, pend_n);
+        if (rc != BIGSI_OK)
+            for (bigsi_hip_batch *&w : ix->classify_ws) drop_workspace(w);
     }
-    if (rc == BIGSI_OK && pend_slot >= 0) rc = classify_collect(ix, pend_slot, records + pend_s0, pend_n);
-    if (rc != BIGSI_OK)
-        for (bigsi_hip_batch *&w : ix->classify_ws) {
-            bigsi_hip_batch *b = w;
-            w = nullptr;
-            if (b) bigsi_hip_batch_destroy(b);      // leaves the thread's error message of the failed call above in place
-        }
     return rc;
 }
 

@@ -849,18 +849,31 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         with self._device_lock():
             used, need, off, colours, records = self.storage.window_search(seqs, k, window, threshold)
             excluded = self._excluded_colours()
-        n = self.num_samples
-
-        def name_of(c):          # (a column the metadata has no record of is reported by its colour alone)
-            try:
-                return self.colour_to_sample(c) if c < n else None
-            except KeyError:
-                return None
-        return assemble(seqs, k, window, threshold, used, need, off, colours, records, name_of, excluded)
+        return assemble(seqs, k, window, threshold, used, need, off, colours, records, self._name_of(), excluded)
 
     def search_windows(self, seq, window, threshold=1.0):
         """search_windows_many for one sequence: its dict."""
         return self.search_windows_many([seq], window, threshold)[0]
+
+    def _name_of(self):
+        """name_of(c) for the colours a device call reports: the sample's name, None for a column the metadata has no record of
+        (it is then reported by its colour alone)."""
+        n = self.num_samples
+
+        def name_of(c):
+            try:
+                return self.colour_to_sample(c) if c < n else None
+            except KeyError:
+                return None
+        return name_of
+
+    @staticmethod
+    def _check_stream_query(seqs, threshold):
+        """What tally and classify_arrays refuse before any device call: one sequence in place of an iterable, a threshold above 1."""
+        if isinstance(seqs, (str, bytes)):
+            raise TypeError("seqs must be an iterable of sequences, got %r" % type(seqs))
+        if not threshold <= 1:
+            raise ValueError("threshold must be <= 1, got %r" % (threshold,))
 
     # ------------------------------------------------------------------ query-set tally
     def tally(self, seqs, threshold=1.0, limit=None, batch_kmers=1 << 19):
@@ -875,10 +888,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         k-mers, as search_stream slices its input.  Multi-GPU (devices=[...]) indexes are refused."""
         from ..tally import record
         limit = check_limit(limit)
-        if isinstance(seqs, (str, bytes)):
-            raise TypeError("seqs must be an iterable of sequences, got %r" % type(seqs))
-        if not threshold <= 1:
-            raise ValueError("threshold must be <= 1, got %r" % (threshold,))
+        self._check_stream_query(seqs, threshold)
         self._refuse_group("a query-set tally")
         k = int(self.kmer_size)
         with self._device_lock():
@@ -890,14 +900,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
             finally:
                 t.close()
             excluded = self._excluded_colours()
-        n = self.num_samples
-
-        def name_of(c):          # (a column the metadata has no record of is reported by its colour alone)
-            try:
-                return self.colour_to_sample(c) if c < n else None
-            except KeyError:
-                return None
-        return record(hit, found, totals, name_of, excluded, limit)
+        return record(hit, found, totals, self._name_of(), excluded, limit)
 
     # ------------------------------------------------------------------ read classification
     def _classify_groups(self, groups, others):
@@ -924,10 +927,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         classify.classify_plan(names, groups, others) gives.  `groups` is what collapse takes (a mapping group -> [samples] or (sample,
         group) pairs); `seqs` is any iterable of ASCII sequences, fed in slices of about 8 x `batch_kmers` k-mers, as tally slices its
         input.  Multi-GPU (devices=[...]) indexes are refused."""
-        if isinstance(seqs, (str, bytes)):
-            raise TypeError("seqs must be an iterable of sequences, got %r" % type(seqs))
-        if not threshold <= 1:
-            raise ValueError("threshold must be <= 1, got %r" % (threshold,))
+        self._check_stream_query(seqs, threshold)
         from ..collapse import check_groups
         check_groups(groups)
         self._refuse_group("read classification")
@@ -953,14 +953,7 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         records = np.concatenate(parts) if parts else np.zeros(0, RECORD_DTYPE)
         with self._device_lock():
             _, group_names = self._classify_groups(groups, others)
-        n = self.num_samples
-
-        def name_of(c):          # (a column the metadata has no record of is reported by its colour alone)
-            try:
-                return self.colour_to_sample(c) if c < n else None
-            except KeyError:
-                return None
-        return result(records, group_names, name_of, margin)
+        return result(records, group_names, self._name_of(), margin)
 
     # ------------------------------------------------------------------ column compaction: vacuum / extract
     def _colour_names(self):

@@ -320,6 +320,14 @@ def test_refusals():
         d.lib.check(L.bigsi_hip_set_num_cols(d.ix, 64))
         assert L.bigsi_hip_tally_add_batch(t, b) == ERR_STATE and d.fetch_rc(t)[0] == ERR_STATE and L.bigsi_hip_tally_reset(t) == ERR_STATE
         assert L.bigsi_hip_tally_add_stream(t, blob, ptr(off), 9, T.K, 1.0) == ERR_STATE and b"changed" in d.raw.err()
+        # ... and under the batch: a tally made now is refused the batch that ran at 65 columns, and nothing is added to it
+        t64 = d.tally()
+        try:
+            assert L.bigsi_hip_tally_add_batch(t64, b) == ERR_STATE and b"num_cols changed" in d.raw.err()
+            rc, qh, kf, totals = d.fetch_rc(t64)
+            assert rc == 0 and not qh[:64].any() and not kf[:64].any() and not totals.any()
+        finally:
+            d.drop(t64)
         d.lib.check(L.bigsi_hip_set_num_cols(d.ix, 65))
         d.lib.check(L.bigsi_hip_set_num_hashes(d.ix, 2))
         assert L.bigsi_hip_tally_add_batch(t, b) == ERR_STATE and d.fetch_rc(t)[0] == ERR_STATE

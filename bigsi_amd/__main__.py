@@ -185,7 +185,16 @@ def build_parser():
     sp.add_argument("--others", default=None, metavar="NAME", help="samples the file does not name form one more group called NAME")
     sp.add_argument("--format", choices=["tsv", "json"], default="tsv")
     sp.add_argument("--summary-only", action="store_true", help="reads per group, ambiguous, unclassified and skipped only")
-    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally", "window_search", "classify"):          # (named so that the refusal says why)
+    sp = common(sub.add_parser("associate", help="for every record of a FASTA file (unitigs, genes, probes): how many samples of each group hold it, "
+                                                 "with prevalence, odds ratio and chi-square per group (counted on the device; one line per record)"))
+    sp.add_argument("fasta")
+    sp.add_argument("--groups", required=True, metavar="FILE", help="sample<TAB>group lines, as for collapse; a group's id follows its first appearance")
+    sp.add_argument("--threshold", "-t", type=float, default=1.0)
+    sp.add_argument("--others", default=None, metavar="NAME", help="samples the file does not name form one more group called NAME")
+    sp.add_argument("--min-af", type=float, default=None, metavar="F",
+                    help="drop the records held by less than F or more than 1 - F of the grouped samples (0 .. 0.5)")
+    sp.add_argument("--format", choices=["tsv", "json"], default="tsv")
+    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally", "window_search", "classify", "associate"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -340,6 +349,16 @@ def classify_text(index, records, pairs, threshold=1.0, margin=1, others=None, f
     return to_json(res, names, summary_only) if fmt == "json" else to_tsv(res, names, summary_only)
 
 
+def associate_text(index, records, pairs, threshold=1.0, others=None, min_af=None, fmt="tsv"):
+    """`associate`: BIGSI.associate over the (name, sequence) records of a FASTA file.  TSV: name, num_kmers, samples_hit, then per
+    group <group>:hit, :prevalence, :log2_odds, :chi2, :p -- one line per kept record, `# dropped<TAB>n` behind them; JSON: the result,
+    each record with its "name" first."""
+    from .associate import to_json, to_tsv
+    names = [n for n, _ in records]
+    res = index.associate([s for _, s in records], pairs, threshold=threshold, others=others, min_af=min_af)
+    return to_json(res, names) if fmt == "json" else to_tsv(res, names)
+
+
 def window_search_text(index, queries, window, threshold=1.0, fmt="json"):
     """`window_search`: BIGSI.search_windows_many over the queries, one device call per query (a long query is a call's worth of work,
     and the device keeps counters per sequence).  JSON: the dicts, each with its "query" first; CSV: record,<result fields>, one line
@@ -429,6 +448,20 @@ def main(argv=None):
             check_groups(classify_pairs)
         except (OSError, ValueError) as e:
             p.error("classify --groups: %s" % e)
+    if getattr(a, "sharded", False) and a.cmd == "associate":
+        p.error("associate is not available with --sharded: a group's samples may lie on several shards and the per-shard counts plus a host merge "
+                "are not implemented (use a single index)")
+    if a.cmd == "associate":
+        from .collapse import check_groups
+        if not a.threshold <= 1:
+            p.error("associate: the threshold must be <= 1, got %r" % (a.threshold,))
+        if a.min_af is not None and not 0.0 <= a.min_af <= 0.5:
+            p.error("associate: --min-af must be within 0 .. 0.5, got %r" % (a.min_af,))
+        try:
+            associate_pairs = collapse_groups(a.groups)
+            check_groups(associate_pairs)
+        except (OSError, ValueError) as e:
+            p.error("associate --groups: %s" % e)
     if getattr(a, "sharded", False) and a.cmd == "window_search":
         p.error("window_search is not available with --sharded: the per-shard sweep is not implemented (use a single index)")
     if a.cmd == "window_search" and (a.seq is None) == (a.fasta is None):
@@ -526,6 +559,8 @@ def main(argv=None):
         print(tally_text(BIGSI(config), [s for _, s in read_fasta(a.fasta)], a.threshold, a.limit, a.format))
     elif a.cmd == "classify":
         print(classify_text(BIGSI(config), read_fasta(a.fasta), classify_pairs, a.threshold, a.margin, a.others, a.format, a.summary_only))
+    elif a.cmd == "associate":
+        print(associate_text(BIGSI(config), read_fasta(a.fasta), associate_pairs, a.threshold, a.others, a.min_af, a.format))
     elif a.cmd == "distances":
         against = None
         if a.against_file:

@@ -26,6 +26,7 @@
 #include "bigsi_cpu_window.h"
 #include "bigsi_cpu_tally.h"
 #include "bigsi_cpu_classify.h"
+#include "bigsi_cpu_associate.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1189,6 +1190,49 @@ int bigsi_cpu_classify(bigsi_cpu_index *ix, const char *seqs, const uint64_t *of
     }
     TRY(bdb_read_failed(ix));
     memcpy(records, out.data(), n_seqs * sizeof(bigsi_hip_classify_record));
+    return BIGSI_OK;
+}
+
+// group association: every sequence searched in the reference's shape, then a loop over its hit columns (ascending colours): one more
+// sample hit, and one more for the column's group when it has one.  A threshold below 0 asks for what 0 asks for.
+int bigsi_cpu_associate(bigsi_cpu_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
+                        const uint32_t *group_of, uint64_t n_entries, uint32_t n_groups, uint32_t *counts, bigsi_hip_associate_info *info)
+{
+    if (!ix || !group_of || !counts || !info) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_seqs(seqs, offsets, n_seqs, k));
+    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    if (n_entries != ix->n_cols)
+        return fail(BIGSI_ERR_INVALID, "group_of has %llu entries, the index has %llu columns", (unsigned long long)n_entries, (unsigned long long)ix->n_cols);
+    if (n_groups == 0 || n_groups > BIGSI_ASSOCIATE_MAX_GROUPS) return fail(BIGSI_ERR_INVALID, "n_groups must be 1 .. BIGSI_ASSOCIATE_MAX_GROUPS = %u (got %u)", BIGSI_ASSOCIATE_MAX_GROUPS, n_groups);
+    for (uint64_t c = 0; c < n_entries; c++)
+        if (group_of[c] != BIGSI_ASSOCIATE_NONE && group_of[c] >= n_groups)
+            return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither below n_groups (%u) nor BIGSI_ASSOCIATE_NONE", (unsigned long long)c, group_of[c], n_groups);
+    const uint64_t n_cols = ix->n_cols;
+    std::vector<uint32_t> col(n_cols), cnt(n_cols), out((size_t)n_seqs * n_groups, 0u);
+    std::vector<bigsi_hip_associate_info> out_info(n_seqs);
+    QueryKmers q;
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        uint32_t nk, nu, mk;
+        Hits hits{nullptr, col.data(), cnt.data(), n_cols};
+        search_reference_shaped(ix, seqs + offsets[i], offsets[i + 1] - offsets[i], k, threshold < 0.0 ? 0.0 : threshold, q, &nk, &nu, &mk, hits);
+        bigsi_hip_associate_info r = {0, 0, 0, 0};
+        if (nu) {
+            r.num_unique = nu;
+            r.min_kmers = mk;
+            for (uint64_t j = 0; j < hits.total; j++) {
+                const uint32_t g = group_of[col[j]];
+                r.samples_hit++;
+                if (g == BIGSI_ASSOCIATE_NONE) continue;
+                r.grouped_hit++;
+                out[(size_t)i * n_groups + g]++;
+            }
+        }
+        out_info[i] = r;
+    }
+    TRY(bdb_read_failed(ix));
+    memcpy(counts, out.data(), out.size() * sizeof(uint32_t));
+    memcpy(info, out_info.data(), n_seqs * sizeof(bigsi_hip_associate_info));
     return BIGSI_OK;
 }
 

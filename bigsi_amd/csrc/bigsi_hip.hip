@@ -387,7 +387,8 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
     }
     if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_close: %d view(s) of this index are still open (close them first)", ix->views.load());
     const std::pair<bigsi_hip_batch **, int> workspaces[] = {{&ix->search_ws, 1},   {ix->stream_ws, 4},   {&ix->prevalence_ws, 1},
-                                                             {ix->tally_ws, 2},     {ix->classify_ws, 2}, {&ix->window_ws, 1}};
+                                                             {ix->tally_ws, 2},     {ix->classify_ws, 2}, {&ix->window_ws, 1},
+                                                             {ix->associate_ws, 2}};
     for (const auto &[ws, n] : workspaces)
         for (int i = 0; i < n; i++) drop_workspace(ws[i]);
     hipError_t e = hipSetDevice(ix->device);
@@ -409,8 +410,13 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
         if (ix->classify_pin[s_]) e = hipHostFree(ix->classify_pin[s_]);
         if (ix->classify_ev[s_]) e = hipEventDestroy(ix->classify_ev[s_]);
         ix->classify_rec[s_].release();
+        if (ix->associate_pin[s_]) e = hipHostFree(ix->associate_pin[s_]);
+        if (ix->associate_ev[s_]) e = hipEventDestroy(ix->associate_ev[s_]);
+        ix->associate_out[s_].release();
     }
     ix->classify_groups.release();
+    ix->associate_groups.release();
+    ix->associate_masks.release();
     if (ix->view_of) ix->view_of->views--;
     if (ix->d_index && ix->attach == bigsi_hip_index::kOwner) e = hipFree(ix->d_index);
     else if (ix->d_index && ix->attach == bigsi_hip_index::kIpc) e = hipIpcCloseMemHandle(ix->d_index);
@@ -3567,6 +3573,138 @@ extern "C" int bigsi_hip_classify_stream(bigsi_hip_index *ix, const char *seqs, 
         rc = classify_collect(ix, pend_slot, records + pend_s0, pend_n);
         if (rc != BIGSI_OK)
             for (bigsi_hip_batch *&w : ix->classify_ws) drop_workspace(w);
+    }
+    return rc;
+}
+
+// Group association (include/bigsi_hip_associate.h; k_group_masks + k_group_counts, launch shape: plan_associate): per query every
+// group's number of hit columns over the result vectors of a run made with BIGSI_RUN_SKIP_COMPACT.  The third consumer: no counter is
+// read, so there is no with_counters here.  The index keeps the uploaded group_of, the masks built from it, a device output buffer
+// per stream slot (a chunk's infos, its counts behind them) and, for the stream call, a pinned twin and an event per slot.
+static_assert(sizeof(bigsi_hip_associate_info) == 16, "info layout: one uint4 per query (k_group_counts)");
+static_assert(BIGSI_ASSOCIATE_NONE == kAssociateNoGroup && BIGSI_ASSOCIATE_MAX_GROUPS == kAssociateMaxGroups, "header and planner");
+constexpr VectorConsumer kAssociateConsumer = {"an association", "counts", false};
+
+// classify_check_groups' rules and message shapes under this header's names; then group_of goes up and the masks are built, both on `st`
+static int associate_groups(bigsi_hip_index *ix, const uint32_t *group_of, uint64_t n_entries, uint32_t n_groups)
+{
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    if (n_entries != ix->n_cols)
+        return fail(BIGSI_ERR_INVALID, "group_of has %llu entries, the index has %llu columns", (unsigned long long)n_entries, (unsigned long long)ix->n_cols);
+    if (plan_associate(1, ix->wv(), n_groups).bad_groups)
+        return fail(BIGSI_ERR_INVALID, "n_groups must be 1 .. BIGSI_ASSOCIATE_MAX_GROUPS = %u (got %u)", kAssociateMaxGroups, n_groups);
+    const uint64_t bad = classify_bad_column(group_of, n_entries, n_groups);
+    if (bad != n_entries)
+        return fail(BIGSI_ERR_INVALID, "group_of[%llu] = %u is neither below n_groups (%u) nor BIGSI_ASSOCIATE_NONE", (unsigned long long)bad, group_of[bad], n_groups);
+    return BIGSI_OK;
+}
+
+static int associate_masks(bigsi_hip_index *ix, const uint32_t *group_of, uint32_t n_groups, hipStream_t st)
+{
+    const AssociatePlan p = plan_associate(1, ix->wv(), n_groups);
+    if (p.too_large) return fail(BIGSI_ERR_INVALID, "index too wide for one mask launch (%llu workgroups)", (unsigned long long)p.too_large);
+    TRY(ix->associate_groups.reserve((size_t)ix->n_cols * 4));
+    TRY(ix->associate_masks.reserve((size_t)p.mask_bytes));
+    HIP_TRY(hipMemcpyAsync(ix->associate_groups.p, group_of, (size_t)ix->n_cols * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_group_masks, dim3((unsigned)p.mask_grid), dim3(p.block), 0, st, ix->associate_groups.as<uint32_t>(), ix->n_cols, (uint32_t)ix->wv(),
+                       n_groups, ix->associate_masks.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    return BIGSI_OK;
+}
+
+// the count kernel for a batch that passed check_consumer_batch, on its consumer_stream `st`, its outputs into `slot`'s device buffer
+// (info[n_seqs] | counts[n_seqs][n_groups]: the uint4 stores stay aligned), and finish_consumer.  The masks are on the device already, ordered before the kernel.
+static int associate_launch(bigsi_hip_batch *b, uint32_t n_groups, int slot, hipStream_t st)
+{
+    bigsi_hip_index *ix = b->ix;
+    const AssociatePlan p = plan_associate(b->n_seqs, b->wv, n_groups);
+    if (p.too_large || p.bad_groups) return fail(BIGSI_ERR_INVALID, "batch too large for one association launch (%llu workgroups)", (unsigned long long)p.too_large);
+    const size_t info_bytes = (size_t)b->n_seqs * sizeof(bigsi_hip_associate_info);
+    TRY(ix->associate_out[slot].reserve(info_bytes + (size_t)b->n_seqs * n_groups * 4));
+    uint8_t *out = static_cast<uint8_t *>(ix->associate_out[slot].p);
+    EventPair ep{};
+    TRY(bigsi_ev_begin(ix, &ep, st));
+    hipLaunchKernelGGL(k_group_counts, dim3((unsigned)p.grid), dim3(p.block), 0, st, static_cast<const uint64_t *>(b->bit_vectors()), b->wv_pad, (uint32_t)b->wv,
+                       ix->n_cols, b->num_unique.as<uint32_t>(), b->threshold, (uint32_t)b->n_seqs, ix->associate_masks.as<uint64_t>(), n_groups,
+                       reinterpret_cast<uint32_t *>(out + info_bytes), reinterpret_cast<uint4 *>(out));
+    HIP_TRY(hipGetLastError());
+    TRY(bigsi_ev_end(ix, &ep, ix->ev_cp, st, 1));      // (timed with the compaction it stands in for: bigsi_hip_stats' compact_ms)
+    return finish_consumer(b, st);
+}
+
+extern "C" int bigsi_hip_associate_batch(bigsi_hip_batch *b, const uint32_t *group_of, uint64_t n_entries, uint32_t n_groups, uint32_t *counts,
+                                         bigsi_hip_associate_info *info, uint64_t capacity)
+{
+    BIGSI_ENTER(b ? b->ix : nullptr);
+    if (!b || !group_of || !counts || !info) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    bigsi_hip_index *ix = b->ix;
+    TRY(associate_groups(ix, group_of, n_entries, n_groups));
+    TRY(check_consumer_batch(b, kAssociateConsumer));
+    if (capacity < b->n_seqs)
+        return fail(BIGSI_ERR_CAPACITY, "the output buffers hold %llu sequences, %u needed", (unsigned long long)capacity, b->n_seqs);
+    TRY(use_device(ix));
+    hipStream_t st = consumer_stream(b);
+    TRY(associate_masks(ix, group_of, n_groups, st));
+    TRY(associate_launch(b, n_groups, 0, st));
+    const size_t info_bytes = (size_t)b->n_seqs * sizeof(bigsi_hip_associate_info);
+    const uint8_t *out = static_cast<const uint8_t *>(ix->associate_out[0].p);
+    HIP_TRY(hipMemcpyAsync(info, out, info_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counts, out + info_bytes, (size_t)b->n_seqs * n_groups * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return BIGSI_OK;
+}
+
+// consume_stream over the index's associate_ws: the outputs of chunk i - 1 are collected (its slot's event, then two host copies out of
+// the pinned twin, which is laid out as the device buffer is) once chunk i is queued.
+static int associate_collect(bigsi_hip_index *ix, int slot, uint32_t n_groups, uint32_t *counts, bigsi_hip_associate_info *info, uint64_t n)
+{
+    HIP_TRY(hipEventSynchronize(ix->associate_ev[slot]));
+    const uint8_t *pin = static_cast<const uint8_t *>(ix->associate_pin[slot]);
+    memcpy(info, pin, (size_t)n * sizeof(bigsi_hip_associate_info));
+    memcpy(counts, pin + (size_t)n * sizeof(bigsi_hip_associate_info), (size_t)n * n_groups * 4);
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_associate_stream(bigsi_hip_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
+                                          const uint32_t *group_of, uint64_t n_entries, uint32_t n_groups, uint32_t *counts,
+                                          bigsi_hip_associate_info *info)
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !offsets || !group_of || !counts || !info) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_stream_args(seqs, offsets, n_seqs, k, threshold));
+    TRY(associate_groups(ix, group_of, n_entries, n_groups));
+    TRY(use_device(ix));
+    // (a slot for the largest chunk of the widest partition: kTallyChunkSeqs x (n_groups + 4) x 4 bytes at n_groups = 64, 1.1 MB)
+    const size_t slot_bytes = (size_t)kTallyChunkSeqs * (kAssociateMaxGroups + 4) * 4;
+    for (int s = 0; s < 2; s++) {
+        if (!ix->associate_pin[s]) HIP_TRY(hipHostMalloc(&ix->associate_pin[s], slot_bytes, hipHostMallocDefault));
+        if (!ix->associate_ev[s]) HIP_TRY(hipEventCreateWithFlags(&ix->associate_ev[s], hipEventDisableTiming));
+    }
+    TRY(associate_masks(ix, group_of, n_groups, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));      // (a pageable source, and the masks are there whichever stream a chunk runs on)
+    const size_t per_seq = ((size_t)n_groups + 4) * 4;
+    uint64_t pend_s0 = 0, pend_n = 0;      // the chunk whose outputs are still on their way: slot pend_slot
+    int pend_slot = -1;
+    int rc = consume_stream(
+        ix, ix->associate_ws, kAssociateConsumer, seqs, offsets, n_seqs, k, threshold,
+        [&](uint64_t s0, uint64_t s1) {
+            memset(counts + s0 * n_groups, 0, (size_t)(s1 - s0) * n_groups * 4);
+            memset(info + s0, 0, (size_t)(s1 - s0) * sizeof(bigsi_hip_associate_info));
+        },
+        [&](bigsi_hip_batch *b, int slot, uint64_t s0, uint64_t s1) -> int {
+            hipStream_t st = consumer_stream(b);
+            TRY(associate_launch(b, n_groups, slot, st));
+            hipError_t e = hipMemcpyAsync(ix->associate_pin[slot], ix->associate_out[slot].p, (size_t)(s1 - s0) * per_seq, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipEventRecord(ix->associate_ev[slot], st);
+            if (e != hipSuccess) return fail(BIGSI_ERR_HIP, "queueing the count download: %s", hipGetErrorString(e));
+            if (pend_slot >= 0) TRY(associate_collect(ix, pend_slot, n_groups, counts + pend_s0 * n_groups, info + pend_s0, pend_n));
+            pend_slot = slot; pend_s0 = s0; pend_n = s1 - s0;
+            return BIGSI_OK;
+        });
+    if (rc == BIGSI_OK && pend_slot >= 0) {
+        rc = associate_collect(ix, pend_slot, n_groups, counts + pend_s0 * n_groups, info + pend_s0, pend_n);
+        if (rc != BIGSI_OK)
+            for (bigsi_hip_batch *&w : ix->associate_ws) drop_workspace(w);
     }
     return rc;
 }

@@ -4,6 +4,7 @@
 // bigsi_text.cpp: FASTA / FASTQ text; bigsi_rowsfile.cpp: the file side of that pipeline -- host only, it does not include this header).
 #pragma once
 #include "bigsi_hip.h"
+#include "bigsi_hip_associate.h"
 #include "bigsi_hip_classify.h"
 #include "bigsi_hip_collapse.h"
 #include "bigsi_hip_compact.h"
@@ -108,6 +109,11 @@ struct bigsi_hip_index {
     DevBuf classify_groups, classify_rec[2];          // read classification: the uploaded group_of; a device record buffer per stream slot ...
     void *classify_pin[2] = {nullptr, nullptr};       // ... its pinned twin (stream call) and the event behind the download into it
     hipEvent_t classify_ev[2] = {nullptr, nullptr};
+    struct bigsi_hip_batch *associate_ws[2] = {};     // bigsi_hip_associate_stream's workspaces, created at its first call
+    DevBuf associate_groups, associate_masks;         // group association: the uploaded group_of; masks[n_groups][wv], rebuilt by every call ...
+    DevBuf associate_out[2];                          // ... per stream slot the infos of a chunk and, behind them, its counts ...
+    void *associate_pin[2] = {nullptr, nullptr};      // ... their pinned twin (stream call) and the event behind the download into it
+    hipEvent_t associate_ev[2] = {nullptr, nullptr};
     struct bigsi_hip_batch *window_ws = nullptr;     // bigsi_hip_window_search's workspace, created at its first call
     uint64_t window_starts = 0, window_cap = 0;       // bigsi_hip_window_set_limits: starts per segment, partial bytes cap (0: the planner's)
     uint32_t band_windows = 0, band_segs = 0;         // bigsi_hip_band_set_limits: windows per band, segments per launch (0: the planner's)

@@ -4145,4 +4145,130 @@ __global__ __launch_bounds__(kBlock) void k_classify_groups(
     }
 }
 
+// ------------------------------------------------------------------------------ group association: per-query sample counts per group
+// The hit-dense sibling of the classification (include/bigsi_hip_associate.h has the definition): per query and group of columns how
+// many columns are hit -- every group's count, the zeros included.  No work per hit: a result word is ANDed with one mask word per
+// group and popcounted, so the cost is the same whether a query hits nothing or every column.
+//
+// k_group_masks (one wavefront per result word w): group_of -> masks[n_groups][wv] in the bit layout K4 and the tally read -- lane l
+//   of word w is column 64 w + l at bit bit_of_col(l).  bit_of_col is its own inverse, so the lane takes the column whose bit it is
+//   (64 w + bit_of_col(lane): the same 256 contiguous bytes of group_of) and __ballot(group == g) is the mask word as stored.  A column
+//   at or behind num_cols, or in no group, is set in no mask: valid_mask is implicit in every group count.
+// k_group_counts (launch shape: plan_associate): a workgroup takes Q = kAssociateQueries = 4 queries; n_groups is taken in passes of
+//   GB = kAssociateGroupBlock = 8 groups.  In a pass thread t sweeps words w = t, t + kBlock, ...: GB mask words and Q result words
+//   (12 independent 8-byte loads; the masks from L2, shared by every workgroup; a result word from HBM in the first pass, from L2 in
+//   the later ones) feed Q x GB popcounts into 32 register accumulators -- a mask word is loaded once for four queries, which is
+//   what Q = 4 is for; GB = 8 keeps the accumulators, the masks and the result words of an iteration in 60 registers (the kernel
+//   takes 93 VGPRs in all, no scratch, no spill).  The first pass also counts popcount(x & valid_mask(w, n_cols)) per query:
+//   samples_hit.  Never w >= wv: the pad word of wv_pad is not read.  A query with num_unique == 0 (or behind n_seqs) loads nothing
+//   and counts nothing.
+//   reduce  the 32 accumulators of a wavefront by a halving exchange: in the step at distance d a lane keeps one half of its values,
+//           sends the other half to lane ^ d and adds what it receives -- 16 + 8 + 4 + 2 + 1 shuffles, then one more over the last
+//           pair, instead of 32 x 6 -- and lane 2 j holds the wavefront's sum of accumulator j; through static LDS to the
+//           workgroup's sums; thread q * GB + g stores counts[q0 + q][g0 + g] plainly, and thread q < Q keeps the query's running
+//           grouped_hit over the passes and writes the info behind the last.
+// Integer AND, popcount and add only; no atomic anywhere, no early exit: the one sweep per pass is the whole cost.
+__global__ __launch_bounds__(kBlock) void k_group_masks(const uint32_t *__restrict__ group_of, uint64_t n_cols, uint32_t wv, uint32_t n_groups,
+                                                        uint64_t *__restrict__ masks)
+{
+    const uint32_t w = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (w >= wv) return;                                     // (uniform over the wavefront)
+    const uint64_t col = (uint64_t)w * 64 + bit_of_col(lane);
+    const uint32_t mine = col < n_cols ? group_of[col] : kAssociateNoGroup;
+    for (uint32_t g = 0; g < n_groups; g++) {
+        const uint64_t m = __ballot((int)(mine == g));
+        if (lane == 0) masks[(uint64_t)g * wv + w] = m;
+    }
+}
+
+// one step of the halving exchange at distance 2 N over acc[0 .. 2 N), and the steps below it (every index a constant: registers)
+template <uint32_t N>
+__device__ __forceinline__ void group_halve(uint32_t (&acc)[kAssociateQueries * kAssociateGroupBlock], uint32_t lane)
+{
+    const bool upper = (lane & (2 * N)) != 0;
+#pragma unroll
+    for (uint32_t i = 0; i < N; i++) {
+        const uint32_t send = upper ? acc[i] : acc[i + N], keep = upper ? acc[i + N] : acc[i];
+        acc[i] = keep + __shfl_xor(send, (int)(2 * N));
+    }
+    if constexpr (N > 1) group_halve<N / 2>(acc, lane);
+}
+
+__global__ __launch_bounds__(kBlock) void k_group_counts(
+    const uint64_t *__restrict__ bitmaps, uint64_t bm_stride, uint32_t wv, uint64_t n_cols, const uint32_t *__restrict__ num_unique, double threshold,
+    uint32_t n_seqs, const uint64_t *__restrict__ masks, uint32_t n_groups, uint32_t *__restrict__ counts, uint4 *__restrict__ info)
+{
+    constexpr uint32_t Q = kAssociateQueries, GB = kAssociateGroupBlock, NV = Q * GB, WAVES = kBlock / 64;
+    static_assert(NV == 32, "the halving exchange below leaves accumulator j in lanes 2 j and 2 j + 1 of a 64-lane wavefront");
+    __shared__ uint32_t part[WAVES][NV];
+    __shared__ uint32_t part_hit[WAVES][Q];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint64_t q0 = (uint64_t)blockIdx.x * Q;
+    uint32_t u[Q];
+    bool live[Q];
+#pragma unroll
+    for (uint32_t q = 0; q < Q; q++) {
+        u[q] = q0 + q < n_seqs ? num_unique[q0 + q] : 0u;
+        live[q] = u[q] != 0;
+    }
+    uint32_t grouped = 0;                                    // thread q < Q: the query's counts summed over the passes
+    uint32_t hit_all = 0;                                    // thread q < Q: samples_hit (first pass)
+    for (uint32_t g0 = 0; g0 < n_groups; g0 += GB) {
+        uint32_t acc[NV], hit[Q];
+#pragma unroll
+        for (uint32_t i = 0; i < NV; i++) acc[i] = 0u;
+#pragma unroll
+        for (uint32_t q = 0; q < Q; q++) hit[q] = 0u;
+#pragma unroll 1
+        for (uint32_t w = threadIdx.x; w < wv; w += kBlock) {
+            uint64_t m[GB], x[Q];
+#pragma unroll
+            for (uint32_t g = 0; g < GB; g++) m[g] = g0 + g < n_groups ? masks[(uint64_t)(g0 + g) * wv + w] : 0ull;
+#pragma unroll
+            for (uint32_t q = 0; q < Q; q++) x[q] = live[q] ? bitmaps[(q0 + q) * bm_stride + w] : 0ull;
+#pragma unroll
+            for (uint32_t q = 0; q < Q; q++)
+#pragma unroll
+                for (uint32_t g = 0; g < GB; g++) acc[q * GB + g] += (uint32_t)__popcll(x[q] & m[g]);
+            if (g0 == 0) {
+                const uint64_t vm = valid_mask(w, n_cols);
+#pragma unroll
+                for (uint32_t q = 0; q < Q; q++) hit[q] += (uint32_t)__popcll(x[q] & vm);
+            }
+        }
+        group_halve<NV / 2>(acc, lane);
+        acc[0] += __shfl_xor(acc[0], 1);
+        if ((lane & 1u) == 0) part[wave][lane >> 1] = acc[0];
+        if (g0 == 0) {
+#pragma unroll
+            for (uint32_t q = 0; q < Q; q++) {
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) hit[q] += __shfl_xor(hit[q], d);
+                if (lane == 0) part_hit[wave][q] = hit[q];
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < NV) {
+            const uint32_t q = threadIdx.x / GB, g = threadIdx.x % GB;
+            uint32_t sum = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < WAVES; i++) sum += part[i][threadIdx.x];
+            if (q0 + q < n_seqs && g0 + g < n_groups) counts[(q0 + q) * n_groups + g0 + g] = sum;
+        }
+        if (threadIdx.x < Q) {
+            for (uint32_t i = 0; i < WAVES; i++) {
+                for (uint32_t g = 0; g < GB; g++) grouped += part[i][threadIdx.x * GB + g];
+                if (g0 == 0) hit_all += part_hit[i][threadIdx.x];
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < Q && q0 + threadIdx.x < n_seqs) {
+        const uint32_t uq = num_unique[q0 + threadIdx.x];
+        const double mkd = ceil((double)uq * threshold);          // min_kmers as K1 computes it
+        const uint32_t mk = mkd > 0.0 ? (uint32_t)mkd : 0u;
+        info[q0 + threadIdx.x] = make_uint4(uq, uq ? mk : 0u, hit_all, grouped);
+    }
+}
+
 }   // namespace bigsi

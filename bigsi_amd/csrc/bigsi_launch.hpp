@@ -1053,6 +1053,38 @@ static inline uint64_t classify_bad_column(const uint32_t *group_of, uint64_t n_
     return n_entries;
 }
 
+// ------------------------------------------------------------------------------ group association (k_group_masks, k_group_counts)
+// k_group_masks: one wavefront per result word, kBlock / 64 words per workgroup -> masks[n_groups][wv].  k_group_counts: a workgroup of
+// kBlock threads takes kAssociateQueries queries and sweeps their wv words once per pass of kAssociateGroupBlock groups (GB), whose
+// kAssociateQueries x GB partial counts stay in registers; static LDS holds the wavefronts' partial sums (the counts and, in the first
+// pass, one samples_hit per query).  Refused: more than 2^31 - 1 workgroups in either launch, n_groups outside 1 .. kAssociateMaxGroups.
+constexpr uint32_t kAssociateMaxGroups = 64;                // BIGSI_ASSOCIATE_MAX_GROUPS (include/bigsi_hip_associate.h)
+constexpr uint32_t kAssociateNoGroup = 0xFFFFFFFFu;         // BIGSI_ASSOCIATE_NONE
+static_assert(kAssociateNoGroup == kClassifyNoGroup, "classify_bad_column serves both");
+constexpr uint32_t kAssociateQueries = 4;                   // queries per workgroup of k_group_counts
+constexpr uint32_t kAssociateGroupBlock = 8;                // GB: groups per pass of k_group_counts
+struct AssociatePlan {
+    uint32_t block = kBlock;
+    uint64_t grid = 0, mask_grid = 0;                         // k_group_counts; k_group_masks
+    uint32_t lds_bytes = 0, passes = 0;                       // static LDS of k_group_counts; its passes over a query's result vector
+    uint64_t mask_bytes = 0;                                  // masks[n_groups][wv]
+    uint64_t too_large = 0;                                   // != 0: the workgroups one launch would take (more than 2^31 - 1): refused
+    bool bad_groups = false;                                  // n_groups is 0 or above kAssociateMaxGroups: refused
+};
+static inline AssociatePlan plan_associate(uint64_t n_seqs, uint64_t wv, uint64_t n_groups)
+{
+    AssociatePlan p;
+    p.grid = (n_seqs + kAssociateQueries - 1) / kAssociateQueries;
+    p.mask_grid = (wv + kBlock / 64 - 1) / (kBlock / 64);
+    p.lds_bytes = (kBlock / 64) * kAssociateQueries * (kAssociateGroupBlock + 1) * 4;
+    if (p.grid > 0x7FFFFFFFull) p.too_large = p.grid;
+    else if (p.mask_grid > 0x7FFFFFFFull) p.too_large = p.mask_grid;
+    if (n_groups == 0 || n_groups > kAssociateMaxGroups) { p.bad_groups = true; return p; }
+    p.passes = (uint32_t)((n_groups + kAssociateGroupBlock - 1) / kAssociateGroupBlock);
+    p.mask_bytes = n_groups * wv * 8;
+    return p;
+}
+
 // ------------------------------------------------------------------------------ windowed search (k_window_max, k_window_combine)
 // plan_window_search: sequence q of a batch has n[q] k-mer positions, a window of We = min(W, n[q]) of them and the window starts
 // [0, n[q] - We]; the sweep cuts every sequence's starts into segments of at most S and a wavefront of k_window_max owns one

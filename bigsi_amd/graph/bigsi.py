@@ -955,6 +955,62 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
             _, group_names = self._classify_groups(groups, others)
         return result(records, group_names, self._name_of(), margin)
 
+    # ------------------------------------------------------------------ group association
+    def _associate_groups(self, groups, others):
+        """(group_of uint32[matrix columns], group names, sizes) of associate.associate_plan over this index's colours, placed as
+        _classify_groups places its own: a deleted sample, a colour without a metadata record and a column behind the metadata are in
+        no group."""
+        from ..associate import associate_plan
+        from ..classify import NONE
+        names = []
+        for c in range(self.num_samples):
+            try:
+                names.append(self.colour_to_sample(c))
+            except KeyError:
+                names.append(DELETION_SPECIAL_SAMPLE_NAME)
+        group_of, group_names, _ = associate_plan(names, groups, others)
+        n_cols = int(self.storage.get_integer("number_of_cols"))
+        full = np.full(n_cols, NONE, dtype=np.uint32)
+        full[:min(n_cols, group_of.size)] = group_of[:n_cols]
+        sizes = np.bincount(full[full != NONE].astype(np.int64), minlength=len(group_names)).astype(np.int64)
+        return full, group_names, sizes
+
+    def associate_arrays(self, seqs, groups, threshold=1.0, others=None, batch_kmers=1 << 19):
+        """The question of a GWAS or a marker screen: for every sequence (unitig, gene, probe), how many samples of each GROUP hold it
+        -- answered on the device (bigsi_hip_associate_stream: the result vectors ANDed with one mask per group and popcounted behind
+        the row-AND kernels; no hit list is built and n_groups + 4 integers per sequence leave the device).  Yields (slice, counts,
+        info) per slice of the input: the slice's sequences, counts uint32[len(slice), n_groups] in the group order
+        associate.associate_plan(names, groups, others) gives, and a structured array of associate.INFO_DTYPE.  `groups` is what
+        collapse takes (a mapping group -> [samples] or (sample, group) pairs); `seqs` is any iterable of ASCII sequences, fed in
+        slices of about 8 x `batch_kmers` k-mers, as classify slices its input.  Multi-GPU (devices=[...]) indexes are refused."""
+        self._check_stream_query(seqs, threshold)
+        from ..collapse import check_groups
+        check_groups(groups)
+        self._refuse_group("group association")
+        k = int(self.kmer_size)
+        with self._device_lock():
+            group_of, group_names, _ = self._associate_groups(groups, others)
+            for chunk in self._slices(iter(seqs), 64, None, batch_kmers * 8, k):
+                for s in chunk:
+                    if not isinstance(s, str) or not s.isascii():
+                        raise ValueError("group association takes ASCII sequences (queries with other characters are out of scope)")
+                counts, info = self.storage.associate(chunk, k, threshold, group_of, len(group_names))
+                yield chunk, counts, info
+
+    def associate(self, seqs, groups, threshold=1.0, others=None, min_af=None):
+        """associate_arrays over all of `seqs`, as associate.result gives it: {"groups": [group names in id order], "sizes": the live
+        samples of each, "total", "records": [per kept sequence "index", "num_kmers", "min_kmers", "samples_hit", "grouped_hit" and
+        "groups": {name: "hit", "prevalence", "log2_odds", "chi2", "p" -- group against the rest of the grouped samples}], "dropped"}.
+        min_af=F drops the sequences whose grouped hit fraction lies outside [F, 1 - F]."""
+        from ..associate import INFO_DTYPE, result
+        result(np.zeros((0, 1), np.uint32), np.zeros(0, INFO_DTYPE), ["x"], [0], min_af)          # (min_af is checked before any device call)
+        parts = [(c, i) for _, c, i in self.associate_arrays(seqs, groups, threshold, others)]
+        with self._device_lock():
+            _, group_names, sizes = self._associate_groups(groups, others)
+        counts = np.concatenate([c for c, _ in parts]) if parts else np.zeros((0, len(group_names)), np.uint32)
+        info = np.concatenate([i for _, i in parts]) if parts else np.zeros(0, INFO_DTYPE)
+        return result(counts, info, group_names, sizes, min_af)
+
     # ------------------------------------------------------------------ column compaction: vacuum / extract
     def _colour_names(self):
         """names[c] of every colour, DELETION_SPECIAL_SAMPLE_NAME for a deleted one; the matrix must be as wide as the metadata."""

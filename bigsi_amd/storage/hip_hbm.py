@@ -696,6 +696,25 @@ class HipHbmStorage(BaseStorage):
                                                    int(n_groups), _lib.ptr(records)))
         return records
 
+    def associate(self, seqs, k, threshold, group_of, n_groups):
+        """Per sequence how many samples of every group hold it (bigsi_hip_associate_stream: mask-and-popcount over the result vectors
+        on the device, n_groups + 4 integers per sequence leave it; include/bigsi_hip_associate.h).  group_of: one uint32 per column,
+        below n_groups or bigsi_amd.classify.NONE.  Returns (counts uint32[len(seqs), n_groups], info: a structured array of
+        bigsi_amd.associate.INFO_DTYPE[len(seqs)])."""
+        from ..associate import INFO_DTYPE
+        self._single_gpu("group association")
+        res = self._opened()
+        seqs = list(seqs)
+        counts = np.zeros((len(seqs), int(n_groups)), np.uint32)
+        info = np.zeros(len(seqs), INFO_DTYPE)
+        if not seqs:
+            return counts, info
+        group_of = np.ascontiguousarray(group_of, dtype=np.uint32)
+        blob, off = _lib.pack_seqs(seqs)
+        check(_lib.lib().bigsi_hip_associate_stream(self.handle, blob, _lib.ptr(off), len(seqs), int(k), float(threshold), _lib.ptr(group_of), group_of.size,
+                                                    int(n_groups), _lib.ptr(counts), _lib.ptr(info)))
+        return counts, info
+
     def fill_synthetic(self, seed, shard=0, and_draws=2):
         if self.res.is_group:       # shard i of the group is filled as (seed, shard i)
             check(_lib.lib().bigsi_hip_group_fill_synthetic(self.res.ix, int(seed), int(and_draws)))

@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] [classify] [window] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] [classify] [associate] [window] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -922,6 +922,96 @@ def classify():
     reads = rand_seqs(rng, 65536, 61)
     for thr in (1.0, 0.4):
         line("classify_c2_reads", st, 10_000, reads, thr, "65 536 reads of 61 bp")
+    st.delete_all()
+
+
+ASSOCIATE_INPUTS = ("sparse", "dense")
+ASSOCIATE_CALLS = ("tally", "tally", "classify2", "classify64", "associate2", "associate64")
+
+
+def associate():
+    """Group association (bigsi_hip_associate_stream) beside the read classification (bigsi_hip_classify_stream) and the query-set
+    tally (bigsi_hip_tally_add_stream + fetch), ONE PROCESS PER FIGURE: without BIGSI_ASSOCIATE_FIGURE this leg starts a fresh child
+    process of itself for every (input, call) pair, one after the other, and relays their lines; with BIGSI_ASSOCIATE_FIGURE =
+    "<input>:<call>" it measures that one.  Inputs, on the C3 index (10 M x 100 k, h = 4), threshold 1.0: "sparse" -- 8192 x 1 kbp as
+    drawn, the classify leg's input; "dense" -- 256 x 1 kbp, each held whole by the same random half of the columns (one insert_kmers
+    per column, as the dense bench legs plant theirs).  Calls: the tally (twice per input: what two processes of a session differ by),
+    the classifier and the association with 2 groups (colour parity) and 64 (colour mod 64).  Per line: wall ms of the call (best of
+    3 after a warm call, and all three), and from one profiled call (level 1) the consumer kernels' own time by HIP events
+    (k_group_counts, k_classify_groups, k_tally_hits + k_tally_totals: compact_ms of bigsi_hip_stats) beside that call's row-AND and
+    K1 time; hit_columns for the lines of an input to be compared."""
+    import subprocess
+    figure = os.environ.get("BIGSI_ASSOCIATE_FIGURE")
+    if not figure:
+        for inp in ASSOCIATE_INPUTS:
+            for call in ASSOCIATE_CALLS:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "associate"], env=dict(os.environ, BIGSI_ASSOCIATE_FIGURE="%s:%s" % (inp, call)),
+                                   capture_output=True, text=True, timeout=600)
+                sys.stdout.write(r.stdout)
+                sys.stdout.flush()
+                if r.returncode != 0:          # nothing more is started on the device behind a process that failed
+                    sys.stderr.write(r.stderr[-4000:])
+                    raise SystemExit("associate figure %s:%s exited with %d" % (inp, call, r.returncode))
+        return
+    inp, call = figure.split(":")
+    assert inp in ASSOCIATE_INPUTS and call in ASSOCIATE_CALLS, figure
+    L = _lib.lib()
+    from bigsi_amd.associate import INFO_DTYPE
+    from bigsi_amd.classify import RECORD_DTYPE
+    m, n, h, k = 10_000_000, 100_000, 4, 31
+    st, fill_s = open_index("associate", m, n, h)
+    rng = np.random.default_rng(11)
+    seqs = rand_seqs(rng, 8192, 1000)
+    plant_s = 0.0
+    if inp == "dense":
+        seqs = seqs[:256]
+        blob, off = _lib.pack_seqs(seqs)
+        cols = np.sort(rng.choice(n, size=n // 2, replace=False))
+        t0 = time.time()
+        insert = st.res.fn("insert_kmers")
+        for c in cols:
+            check(insert(st.res.ix, int(c), blob, _lib.ptr(off), len(seqs), k))
+        check(L.bigsi_hip_synchronize(st.handle))
+        plant_s = time.time() - t0
+    blob, off = _lib.pack_seqs(seqs)
+    n_groups = 2 if call.endswith("2") else 64
+    group_of = (np.arange(n, dtype=np.uint64) % n_groups).astype(np.uint32)
+    if call == "tally":
+        t = st.new_tally()
+
+        def one():
+            t.reset()
+            check(L.bigsi_hip_tally_add_stream(t.b, blob, _lib.ptr(off), len(seqs), k, 1.0))
+            return int(t.fetch()[0].sum())
+    elif call.startswith("classify"):
+        records = np.zeros(len(seqs), RECORD_DTYPE)
+
+        def one():
+            check(L.bigsi_hip_classify_stream(st.handle, blob, _lib.ptr(off), len(seqs), k, 1.0, _lib.ptr(group_of), n, n_groups, _lib.ptr(records)))
+            return int(records["samples_hit"].astype(np.uint64).sum())
+    else:
+        counts, info = np.zeros((len(seqs), n_groups), np.uint32), np.zeros(len(seqs), INFO_DTYPE)
+
+        def one():
+            check(L.bigsi_hip_associate_stream(st.handle, blob, _lib.ptr(off), len(seqs), k, 1.0, _lib.ptr(group_of), n, n_groups, _lib.ptr(counts), _lib.ptr(info)))
+            assert int(counts.astype(np.uint64).sum()) == int(info["grouped_hit"].astype(np.uint64).sum()) == int(info["samples_hit"].astype(np.uint64).sum())
+            return int(info["samples_hit"].astype(np.uint64).sum())
+    one()
+    walls = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        hits = one()
+        walls.append((time.perf_counter() - t0) * 1e3)
+    check(L.bigsi_hip_set_profiling(st.handle, 1))
+    stats(st)
+    one()
+    s_ = stats(st)
+    check(L.bigsi_hip_set_profiling(st.handle, 0))
+    emit("associate_" + inp, call=call, threshold=1.0, n_seqs=len(seqs), cols=n, n_groups=None if call == "tally" else n_groups, hit_columns=hits,
+         call_ms=min(walls), call_ms_all=walls, consumer_kernels_ms=s_.compact_ms, row_and_ms=s_.and_ms, k1_ms=s_.kmerize_ms,
+         note="fill %.1f s, planted in %.1f s; a process of its own" % (fill_s, plant_s))
+    if call == "tally":
+        t.close()
     st.delete_all()
 
 

@@ -66,7 +66,7 @@ class RowAndPath(C.Structure):
     """bigsi_hip_row_and_path (include/bigsi_hip_testing.h): the route a batch's last run took through K1, the row sort and the row-AND"""
     _fields_ = [(name, C.c_uint32) for name in ("k1_route", "band_taken", "band_windows", "band_launches", "slices", "block", "tiles", "chunk_q",
                                                 "n_launches", "last_slices", "last_block", "last_unroll", "sorted_by", "early_exit", "preset_by",
-                                                "zero_copy")]
+                                                "zero_copy", "k1_parts", "k1_arg_bytes")]
 
 
 K1_ELEMENTS, K1_WAVE, K1_LDS, K1_GLOBAL = 0, 1, 2, 3
@@ -209,6 +209,7 @@ SIGNATURES = {
     "bigsi_hip_hits_last_path": (_i32, [_P, _u32, C.POINTER(HitsPath)]),                  # (include/bigsi_hip_testing.h)
     "bigsi_hip_batch_last_row_and": (_i32, [_P, _u32, C.POINTER(RowAndPath)]),            # (include/bigsi_hip_testing.h)
     "bigsi_hip_batch_fetch_rows_sorted": (_i32, [_P, _u32, _P, _u64, C.POINTER(_u32)]),   # (include/bigsi_hip_testing.h)
+    "bigsi_hip_batch_fetch_positions": (_i32, [_P, _u32, _P, _P, _u64]),                  # (include/bigsi_hip_testing.h)
     "bigsi_hip_rank_select_arrays": (_i32, [_i32, _P, _u64, _u32, _u32, _P, _u32, _P, _P, _P, _u32, _u32, _P]),   # (include/bigsi_hip_testing.h)
 }
 

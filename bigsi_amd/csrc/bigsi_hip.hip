@@ -1965,6 +1965,8 @@ static int launch_reads_fused(bigsi_hip_batch *b, hipStream_t st = nullptr, bool
     const K1Src src = k1_src(b);
     // one read read in place: its bytes go in the kernel arguments, not over the host link (SeqArg, bigsi_kernels.hpp)
     const bool by_arg = src.one_len && src.one_len <= kSeqArgRead;
+    b->rpath.k1_parts = 1u;      // (bigsi_hip_batch_last_row_and: all a read run reports)
+    b->rpath.k1_arg_bytes = by_arg ? kSeqArgRead : 0u;
     SeqArg<kSeqArgRead> read_arg;
     if (by_arg) read_arg = src.by_value<kSeqArgRead>();
     else memset(read_arg.w, 0, sizeof read_arg.w);
@@ -2040,6 +2042,8 @@ static int run_kmerize(bigsi_hip_batch *b, double threshold, const K1Plan &plan,
     if (b->g_done && b->gstream && b->gstream != ks) HIP_TRY(hipStreamWaitEvent(ks, b->g_done, 0));
     TRY(b->rows.reserve(std::max<uint64_t>(b->total_pos, 1) * ix->h * 8));
     const K1Src src = k1_src(b);
+    b->rpath.k1_parts = 1u;                // (bigsi_hip_batch_last_row_and; the LDS route says below what it took)
+    b->rpath.k1_arg_bytes = 0u;
     if (plan.route == K1_ELEMENTS) {       // explicit k-mers: only the hashing is left of K1
         TRY(ev_begin(ix, &ep, ks));
         hipLaunchKernelGGL(k_rows_raw, dim3(b->n_seqs), dim3(kBlock), 0, ks, b->seqs.as<char>(), b->d_seq_off.as<uint64_t>(), b->elem_seq_off.as<uint64_t>(),
@@ -2097,6 +2101,8 @@ static int run_kmerize(bigsi_hip_batch *b, double threshold, const K1Plan &plan,
     else BIGSI_K1_LDS_(KF, 0, SeqArg<0>{})
         if (b->k == 31) BIGSI_K1_LDS(31);
         else BIGSI_K1_LDS(0);
+        b->rpath.k1_parts = parts;
+        b->rpath.k1_arg_bytes = !src.one_len ? 0u : src.one_len <= kSeqArgSmall ? kSeqArgSmall : src.one_len <= kSeqArgLarge ? kSeqArgLarge : 0u;
 #undef BIGSI_K1_LDS
 #undef BIGSI_K1_LDS_
         if (preset) preset->done = ps_p != nullptr;
@@ -2789,6 +2795,21 @@ extern "C" int bigsi_hip_batch_fetch_rows_sorted(bigsi_hip_batch *b, uint32_t se
         *shift = sort_shift(b->ix->m, tsize);
     } else *shift = sort_shift(b->ix->m, kSortBuckets);
     if (n) HIP_TRY(hipMemcpy(rows, b->rows_sorted.as<uint64_t>() + b->pos_off[seq] * b->ix->h, n * 8, hipMemcpyDeviceToHost));
+    return BIGSI_OK;
+}
+
+// include/bigsi_hip_testing.h: K1's per-position maps of one sequence (two copies, no kernel)
+extern "C" int bigsi_hip_batch_fetch_positions(bigsi_hip_batch *b, uint32_t seq, uint32_t *rep, uint32_t *pos_unique, uint64_t capacity)
+{
+    BIGSI_ENTER(b ? b->ix : nullptr);
+    TRY(need_run(b));
+    if (seq >= b->n_seqs) return fail(BIGSI_ERR_RANGE, "sequence %u out of range", seq);
+    if (b->elements) return fail(BIGSI_ERR_STATE, "a batch of explicit k-mers has no representatives");
+    TRY(host_counts(b));
+    const uint64_t n = b->h_num_kmers[seq];
+    if (n > capacity) return fail(BIGSI_ERR_CAPACITY, "position buffers hold %llu, %llu needed", (unsigned long long)capacity, (unsigned long long)n);
+    if (n && rep) HIP_TRY(hipMemcpy(rep, b->rep.as<uint32_t>() + b->pos_off[seq], n * 4, hipMemcpyDeviceToHost));
+    if (n && pos_unique) HIP_TRY(hipMemcpy(pos_unique, b->pos_unique.as<uint32_t>() + b->pos_off[seq], n * 4, hipMemcpyDeviceToHost));
     return BIGSI_OK;
 }
 

@@ -1083,6 +1083,14 @@ class QueryBatch(object):
         check(_lib.lib().bigsi_hip_batch_fetch_rows(self.b, i, _lib.ptr(out), out.size))
         return out[:int(num_unique)]
 
+    def positions(self, i, num_kmers):
+        """(rep uint32[num_kmers], pos_unique uint32[num_kmers]) of sequence i: per k-mer position the first position that holds its
+        k-mer and that k-mer's index among the unique ones (bigsi_hip_batch_fetch_positions: a test hook, two copies)."""
+        self._single_only("positions()")
+        rep, pu = np.zeros(max(int(num_kmers), 1), np.uint32), np.zeros(max(int(num_kmers), 1), np.uint32)
+        check(_lib.lib().bigsi_hip_batch_fetch_positions(self.b, i, _lib.ptr(rep), _lib.ptr(pu), rep.size))
+        return rep[:int(num_kmers)], pu[:int(num_kmers)]
+
     def lookup(self, i, num_unique):
         self._single_only("lookup()")
         rb = max(int(self.storage.res.info().row_bytes), 1)

@@ -149,10 +149,13 @@ int bigsi_hip_hits_last_path(const void *owner, uint32_t kind, bigsi_hip_hits_pa
  *   early_exit               BIGSI_RUN_EARLY_EXIT reached the kernel
  *   preset_by                who set the result words a sliced exact run ANDs into: 0 nobody (not sliced), 1 K1, 2 a memset
  *   zero_copy                K1 read the sequences in place from the caller's pinned staging (a one-call search)
- * A one-launch read run (k_reads_fused) leaves the record zero. */
+ *   k1_parts                 workgroups per query of K1: 8 where k_kmerize_lds spread a query's hashing (`parts`), else 1
+ *   k1_arg_bytes             the instance that took the ONE sequence of a one-call search by value in its kernel arguments (SeqArg):
+ *                            96 (k_reads_fused), 1024 or 3072 (k_kmerize_lds); 0: K1 read the sequences from memory
+ * A one-launch read run (k_reads_fused) fills k1_parts (1) and k1_arg_bytes and leaves the rest of the record zero. */
 typedef struct bigsi_hip_row_and_path {
     uint32_t k1_route, band_taken, band_windows, band_launches, slices, block, tiles, chunk_q, n_launches, last_slices, last_block,
-        last_unroll, sorted_by, early_exit, preset_by, zero_copy;
+        last_unroll, sorted_by, early_exit, preset_by, zero_copy, k1_parts, k1_arg_bytes;
 } bigsi_hip_row_and_path;
 #define BIGSI_SORTED_BY_NONE 0u
 #define BIGSI_SORTED_BY_K1 1u
@@ -164,6 +167,12 @@ int bigsi_hip_batch_last_row_and(const void *owner, uint32_t kind, bigsi_hip_row
  * table) on K1's LDS route, sort_shift(m, 8192) for k_sort_rows.  One device-to-host copy, no kernel.  BIGSI_ERR_STATE when the
  * last run made no sorted list, BIGSI_ERR_RANGE / BIGSI_ERR_CAPACITY as bigsi_hip_batch_fetch_rows. */
 int bigsi_hip_batch_fetch_rows_sorted(bigsi_hip_batch *b, uint32_t seq, uint64_t *rows, uint64_t capacity, uint32_t *shift);
+/* K1's two per-position maps of sequence `seq` as the last run of `b` left them, num_kmers entries each, `capacity` at least:
+ * rep[p] the first position that holds position p's k-mer, pos_unique[p] the index of that k-mer among the sequence's unique k-mers
+ * (what the presence strings expand by).  Either pointer may be NULL.  One device-to-host copy per array, no kernel.
+ * BIGSI_ERR_STATE on a batch of explicit k-mers (its K1 dedupes nothing), BIGSI_ERR_RANGE / BIGSI_ERR_CAPACITY as
+ * bigsi_hip_batch_fetch_rows. */
+int bigsi_hip_batch_fetch_positions(bigsi_hip_batch *b, uint32_t seq, uint32_t *rep, uint32_t *pos_unique, uint64_t capacity);
 
 /* THE TOP-N SELECTION ON CALLER DATA (k_rank_select; its peer for K6 is bigsi_hip_score_presence): no index, no batch.  For n_seqs
  * queries the call stages

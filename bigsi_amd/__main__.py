@@ -194,7 +194,13 @@ def build_parser():
     sp.add_argument("--min-af", type=float, default=None, metavar="F",
                     help="drop the records held by less than F or more than 1 - F of the grouped samples (0 .. 0.5)")
     sp.add_argument("--format", choices=["tsv", "json"], default="tsv")
-    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally", "window_search", "classify", "associate"):          # (named so that the refusal says why)
+    sp = common(sub.add_parser("genotype", help="every sample's call (0/0, 0/1, 1/1, ./.) for a panel of variants: concatenated `mykrobe variants make-probes` "
+                                                "output, ref- records opening a variant (the probes are ORed into one bit plane per allele on the device)"))
+    sp.add_argument("panel")
+    sp.add_argument("--threshold", "-t", type=float, default=1.0)
+    sp.add_argument("--format", choices=["tsv", "json"], default="tsv")
+    sp.add_argument("--summary-only", action="store_true", help="per-variant counts and per-sample carried / called only (the planes are never downloaded)")
+    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally", "window_search", "classify", "associate", "genotype"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -359,6 +365,14 @@ def associate_text(index, records, pairs, threshold=1.0, others=None, min_af=Non
     return to_json(res, names) if fmt == "json" else to_tsv(res, names)
 
 
+def genotype_text(index, panel, threshold=1.0, fmt="tsv", summary_only=False):
+    """`genotype`: BIGSI.genotype_panel over a panel file.  TSV: the matrix -- header variant<TAB>sample..., cells 0/0 0/1 1/1 ./. --, or
+    with --summary-only the per-variant counts and the per-sample carried / called; JSON: the result."""
+    from .genotype import to_json, to_tsv
+    res = index.genotype_panel(panel, threshold=threshold, summary_only=summary_only)
+    return to_json(res) if fmt == "json" else to_tsv(res, summary_only)
+
+
 def window_search_text(index, queries, window, threshold=1.0, fmt="json"):
     """`window_search`: BIGSI.search_windows_many over the queries, one device call per query (a long query is a call's worth of work,
     and the device keeps counters per sequence).  JSON: the dicts, each with its "query" first; CSV: record,<result fields>, one line
@@ -462,6 +476,19 @@ def main(argv=None):
             check_groups(associate_pairs)
         except (OSError, ValueError) as e:
             p.error("associate --groups: %s" % e)
+    if getattr(a, "sharded", False) and a.cmd == "genotype":
+        p.error("genotype is not available with --sharded: the per-shard planes plus a host merge are not implemented (use a single index)")
+    if a.cmd == "genotype":
+        if not a.threshold <= 1:
+            p.error("genotype: the threshold must be <= 1, got %r" % (a.threshold,))
+        try:
+            with open(a.panel) as f:
+                genotype_panel = f.read()
+            from .genotype import parse_panel
+            if not parse_panel(genotype_panel)[0]:
+                raise ValueError("no variant in it")
+        except (OSError, ValueError) as e:
+            p.error("genotype: the panel %s: %s" % (a.panel, e))
     if getattr(a, "sharded", False) and a.cmd == "window_search":
         p.error("window_search is not available with --sharded: the per-shard sweep is not implemented (use a single index)")
     if a.cmd == "window_search" and (a.seq is None) == (a.fasta is None):
@@ -559,6 +586,8 @@ def main(argv=None):
         print(tally_text(BIGSI(config), [s for _, s in read_fasta(a.fasta)], a.threshold, a.limit, a.format))
     elif a.cmd == "classify":
         print(classify_text(BIGSI(config), read_fasta(a.fasta), classify_pairs, a.threshold, a.margin, a.others, a.format, a.summary_only))
+    elif a.cmd == "genotype":
+        print(genotype_text(BIGSI(config), genotype_panel, a.threshold, a.format, a.summary_only))
     elif a.cmd == "associate":
         print(associate_text(BIGSI(config), read_fasta(a.fasta), associate_pairs, a.threshold, a.others, a.min_af, a.format))
     elif a.cmd == "distances":

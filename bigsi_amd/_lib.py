@@ -277,6 +277,16 @@ ASSOCIATE_SIGNATURES = {
     "bigsi_hip_associate_stream": (_i32, [_P, C.c_char_p, _P, _u64, _u32, _dbl, _P, _u64, _u32, _P, _P]),
 }
 
+# every symbol include/bigsi_hip_genotype.h declares (panel genotyping: the probes' result vectors ORed into one plane per allele, calls and counts on the device)
+GENOTYPE_SIGNATURES = {
+    "bigsi_hip_genotype_create": (_i32, [_P, _u32, _P, C.POINTER(_P)]),
+    "bigsi_hip_genotype_destroy": (_i32, [_P]),
+    "bigsi_hip_genotype_reset": (_i32, [_P]),
+    "bigsi_hip_genotype_add_batch": (_i32, [_P, _P, _P, _u64]),
+    "bigsi_hip_genotype_add_stream": (_i32, [_P, C.c_char_p, _P, _u64, _u32, _dbl, _P]),
+    "bigsi_hip_genotype_fetch": (_i32, [_P, _P, _P, _u64, _P, _P, _u64, _P]),
+}
+
 # every symbol include/bigsi_hip_kmercount.h declares (exact k-mer counter: Bloom filters from raw reads, min-count on the device); the
 # host twin's library has the same eight under its own prefix (bigsi_amd/kmercount.py binds either set from this table)
 KMERCOUNT_SIGNATURES = {
@@ -310,7 +320,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()) + list(TALLY_SIGNATURES.items()) + list(CLASSIFY_SIGNATURES.items()) + list(KMERCOUNT_SIGNATURES.items()) + list(ASSOCIATE_SIGNATURES.items()) + list(WINDOW_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()) + list(TALLY_SIGNATURES.items()) + list(CLASSIFY_SIGNATURES.items()) + list(KMERCOUNT_SIGNATURES.items()) + list(ASSOCIATE_SIGNATURES.items()) + list(GENOTYPE_SIGNATURES.items()) + list(WINDOW_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

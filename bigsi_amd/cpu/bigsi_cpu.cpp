@@ -27,6 +27,7 @@
 #include "bigsi_cpu_tally.h"
 #include "bigsi_cpu_classify.h"
 #include "bigsi_cpu_associate.h"
+#include "bigsi_cpu_genotype.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1233,6 +1234,65 @@ int bigsi_cpu_associate(bigsi_cpu_index *ix, const char *seqs, const uint64_t *o
     TRY(bdb_read_failed(ix));
     memcpy(counts, out.data(), out.size() * sizeof(uint32_t));
     memcpy(info, out_info.data(), n_seqs * sizeof(bigsi_hip_associate_info));
+    return BIGSI_OK;
+}
+
+// panel genotyping: every probe searched in the reference's shape, then a loop over its hit columns: the column's bit of the probe's
+// allele plane is set when the column is selected.  The calls and counts follow column by column, variant by variant, as genotypes()
+// of bigsi_amd/variant_search.py takes them.  A threshold below 0 asks for what 0 asks for.
+int bigsi_cpu_genotype(bigsi_cpu_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
+                       const uint32_t *allele_of, uint32_t n_variants, const uint8_t *columns, uint8_t *ref_planes, uint8_t *alt_planes,
+                       uint64_t plane_capacity_bytes, uint32_t *variant_counts, uint32_t *sample_counts, uint64_t sample_capacity, uint32_t *allele_probes)
+{
+    if (!ix || !allele_of || !variant_counts || !sample_counts || !allele_probes) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_seqs(seqs, offsets, n_seqs, k));
+    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    if (n_variants == 0 || n_variants > BIGSI_GENOTYPE_MAX_VARIANTS)
+        return fail(BIGSI_ERR_INVALID, "n_variants must be 1 .. BIGSI_GENOTYPE_MAX_VARIANTS = %u (got %u)", BIGSI_GENOTYPE_MAX_VARIANTS, n_variants);
+    for (uint64_t i = 0; i < n_seqs; i++)
+        if (allele_of[i] != BIGSI_GENOTYPE_NONE && allele_of[i] >= 2ull * n_variants)
+            return fail(BIGSI_ERR_INVALID, "allele_of[%llu] = %u is neither below 2 x n_variants (%llu) nor BIGSI_GENOTYPE_NONE", (unsigned long long)i, allele_of[i],
+                        2ull * n_variants);
+    const uint64_t n_cols = ix->n_cols, rb = (n_cols + 7) / 8;
+    if (rb > BIGSI_GENOTYPE_PLANE_BYTES / (2ull * n_variants))
+        return fail(BIGSI_ERR_NOMEM, "the planes of %u variants over %llu columns take 2 x %u x %llu bytes, above BIGSI_GENOTYPE_PLANE_BYTES = %llu", n_variants,
+                    (unsigned long long)n_cols, n_variants, (unsigned long long)rb, (unsigned long long)BIGSI_GENOTYPE_PLANE_BYTES);
+    if ((ref_planes || alt_planes) && plane_capacity_bytes < n_variants * rb)
+        return fail(BIGSI_ERR_CAPACITY, "a plane buffer holds %llu bytes, %u variants x %llu bytes needed", (unsigned long long)plane_capacity_bytes, n_variants,
+                    (unsigned long long)rb);
+    if (sample_capacity < n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "sample_counts holds %llu entries, %llu needed", (unsigned long long)sample_capacity, (unsigned long long)n_cols);
+    auto selected = [&](uint64_t c) { return !columns || ((columns[c >> 3] >> (7 - (c & 7))) & 1u) != 0; };
+    std::vector<uint8_t> plane[2] = {std::vector<uint8_t>((size_t)n_variants * rb, 0), std::vector<uint8_t>((size_t)n_variants * rb, 0)};
+    std::vector<uint32_t> col(n_cols), cnt(n_cols), used((size_t)n_variants * 2, 0u);
+    QueryKmers q;
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        if (allele_of[i] == BIGSI_GENOTYPE_NONE) continue;
+        uint32_t nk, nu, mk;
+        Hits hits{nullptr, col.data(), cnt.data(), n_cols};
+        search_reference_shaped(ix, seqs + offsets[i], offsets[i + 1] - offsets[i], k, threshold < 0.0 ? 0.0 : threshold, q, &nk, &nu, &mk, hits);
+        if (!nu) continue;
+        used[allele_of[i]]++;
+        uint8_t *row = plane[allele_of[i] & 1u].data() + (size_t)(allele_of[i] >> 1) * rb;
+        for (uint64_t j = 0; j < hits.total; j++)
+            if (selected(col[j])) row[col[j] >> 3] |= (uint8_t)(0x80u >> (col[j] & 7));
+    }
+    TRY(bdb_read_failed(ix));
+    std::vector<uint32_t> vc((size_t)n_variants * 4, 0u), sc((size_t)n_cols * 2, 0u);
+    for (uint32_t v = 0; v < n_variants; v++)
+        for (uint64_t c = 0; c < n_cols; c++) {
+            if (!selected(c)) continue;
+            const bool r = (plane[0][(size_t)v * rb + (c >> 3)] >> (7 - (c & 7))) & 1u, a = (plane[1][(size_t)v * rb + (c >> 3)] >> (7 - (c & 7))) & 1u;
+            vc[(size_t)v * 4 + (r ? (a ? 1 : 0) : (a ? 2 : 3))]++;
+            sc[c * 2] += a ? 1u : 0u;
+            sc[c * 2 + 1] += (r || a) ? 1u : 0u;
+        }
+    if (ref_planes) memcpy(ref_planes, plane[0].data(), plane[0].size());
+    if (alt_planes) memcpy(alt_planes, plane[1].data(), plane[1].size());
+    memcpy(variant_counts, vc.data(), vc.size() * 4);
+    memcpy(sample_counts, sc.data(), sc.size() * 4);
+    memcpy(allele_probes, used.data(), used.size() * 4);
     return BIGSI_OK;
 }
 

@@ -388,7 +388,7 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
     if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_close: %d view(s) of this index are still open (close them first)", ix->views.load());
     const std::pair<bigsi_hip_batch **, int> workspaces[] = {{&ix->search_ws, 1},   {ix->stream_ws, 4},   {&ix->prevalence_ws, 1},
                                                              {ix->tally_ws, 2},     {ix->classify_ws, 2}, {&ix->window_ws, 1},
-                                                             {ix->associate_ws, 2}};
+                                                             {ix->associate_ws, 2}, {ix->genotype_ws, 2}};
     for (const auto &[ws, n] : workspaces)
         for (int i = 0; i < n; i++) drop_workspace(ws[i]);
     hipError_t e = hipSetDevice(ix->device);
@@ -3728,6 +3728,254 @@ extern "C" int bigsi_hip_associate_stream(bigsi_hip_index *ix, const char *seqs,
             for (bigsi_hip_batch *&w : ix->associate_ws) drop_workspace(w);
     }
     return rc;
+}
+
+// Panel genotyping (include/bigsi_hip_genotype.h; k_allele_or + k_genotype_variants + k_genotype_samples, launch shapes:
+// plan_genotype): the fourth consumer, a segmented OR of the result vectors into one plane per allele.  No counter is read.  The
+// accumulator owns planes[2 n_variants][wv], used[2 n_variants], the selection vector sel[wv] (columns & valid_mask, built at create),
+// the two count outputs of a fetch, and two staging slots for allele_of (pinned host + device): an add copies its entries into the
+// slot of its turn and uploads from there, so the caller's array is not read after the call returns and no add waits for its own
+// kernel.  `last` orders the accumulator with itself, as the tally's does.
+static_assert(BIGSI_GENOTYPE_NONE == kGenotypeNone && BIGSI_GENOTYPE_MAX_VARIANTS == kGenotypeMaxVariants && BIGSI_GENOTYPE_PLANE_BYTES == kGenotypePlaneBytes,
+              "header and planner");
+constexpr VectorConsumer kGenotypeConsumer = {"a genotyping", "folds", false};
+
+struct bigsi_hip_genotype {
+    bigsi_hip_index *ix = nullptr;
+    uint64_t n_cols = 0, m = 0, wv = 0;
+    uint32_t h = 0, n_variants = 0, n_selected = 0;
+    DevBuf planes, used, sel, variant_counts, sample_counts;
+    DevBuf d_allele[2];
+    void *pin[2] = {nullptr, nullptr};
+    size_t pin_cap[2] = {0, 0};
+    hipEvent_t pin_ev[2] = {nullptr, nullptr};      // behind the upload out of pin[slot]
+    unsigned turn = 0;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool unusable = false;                          // a genotype_add_stream failed half way: until genotype_reset
+    size_t plane_bytes() const { return (size_t)2 * n_variants * wv * 8; }
+    uint64_t row_bytes() const { return (n_cols + 7) / 8; }
+};
+
+static int genotype_check(const bigsi_hip_genotype *g, bool usable = true)
+{
+    const bigsi_hip_index *ix = g->ix;
+    if (ix->n_cols != g->n_cols || ix->m != g->m || ix->h != g->h)
+        return fail(BIGSI_ERR_STATE, "the index has changed since bigsi_hip_genotype_create (%llu columns, %llu rows, %u hashes then; %llu, %llu, %u now)",
+                    (unsigned long long)g->n_cols, (unsigned long long)g->m, g->h, (unsigned long long)ix->n_cols, (unsigned long long)ix->m, ix->h);
+    if (usable && g->unusable)
+        return fail(BIGSI_ERR_STATE, "a bigsi_hip_genotype_add_stream on this accumulator failed half way: bigsi_hip_genotype_reset starts over");
+    return BIGSI_OK;
+}
+
+// what is queued on `st` next comes after everything queued on behalf of the accumulator so far
+static int genotype_order(bigsi_hip_genotype *g, hipStream_t st)
+{
+    if (g->last && g->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, g->last, 0));
+    return BIGSI_OK;
+}
+
+static int genotype_mark(bigsi_hip_genotype *g, hipStream_t st)
+{
+    if (!g->last) HIP_TRY(hipEventCreateWithFlags(&g->last, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(g->last, st));
+    g->last_stream = st;
+    return BIGSI_OK;
+}
+
+static int genotype_zero(bigsi_hip_genotype *g, hipStream_t st)
+{
+    HIP_TRY(hipMemsetAsync(g->planes.p, 0, g->plane_bytes(), st));
+    HIP_TRY(hipMemsetAsync(g->used.p, 0, (size_t)2 * g->n_variants * 4, st));
+    return genotype_mark(g, st);
+}
+
+extern "C" int bigsi_hip_genotype_create(bigsi_hip_index *ix, uint32_t n_variants, const uint8_t *columns, bigsi_hip_genotype **out)
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    const uint64_t wv = ix->wv();
+    const GenotypePlan p = plan_genotype(1, wv, n_variants);
+    if (p.bad_variants)
+        return fail(BIGSI_ERR_INVALID, "n_variants must be 1 .. BIGSI_GENOTYPE_MAX_VARIANTS = %u (got %u)", kGenotypeMaxVariants, n_variants);
+    if (p.too_many_bytes)
+        return fail(BIGSI_ERR_NOMEM, "the planes of %u variants over %llu columns take 2 x %u x %llu x 8 bytes, above BIGSI_GENOTYPE_PLANE_BYTES = %llu: slice the panel by variant",
+                    n_variants, (unsigned long long)ix->n_cols, n_variants, (unsigned long long)wv, (unsigned long long)kGenotypePlaneBytes);
+    if (p.too_large || p.variants_grid > 0x7FFFFFFFull) return fail(BIGSI_ERR_INVALID, "index too wide for one genotype launch (%llu workgroups)", (unsigned long long)p.too_large);
+    TRY(use_device(ix));
+    bigsi_hip_genotype *g = new (std::nothrow) bigsi_hip_genotype();
+    if (!g) return fail(BIGSI_ERR_NOMEM, "host allocation failed");
+    g->ix = ix;
+    g->n_cols = ix->n_cols; g->m = ix->m; g->h = ix->h; g->wv = wv;
+    g->n_variants = n_variants;
+    std::vector<uint64_t> sel(wv, columns ? 0ull : ~0ull);
+    if (columns) memcpy(sel.data(), columns, g->row_bytes());      // (row format = the little-endian words the kernels load)
+    uint64_t n_selected = 0;
+    for (uint64_t w = 0; w < wv; w++) {
+        sel[w] &= valid_mask(w, g->n_cols);
+        n_selected += (uint64_t)__builtin_popcountll(sel[w]);
+    }
+    g->n_selected = (uint32_t)n_selected;
+    int rc = g->planes.reserve(g->plane_bytes());
+    if (rc == BIGSI_OK) rc = g->used.reserve((size_t)2 * n_variants * 4);
+    if (rc == BIGSI_OK) rc = g->sel.reserve((size_t)wv * 8);
+    if (rc == BIGSI_OK) rc = g->variant_counts.reserve((size_t)n_variants * 16);
+    if (rc == BIGSI_OK) rc = g->sample_counts.reserve((size_t)wv * 64 * 8);
+    if (rc == BIGSI_OK) {
+        hipError_t e = hipMemcpyAsync(g->sel.p, sel.data(), (size_t)wv * 8, hipMemcpyHostToDevice, ix->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);      // (a pageable source that dies with this call)
+        if (e != hipSuccess) rc = fail(BIGSI_ERR_HIP, "uploading the column selection: %s", hipGetErrorString(e));
+    }
+    if (rc == BIGSI_OK) rc = genotype_zero(g, ix->stream);
+    if (rc != BIGSI_OK) { bigsi_hip_genotype_destroy(g); return rc; }
+    *out = g;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_genotype_destroy(bigsi_hip_genotype *g)
+{
+    BusyGuard busy_guard_(g ? g->ix : nullptr, /*wait=*/true);
+    if (!g) return BIGSI_OK;
+    hipError_t e = hipSetDevice(g->ix->device);
+    if (g->last) { e = hipEventSynchronize(g->last); e = hipEventDestroy(g->last); }
+    for (int s = 0; s < 2; s++) {
+        if (g->pin_ev[s]) { e = hipEventSynchronize(g->pin_ev[s]); e = hipEventDestroy(g->pin_ev[s]); }
+        if (g->pin[s]) e = hipHostFree(g->pin[s]);
+        g->d_allele[s].release();
+    }
+    (void)e;
+    g->planes.release(); g->used.release(); g->sel.release(); g->variant_counts.release(); g->sample_counts.release();
+    delete g;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_genotype_reset(bigsi_hip_genotype *g)
+{
+    BIGSI_ENTER(g ? g->ix : nullptr);
+    if (!g) return fail(BIGSI_ERR_INVALID, "NULL accumulator");
+    TRY(genotype_check(g, false));
+    TRY(use_device(g->ix));
+    hipStream_t st = g->ix->stream;
+    TRY(genotype_order(g, st));
+    TRY(genotype_zero(g, st));
+    g->unusable = false;
+    return BIGSI_OK;
+}
+
+static int genotype_validate(const bigsi_hip_genotype *g, const uint32_t *allele_of, uint64_t n_entries)
+{
+    const uint64_t bad = genotype_bad_allele(allele_of, n_entries, g->n_variants);
+    if (bad != n_entries)
+        return fail(BIGSI_ERR_INVALID, "allele_of[%llu] = %u is neither below 2 x n_variants (%u) nor BIGSI_GENOTYPE_NONE", (unsigned long long)bad, allele_of[bad],
+                    2 * g->n_variants);
+    return BIGSI_OK;
+}
+
+// k_allele_or for a batch that passed check_consumer_batch (its result vectors are then as wide as the planes) and whose validated
+// allele_of entries are `allele_of`, and finish_consumer
+static int genotype_launch(bigsi_hip_genotype *g, bigsi_hip_batch *b, const uint32_t *allele_of)
+{
+    bigsi_hip_index *ix = b->ix;
+    hipStream_t st = consumer_stream(b);
+    const GenotypePlan p = plan_genotype(b->n_seqs, b->wv, g->n_variants);
+    if (p.too_large) return fail(BIGSI_ERR_INVALID, "batch too large for one genotype launch (%llu workgroups)", (unsigned long long)p.too_large);
+    if (p.grid == 0) return BIGSI_OK;
+    const int slot = (int)(g->turn++ & 1u);
+    const size_t bytes = (size_t)b->n_seqs * 4;
+    if (g->pin_ev[slot]) HIP_TRY(hipEventSynchronize(g->pin_ev[slot]));      // (the upload of two adds ago has left the pinned slot)
+    else HIP_TRY(hipEventCreateWithFlags(&g->pin_ev[slot], hipEventDisableTiming));
+    if (g->pin_cap[slot] < bytes) {
+        if (g->pin[slot]) { HIP_TRY(hipHostFree(g->pin[slot])); g->pin[slot] = nullptr; g->pin_cap[slot] = 0; }
+        const size_t want = std::max<size_t>(bytes, (size_t)kTallyChunkSeqs * 4);
+        HIP_TRY(hipHostMalloc(&g->pin[slot], want, hipHostMallocDefault));
+        g->pin_cap[slot] = want;
+    }
+    memcpy(g->pin[slot], allele_of, bytes);
+    TRY(genotype_order(g, st));                      // (also: the kernel that read this slot's device copy two adds ago is behind us)
+    if (g->d_allele[slot].cap < bytes) HIP_TRY(hipStreamSynchronize(st));      // (growing frees the old copy)
+    TRY(g->d_allele[slot].reserve(std::max<size_t>(bytes, (size_t)kTallyChunkSeqs * 4)));
+    HIP_TRY(hipMemcpyAsync(g->d_allele[slot].p, g->pin[slot], bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(g->pin_ev[slot], st));
+    EventPair ep{};
+    TRY(bigsi_ev_begin(ix, &ep, st));
+    hipLaunchKernelGGL(k_allele_or, dim3((unsigned)p.grid), dim3(p.block), 0, st, static_cast<const uint64_t *>(b->bit_vectors()), b->wv_pad, (uint32_t)b->wv,
+                       g->n_cols, b->n_seqs, b->num_unique.as<uint32_t>(), g->d_allele[slot].as<uint32_t>(), (uint32_t)p.word_blocks,
+                       g->planes.as<unsigned long long>(), g->used.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    TRY(bigsi_ev_end(ix, &ep, ix->ev_cp, st, 1));      // (timed with the compaction it stands in for: bigsi_hip_stats' compact_ms)
+    TRY(genotype_mark(g, st));
+    return finish_consumer(b, st);
+}
+
+extern "C" int bigsi_hip_genotype_add_batch(bigsi_hip_genotype *g, bigsi_hip_batch *b, const uint32_t *allele_of, uint64_t n_entries)
+{
+    BIGSI_ENTER(g ? g->ix : nullptr);
+    if (!g || !b || !allele_of) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(genotype_check(g));
+    if (b->ix != g->ix) return fail(BIGSI_ERR_STATE, "the batch belongs to another index than the genotype accumulator");
+    TRY(check_consumer_batch(b, kGenotypeConsumer));
+    if (n_entries != b->n_seqs)
+        return fail(BIGSI_ERR_INVALID, "allele_of has %llu entries, the batch has %u sequences", (unsigned long long)n_entries, b->n_seqs);
+    TRY(genotype_validate(g, allele_of, n_entries));
+    TRY(use_device(g->ix));
+    return genotype_launch(g, b, allele_of);
+}
+
+// consume_stream over the index's genotype_ws.  A chunk without a k-mer position adds nothing: used counts only probes with k-mers.
+extern "C" int bigsi_hip_genotype_add_stream(bigsi_hip_genotype *g, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
+                                             const uint32_t *allele_of)
+{
+    BIGSI_ENTER(g ? g->ix : nullptr);
+    if (!g || !offsets || !allele_of) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(genotype_check(g));
+    TRY(check_stream_args(seqs, offsets, n_seqs, k, threshold));
+    TRY(genotype_validate(g, allele_of, n_seqs));
+    TRY(use_device(g->ix));
+    const int rc = consume_stream(
+        g->ix, g->ix->genotype_ws, kGenotypeConsumer, seqs, offsets, n_seqs, k, threshold, [](uint64_t, uint64_t) {},
+        [&](bigsi_hip_batch *b, int, uint64_t s0, uint64_t) { return genotype_launch(g, b, allele_of + s0); });
+    if (rc != BIGSI_OK) g->unusable = true;
+    return rc;
+}
+
+extern "C" int bigsi_hip_genotype_fetch(bigsi_hip_genotype *g, uint8_t *ref_planes, uint8_t *alt_planes, uint64_t plane_capacity_bytes,
+                                        uint32_t *variant_counts, uint32_t *sample_counts, uint64_t sample_capacity, uint32_t *allele_probes)
+{
+    BIGSI_ENTER(g ? g->ix : nullptr);
+    if (!g || !variant_counts || !sample_counts || !allele_probes) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(genotype_check(g));
+    const uint64_t rb = g->row_bytes();
+    if ((ref_planes || alt_planes) && plane_capacity_bytes < (uint64_t)g->n_variants * rb)
+        return fail(BIGSI_ERR_CAPACITY, "a plane buffer holds %llu bytes, %u variants x %llu bytes needed", (unsigned long long)plane_capacity_bytes,
+                    g->n_variants, (unsigned long long)rb);
+    if (sample_capacity < g->n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "sample_counts holds %llu entries, %llu needed", (unsigned long long)sample_capacity, (unsigned long long)g->n_cols);
+    TRY(use_device(g->ix));
+    hipStream_t st = g->ix->stream;
+    TRY(genotype_order(g, st));
+    const GenotypePlan p = plan_genotype(1, g->wv, g->n_variants);
+    hipLaunchKernelGGL(k_genotype_variants, dim3((unsigned)p.variants_grid), dim3(p.block), 0, st, g->planes.as<uint64_t>(), g->sel.as<uint64_t>(), (uint32_t)g->wv,
+                       g->n_variants, g->n_selected, g->variant_counts.as<uint4>());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_genotype_samples, dim3((unsigned)p.samples_grid), dim3(p.block), 0, st, g->planes.as<uint64_t>(), (uint32_t)g->wv, g->n_variants,
+                       g->sample_counts.as<uint2>());
+    HIP_TRY(hipGetLastError());
+    TRY(genotype_mark(g, st));
+    // (downloads into host copies first: a failure half way must not leave a caller's buffer half written)
+    std::vector<uint32_t> vc((size_t)g->n_variants * 4), sc((size_t)g->n_cols * 2), ap((size_t)g->n_variants * 2);
+    HIP_TRY(hipMemcpyAsync(vc.data(), g->variant_counts.p, vc.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(sc.data(), g->sample_counts.p, sc.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ap.data(), g->used.p, ap.size() * 4, hipMemcpyDeviceToHost, st));
+    const uint8_t *dp = static_cast<const uint8_t *>(g->planes.p);
+    if (ref_planes) HIP_TRY(hipMemcpy2DAsync(ref_planes, rb, dp, 2 * g->wv * 8, rb, g->n_variants, hipMemcpyDeviceToHost, st));
+    if (alt_planes) HIP_TRY(hipMemcpy2DAsync(alt_planes, rb, dp + g->wv * 8, 2 * g->wv * 8, rb, g->n_variants, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(variant_counts, vc.data(), vc.size() * 4);
+    memcpy(sample_counts, sc.data(), sc.size() * 4);
+    memcpy(allele_probes, ap.data(), ap.size() * 4);
+    return BIGSI_OK;
 }
 
 // K5 at scale: the presence strings of all hits of the batch (see k_presence_bits).  The host sorts each sequence's hits by

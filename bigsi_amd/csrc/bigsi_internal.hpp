@@ -10,6 +10,7 @@
 #include "bigsi_hip_compact.h"
 #include "bigsi_hip_consensus.h"
 #include "bigsi_hip_fold.h"
+#include "bigsi_hip_genotype.h"
 #include "bigsi_hip_group.h"
 #include "bigsi_hip_kmercount.h"
 #include "bigsi_hip_pairwise.h"
@@ -114,6 +115,7 @@ struct bigsi_hip_index {
     DevBuf associate_out[2];                          // ... per stream slot the infos of a chunk and, behind them, its counts ...
     void *associate_pin[2] = {nullptr, nullptr};      // ... their pinned twin (stream call) and the event behind the download into it
     hipEvent_t associate_ev[2] = {nullptr, nullptr};
+    struct bigsi_hip_batch *genotype_ws[2] = {};      // bigsi_hip_genotype_add_stream's workspaces, created at its first call
     struct bigsi_hip_batch *window_ws = nullptr;     // bigsi_hip_window_search's workspace, created at its first call
     uint64_t window_starts = 0, window_cap = 0;       // bigsi_hip_window_set_limits: starts per segment, partial bytes cap (0: the planner's)
     uint32_t band_windows = 0, band_segs = 0;         // bigsi_hip_band_set_limits: windows per band, segments per launch (0: the planner's)

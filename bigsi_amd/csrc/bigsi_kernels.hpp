@@ -4271,4 +4271,109 @@ __global__ __launch_bounds__(kBlock) void k_group_counts(
     }
 }
 
+// ------------------------------------------------------------------------------ panel genotyping: every sample's call per variant
+// The segmented OR over the result vectors a run made with BIGSI_RUN_SKIP_COMPACT left behind (include/bigsi_hip_genotype.h has the
+// definition): the probes of one allele fold into one bit plane, planes[2 v + a][wv]; the calls come from two planes by AND, AND-NOT
+// and popcount.  No work per hit: a ref probe that hits every column costs what one that hits none costs.
+//
+// k_allele_or (launch shape: plan_genotype): thread = result word w -- consecutive threads take consecutive words, coalesced 8-byte
+//   loads, never w >= wv: the pad word of wv_pad is not read -- and a workgroup owns kBlock words and the probes [q0, q1) of one tile.
+//   A thread walks the tile with (current allele, accumulated word) in registers, kGenotypeLoads loads in flight; allele_of and
+//   num_unique of a probe are uniform, and a probe without k-mers or without an allele is skipped in a uniform branch before its word
+//   is loaded.  valid_mask is applied before the OR.  When the allele changes, or the tile ends, the thread issues ONE 64-bit atomicOr
+//   into planes[allele][w], and only if the word is non-zero: probes grouped by allele cost one atomic per allele, tile and word; any
+//   other order costs more atomics and gives the same planes -- OR is idempotent and order-free, so chunks on two streams may meet in
+//   one plane word.  Thread i of the workgroup that owns word 0 adds probe q0 + i into used[allele].  28 VGPRs, 34 SGPRs, no scratch, no spill.
+// k_genotype_variants: one wavefront per variant.  The lanes sweep the words of both planes under sel[w] (columns & valid_mask, built
+//   once at create), popcount r & ~a, r & a and a & ~r, and the wavefront reduces; one uint4 store per variant, missing = the selected
+//   columns minus the other three; no atomic.  It leaves the planes masked (idempotent).  20 VGPRs, no scratch.
+// k_genotype_samples: a wavefront owns word w, lane l the column 64 w + l at bit bit_of_col(l); a loop over all variants with
+//   wave-uniform loads of the two (masked) words, four variants in flight; one plain uint2 store {carried, called} per column, the
+//   ones behind num_cols included (they are zero: the planes are masked).  No atomic and nothing to zero.  11 VGPRs, no scratch.
+__global__ __launch_bounds__(kBlock) void k_allele_or(
+    const uint64_t *__restrict__ bitmaps, uint64_t bm_stride, uint32_t wv, uint64_t n_cols, uint32_t n_seqs,
+    const uint32_t *__restrict__ num_unique, const uint32_t *__restrict__ allele_of, uint32_t word_blocks,
+    unsigned long long *__restrict__ planes, uint32_t *__restrict__ used)
+{
+    const uint32_t t = blockIdx.x / word_blocks, wb = blockIdx.x - t * word_blocks;
+    const uint32_t w = wb * kBlock + threadIdx.x;
+    const uint32_t q0 = t * kGenotypeTile, q1 = n_seqs - q0 < kGenotypeTile ? n_seqs : q0 + kGenotypeTile;
+    if (wb == 0 && threadIdx.x < q1 - q0) {
+        const uint32_t al = allele_of[q0 + threadIdx.x];
+        if (al != kGenotypeNone && num_unique[q0 + threadIdx.x] != 0) atomicAdd(&used[al], 1u);
+    }
+    if (w >= wv) return;
+    const uint64_t vm = valid_mask(w, n_cols);
+    uint32_t cur = kGenotypeNone;
+    uint64_t acc = 0;
+    for (uint32_t q = q0; q < q1; q += kGenotypeLoads) {
+        uint32_t al[kGenotypeLoads];
+        uint64_t x[kGenotypeLoads];
+#pragma unroll
+        for (uint32_t j = 0; j < kGenotypeLoads; j++) {
+            al[j] = q + j < q1 ? allele_of[q + j] : kGenotypeNone;
+            if (al[j] != kGenotypeNone && num_unique[q + j] == 0) al[j] = kGenotypeNone;
+            x[j] = al[j] != kGenotypeNone ? bitmaps[(uint64_t)(q + j) * bm_stride + w] : 0ull;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kGenotypeLoads; j++) {
+            if (al[j] == kGenotypeNone) continue;                       // (uniform)
+            if (al[j] != cur) {
+                if (acc) atomicOr(&planes[(uint64_t)cur * wv + w], (unsigned long long)acc);
+                cur = al[j];
+                acc = 0;
+            }
+            acc |= x[j] & vm;
+        }
+    }
+    if (acc) atomicOr(&planes[(uint64_t)cur * wv + w], (unsigned long long)acc);
+}
+
+__global__ __launch_bounds__(kBlock) void k_genotype_variants(uint64_t *__restrict__ planes, const uint64_t *__restrict__ sel, uint32_t wv,
+                                                              uint32_t n_variants, uint32_t n_selected, uint4 *__restrict__ variant_counts)
+{
+    const uint32_t v = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (v >= n_variants) return;                                        // (uniform over the wavefront)
+    uint64_t *ref = planes + (uint64_t)(2 * v) * wv, *alt = ref + wv;
+    uint32_t hom_ref = 0, het = 0, hom_alt = 0;
+    for (uint32_t w = lane; w < wv; w += 64) {
+        const uint64_t s = sel[w], r = ref[w] & s, a = alt[w] & s;
+        ref[w] = r;
+        alt[w] = a;
+        hom_ref += (uint32_t)__popcll(r & ~a);
+        het += (uint32_t)__popcll(r & a);
+        hom_alt += (uint32_t)__popcll(a & ~r);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        hom_ref += __shfl_xor(hom_ref, d);
+        het += __shfl_xor(het, d);
+        hom_alt += __shfl_xor(hom_alt, d);
+    }
+    if (lane == 0) variant_counts[v] = make_uint4(hom_ref, het, hom_alt, n_selected - hom_ref - het - hom_alt);
+}
+
+__global__ __launch_bounds__(kBlock) void k_genotype_samples(const uint64_t *__restrict__ planes, uint32_t wv, uint32_t n_variants,
+                                                             uint2 *__restrict__ sample_counts)
+{
+    const uint32_t w = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    if (w >= wv) return;
+    const uint32_t bit = bit_of_col(lane);
+    uint32_t carried = 0, called = 0;
+    for (uint32_t v = 0; v < n_variants; v += 4) {
+        uint64_t r[4], a[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            r[j] = v + j < n_variants ? planes[(uint64_t)(2 * (v + j)) * wv + w] : 0ull;
+            a[j] = v + j < n_variants ? planes[(uint64_t)(2 * (v + j) + 1) * wv + w] : 0ull;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            carried += (uint32_t)((a[j] >> bit) & 1ull);
+            called += (uint32_t)(((r[j] | a[j]) >> bit) & 1ull);
+        }
+    }
+    sample_counts[(uint64_t)w * 64 + lane] = make_uint2(carried, called);
+}
+
 }   // namespace bigsi

@@ -1085,6 +1085,51 @@ static inline AssociatePlan plan_associate(uint64_t n_seqs, uint64_t wv, uint64_
     return p;
 }
 
+// ------------------------------------------------------------------------------ panel genotyping (k_allele_or, k_genotype_variants, k_genotype_samples)
+// k_allele_or: thread = result word, a workgroup owns kBlock consecutive words and one tile of kGenotypeTile probes; workgroup b: word
+// block b % word_blocks, tile b / word_blocks (the tally's order: neighbouring workgroups read neighbouring words of the same probes).
+// A tile costs a word one 64-bit atomic per allele it holds, so it is as long as keeps those rare and as short as still gives a narrow
+// index some workgroups; it is at most kBlock, since thread i of the workgroup that owns word 0 counts probe i of the tile into `used`.
+// k_genotype_variants: one wavefront per variant, kBlock / 64 per workgroup.  k_genotype_samples: one wavefront per result word.
+// plane_bytes is both planes of all variants as the device holds them (rows of wv words).  Refused: n_variants outside 1 ..
+// kGenotypeMaxVariants, planes above kGenotypePlaneBytes, more than 2^31 - 1 workgroups in a launch.
+constexpr uint32_t kGenotypeNone = 0xFFFFFFFFu;             // BIGSI_GENOTYPE_NONE (include/bigsi_hip_genotype.h)
+constexpr uint32_t kGenotypeMaxVariants = 1u << 20;         // BIGSI_GENOTYPE_MAX_VARIANTS
+constexpr uint64_t kGenotypePlaneBytes = 4ull << 30;        // BIGSI_GENOTYPE_PLANE_BYTES: a design limit, not a measured one
+constexpr uint32_t kGenotypeTile = 64;                      // probes per workgroup of k_allele_or
+constexpr uint32_t kGenotypeLoads = 8;                      // result words a thread of k_allele_or has in flight
+static_assert(kGenotypeTile <= (uint32_t)kBlock && kGenotypeTile % kGenotypeLoads == 0, "k_allele_or: thread i counts probe i; whole load groups");
+struct GenotypePlan {
+    uint32_t block = kBlock, tile = kGenotypeTile;
+    uint64_t word_blocks = 0, tiles = 0, grid = 0;            // k_allele_or: grid = word_blocks * tiles
+    uint64_t variants_grid = 0, samples_grid = 0;             // k_genotype_variants; k_genotype_samples
+    uint64_t plane_bytes = 0;                                 // planes[2 n_variants][wv]
+    uint64_t too_large = 0;                                   // != 0: the workgroups one launch would take (more than 2^31 - 1): refused
+    bool bad_variants = false, too_many_bytes = false;        // n_variants outside 1 .. kGenotypeMaxVariants; planes above kGenotypePlaneBytes
+};
+static inline GenotypePlan plan_genotype(uint64_t n_seqs, uint64_t wv, uint64_t n_variants)
+{
+    GenotypePlan p;
+    p.word_blocks = ceil_div(wv, (uint64_t)kBlock);
+    p.tiles = ceil_div(n_seqs, (uint64_t)p.tile);
+    p.grid = p.tiles && p.word_blocks > ~0ull / p.tiles ? ~0ull : p.word_blocks * p.tiles;      // (saturates: the product may not fit 64 bits)
+    p.samples_grid = ceil_div(wv, (uint64_t)(kBlock / 64));
+    if (p.grid > 0x7FFFFFFFull) p.too_large = p.grid;
+    else if (p.samples_grid > 0x7FFFFFFFull) p.too_large = p.samples_grid;
+    if (n_variants == 0 || n_variants > kGenotypeMaxVariants) { p.bad_variants = true; return p; }
+    p.variants_grid = ceil_div(n_variants, (uint64_t)(kBlock / 64));
+    if (wv > kGenotypePlaneBytes / (16 * n_variants)) p.too_many_bytes = true;      // (by division: the product may not fit 64 bits)
+    else p.plane_bytes = 2 * n_variants * wv * 8;
+    return p;
+}
+// the first allele_of entry that is neither below 2 n_variants nor kGenotypeNone; n_entries when there is none
+static inline uint64_t genotype_bad_allele(const uint32_t *allele_of, uint64_t n_entries, uint64_t n_variants)
+{
+    for (uint64_t i = 0; i < n_entries; i++)
+        if (allele_of[i] != kGenotypeNone && allele_of[i] >= 2 * n_variants) return i;
+    return n_entries;
+}
+
 // ------------------------------------------------------------------------------ windowed search (k_window_max, k_window_combine)
 // plan_window_search: sequence q of a batch has n[q] k-mer positions, a window of We = min(W, n[q]) of them and the window starts
 // [0, n[q] - We]; the sweep cuts every sequence's starts into segments of at most S and a wavefront of k_window_max owns one

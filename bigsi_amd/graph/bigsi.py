@@ -1011,6 +1011,76 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         info = np.concatenate([i for _, i in parts]) if parts else np.zeros(0, INFO_DTYPE)
         return result(counts, info, group_names, sizes, min_af)
 
+    # ------------------------------------------------------------------ panel genotyping
+    def genotype_arrays(self, probes, allele_of, n_variants, threshold=1.0, plane_bytes=1 << 30, planes=True):
+        """Every sample's call for a panel of variants -- answered on the device (bigsi_hip_genotype: the probes' result vectors are
+        ORed into one bit plane per allele behind the row-AND kernels, the calls and counts come from the planes by AND, AND-NOT and
+        popcount; no hit list is built).  probes: ASCII sequences; allele_of[i]: 2 v + a (a = 0 ref, 1 alt) for probe i of variant
+        v < n_variants, or genotype.NONE.  Returns (ref_planes, alt_planes: uint8[n_variants, ceil(num_cols / 8)] in the row format,
+        or None with planes=False -- they are then never downloaded --, variant_counts uint32[n_variants, 4]: 0/0, 0/1, 1/1, missing,
+        sample_counts uint32[num_cols, 2]: carried, called, allele_probes uint32[n_variants, 2]: the ref / alt probes with k-mers).
+        Deleted samples are left out on the device: their bits are zero and they count nowhere.  The panel is cut by variant into
+        slices whose planes fit `plane_bytes` of device memory, each with an accumulator of its own; a probe goes to its variant's
+        slice only.  Multi-GPU (devices=[...]) indexes are refused."""
+        from ..genotype import MAX_VARIANTS, NONE, slices
+        self._check_stream_query(probes, threshold)
+        probes = list(probes)
+        allele_of = np.ascontiguousarray(allele_of, dtype=np.uint32).reshape(-1)
+        n_variants = int(n_variants)
+        if allele_of.size != len(probes):
+            raise ValueError("allele_of has %d entries for %d probes" % (allele_of.size, len(probes)))
+        if n_variants < 1:
+            raise ValueError("n_variants must be >= 1, got %d" % n_variants)
+        bad = np.flatnonzero((allele_of != NONE) & (allele_of.astype(np.int64) >= 2 * n_variants))
+        if bad.size:
+            raise ValueError("allele_of[%d] = %d is neither below 2 x n_variants (%d) nor NONE" % (bad[0], allele_of[bad[0]], 2 * n_variants))
+        if int(plane_bytes) < 1:
+            raise ValueError("plane_bytes must be >= 1, got %r" % (plane_bytes,))
+        for s in probes:
+            if not isinstance(s, str) or not s.isascii():
+                raise ValueError("panel genotyping takes ASCII sequences (probes with other characters are out of scope)")
+        self._refuse_group("panel genotyping")
+        k = int(self.kmer_size)
+        with self._device_lock():
+            n_cols = int(self.storage.get_integer("number_of_cols"))
+            rb = (n_cols + 7) // 8
+            bits = np.ones(rb * 8, np.uint8)
+            ex = self._excluded_colours()
+            bits[ex[ex < n_cols]] = 0
+            columns = np.packbits(bits)
+            ref = np.zeros((n_variants, rb), np.uint8) if planes else None
+            alt = np.zeros((n_variants, rb), np.uint8) if planes else None
+            vc, sc, ap = np.zeros((n_variants, 4), np.uint32), np.zeros((n_cols, 2), np.uint32), np.zeros((n_variants, 2), np.uint32)
+            for v0, v1, idx, rel in slices(allele_of, n_variants, rb, min(int(plane_bytes), 4 << 30)):
+                if v1 - v0 > MAX_VARIANTS:
+                    raise ValueError("a slice of %d variants: at most %d fit one accumulator (lower plane_bytes)" % (v1 - v0, MAX_VARIANTS))
+                g = self.storage.new_genotype(v1 - v0, columns)
+                try:
+                    g.add([probes[i] for i in idx], k, threshold, rel)
+                    r, a, vc[v0:v1], s, ap[v0:v1] = g.fetch(planes)
+                finally:
+                    g.close()
+                sc += s
+                if planes:
+                    ref[v0:v1], alt[v0:v1] = r, a
+        return ref, alt, vc, sc, ap
+
+    def genotype_panel(self, panel, threshold=1.0, summary_only=False, plane_bytes=1 << 30):
+        """genotype_arrays over a panel of probes -- concatenated `mykrobe variants make-probes` output: FASTA text, bytes or a path
+        (genotype.parse_panel) -- as names: {"variants": [{"name", "ref_probes", "alt_probes", "counts": {"0/0", "0/1", "1/1", "./."},
+        "calls": {sample_name: genotype, missing left out}}], "samples": [{"sample_name", "colour", "carried", "called"}]}; a variant
+        one of whose alleles has no probe with k-mers is flagged "uncallable": True.  Deleted samples appear nowhere.
+        summary_only=True leaves "calls" out, and the planes are then never downloaded."""
+        from ..genotype import calls, parse_panel, result
+        names, probes, allele_of = parse_panel(panel)
+        if not names:
+            raise ValueError("the panel holds no variant")
+        ref, alt, vc, sc, ap = self.genotype_arrays(probes, allele_of, len(names), threshold, plane_bytes, planes=not summary_only)
+        with self._device_lock():
+            excluded = self._excluded_colours()
+        matrix = None if summary_only else calls(ref, alt, sc.shape[0], excluded)
+        return result(names, vc, sc, ap, self._name_of(), excluded, matrix)
+
     # ------------------------------------------------------------------ column compaction: vacuum / extract
     def _colour_names(self):
         """names[c] of every colour, DELETION_SPECIAL_SAMPLE_NAME for a deleted one; the matrix must be as wide as the metadata."""

@@ -715,6 +715,12 @@ class HipHbmStorage(BaseStorage):
                                                     int(n_groups), _lib.ptr(counts), _lib.ptr(info)))
         return counts, info
 
+    def new_genotype(self, n_variants, columns=None):
+        """A Genotype over this index: zeroed allele planes for n_variants on the device (bigsi_hip_genotype_create).  columns: a bit
+        vector in the row format (uint8[ceil(num_cols / 8)]) of the samples to call, None for all."""
+        self._single_gpu("panel genotyping")
+        return Genotype(self, n_variants, columns)
+
     def fill_synthetic(self, seed, shard=0, and_draws=2):
         if self.res.is_group:       # shard i of the group is filled as (seed, shard i)
             check(_lib.lib().bigsi_hip_group_fill_synthetic(self.res.ix, int(seed), int(and_draws)))
@@ -965,6 +971,71 @@ class Tally(object):
     def close(self):
         if self.b is not None:
             check(_lib.lib().bigsi_hip_tally_destroy(self.b))
+            self.b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class Genotype(object):
+    """The allele planes of a variant panel (bigsi_hip_genotype): add() probes with their allele_of or add_batch() a QueryBatch whose
+    last run was made with skip_compact=True, fetch() planes and counts, reset(), close().  Single index only."""
+
+    def __init__(self, storage, n_variants, columns=None):
+        self.storage = storage
+        self.b = None
+        self.n_variants = int(n_variants)
+        self.num_cols = int(storage.res.info().num_cols)
+        self.row_bytes = (self.num_cols + 7) // 8
+        if columns is not None:
+            columns = np.ascontiguousarray(columns, dtype=np.uint8)
+            if columns.size != self.row_bytes:
+                raise ValueError("columns must hold %d bytes, got %d" % (self.row_bytes, columns.size))
+        out = _lib.C.c_void_p()
+        check(_lib.lib().bigsi_hip_genotype_create(storage.handle, self.n_variants, None if columns is None else _lib.ptr(columns), _lib.C.byref(out)))
+        self.b = out
+        storage.res.batches.add(self)          # (it holds the index handle and must die before it, as a batch)
+
+    def add(self, seqs, k, threshold, allele_of):
+        """bigsi_hip_genotype_add_stream over a list of probes (an empty list adds nothing)."""
+        seqs = seqs if isinstance(seqs, (list, tuple)) else list(seqs)
+        allele_of = np.ascontiguousarray(allele_of, dtype=np.uint32)
+        if allele_of.size != len(seqs):
+            raise ValueError("allele_of has %d entries for %d probes" % (allele_of.size, len(seqs)))
+        if not seqs:
+            return self
+        blob, off = _lib.pack_seqs(seqs)
+        check(_lib.lib().bigsi_hip_genotype_add_stream(self.b, blob, _lib.ptr(off), len(seqs), int(k), float(threshold), _lib.ptr(allele_of)))
+        return self
+
+    def add_batch(self, batch, allele_of):
+        if batch.group:
+            raise BigsiHipError(_lib.ERR_STATE, "panel genotyping is not available on a multi-GPU batch")
+        allele_of = np.ascontiguousarray(allele_of, dtype=np.uint32)
+        check(_lib.lib().bigsi_hip_genotype_add_batch(self.b, batch.b, _lib.ptr(allele_of), allele_of.size))
+        return self
+
+    def reset(self):
+        check(_lib.lib().bigsi_hip_genotype_reset(self.b))
+        return self
+
+    def fetch(self, planes=True):
+        """(ref_planes, alt_planes: uint8[n_variants, ceil(num_cols / 8)] or None with planes=False -- they are then never downloaded
+        --, variant_counts uint32[n_variants, 4], sample_counts uint32[num_cols, 2], allele_probes uint32[n_variants, 2])"""
+        n, nv = self.num_cols, self.n_variants
+        ref = np.zeros((nv, self.row_bytes), np.uint8) if planes else None
+        alt = np.zeros((nv, self.row_bytes), np.uint8) if planes else None
+        vc, sc, ap = np.zeros((nv, 4), np.uint32), np.zeros((n, 2), np.uint32), np.zeros((nv, 2), np.uint32)
+        check(_lib.lib().bigsi_hip_genotype_fetch(self.b, _lib.ptr(ref) if planes else None, _lib.ptr(alt) if planes else None, nv * self.row_bytes if planes else 0,
+                                                  _lib.ptr(vc), _lib.ptr(sc), n, _lib.ptr(ap)))
+        return ref, alt, vc, sc, ap
+
+    def close(self):
+        if self.b is not None:
+            check(_lib.lib().bigsi_hip_genotype_destroy(self.b))
             self.b = None
 
     def __del__(self):

@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] [classify] [associate] [window] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] [classify] [associate] [genotype] [window] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -1073,6 +1073,52 @@ def window():
              note="fill %.2f s; every %d-th window start timed through search_stream and SCALED to all %d starts" % (fill, every, starts))
     batch.close()
     st.delete_all()
+
+
+def genotype():
+    """Panel genotyping (BIGSI.genotype_panel, bigsi_hip_genotype) beside the route without the feature, BIGSIVariantSearch.genotype_many
+    (one search_batch at threshold 1, a list of sample-name dicts per probe, Python sets), on one hit-dense index: N samples, V variants
+    with one 41-base ref and one alt probe each, every ref probe held by every sample and the alt probe of every 10th variant by every
+    other sample.  Wall clock, best of 3 calls each, one process; the two results are compared call for call.
+    BIGSI_GENOTYPE_SHAPE="NxV" replaces the shape."""
+    import bigsi_amd
+    from bigsi_amd.genotype import parse_panel
+    from bigsi_amd.utils import seq_to_kmers
+    from bigsi_amd.variant_search import BIGSIVariantSearch
+    n, v_n, k, m, h = 20_000, 200, 21, 20011, 3
+    if os.environ.get("BIGSI_GENOTYPE_SHAPE"):
+        n, v_n = (int(x) for x in os.environ["BIGSI_GENOTYPE_SHAPE"].split("x"))
+    rng = np.random.default_rng(5)
+    refs = rand_seqs(rng, v_n, 41)
+    alts = [r[:20] + ("A" if r[20] != "A" else "C") + r[21:] for r in refs]
+    cfg = {"storage-engine": "hip-hbm", "storage-config": {"name": "measure_genotype"}, "k": k, "m": m, "h": h}
+    kr = [km for r in refs for km in seq_to_kmers(r, k)]
+    ka = [km for v, a in enumerate(alts) if v % 10 == 0 for km in seq_to_kmers(a, k)]
+    every, other = bigsi_amd.BIGSI.bloom(cfg, kr), bigsi_amd.BIGSI.bloom(cfg, kr + ka)
+    b = bigsi_amd.BIGSI.build(cfg, [other if s % 2 else every for s in range(n)], ["s%d" % s for s in range(n)])
+    panel = "".join(">ref-V%d?x\n%s\n>alt-V%d-0\n%s\n" % (v, r, v, a) for v, (r, a) in enumerate(zip(refs, alts)))
+    _, probes, allele_of = parse_panel(panel)
+    vs = BIGSIVariantSearch(b, "ref.fa")
+
+    def best(fn):
+        ms = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            out = fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return min(ms), out
+    try:
+        many_ms, many = best(lambda: vs.genotype_many([([r], [a]) for r, a in zip(refs, alts)]))
+        panel_ms, res = best(lambda: b.genotype_panel(panel))
+        summary_ms, _ = best(lambda: b.genotype_panel(panel, summary_only=True))
+        arrays_ms, _ = best(lambda: b.genotype_arrays(probes, allele_of, v_n))
+        for var, one in zip(res["variants"], many):
+            assert var["calls"] == {r["sample_name"]: r["genotype"] for r in one}
+        emit("genotype", samples=n, variants=v_n, probes=len(probes), calls=sum(len(one) for one in many), het=sum(var["counts"]["0/1"] for var in res["variants"]),
+             genotype_many_ms=many_ms, genotype_panel_ms=panel_ms, genotype_panel_summary_ms=summary_ms, genotype_arrays_ms=arrays_ms,
+             many_over_panel=many_ms / panel_ms, note="wall clock, best of 3; genotype_panel names every call, summary_only and genotype_arrays do not")
+    finally:
+        b.delete()
 
 
 if __name__ == "__main__":

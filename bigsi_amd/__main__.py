@@ -200,7 +200,15 @@ def build_parser():
     sp.add_argument("--threshold", "-t", type=float, default=1.0)
     sp.add_argument("--format", choices=["tsv", "json"], default="tsv")
     sp.add_argument("--summary-only", action="store_true", help="per-variant counts and per-sample carried / called only (the planes are never downloaded)")
-    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally", "window_search", "classify", "associate", "genotype"):          # (named so that the refusal says why)
+    sp = common(sub.add_parser("typing", help="which allele of each locus every sample carries (MLST, cgMLST, serotype or resistance-gene typing): a FASTA scheme of "
+                                              "allele records named locus_allele; per (locus, sample) the record with the highest fraction of its k-mers found is taken on the device"))
+    sp.add_argument("scheme")
+    sp.add_argument("--loci-map", default=None, metavar="FILE", help="record<TAB>locus lines: the locus of the records named there (default: the record name up to its last _)")
+    sp.add_argument("--profiles", default=None, metavar="FILE", help="a PubMLST profiles table (ST<TAB>locus...): adds the sequence type of every sample")
+    sp.add_argument("--threshold", "-t", type=float, default=1.0)
+    sp.add_argument("--format", choices=["tsv", "json"], default="tsv")
+    sp.add_argument("--summary-only", action="store_true", help="per-locus and per-sample counts only (the cells are never downloaded)")
+    for name in ("vacuum", "extract", "fold", "prevalence", "collapse", "consensus", "distances", "cluster", "tally", "window_search", "classify", "associate", "genotype", "typing"):          # (named so that the refusal says why)
         sub.choices[name].add_argument("--sharded", action="store_true", help=argparse.SUPPRESS)
     return p, search_parser, bulk_parser
 
@@ -373,6 +381,15 @@ def genotype_text(index, panel, threshold=1.0, fmt="tsv", summary_only=False):
     return to_json(res) if fmt == "json" else to_tsv(res, summary_only)
 
 
+def typing_text(index, scheme, threshold=1.0, fmt="tsv", summary_only=False, profiles=None, loci_map=None):
+    """`typing`: BIGSI.type_samples over a scheme file.  TSV: the matrix -- header sample<TAB>[ST<TAB>]locus..., a cell the allele of an
+    exact call, allele~fraction of a partial one, - without a call --, or with --summary-only the per-locus and per-sample counts;
+    JSON: the result."""
+    from .locus_typing import to_json, to_tsv
+    res = index.type_samples(scheme, threshold=threshold, profiles=profiles, summary_only=summary_only, loci_map=loci_map)
+    return to_json(res) if fmt == "json" else to_tsv(res, summary_only)
+
+
 def window_search_text(index, queries, window, threshold=1.0, fmt="json"):
     """`window_search`: BIGSI.search_windows_many over the queries, one device call per query (a long query is a call's worth of work,
     and the device keeps counters per sequence).  JSON: the dicts, each with its "query" first; CSV: record,<result fields>, one line
@@ -489,6 +506,28 @@ def main(argv=None):
                 raise ValueError("no variant in it")
         except (OSError, ValueError) as e:
             p.error("genotype: the panel %s: %s" % (a.panel, e))
+    if getattr(a, "sharded", False) and a.cmd == "typing":
+        p.error("typing is not available with --sharded: the per-shard cells plus a host merge are not implemented (use a single index)")
+    if a.cmd == "typing":
+        if not a.threshold <= 1:
+            p.error("typing: the threshold must be <= 1, got %r" % (a.threshold,))
+        try:
+            from .locus_typing import parse_loci_map, parse_profiles, parse_scheme
+            with open(a.scheme) as f:
+                typing_scheme = f.read()
+            typing_map = typing_profiles = None
+            if a.loci_map is not None:
+                with open(a.loci_map) as f:
+                    typing_map = parse_loci_map(f.read() + "\n")
+            typing_loci = parse_scheme(typing_scheme, typing_map)[0]
+            if not typing_loci:
+                raise ValueError("no record in it")
+            if a.profiles is not None:
+                with open(a.profiles) as f:
+                    typing_profiles = f.read() + "\n"
+                parse_profiles(typing_profiles, typing_loci)
+        except (OSError, ValueError) as e:
+            p.error("typing: the scheme %s: %s" % (a.scheme, e))
     if getattr(a, "sharded", False) and a.cmd == "window_search":
         p.error("window_search is not available with --sharded: the per-shard sweep is not implemented (use a single index)")
     if a.cmd == "window_search" and (a.seq is None) == (a.fasta is None):
@@ -588,6 +627,8 @@ def main(argv=None):
         print(classify_text(BIGSI(config), read_fasta(a.fasta), classify_pairs, a.threshold, a.margin, a.others, a.format, a.summary_only))
     elif a.cmd == "genotype":
         print(genotype_text(BIGSI(config), genotype_panel, a.threshold, a.format, a.summary_only))
+    elif a.cmd == "typing":
+        print(typing_text(BIGSI(config), typing_scheme, a.threshold, a.format, a.summary_only, typing_profiles, typing_map))
     elif a.cmd == "associate":
         print(associate_text(BIGSI(config), read_fasta(a.fasta), associate_pairs, a.threshold, a.others, a.min_af, a.format))
     elif a.cmd == "distances":

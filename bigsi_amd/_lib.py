@@ -287,6 +287,16 @@ GENOTYPE_SIGNATURES = {
     "bigsi_hip_genotype_fetch": (_i32, [_P, _P, _P, _u64, _P, _P, _u64, _P]),
 }
 
+# every symbol include/bigsi_hip_typing.h declares (locus typing: per (locus, sample) the record with the highest fraction of its k-mers found, a segmented max on the device)
+TYPING_SIGNATURES = {
+    "bigsi_hip_typing_create": (_i32, [_P, _u32, _P, C.POINTER(_P)]),
+    "bigsi_hip_typing_destroy": (_i32, [_P]),
+    "bigsi_hip_typing_reset": (_i32, [_P]),
+    "bigsi_hip_typing_add_batch": (_i32, [_P, _P, _P, _P, _u64]),
+    "bigsi_hip_typing_add_stream": (_i32, [_P, C.c_char_p, _P, _u64, _u32, _dbl, _P, _P]),
+    "bigsi_hip_typing_fetch": (_i32, [_P, _P, _P, _u64, _P, _P, _u64, _P]),
+}
+
 # every symbol include/bigsi_hip_kmercount.h declares (exact k-mer counter: Bloom filters from raw reads, min-count on the device); the
 # host twin's library has the same eight under its own prefix (bigsi_amd/kmercount.py binds either set from this table)
 KMERCOUNT_SIGNATURES = {
@@ -320,7 +330,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()) + list(TALLY_SIGNATURES.items()) + list(CLASSIFY_SIGNATURES.items()) + list(KMERCOUNT_SIGNATURES.items()) + list(ASSOCIATE_SIGNATURES.items()) + list(GENOTYPE_SIGNATURES.items()) + list(WINDOW_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()) + list(FOLD_SIGNATURES.items()) + list(PREVALENCE_SIGNATURES.items()) + list(COLLAPSE_SIGNATURES.items()) + list(CONSENSUS_SIGNATURES.items()) + list(PAIRWISE_SIGNATURES.items()) + list(TALLY_SIGNATURES.items()) + list(CLASSIFY_SIGNATURES.items()) + list(KMERCOUNT_SIGNATURES.items()) + list(ASSOCIATE_SIGNATURES.items()) + list(GENOTYPE_SIGNATURES.items()) + list(TYPING_SIGNATURES.items()) + list(WINDOW_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError here = header and library out of sync
             fn.restype = res
             fn.argtypes = args

@@ -28,6 +28,7 @@
 #include "bigsi_cpu_classify.h"
 #include "bigsi_cpu_associate.h"
 #include "bigsi_cpu_genotype.h"
+#include "bigsi_cpu_typing.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1293,6 +1294,74 @@ int bigsi_cpu_genotype(bigsi_cpu_index *ix, const char *seqs, const uint64_t *of
     memcpy(variant_counts, vc.data(), vc.size() * 4);
     memcpy(sample_counts, sc.data(), sc.size() * 4);
     memcpy(allele_probes, used.data(), used.size() * 4);
+    return BIGSI_OK;
+}
+
+// locus typing: every record searched in the reference's shape, then a loop over its hit columns: a selected column's cell of the
+// record's locus takes the larger key -- floor(count (2^32 - 1) / unique) above the complement of the allele identity, written out
+// here on its own -- and one more hit.  The counts follow cell by cell.  A threshold below 0 asks for what 0 asks for.
+int bigsi_cpu_typing(bigsi_cpu_index *ix, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
+                     const uint32_t *locus_of, const uint32_t *allele_of, uint32_t n_loci, const uint8_t *columns, uint64_t *best, uint32_t *hits,
+                     uint64_t cell_capacity, uint32_t *locus_counts, uint32_t *sample_counts, uint64_t sample_capacity, uint32_t *records)
+{
+    if (!ix || !locus_of || !allele_of || !locus_counts || !sample_counts || !records) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(check_seqs(seqs, offsets, n_seqs, k));
+    if (!(threshold <= 1.0)) return fail(BIGSI_ERR_INVALID, "threshold must be <= 1, got %g", threshold);
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    if (n_loci == 0 || n_loci > BIGSI_TYPING_MAX_LOCI)
+        return fail(BIGSI_ERR_INVALID, "n_loci must be 1 .. BIGSI_TYPING_MAX_LOCI = %u (got %u)", BIGSI_TYPING_MAX_LOCI, n_loci);
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        if (locus_of[i] == BIGSI_TYPING_NONE) continue;
+        if (locus_of[i] >= n_loci)
+            return fail(BIGSI_ERR_INVALID, "locus_of[%llu] = %u is neither below n_loci (%u) nor BIGSI_TYPING_NONE", (unsigned long long)i, locus_of[i], n_loci);
+        if (allele_of[i] > BIGSI_TYPING_MAX_ALLELE)
+            return fail(BIGSI_ERR_INVALID, "allele_of[%llu] = %u is above BIGSI_TYPING_MAX_ALLELE = %u", (unsigned long long)i, allele_of[i], BIGSI_TYPING_MAX_ALLELE);
+    }
+    const uint64_t n_cols = ix->n_cols, wv = (n_cols + 63) / 64;
+    if (wv > BIGSI_TYPING_CELL_BYTES / (768ull * n_loci))
+        return fail(BIGSI_ERR_NOMEM, "the cells of %u loci over %llu columns take %u x %llu x 64 x 12 bytes, above BIGSI_TYPING_CELL_BYTES = %llu", n_loci,
+                    (unsigned long long)n_cols, n_loci, (unsigned long long)wv, (unsigned long long)BIGSI_TYPING_CELL_BYTES);
+    if ((best || hits) && cell_capacity < n_loci * n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "a cell buffer holds %llu entries, %u loci x %llu columns needed", (unsigned long long)cell_capacity, n_loci,
+                    (unsigned long long)n_cols);
+    if (sample_capacity < n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "sample_counts holds %llu entries, %llu needed", (unsigned long long)sample_capacity, (unsigned long long)n_cols);
+    auto selected = [&](uint64_t c) { return !columns || ((columns[c >> 3] >> (7 - (c & 7))) & 1u) != 0; };
+    std::vector<uint64_t> top((size_t)n_loci * n_cols, 0ull);
+    std::vector<uint32_t> nh((size_t)n_loci * n_cols, 0u), col(n_cols), cnt(n_cols), rec(n_loci, 0u);
+    QueryKmers q;
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        if (locus_of[i] == BIGSI_TYPING_NONE) continue;
+        uint32_t nk, nu, mk;
+        Hits found{nullptr, col.data(), cnt.data(), n_cols};
+        search_reference_shaped(ix, seqs + offsets[i], offsets[i + 1] - offsets[i], k, threshold < 0.0 ? 0.0 : threshold, q, &nk, &nu, &mk, found);
+        if (!nu) continue;
+        rec[locus_of[i]]++;
+        const size_t row = (size_t)locus_of[i] * n_cols;
+        for (uint64_t j = 0; j < found.total; j++) {
+            if (!selected(col[j])) continue;
+            const uint64_t key = ((uint64_t)cnt[j] * 0xFFFFFFFFull / nu) << 32 | (uint64_t)(0xFFFFFFFFu - allele_of[i]);
+            if (key > top[row + col[j]]) top[row + col[j]] = key;
+            nh[row + col[j]]++;
+        }
+    }
+    TRY(bdb_read_failed(ix));
+    std::vector<uint32_t> lc((size_t)n_loci * 3, 0u), sc((size_t)n_cols * 2, 0u);
+    for (uint32_t l = 0; l < n_loci; l++)
+        for (uint64_t c = 0; c < n_cols; c++) {
+            const uint64_t b = top[(size_t)l * n_cols + c];
+            const bool exact = (b >> 32) == 0xFFFFFFFFull;
+            lc[(size_t)l * 3] += b ? 1u : 0u;
+            lc[(size_t)l * 3 + 1] += exact ? 1u : 0u;
+            lc[(size_t)l * 3 + 2] += nh[(size_t)l * n_cols + c] > 1u ? 1u : 0u;
+            sc[c * 2] += b ? 1u : 0u;
+            sc[c * 2 + 1] += exact ? 1u : 0u;
+        }
+    if (best) memcpy(best, top.data(), top.size() * 8);
+    if (hits) memcpy(hits, nh.data(), nh.size() * 4);
+    memcpy(locus_counts, lc.data(), lc.size() * 4);
+    memcpy(sample_counts, sc.data(), sc.size() * 4);
+    memcpy(records, rec.data(), rec.size() * 4);
     return BIGSI_OK;
 }
 

@@ -388,7 +388,7 @@ extern "C" int bigsi_hip_close(bigsi_hip_index *ix)
     if (ix->views.load() > 0) return fail(BIGSI_ERR_STATE, "bigsi_hip_close: %d view(s) of this index are still open (close them first)", ix->views.load());
     const std::pair<bigsi_hip_batch **, int> workspaces[] = {{&ix->search_ws, 1},   {ix->stream_ws, 4},   {&ix->prevalence_ws, 1},
                                                              {ix->tally_ws, 2},     {ix->classify_ws, 2}, {&ix->window_ws, 1},
-                                                             {ix->associate_ws, 2}, {ix->genotype_ws, 2}};
+                                                             {ix->associate_ws, 2}, {ix->genotype_ws, 2}, {ix->typing_ws, 2}};
     for (const auto &[ws, n] : workspaces)
         for (int i = 0; i < n; i++) drop_workspace(ws[i]);
     hipError_t e = hipSetDevice(ix->device);
@@ -3975,6 +3975,254 @@ extern "C" int bigsi_hip_genotype_fetch(bigsi_hip_genotype *g, uint8_t *ref_plan
     memcpy(variant_counts, vc.data(), vc.size() * 4);
     memcpy(sample_counts, sc.data(), sc.size() * 4);
     memcpy(allele_probes, ap.data(), ap.size() * 4);
+    return BIGSI_OK;
+}
+
+// Locus typing (include/bigsi_hip_typing.h; k_locus_best + k_locus_counts, launch shapes: plan_typing): the fifth consumer, a
+// segmented max with argmax over the result vectors and the counters -- the first whose answer depends on the counter VALUES of
+// competing records.  The accumulator owns best[n_loci][wv * 64] (uint64), hits[n_loci][wv * 64] and records[n_loci] (uint32), the
+// selection vector sel[wv] (columns & valid_mask, built at create), the two count outputs of a fetch, and two staging slots for the
+// labels (pinned host + device; locus_of in the first half of a slot, allele_of in the second): an add copies its entries into the
+// slot of its turn and uploads from there, so the caller's arrays are not read after the call returns and no add waits for its own
+// kernel.  `last` orders the accumulator with itself, as the tally's does.
+static_assert(BIGSI_TYPING_NONE == kTypingNone && BIGSI_TYPING_MAX_ALLELE == kTypingMaxAllele && BIGSI_TYPING_MAX_LOCI == kTypingMaxLoci &&
+                  BIGSI_TYPING_CELL_BYTES == kTypingCellBytes,
+              "header and planner");
+constexpr VectorConsumer kTypingConsumer = {"a typing", "ranks", false};
+
+struct bigsi_hip_typing {
+    bigsi_hip_index *ix = nullptr;
+    uint64_t n_cols = 0, m = 0, wv = 0;
+    uint32_t h = 0, n_loci = 0;
+    DevBuf best, hits, records, sel, locus_counts, sample_counts;
+    DevBuf d_labels[2];
+    void *pin[2] = {nullptr, nullptr};
+    size_t pin_cap[2] = {0, 0};
+    hipEvent_t pin_ev[2] = {nullptr, nullptr};      // behind the upload out of pin[slot]
+    unsigned turn = 0;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool unusable = false;                          // a typing_add_stream failed half way: until typing_reset
+    size_t cells() const { return (size_t)n_loci * wv * 64; }
+};
+
+static int typing_check(const bigsi_hip_typing *t, bool usable = true)
+{
+    const bigsi_hip_index *ix = t->ix;
+    if (ix->n_cols != t->n_cols || ix->m != t->m || ix->h != t->h)
+        return fail(BIGSI_ERR_STATE, "the index has changed since bigsi_hip_typing_create (%llu columns, %llu rows, %u hashes then; %llu, %llu, %u now)",
+                    (unsigned long long)t->n_cols, (unsigned long long)t->m, t->h, (unsigned long long)ix->n_cols, (unsigned long long)ix->m, ix->h);
+    if (usable && t->unusable)
+        return fail(BIGSI_ERR_STATE, "a bigsi_hip_typing_add_stream on this accumulator failed half way: bigsi_hip_typing_reset starts over");
+    return BIGSI_OK;
+}
+
+// what is queued on `st` next comes after everything queued on behalf of the accumulator so far
+static int typing_order(bigsi_hip_typing *t, hipStream_t st)
+{
+    if (t->last && t->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, t->last, 0));
+    return BIGSI_OK;
+}
+
+static int typing_mark(bigsi_hip_typing *t, hipStream_t st)
+{
+    if (!t->last) HIP_TRY(hipEventCreateWithFlags(&t->last, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(t->last, st));
+    t->last_stream = st;
+    return BIGSI_OK;
+}
+
+static int typing_zero(bigsi_hip_typing *t, hipStream_t st)
+{
+    HIP_TRY(hipMemsetAsync(t->best.p, 0, t->cells() * 8, st));
+    HIP_TRY(hipMemsetAsync(t->hits.p, 0, t->cells() * 4, st));
+    HIP_TRY(hipMemsetAsync(t->records.p, 0, (size_t)t->n_loci * 4, st));
+    return typing_mark(t, st);
+}
+
+extern "C" int bigsi_hip_typing_create(bigsi_hip_index *ix, uint32_t n_loci, const uint8_t *columns, bigsi_hip_typing **out)
+{
+    BIGSI_ENTER(ix);
+    if (!ix || !out) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (ix->n_cols == 0) return fail(BIGSI_ERR_STATE, "index has no columns");
+    const uint64_t wv = ix->wv();
+    const TypingPlan p = plan_typing(1, wv, n_loci);
+    if (p.bad_loci) return fail(BIGSI_ERR_INVALID, "n_loci must be 1 .. BIGSI_TYPING_MAX_LOCI = %u (got %u)", kTypingMaxLoci, n_loci);
+    if (p.too_many_bytes)
+        return fail(BIGSI_ERR_NOMEM, "the cells of %u loci over %llu columns take %u x %llu x 64 x 12 bytes, above BIGSI_TYPING_CELL_BYTES = %llu: slice the scheme by locus",
+                    n_loci, (unsigned long long)ix->n_cols, n_loci, (unsigned long long)wv, (unsigned long long)kTypingCellBytes);
+    if (p.too_large) return fail(BIGSI_ERR_INVALID, "index too wide for one typing launch (%llu workgroups)", (unsigned long long)p.too_large);
+    TRY(use_device(ix));
+    bigsi_hip_typing *t = new (std::nothrow) bigsi_hip_typing();
+    if (!t) return fail(BIGSI_ERR_NOMEM, "host allocation failed");
+    t->ix = ix;
+    t->n_cols = ix->n_cols; t->m = ix->m; t->h = ix->h; t->wv = wv;
+    t->n_loci = n_loci;
+    std::vector<uint64_t> sel(wv, columns ? 0ull : ~0ull);
+    if (columns) memcpy(sel.data(), columns, (size_t)((t->n_cols + 7) / 8));      // (row format = the little-endian words the kernels load)
+    for (uint64_t w = 0; w < wv; w++) sel[w] &= valid_mask(w, t->n_cols);
+    int rc = t->best.reserve(t->cells() * 8);
+    if (rc == BIGSI_OK) rc = t->hits.reserve(t->cells() * 4);
+    if (rc == BIGSI_OK) rc = t->records.reserve((size_t)n_loci * 4);
+    if (rc == BIGSI_OK) rc = t->sel.reserve((size_t)wv * 8);
+    if (rc == BIGSI_OK) rc = t->locus_counts.reserve((size_t)n_loci * 12);
+    if (rc == BIGSI_OK) rc = t->sample_counts.reserve((size_t)wv * 64 * 8);
+    if (rc == BIGSI_OK) {
+        hipError_t e = hipMemcpyAsync(t->sel.p, sel.data(), (size_t)wv * 8, hipMemcpyHostToDevice, ix->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);      // (a pageable source that dies with this call)
+        if (e != hipSuccess) rc = fail(BIGSI_ERR_HIP, "uploading the column selection: %s", hipGetErrorString(e));
+    }
+    if (rc == BIGSI_OK) rc = typing_zero(t, ix->stream);
+    if (rc != BIGSI_OK) { bigsi_hip_typing_destroy(t); return rc; }
+    *out = t;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_typing_destroy(bigsi_hip_typing *t)
+{
+    BusyGuard busy_guard_(t ? t->ix : nullptr, /*wait=*/true);
+    if (!t) return BIGSI_OK;
+    hipError_t e = hipSetDevice(t->ix->device);
+    if (t->last) { e = hipEventSynchronize(t->last); e = hipEventDestroy(t->last); }
+    for (int s = 0; s < 2; s++) {
+        if (t->pin_ev[s]) { e = hipEventSynchronize(t->pin_ev[s]); e = hipEventDestroy(t->pin_ev[s]); }
+        if (t->pin[s]) e = hipHostFree(t->pin[s]);
+        t->d_labels[s].release();
+    }
+    (void)e;
+    t->best.release(); t->hits.release(); t->records.release(); t->sel.release(); t->locus_counts.release(); t->sample_counts.release();
+    delete t;
+    return BIGSI_OK;
+}
+
+extern "C" int bigsi_hip_typing_reset(bigsi_hip_typing *t)
+{
+    BIGSI_ENTER(t ? t->ix : nullptr);
+    if (!t) return fail(BIGSI_ERR_INVALID, "NULL accumulator");
+    TRY(typing_check(t, false));
+    TRY(use_device(t->ix));
+    hipStream_t st = t->ix->stream;
+    TRY(typing_order(t, st));
+    TRY(typing_zero(t, st));
+    t->unusable = false;
+    return BIGSI_OK;
+}
+
+static int typing_validate(const bigsi_hip_typing *t, const uint32_t *locus_of, const uint32_t *allele_of, uint64_t n_entries)
+{
+    const uint64_t bad = typing_bad_label(locus_of, allele_of, n_entries, t->n_loci);
+    if (bad == n_entries) return BIGSI_OK;
+    if (locus_of[bad] >= t->n_loci)
+        return fail(BIGSI_ERR_INVALID, "locus_of[%llu] = %u is neither below n_loci (%u) nor BIGSI_TYPING_NONE", (unsigned long long)bad, locus_of[bad], t->n_loci);
+    return fail(BIGSI_ERR_INVALID, "allele_of[%llu] = %u is above BIGSI_TYPING_MAX_ALLELE = %u", (unsigned long long)bad, allele_of[bad], kTypingMaxAllele);
+}
+
+// k_locus_best for a batch that passed check_consumer_batch (its result vectors are then as wide as the cells' rows) and whose
+// validated labels are `locus_of` and `allele_of`, and finish_consumer
+static int typing_launch(bigsi_hip_typing *t, bigsi_hip_batch *b, const uint32_t *locus_of, const uint32_t *allele_of)
+{
+    bigsi_hip_index *ix = b->ix;
+    hipStream_t st = consumer_stream(b);
+    const TypingPlan p = plan_typing(b->n_seqs, b->wv, t->n_loci);
+    if (p.too_large) return fail(BIGSI_ERR_INVALID, "batch too large for one typing launch (%llu workgroups)", (unsigned long long)p.too_large);
+    if (p.grid == 0) return BIGSI_OK;
+    const int slot = (int)(t->turn++ & 1u);
+    const size_t half = (size_t)b->n_seqs * 4, bytes = 2 * half;
+    if (t->pin_ev[slot]) HIP_TRY(hipEventSynchronize(t->pin_ev[slot]));      // (the upload of two adds ago has left the pinned slot)
+    else HIP_TRY(hipEventCreateWithFlags(&t->pin_ev[slot], hipEventDisableTiming));
+    if (t->pin_cap[slot] < bytes) {
+        if (t->pin[slot]) { HIP_TRY(hipHostFree(t->pin[slot])); t->pin[slot] = nullptr; t->pin_cap[slot] = 0; }
+        const size_t want = std::max<size_t>(bytes, (size_t)kTallyChunkSeqs * 8);
+        HIP_TRY(hipHostMalloc(&t->pin[slot], want, hipHostMallocDefault));
+        t->pin_cap[slot] = want;
+    }
+    memcpy(t->pin[slot], locus_of, half);
+    memcpy(static_cast<char *>(t->pin[slot]) + half, allele_of, half);
+    TRY(typing_order(t, st));                        // (also: the kernel that read this slot's device copy two adds ago is behind us)
+    if (t->d_labels[slot].cap < bytes) HIP_TRY(hipStreamSynchronize(st));      // (growing frees the old copy)
+    TRY(t->d_labels[slot].reserve(std::max<size_t>(bytes, (size_t)kTallyChunkSeqs * 8)));
+    HIP_TRY(hipMemcpyAsync(t->d_labels[slot].p, t->pin[slot], bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(t->pin_ev[slot], st));
+    const uint32_t *d_locus = t->d_labels[slot].as<uint32_t>(), *d_allele = d_locus + b->n_seqs;
+    const uint64_t *bm = static_cast<const uint64_t *>(b->bit_vectors());
+    const uint64_t cstride = b->wv_pad * 64;
+    EventPair ep{};
+    TRY(bigsi_ev_begin(ix, &ep, st));
+    with_counters(b, [&](auto exact, const auto *cnt) {
+        using CountT = std::remove_const_t<std::remove_pointer_t<decltype(cnt)>>;
+        hipLaunchKernelGGL((k_locus_best<CountT, decltype(exact)::value>), dim3((unsigned)p.grid), dim3(p.block), 0, st, bm, b->wv_pad, (uint32_t)b->wv, b->n_seqs,
+                           b->num_unique.as<uint32_t>(), cnt, cstride, d_locus, d_allele, t->sel.as<uint64_t>(), (uint32_t)p.word_groups,
+                           t->best.as<unsigned long long>(), t->hits.as<uint32_t>(), t->records.as<uint32_t>());
+    });
+    HIP_TRY(hipGetLastError());
+    TRY(bigsi_ev_end(ix, &ep, ix->ev_cp, st, 1));      // (timed with the compaction it stands in for: bigsi_hip_stats' compact_ms)
+    TRY(typing_mark(t, st));
+    return finish_consumer(b, st);
+}
+
+extern "C" int bigsi_hip_typing_add_batch(bigsi_hip_typing *t, bigsi_hip_batch *b, const uint32_t *locus_of, const uint32_t *allele_of, uint64_t n_entries)
+{
+    BIGSI_ENTER(t ? t->ix : nullptr);
+    if (!t || !b || !locus_of || !allele_of) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(typing_check(t));
+    if (b->ix != t->ix) return fail(BIGSI_ERR_STATE, "the batch belongs to another index than the typing accumulator");
+    TRY(check_consumer_batch(b, kTypingConsumer));
+    if (n_entries != b->n_seqs)
+        return fail(BIGSI_ERR_INVALID, "locus_of and allele_of have %llu entries, the batch has %u sequences", (unsigned long long)n_entries, b->n_seqs);
+    TRY(typing_validate(t, locus_of, allele_of, n_entries));
+    TRY(use_device(t->ix));
+    return typing_launch(t, b, locus_of, allele_of);
+}
+
+// consume_stream over the index's typing_ws.  A chunk without a k-mer position adds nothing: records counts only records with k-mers.
+extern "C" int bigsi_hip_typing_add_stream(bigsi_hip_typing *t, const char *seqs, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, double threshold,
+                                           const uint32_t *locus_of, const uint32_t *allele_of)
+{
+    BIGSI_ENTER(t ? t->ix : nullptr);
+    if (!t || !offsets || !locus_of || !allele_of) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(typing_check(t));
+    TRY(check_stream_args(seqs, offsets, n_seqs, k, threshold));
+    TRY(typing_validate(t, locus_of, allele_of, n_seqs));
+    TRY(use_device(t->ix));
+    const int rc = consume_stream(
+        t->ix, t->ix->typing_ws, kTypingConsumer, seqs, offsets, n_seqs, k, threshold, [](uint64_t, uint64_t) {},
+        [&](bigsi_hip_batch *b, int, uint64_t s0, uint64_t) { return typing_launch(t, b, locus_of + s0, allele_of + s0); });
+    if (rc != BIGSI_OK) t->unusable = true;
+    return rc;
+}
+
+extern "C" int bigsi_hip_typing_fetch(bigsi_hip_typing *t, uint64_t *best, uint32_t *hits, uint64_t cell_capacity, uint32_t *locus_counts,
+                                      uint32_t *sample_counts, uint64_t sample_capacity, uint32_t *records)
+{
+    BIGSI_ENTER(t ? t->ix : nullptr);
+    if (!t || !locus_counts || !sample_counts || !records) return fail(BIGSI_ERR_INVALID, "NULL argument");
+    TRY(typing_check(t));
+    if ((best || hits) && cell_capacity < (uint64_t)t->n_loci * t->n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "a cell buffer holds %llu entries, %u loci x %llu columns needed", (unsigned long long)cell_capacity, t->n_loci,
+                    (unsigned long long)t->n_cols);
+    if (sample_capacity < t->n_cols)
+        return fail(BIGSI_ERR_CAPACITY, "sample_counts holds %llu entries, %llu needed", (unsigned long long)sample_capacity, (unsigned long long)t->n_cols);
+    TRY(use_device(t->ix));
+    hipStream_t st = t->ix->stream;
+    TRY(typing_order(t, st));
+    const TypingPlan p = plan_typing(1, t->wv, t->n_loci);
+    hipLaunchKernelGGL(k_locus_counts, dim3((unsigned)p.counts_grid), dim3(p.block), 0, st, t->best.as<uint64_t>(), t->hits.as<uint32_t>(), (uint32_t)t->wv, t->n_loci,
+                       (uint32_t)p.loci_grid, t->locus_counts.as<uint32_t>(), t->sample_counts.as<uint2>());
+    HIP_TRY(hipGetLastError());
+    TRY(typing_mark(t, st));
+    // (downloads into host copies first: a failure half way must not leave a caller's buffer half written)
+    std::vector<uint32_t> lc((size_t)t->n_loci * 3), sc((size_t)t->n_cols * 2), rec((size_t)t->n_loci);
+    HIP_TRY(hipMemcpyAsync(lc.data(), t->locus_counts.p, lc.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(sc.data(), t->sample_counts.p, sc.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(rec.data(), t->records.p, rec.size() * 4, hipMemcpyDeviceToHost, st));
+    const size_t row = (size_t)t->wv * 64;      // (cell 64 w + lane of a row is column 64 w + lane: a row's first num_cols cells are the columns)
+    if (best) HIP_TRY(hipMemcpy2DAsync(best, t->n_cols * 8, t->best.p, row * 8, t->n_cols * 8, t->n_loci, hipMemcpyDeviceToHost, st));
+    if (hits) HIP_TRY(hipMemcpy2DAsync(hits, t->n_cols * 4, t->hits.p, row * 4, t->n_cols * 4, t->n_loci, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(locus_counts, lc.data(), lc.size() * 4);
+    memcpy(sample_counts, sc.data(), sc.size() * 4);
+    memcpy(records, rec.data(), rec.size() * 4);
     return BIGSI_OK;
 }
 

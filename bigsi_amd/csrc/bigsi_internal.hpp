@@ -16,6 +16,7 @@
 #include "bigsi_hip_pairwise.h"
 #include "bigsi_hip_prevalence.h"
 #include "bigsi_hip_tally.h"
+#include "bigsi_hip_typing.h"
 #include "bigsi_hip_testing.h"
 #include "bigsi_hip_text.h"
 #include "bigsi_hip_window.h"
@@ -116,6 +117,7 @@ struct bigsi_hip_index {
     void *associate_pin[2] = {nullptr, nullptr};      // ... their pinned twin (stream call) and the event behind the download into it
     hipEvent_t associate_ev[2] = {nullptr, nullptr};
     struct bigsi_hip_batch *genotype_ws[2] = {};      // bigsi_hip_genotype_add_stream's workspaces, created at its first call
+    struct bigsi_hip_batch *typing_ws[2] = {};        // bigsi_hip_typing_add_stream's workspaces, created at its first call
     struct bigsi_hip_batch *window_ws = nullptr;     // bigsi_hip_window_search's workspace, created at its first call
     uint64_t window_starts = 0, window_cap = 0;       // bigsi_hip_window_set_limits: starts per segment, partial bytes cap (0: the planner's)
     uint32_t band_windows = 0, band_segs = 0;         // bigsi_hip_band_set_limits: windows per band, segments per launch (0: the planner's)

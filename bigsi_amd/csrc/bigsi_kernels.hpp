@@ -4376,4 +4376,115 @@ __global__ __launch_bounds__(kBlock) void k_genotype_samples(const uint64_t *__r
     sample_counts[(uint64_t)w * 64 + lane] = make_uint2(carried, called);
 }
 
+// ------------------------------------------------------------------------------ locus typing: each sample's best allele per locus
+// The segmented max with argmax over the result vectors AND counters a run made with BIGSI_RUN_SKIP_COMPACT left behind
+// (include/bigsi_hip_typing.h has the definition): per (locus, column) the largest typing_key of the locus's records that hit the
+// column -- best[l][64 w + lane], 0: no hit --, the number of such records -- hits[l][..] -- and per locus its records with k-mers.
+//
+// k_locus_best (launch shape: plan_typing): k_tally_hits' shape.  A wavefront owns result word w -- lane l the column 64 w + l at bit
+//   bit_of_col(l) -- and the records [q0, q1) of one tile.  Per record ONE wave-uniform 8-byte load of the word, kTypingLoads in
+//   flight, ANDed with sel[w] (columns & valid_mask, built once at create: bits behind num_cols are never trusted, and only words
+//   < wv are read).  A zero word is skipped in a uniform branch before anything else of the record is touched; otherwise locus_of,
+//   num_unique and allele_of of the record are uniform loads (no locus or no k-mers: skipped), and a lane whose bit is set loads its
+//   own counter (a predicated load; in sparse mode the counters of a word that holds a hit are valid; EXACT never reads one: c = u),
+//   takes typing_key -- the 64-bit division runs only here, in plain C++ -- and keeps (current locus, best key, hit count) in
+//   registers.  On a locus change or at the tile end a lane issues one 64-bit atomicMax and one 32-bit atomicAdd, each only when
+//   non-zero: records grouped by locus cost one pair per locus, tile and column; any other order costs more atomics and gives the same
+//   cells -- max and add of integers are order-free, so chunks on two streams may meet in one cell.  Thread i of the workgroup that
+//   owns word 0 adds record q0 + i to records[locus].  No LDS, no scratch, no spill.
+// k_locus_counts (one launch at fetch, no atomics): workgroups below loci_grid give a wavefront to each locus -- the lanes sweep its
+//   row of cells, count best != 0, score == 2^32 - 1 and hits > 1, and reduce by shuffles; three stores per locus.  The workgroups
+//   behind them give a wavefront to each result word, lane = column, and loop over the loci (coalesced 8-byte loads, four in flight);
+//   one uint2 store {called, exact} per column, the ones behind num_cols included (they are zero: their cells never got a key).
+template <typename CountT, bool EXACT>
+__global__ __launch_bounds__(kBlock) void k_locus_best(
+    const uint64_t *__restrict__ bitmaps, uint64_t bm_stride, uint32_t wv, uint32_t n_seqs, const uint32_t *__restrict__ num_unique,
+    const CountT *__restrict__ counters, uint64_t counter_stride, const uint32_t *__restrict__ locus_of, const uint32_t *__restrict__ allele_of,
+    const uint64_t *__restrict__ sel, uint32_t word_groups, unsigned long long *__restrict__ best, uint32_t *__restrict__ hits,
+    uint32_t *__restrict__ records)
+{
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    const uint32_t t = blockIdx.x / word_groups, wg = blockIdx.x - t * word_groups, w = wg * (kBlock / 64) + wave;
+    const uint32_t q0 = t * kTypingTile, q1 = n_seqs - q0 < kTypingTile ? n_seqs : q0 + kTypingTile;
+    if (wg == 0 && threadIdx.x < q1 - q0) {
+        const uint32_t l = locus_of[q0 + threadIdx.x];
+        if (l != kTypingNone && num_unique[q0 + threadIdx.x] != 0) atomicAdd(&records[l], 1u);
+    }
+    if (w >= wv) return;
+    const uint64_t sm = sel[w], row = (uint64_t)wv * 64, cell = (uint64_t)w * 64 + lane;
+    const uint32_t bit = bit_of_col(lane);
+    uint32_t cur = kTypingNone, n_hits = 0;
+    unsigned long long key = 0;
+    for (uint32_t q = q0; q < q1; q += kTypingLoads) {
+        uint64_t x[kTypingLoads];
+#pragma unroll
+        for (uint32_t j = 0; j < kTypingLoads; j++) x[j] = q + j < q1 ? bitmaps[(uint64_t)(q + j) * bm_stride + w] & sm : 0ull;
+#pragma unroll
+        for (uint32_t j = 0; j < kTypingLoads; j++) {
+            if (x[j] == 0) continue;                                    // (uniform)
+            const uint32_t l = locus_of[q + j];
+            if (l == kTypingNone) continue;
+            const uint32_t u = num_unique[q + j];
+            if (u == 0) continue;
+            if (l != cur) {
+                if (key) atomicMax(&best[(uint64_t)cur * row + cell], key);
+                if (n_hits) atomicAdd(&hits[(uint64_t)cur * row + cell], n_hits);
+                cur = l;
+                key = 0;
+                n_hits = 0;
+            }
+            if ((x[j] >> bit) & 1ull) {
+                const uint32_t al = allele_of[q + j];
+                const unsigned long long mine =
+                    EXACT ? typing_key(1u, 1u, al) : typing_key((uint32_t)counters[(uint64_t)(q + j) * counter_stride + cell], u, al);
+                key = mine > key ? mine : key;
+                n_hits++;
+            }
+        }
+    }
+    if (key) atomicMax(&best[(uint64_t)cur * row + cell], key);
+    if (n_hits) atomicAdd(&hits[(uint64_t)cur * row + cell], n_hits);
+}
+
+__global__ __launch_bounds__(kBlock) void k_locus_counts(const uint64_t *__restrict__ best, const uint32_t *__restrict__ hits, uint32_t wv, uint32_t n_loci,
+                                                         uint32_t loci_grid, uint32_t *__restrict__ locus_counts, uint2 *__restrict__ sample_counts)
+{
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    const uint64_t row = (uint64_t)wv * 64;
+    if (blockIdx.x < loci_grid) {
+        const uint32_t l = blockIdx.x * (kBlock / 64) + wave;
+        if (l >= n_loci) return;                                        // (uniform over the wavefront)
+        uint32_t called = 0, exact = 0, multiple = 0;
+        for (uint64_t i = lane; i < row; i += 64) {
+            const uint64_t b = best[(uint64_t)l * row + i];
+            called += b != 0 ? 1u : 0u;
+            exact += (b >> 32) == 0xFFFFFFFFull ? 1u : 0u;
+            multiple += hits[(uint64_t)l * row + i] > 1u ? 1u : 0u;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            called += __shfl_xor(called, d);
+            exact += __shfl_xor(exact, d);
+            multiple += __shfl_xor(multiple, d);
+        }
+        if (lane < 3) locus_counts[(uint64_t)l * 3 + lane] = lane == 0 ? called : lane == 1 ? exact : multiple;
+        return;
+    }
+    const uint32_t w = (blockIdx.x - loci_grid) * (kBlock / 64) + wave;
+    if (w >= wv) return;
+    const uint64_t cell = (uint64_t)w * 64 + lane;
+    uint32_t called = 0, exact = 0;
+    for (uint32_t l = 0; l < n_loci; l += 4) {
+        uint64_t b[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) b[j] = l + j < n_loci ? best[(uint64_t)(l + j) * row + cell] : 0ull;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            called += b[j] != 0 ? 1u : 0u;
+            exact += (b[j] >> 32) == 0xFFFFFFFFull ? 1u : 0u;
+        }
+    }
+    sample_counts[cell] = make_uint2(called, exact);
+}
+
 }   // namespace bigsi

@@ -1130,6 +1130,67 @@ static inline uint64_t genotype_bad_allele(const uint32_t *allele_of, uint64_t n
     return n_entries;
 }
 
+// ------------------------------------------------------------------------------ locus typing (k_locus_best, k_locus_counts)
+// k_locus_best: the tally's shape -- a wavefront owns ONE result word (64 columns, lane = column) and a tile of kTypingTile records;
+// the kBlock / 64 wavefronts of a workgroup own neighbouring words of the same tile; workgroup b: word group b % word_groups, tile
+// b / word_groups.  A tile costs a column one 64-bit atomicMax and one 32-bit atomicAdd per locus it holds a hit of, so it is as long as
+// keeps those rare and as short as still gives a narrow index some workgroups; it is at most kBlock, since thread i of the workgroup
+// that owns word 0 counts record i of the tile into `records`.  k_locus_counts: one launch, two parts -- the first loci_grid
+// workgroups give a wavefront to each locus, the words_grid behind them a wavefront to each result word.  cell_bytes is best (8 bytes)
+// and hits (4 bytes) of every (locus, column) as the device holds them (rows of wv * 64 cells).  Refused: n_loci outside 1 ..
+// kTypingMaxLoci, cells above kTypingCellBytes, more than 2^31 - 1 workgroups in a launch.
+constexpr uint32_t kTypingNone = 0xFFFFFFFFu;               // BIGSI_TYPING_NONE (include/bigsi_hip_typing.h)
+constexpr uint32_t kTypingMaxAllele = 0xFFFFFFFEu;          // BIGSI_TYPING_MAX_ALLELE
+constexpr uint32_t kTypingMaxLoci = 1u << 20;               // BIGSI_TYPING_MAX_LOCI
+constexpr uint64_t kTypingCellBytes = 4ull << 30;           // BIGSI_TYPING_CELL_BYTES: a design limit, not a measured one
+constexpr uint32_t kTypingTile = 64;                        // records per workgroup of k_locus_best
+constexpr uint32_t kTypingLoads = 8;                        // result words a wavefront of k_locus_best has in flight
+static_assert(kTypingTile <= (uint32_t)kBlock && kTypingTile % kTypingLoads == 0, "k_locus_best: thread i counts record i; whole load groups");
+// The key of a hit (include/bigsi_hip_typing.h): the fraction c / u of the record's k-mers found, as floor(c (2^32 - 1) / u), above the
+// complement of the allele identity -- the highest fraction wins, ties go to the lowest identity, and the key of a hit is never 0.
+// c <= u < 2^32 and u > 0: the product fits 64 bits.  Two different fractions share a score only when u_i * u_j > 2^32.  constexpr: the
+// kernel and the host tests compile this one function, so its CPU pin is the pin of the kernel's arithmetic.
+constexpr uint64_t typing_key(uint32_t c, uint32_t u, uint32_t allele)
+{
+    return ((uint64_t)c * 0xFFFFFFFFull / u) << 32 | (uint64_t)(0xFFFFFFFFu - allele);
+}
+struct TypingPlan {
+    uint32_t block = kBlock, tile = kTypingTile;
+    uint64_t word_groups = 0, tiles = 0, grid = 0;            // k_locus_best: grid = word_groups * tiles
+    uint64_t loci_grid = 0, words_grid = 0, counts_grid = 0;  // k_locus_counts: counts_grid = loci_grid + words_grid
+    uint64_t cell_bytes = 0;                                  // best[n_loci][wv * 64] (8 bytes) + hits[n_loci][wv * 64] (4 bytes)
+    uint64_t too_large = 0;                                   // != 0: the workgroups one launch would take (more than 2^31 - 1): refused
+    bool bad_loci = false, too_many_bytes = false;            // n_loci outside 1 .. kTypingMaxLoci; cells above kTypingCellBytes
+};
+static inline TypingPlan plan_typing(uint64_t n_seqs, uint64_t wv, uint64_t n_loci)
+{
+    TypingPlan p;
+    p.word_groups = wv / (kBlock / 64) + (wv % (kBlock / 64) ? 1 : 0);      // (ceil without the sum: wv may be anything)
+    p.tiles = ceil_div(n_seqs, (uint64_t)p.tile);
+    p.grid = p.tiles && p.word_groups > ~0ull / p.tiles ? ~0ull : p.word_groups * p.tiles;      // (saturates: the product may not fit 64 bits)
+    p.words_grid = p.word_groups;
+    if (p.grid > 0x7FFFFFFFull) p.too_large = p.grid;
+    if (n_loci == 0 || n_loci > kTypingMaxLoci) {
+        p.bad_loci = true;
+        if (!p.too_large && p.words_grid > 0x7FFFFFFFull) p.too_large = p.words_grid;
+        return p;
+    }
+    p.loci_grid = ceil_div(n_loci, (uint64_t)(kBlock / 64));
+    p.counts_grid = p.loci_grid + p.words_grid;               // (loci_grid <= 2^18 and words_grid <= 2^62: no overflow)
+    if (!p.too_large && p.counts_grid > 0x7FFFFFFFull) p.too_large = p.counts_grid;
+    if (wv > kTypingCellBytes / (768 * n_loci)) p.too_many_bytes = true;      // (by division: the product may not fit 64 bits)
+    else p.cell_bytes = n_loci * wv * 768;
+    return p;
+}
+// the first record whose labels are refused: a locus that is neither below n_loci nor kTypingNone, or -- for a record with a locus -- an
+// allele identity above kTypingMaxAllele; n_entries when there is none.  The allele of a record without a locus is not looked at.
+static inline uint64_t typing_bad_label(const uint32_t *locus_of, const uint32_t *allele_of, uint64_t n_entries, uint64_t n_loci)
+{
+    for (uint64_t i = 0; i < n_entries; i++)
+        if (locus_of[i] != kTypingNone && (locus_of[i] >= n_loci || allele_of[i] > kTypingMaxAllele)) return i;
+    return n_entries;
+}
+
 // ------------------------------------------------------------------------------ windowed search (k_window_max, k_window_combine)
 // plan_window_search: sequence q of a batch has n[q] k-mer positions, a window of We = min(W, n[q]) of them and the window starts
 // [0, n[q] - We]; the sweep cuts every sequence's starts into segments of at most S and a wavefront of k_window_max owns one

@@ -1081,6 +1081,82 @@ class BIGSI(SampleMetadata, KmerSignatureIndex):
         matrix = None if summary_only else calls(ref, alt, sc.shape[0], excluded)
         return result(names, vc, sc, ap, self._name_of(), excluded, matrix)
 
+    # ------------------------------------------------------------------ locus typing
+    def typing_arrays(self, records, locus_of, n_loci, threshold=1.0, cell_bytes=1 << 30, cells=True, allele_of=None):
+        """Each sample's best record per locus for a catalogue of allele records grouped into loci -- answered on the device
+        (bigsi_hip_typing: a segmented max with argmax over the records' result vectors and counters behind the row-AND kernels; no
+        hit list is built).  records: ASCII sequences; locus_of[i] < n_loci, or locus_typing.NONE; allele_of[i]: the record's
+        identity (default: its position), ties go to the lowest.  Returns (best uint64[n_loci, num_cols] -- the key of
+        include/bigsi_hip_typing.h, 0: no call; locus_typing.decode takes it apart --, hits uint32[n_loci, num_cols], or None, None
+        with cells=False -- they are then never downloaded --, locus_counts uint32[n_loci, 3]: called, exact, multiple,
+        sample_counts uint32[num_cols, 2]: called, exact, records uint32[n_loci]: the locus's records with k-mers).  Deleted
+        samples are left out on the device: their cells are zero and they count nowhere.  The scheme is cut by locus into slices
+        whose cells fit `cell_bytes` of device memory, each with an accumulator of its own; a record goes to its locus's slice only.
+        Multi-GPU (devices=[...]) indexes are refused."""
+        from ..locus_typing import MAX_ALLELE, MAX_LOCI, NONE, slices
+        self._check_stream_query(records, threshold)
+        records = list(records)
+        locus_of = np.ascontiguousarray(locus_of, dtype=np.uint32).reshape(-1)
+        allele_of = np.arange(len(records), dtype=np.uint32) if allele_of is None else np.ascontiguousarray(allele_of, dtype=np.uint32).reshape(-1)
+        n_loci = int(n_loci)
+        if locus_of.size != len(records) or allele_of.size != len(records):
+            raise ValueError("locus_of and allele_of have %d and %d entries for %d records" % (locus_of.size, allele_of.size, len(records)))
+        if n_loci < 1:
+            raise ValueError("n_loci must be >= 1, got %d" % n_loci)
+        bad = np.flatnonzero((locus_of != NONE) & (locus_of.astype(np.int64) >= n_loci))
+        if bad.size:
+            raise ValueError("locus_of[%d] = %d is neither below n_loci (%d) nor NONE" % (bad[0], locus_of[bad[0]], n_loci))
+        bad = np.flatnonzero((locus_of != NONE) & (allele_of > MAX_ALLELE))
+        if bad.size:
+            raise ValueError("allele_of[%d] = %d is above %d" % (bad[0], allele_of[bad[0]], MAX_ALLELE))
+        if int(cell_bytes) < 1:
+            raise ValueError("cell_bytes must be >= 1, got %r" % (cell_bytes,))
+        for s in records:
+            if not isinstance(s, str) or not s.isascii():
+                raise ValueError("locus typing takes ASCII sequences (records with other characters are out of scope)")
+        self._refuse_group("locus typing")
+        k = int(self.kmer_size)
+        with self._device_lock():
+            n_cols = int(self.storage.get_integer("number_of_cols"))
+            bits = np.ones((n_cols + 7) // 8 * 8, np.uint8)
+            ex = self._excluded_colours()
+            bits[ex[ex < n_cols]] = 0
+            columns = np.packbits(bits)
+            best = np.zeros((n_loci, n_cols), np.uint64) if cells else None
+            hits = np.zeros((n_loci, n_cols), np.uint32) if cells else None
+            lc, sc, rec = np.zeros((n_loci, 3), np.uint32), np.zeros((n_cols, 2), np.uint32), np.zeros(n_loci, np.uint32)
+            for l0, l1, idx, rel in slices(locus_of, n_loci, n_cols, min(int(cell_bytes), 4 << 30)):
+                if l1 - l0 > MAX_LOCI:
+                    raise ValueError("a slice of %d loci: at most %d fit one accumulator (lower cell_bytes)" % (l1 - l0, MAX_LOCI))
+                t = self.storage.new_typing(l1 - l0, columns)
+                try:
+                    t.add([records[i] for i in idx], k, threshold, rel, allele_of[idx])
+                    b, h, lc[l0:l1], s, rec[l0:l1] = t.fetch(cells)
+                finally:
+                    t.close()
+                sc += s
+                if cells:
+                    best[l0:l1], hits[l0:l1] = b, h
+        return best, hits, lc, sc, rec
+
+    def type_samples(self, scheme, threshold=1.0, profiles=None, summary_only=False, loci_map=None, cell_bytes=1 << 30):
+        """typing_arrays over a scheme of allele records -- FASTA text, bytes or a path, PubMLST-style names locus_allele or a
+        record<TAB>locus loci_map (locus_typing.parse_scheme) -- as names: {"loci": [{"name", "records", "called", "exact",
+        "multiple"}], "samples": [{"sample_name", "colour", "called", "exact", "ST" (with profiles: a PubMLST profiles table; the
+        matching row's ST when every locus is exact, "novel" when none matches, "-" otherwise), "calls": {locus: {"allele",
+        "fraction", "exact", "n_hits"}, loci without a call left out}}]}.  Deleted samples appear nowhere.  summary_only=True leaves
+        "calls" and "ST" out, and the cells are then never downloaded."""
+        from ..locus_typing import calls, parse_profiles, parse_scheme, result
+        loci, _, alleles, records, locus_of, allele_of = parse_scheme(scheme, loci_map)
+        if not loci:
+            raise ValueError("the scheme holds no record")
+        table = parse_profiles(profiles, loci) if profiles is not None else None
+        best, hits, lc, sc, rec = self.typing_arrays(records, locus_of, len(loci), threshold, cell_bytes, cells=not summary_only, allele_of=allele_of)
+        with self._device_lock():
+            excluded = self._excluded_colours()
+        matrix = None if summary_only else calls(best, alleles, hits)
+        return result(loci, lc, sc, rec, self._name_of(), excluded, matrix, table)
+
     # ------------------------------------------------------------------ column compaction: vacuum / extract
     def _colour_names(self):
         """names[c] of every colour, DELETION_SPECIAL_SAMPLE_NAME for a deleted one; the matrix must be as wide as the metadata."""

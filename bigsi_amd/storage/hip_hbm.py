@@ -721,6 +721,12 @@ class HipHbmStorage(BaseStorage):
         self._single_gpu("panel genotyping")
         return Genotype(self, n_variants, columns)
 
+    def new_typing(self, n_loci, columns=None):
+        """A Typing over this index: zeroed cells (best key, hit count) for n_loci on the device (bigsi_hip_typing_create).  columns: a
+        bit vector in the row format (uint8[ceil(num_cols / 8)]) of the samples to type, None for all."""
+        self._single_gpu("locus typing")
+        return Typing(self, n_loci, columns)
+
     def fill_synthetic(self, seed, shard=0, and_draws=2):
         if self.res.is_group:       # shard i of the group is filled as (seed, shard i)
             check(_lib.lib().bigsi_hip_group_fill_synthetic(self.res.ix, int(seed), int(and_draws)))
@@ -1036,6 +1042,76 @@ class Genotype(object):
     def close(self):
         if self.b is not None:
             check(_lib.lib().bigsi_hip_genotype_destroy(self.b))
+            self.b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class Typing(object):
+    """The cells of a typing scheme (bigsi_hip_typing): add() records with their locus_of and allele_of or add_batch() a QueryBatch
+    whose last run was made with skip_compact=True, fetch() cells and counts, reset(), close().  Single index only."""
+
+    def __init__(self, storage, n_loci, columns=None):
+        self.storage = storage
+        self.b = None
+        self.n_loci = int(n_loci)
+        self.num_cols = int(storage.res.info().num_cols)
+        if columns is not None:
+            columns = np.ascontiguousarray(columns, dtype=np.uint8)
+            if columns.size != (self.num_cols + 7) // 8:
+                raise ValueError("columns must hold %d bytes, got %d" % ((self.num_cols + 7) // 8, columns.size))
+        out = _lib.C.c_void_p()
+        check(_lib.lib().bigsi_hip_typing_create(storage.handle, self.n_loci, None if columns is None else _lib.ptr(columns), _lib.C.byref(out)))
+        self.b = out
+        storage.res.batches.add(self)          # (it holds the index handle and must die before it, as a batch)
+
+    @staticmethod
+    def _labels(locus_of, allele_of, n):
+        locus_of, allele_of = np.ascontiguousarray(locus_of, dtype=np.uint32), np.ascontiguousarray(allele_of, dtype=np.uint32)
+        if locus_of.size != n or allele_of.size != n:
+            raise ValueError("locus_of and allele_of have %d and %d entries for %d records" % (locus_of.size, allele_of.size, n))
+        return locus_of, allele_of
+
+    def add(self, seqs, k, threshold, locus_of, allele_of):
+        """bigsi_hip_typing_add_stream over a list of records (an empty list adds nothing)."""
+        seqs = seqs if isinstance(seqs, (list, tuple)) else list(seqs)
+        locus_of, allele_of = self._labels(locus_of, allele_of, len(seqs))
+        if not seqs:
+            return self
+        blob, off = _lib.pack_seqs(seqs)
+        check(_lib.lib().bigsi_hip_typing_add_stream(self.b, blob, _lib.ptr(off), len(seqs), int(k), float(threshold), _lib.ptr(locus_of), _lib.ptr(allele_of)))
+        return self
+
+    def add_batch(self, batch, locus_of, allele_of):
+        if batch.group:
+            raise BigsiHipError(_lib.ERR_STATE, "locus typing is not available on a multi-GPU batch")
+        locus_of = np.ascontiguousarray(locus_of, dtype=np.uint32)
+        locus_of, allele_of = self._labels(locus_of, allele_of, locus_of.size)
+        check(_lib.lib().bigsi_hip_typing_add_batch(self.b, batch.b, _lib.ptr(locus_of), _lib.ptr(allele_of), locus_of.size))
+        return self
+
+    def reset(self):
+        check(_lib.lib().bigsi_hip_typing_reset(self.b))
+        return self
+
+    def fetch(self, cells=True):
+        """(best uint64[n_loci, num_cols], hits uint32[n_loci, num_cols] or None, None with cells=False -- they are then never
+        downloaded --, locus_counts uint32[n_loci, 3], sample_counts uint32[num_cols, 2], records uint32[n_loci])"""
+        n, nl = self.num_cols, self.n_loci
+        best = np.zeros((nl, n), np.uint64) if cells else None
+        hits = np.zeros((nl, n), np.uint32) if cells else None
+        lc, sc, rec = np.zeros((nl, 3), np.uint32), np.zeros((n, 2), np.uint32), np.zeros(nl, np.uint32)
+        check(_lib.lib().bigsi_hip_typing_fetch(self.b, _lib.ptr(best) if cells else None, _lib.ptr(hits) if cells else None, nl * n if cells else 0,
+                                                _lib.ptr(lc), _lib.ptr(sc), n, _lib.ptr(rec)))
+        return best, hits, lc, sc, rec
+
+    def close(self):
+        if self.b is not None:
+            check(_lib.lib().bigsi_hip_typing_destroy(self.b))
             self.b = None
 
     def __del__(self):

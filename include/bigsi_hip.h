@@ -32,6 +32,7 @@
  *       WINDOW     per sample the best window of W k-mer positions of a query and where the passing windows lie: include/bigsi_hip_window.h.
  *       TALLY      over a whole set of queries, per sample the number of queries that hit it and the k-mers they found: include/bigsi_hip_tally.h.
  *       GENOTYPE   over a panel of variant probes, every sample's call per variant, from one bit plane per allele: include/bigsi_hip_genotype.h.
+ *       TYPING     over a catalogue of allele records grouped into loci, every sample's best allele per locus: include/bigsi_hip_typing.h.
  *       SHARING    export_ipc / open_ipc (another process) and open_view (another thread): read-only handles onto ONE resident matrix.
  *       MEASUREMENT  fill_synthetic, set_profiling, stats (calibration probe and device-resident filters: bigsi_hip_testing.h).
  *     Not advertised here (exported all the same, declared in include/bigsi_hip_testing.h): hooks for hosts that bring their own

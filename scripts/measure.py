@@ -1,6 +1,6 @@
 """Per-workload kernel measurements behind DESIGN.md section 5 / profiles/*.json (one JSON object per line on stdout).
 
-    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] [classify] [associate] [genotype] [window] ...
+    python scripts/measure.py [c2stream] [c3batch] [p16] [c4shard] [northstar] [k5] [transpose] [colpop] [compact] [fold] [prevalence] [collapse] [consensus] [pairwise] [tally] [classify] [associate] [genotype] [typing] [window] ...
 
 Every figure is a HIP-event duration recorded by the library around its own kernels (bigsi_hip_set_profiling) over
 `reps` launches; run the same command under `rocprofv3 --kernel-trace --stats` for the per-kernel table that goes to
@@ -1117,6 +1117,84 @@ def genotype():
         emit("genotype", samples=n, variants=v_n, probes=len(probes), calls=sum(len(one) for one in many), het=sum(var["counts"]["0/1"] for var in res["variants"]),
              genotype_many_ms=many_ms, genotype_panel_ms=panel_ms, genotype_panel_summary_ms=summary_ms, genotype_arrays_ms=arrays_ms,
              many_over_panel=many_ms / panel_ms, note="wall clock, best of 3; genotype_panel names every call, summary_only and genotype_arrays do not")
+    finally:
+        b.delete()
+
+
+def typing():
+    """Locus typing (BIGSI.type_samples, bigsi_hip_typing) beside the route without the feature -- search_stream of the scheme's records
+    at the same threshold, then the argmax over every (record, sample) hit on the host -- on one hit-dense index: N samples, a scheme
+    of L loci and A alleles in all (120 bases each, the alleles of a locus two substitutions away from the locus's base sequence),
+    every sample holding one allele of every locus.  Below threshold 1 several alleles of a locus hit every sample and the fraction
+    decides.  Wall clock, best of 3 calls each, one process; the two routes' calls are compared cell for cell.
+    BIGSI_TYPING_SHAPE="NxLxA" replaces the shape, BIGSI_TYPING_THRESHOLD the threshold."""
+    import bigsi_amd
+    from bigsi_amd.locus_typing import EXACT_SCORE, parse_scheme
+    from bigsi_amd.utils import seq_to_kmers
+    n, n_loci, n_alleles, k, m, h = 20_000, 7, 200, 21, 200003, 3
+    if os.environ.get("BIGSI_TYPING_SHAPE"):
+        n, n_loci, n_alleles = (int(x) for x in os.environ["BIGSI_TYPING_SHAPE"].split("x"))
+    thr = float(os.environ.get("BIGSI_TYPING_THRESHOLD", "0.5"))
+    rng = np.random.default_rng(7)
+    per = [n_alleles // n_loci + (1 if l < n_alleles % n_loci else 0) for l in range(n_loci)]
+    alleles = []
+    for l, base in enumerate(rand_seqs(rng, n_loci, 120)):
+        one = []
+        for a in range(per[l]):
+            s = list(base)
+            for pos in rng.choice(120, size=2, replace=False):
+                s[pos] = "ACGT"[("ACGT".index(s[pos]) + 1 + int(rng.integers(3))) % 4]
+            one.append("".join(s))
+        alleles.append(one)
+    scheme = "".join(">locus%d_%d\n%s\n" % (l, a + 1, s) for l, one in enumerate(alleles) for a, s in enumerate(one))
+    cfg = {"storage-engine": "hip-hbm", "storage-config": {"name": "measure_typing"}, "k": k, "m": m, "h": h}
+    blooms = {}
+    for s in range(n):
+        combo = tuple(s % c for c in per)
+        if combo not in blooms:
+            blooms[combo] = bigsi_amd.BIGSI.bloom(cfg, [km for l, a in enumerate(combo) for km in seq_to_kmers(alleles[l][a], k)])
+    b = bigsi_amd.BIGSI.build(cfg, [blooms[tuple(s % c for c in per)] for s in range(n)], ["s%d" % s for s in range(n)])
+    loci, names, labels, records, locus_of, allele_of = parse_scheme(scheme)
+
+    def best(fn):
+        ms = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            out = fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return min(ms), out
+
+    def host_route():
+        """the parent's route: every hit as a result dict, the argmax in Python"""
+        top, dicts = {}, 0
+        for pos, (_, results) in enumerate(b.search_stream(records, thr)):
+            l, ident = int(locus_of[pos]), int(allele_of[pos])
+            for r in results:
+                dicts += 1
+                key = (r["num_kmers_found"] * EXACT_SCORE // r["num_kmers"], -ident)
+                cell = (l, r["sample_name"])
+                if key > top.get(cell, (-1, 0)):
+                    top[cell] = key
+        return top, dicts
+    try:
+        host_ms, (top, dicts) = best(host_route)
+        typed_ms, res = best(lambda: b.type_samples(scheme, threshold=thr))
+        summary_ms, summary = best(lambda: b.type_samples(scheme, threshold=thr, summary_only=True))
+        arrays_ms, arrays = best(lambda: b.typing_arrays(records, locus_of, len(loci), thr, allele_of=allele_of))
+        cells = 0
+        for s in res["samples"]:
+            for l, name in enumerate(loci):
+                c, want = s["calls"].get(name), top.get((l, s["sample_name"]))
+                assert (c is None) == (want is None), (s["sample_name"], name)
+                if c is not None:
+                    assert c["allele"] == labels[-want[1]] and c["fraction"] == want[0] / float(EXACT_SCORE), (s["sample_name"], name, c, want)
+                    cells += 1
+        assert cells == len(top) == sum(x["called"] for x in res["loci"]) and summary["loci"] == res["loci"]
+        emit("typing", samples=n, loci=len(loci), alleles=len(records), threshold=thr, called_cells=cells, exact_cells=sum(x["exact"] for x in res["loci"]),
+             multiple_cells=sum(x["multiple"] for x in res["loci"]), result_dicts=dicts, search_stream_argmax_ms=host_ms, type_samples_ms=typed_ms,
+             type_samples_summary_ms=summary_ms, typing_arrays_ms=arrays_ms, host_over_typed=host_ms / typed_ms, host_over_arrays=host_ms / arrays_ms,
+             cell_bytes_out=int(arrays[0].nbytes + arrays[1].nbytes), count_bytes_out=int(arrays[2].nbytes + arrays[3].nbytes + arrays[4].nbytes),
+             note="wall clock, best of 3; type_samples names every call, summary_only downloads the counts only, typing_arrays the cells as arrays")
     finally:
         b.delete()
 
